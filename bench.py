@@ -18,18 +18,24 @@ csrc/eds_strips.hip; the strip copies that make RE-solves of a frame faster cost
 library pick that kernel by itself on the frames' real first solve (an untimed step), checks that the timed steps launch the same
 one, and pins it with the handle's EDS_FUSED_LAYOUT=tiles knob only because the SAME frames are solved again every step.
 
-OUTPUT (round 6).  The LAST stdout line is a COMPACT record (< 4 KB: `compact_record`, size-tested on the CPU) — the contract's
-keys plus
+A PLAIN run does only what the headline needs: set-up, the untimed first solve, `--warmup` steps, `--steps` timed steps, the
+outputs (`--dump-outputs DIR`: the last timed step's result table, as the caller receives it, to DIR/results.npy in float64 — the
+inputs are seeded, so two builds can be compared row for row) and the result line.  `--full` adds everything else below.
+
+OUTPUT.  The LAST stdout line is a COMPACT record (< 4 KB: `compact_record`, size-tested on the CPU) — the contract's keys
+(`ms_per_step` = milliseconds of one timed step) plus
   roofline      the kernel of the timed region.  `achieved` / `frac` follow the contract: ALGORITHMIC bytes per launch (SURVEY 8d:
                 140 B per point-evaluation bicubic = 112 B residual/Jacobian + 28 B reduction, x alignments x points x passes) / the
                 kernel's duration measured live (HIP events on the library's own stream) / 8 TB/s.  `traffic` = bytes through the
                 fabric per launch from the committed rocprofv3 PMC passes of this workload (profiles/traffic_*.json; gfx950
                 correction of MI355X_MICROARCH.md: 2 x FETCH_SIZE + WRITE_SIZE) and `frac_physical` = that / time / 8 TB/s;
                 `frac_must_move` counts what a fused kernel has to move (84 B per point-evaluation: constants + taps)
+and, with --full only,
   cpu_baseline  the CPU oracle (a port: the reference needs Ceres and cannot be built here) running the SAME iterations on this
                 host's cores, on a bounded sample
+  parity_max_se3  the timed batch against the CPU oracle (exit status 3 beyond tolerance)
   reference_problem, roofline_resjac, roofline_reduce, latency, configs    digests of a few numbers each
-Everything else — every leg in full (bench_detail.py) — goes to bench_detail.json next to this file (and to gpurun_out/).
+With --full, everything else — every leg in full (bench_detail.py) — goes to bench_detail.json next to this file.
 """
 import argparse
 import gc
@@ -63,10 +69,10 @@ def _gen_alignment(args):
     return x, f32
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=4096, help="alignments per GPU (weak scaling)")
     ap.add_argument("--iters", type=int, default=10, help="tracker iterations per alignment")
@@ -88,7 +94,33 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-shared", dest="no_shared", action="store_true", help="skip the informational two-batches-in-flight and shared-frame measurements (the latter launches the "
                     "headline kernel on another workload: keep it out of profiler runs)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: cold per-kernel rooflines, HBM probe, strong scaling, "
+                    "the bench_detail.py legs, parity against the CPU oracle, CPU baselines, bench_detail.json (the --no-* options trim this)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result table to DIR/results.npy (float64, rows = alignments, columns = batch.RESULT_WIDTH)")
+    return ap.parse_args(argv)
+
+
+DUMP_LIMIT = 64 << 20            # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT, seed=0):
+    """Writes each array of `arrays` (name -> array) as DIR/<name>.npy in float64.  An output larger than its share of `limit`
+    is replaced by a fixed, seeded sample of its rows (sorted row indices), so that two runs with the same arguments write the same
+    rows.  Returns the paths written."""
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(len(arrays), 1)
+    written = []
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.nbytes > share:
+            row_bytes = x.nbytes // max(x.shape[0], 1)
+            keep = np.sort(np.random.default_rng(seed).choice(x.shape[0], share // row_bytes, replace=False))
+            x = x[keep]
+        p = os.path.join(dirname, name + ".npy")
+        np.save(p, x)
+        written.append(p)
+    return written
 
 
 def spawn_ranks(a):
@@ -176,7 +208,8 @@ def compact_record(full):
         rec["strong_scaling_config4"] = _pick(full["strong_scaling_config4"], ("ms_per_step", "iterations_per_s", "alignments_per_gpu", "kernel_ms_rank0"))
     if full.get("hbm_probe"):
         rec["hbm_probe_GBps"] = _pick(full["hbm_probe"], ("read_GBps", "copy_GBps"))
-    rec["detail"] = full.get("detail_files") or ["bench_detail.json"]
+    if full.get("detail_files"):                 # (--full only: a plain run writes no detail record)
+        rec["detail"] = full["detail_files"]
     rec = _sig(rec)
     line = json.dumps(rec, separators=(",", ":"))
     # never let an unforeseen string push the record past what the driver keeps: drop digests, least important first
@@ -192,6 +225,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(spawn_ranks(a))
     rank = int(os.environ.get("RANK", "0"))
@@ -362,9 +397,11 @@ def main():
     ms_per_step = 1e3 * elapsed / a.steps
     iters_done = float(np.mean(table[:, 14])) if rank == 0 else 0.0      # only rank 0 holds the gathered table
     value = total * iters_done / (ms_per_step * 1e-3)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"results": table})                  # what the caller of the timed step received in its last step
 
     strong = None
-    if a.exec_ == "device" and a.solver == "lm6" and not a.no_configs:           # every rank takes part
+    if a.full and a.exec_ == "device" and a.solver == "lm6" and not a.no_configs:           # every rank takes part
         strong = strong_scaling_config4(capi, synth, batchmod, a, rank, world, local_rank, dev, forced, dist, torch)
 
     out = None
@@ -390,33 +427,35 @@ def main():
                         f"bytes a fused kernel never moves); frac_physical: bytes through the fabric per launch (PMC passes) / kernel time / 8 TB/s; "
                         f"frac_must_move: {mm} B per point-evaluation (point constants + taps only)"})
             launch_digest = {k: launch[k] for k in ("workgroups", "span_us", "mean_workgroup_us", "covered", "tail_idle_us")}
-        # north_star's two streaming kernels, each on its own and COLD (1 GiB streamed through the caches in front of every repetition:
-        # eds_trk_bench_kernel_cold) — back to back the reduction reads planes the previous kernel just left in the Infinity Cache
-        rj_ms = h.bench_kernel_cold(0, B, ncols=6, which=0, reps=10)
-        red_ms = h.bench_kernel_cold(0, B, ncols=6, which=1, reps=10)
-        rj_warm_ms = h.bench_eval(0, B, ncols=6, with_reduction=False, reps=20)
-        both_ms = h.bench_eval(0, B, ncols=6, with_reduction=True, reps=20)
-        roof_rj = roofline_block("eds_resjac_kernel" + ("<0" if a.sampling == "bicubic" else "<1"), rj_ms, B * N, BYTES_RESJAC[a.sampling],
-                                 BYTES_RESJAC[a.sampling], a, extra={"point_evals_per_s": B * N / (rj_ms * 1e-3), "kernel_ms_back_to_back": rj_warm_ms,
-                                                                      "resjac_plus_reduce_ms_back_to_back": both_ms,
-                                                                      "note": f"stand-alone residual/Jacobian pass, cold; credit = must-move = {BYTES_RESJAC[a.sampling]} B per point "
-                                                                              "(it does write r and J)"})
-        roof_rj["kernel"] = "eds_resjac_kernel"
-        roof_red = roofline_block("eds_reduce_kernel", red_ms, B * N, BYTES_REDUCE, BYTES_REDUCE, a, extra={
-            "kernel_ms_behind_resjac": max(both_ms - rj_warm_ms, 1e-6),
-            "note": f"{BYTES_REDUCE} B per point read once (r + six Jacobian planes, 16-byte loads, four points per lane), COLD: the planes are evicted in front "
-                    "of every repetition; kernel_ms_behind_resjac = (resjac + reduce) - resjac back to back, where the Infinity Cache still holds what the "
-                    "first kernel wrote"})
-        roof_red["kernel"] = "eds_reduce_kernel<6, 4>"
-        # what this box's HBM really streams ("confirm on the box ... and report the measured peak beside the nominal"): the
-        # library's own plain stream kernel over 1 GiB (16 bytes per lane, grid-stride; csrc/eds_capi_solve.hip: eds_probe_kernel)
-        try:
-            hbm_probe = dict(h.hbm_probe(1 << 30, 10), note="library's own stream kernel over 1 GiB, 10 repetitions under HIP events on its stream: read-only pass, "
-                                                            "and copy with read + write counted; nominal peak 8 000 GB/s, the guide's achievable ~6 300")
-        except Exception as ex_:                     # never fail the bench over the probe
-            hbm_probe = {"error": str(ex_)}
-        if roof is None:
-            roof = roof_rj
+        roof_rj = roof_red = hbm_probe = None
+        if a.full:
+            # the unfused path's two streaming kernels, each on its own and COLD (1 GiB streamed through the caches in front of every repetition:
+            # eds_trk_bench_kernel_cold) — back to back the reduction reads planes the previous kernel just left in the Infinity Cache
+            rj_ms = h.bench_kernel_cold(0, B, ncols=6, which=0, reps=10)
+            red_ms = h.bench_kernel_cold(0, B, ncols=6, which=1, reps=10)
+            rj_warm_ms = h.bench_eval(0, B, ncols=6, with_reduction=False, reps=20)
+            both_ms = h.bench_eval(0, B, ncols=6, with_reduction=True, reps=20)
+            roof_rj = roofline_block("eds_resjac_kernel" + ("<0" if a.sampling == "bicubic" else "<1"), rj_ms, B * N, BYTES_RESJAC[a.sampling],
+                                     BYTES_RESJAC[a.sampling], a, extra={"point_evals_per_s": B * N / (rj_ms * 1e-3), "kernel_ms_back_to_back": rj_warm_ms,
+                                                                          "resjac_plus_reduce_ms_back_to_back": both_ms,
+                                                                          "note": f"stand-alone residual/Jacobian pass, cold; credit = must-move = {BYTES_RESJAC[a.sampling]} B per point "
+                                                                                  "(it does write r and J)"})
+            roof_rj["kernel"] = "eds_resjac_kernel"
+            roof_red = roofline_block("eds_reduce_kernel", red_ms, B * N, BYTES_REDUCE, BYTES_REDUCE, a, extra={
+                "kernel_ms_behind_resjac": max(both_ms - rj_warm_ms, 1e-6),
+                "note": f"{BYTES_REDUCE} B per point read once (r + six Jacobian planes, 16-byte loads, four points per lane), COLD: the planes are evicted in front "
+                        "of every repetition; kernel_ms_behind_resjac = (resjac + reduce) - resjac back to back, where the Infinity Cache still holds what the "
+                        "first kernel wrote"})
+            roof_red["kernel"] = "eds_reduce_kernel<6, 4>"
+            # what this box's HBM really streams ("confirm on the box ... and report the measured peak beside the nominal"): the
+            # library's own plain stream kernel over 1 GiB (16 bytes per lane, grid-stride; csrc/eds_capi_solve.hip: eds_probe_kernel)
+            try:
+                hbm_probe = dict(h.hbm_probe(1 << 30, 10), note="library's own stream kernel over 1 GiB, 10 repetitions under HIP events on its stream: read-only pass, "
+                                                                "and copy with read + write counted; nominal peak 8 000 GB/s, ~6 300 achievable")
+            except Exception as ex_:                     # never fail the bench over the probe
+                hbm_probe = {"error": str(ex_)}
+            if roof is None:
+                roof = roof_rj
         pose_err = float(np.median([np.linalg.norm(table[b, 0:3] - als[b % distinct].p_true) for b in range(min(B, distinct))]))
         out = {
             "metric": "tracker_iterations_per_sec", "value": value, "unit": "iterations/s", "n_gpus": world,
@@ -431,9 +470,10 @@ def main():
             "point_evals_per_s_in_solver": total * N * passes / (ms_per_step * 1e-3),
             "iterations_per_alignment": iters_done, "success_fraction": float(np.mean(table[:, 15])),
             "median_translation_error": pose_err,
-            "roofline": roof, "roofline_resjac": roof_rj, "roofline_reduce": roof_red, "hbm_probe": hbm_probe,
-            "input_generation_s": t_gen,
+            "roofline": roof, "input_generation_s": t_gen,
         }
+        if a.full:
+            out.update(roofline_resjac=roof_rj, roofline_reduce=roof_red, hbm_probe=hbm_probe)
         h.set_knob("EDS_FUSED_LAYOUT", None)             # the library's own layout rule again from here on
         if a.exec_ == "device":
             out["launch_digest"] = dict(launch_digest, note="the timed kernel's last launch, from its workgroups' own begin / end stamps: covered = sum of "
@@ -442,7 +482,7 @@ def main():
             out["strong_scaling_config4"] = strong
         if forced:
             out["forced_dist"] = True
-        if world == 1:
+        if world == 1 and a.full:
             ctx = types.SimpleNamespace(h=h, a=a, cfg=cfg, B=B, N=N, H=H, W=W, p0=p0, q0=q0, v0=v0, als=als, frames32=frames32, distinct=distinct,
                                         table=table, passes=passes)
             if a.exec_ == "device" and N <= 2048 and not a.no_ref12:
@@ -450,7 +490,7 @@ def main():
                 out["reference_problem"] = ref12_leg(capi, ctx, "tiles")
             detail_legs(capi, synth, ctx, out)
     h.close()
-    if rank == 0:
+    if rank == 0 and a.full:
         # ---- parity of the timed batch against the CPU oracle (the checker, outside every timed region) ---------------------------
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle as po
@@ -483,7 +523,8 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        out["detail_files"] = write_detail(out) or ["(bench_detail.json could not be written)"]
+        if a.full:
+            out["detail_files"] = write_detail(out) or ["(bench_detail.json could not be written)"]
         rec, line = compact_record(out)
         # RCCL prints its version banner through C stdio, which is flushed when the process exits — behind anything Python printed.
         # The JSON line has to be the LAST line on stdout: empty the C buffers first.
@@ -493,10 +534,11 @@ def main():
         except Exception:
             pass
         sys.stdout.flush()
-        sys.stderr.write(f"[bench] full record: {', '.join(out['detail_files'])} ({len(json.dumps(out))} bytes); compact line {len(line)} bytes\n")
+        if a.full:
+            sys.stderr.write(f"[bench] full record: {', '.join(out['detail_files'])} ({len(json.dumps(out))} bytes); compact line {len(line)} bytes\n")
         sys.stderr.flush()
         print(line, flush=True)
-        if not (out["parity_max_se3"] <= PARITY_TOL) or out["parity"]["iteration_count_mismatches"]:
+        if a.full and (not (out["parity_max_se3"] <= PARITY_TOL) or out["parity"]["iteration_count_mismatches"]):
             sys.stderr.write(f"bench.py: PARITY FAILURE: max SE(3) distance to the oracle {out['parity_max_se3']:.3e} (tolerance {PARITY_TOL}), "
                              f"{out['parity']['iteration_count_mismatches']} iteration-count mismatches\n")
             sys.exit(3)

@@ -138,3 +138,49 @@ def test_every_leg_of_the_record_has_committed_pmc_passes():
     # the headline's own passes, and the reference problem's kernel of this round
     t = json.load(open(os.path.join(ROOT, "profiles", newest)))
     assert any(k.startswith("eds_fused6_kernel<0, 4, 512, 1, 1") for k in t["kernels"]) and any("256, 736" in k for k in t["kernels"])
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain run (`--gpus 1 --steps N --warmup W`) times the headline only; everything beside it waits for `--full`.  `--steps` is
+    the number of timed steps, and a run that would time none is refused before any GPU call."""
+    b = _load_bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = b.parse(["--full", "--dump-outputs", "out_dir"])
+    assert a.full is True and a.dump_outputs == "out_dir"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0"], capture_output=True, text=True, env=_env(), timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr and '"n_gpus"' not in r.stdout
+
+
+def test_compact_record_of_a_plain_run_keeps_the_contract_keys():
+    """A plain run's record has no CPU baseline, parity or leg digests: its line still carries the contract's keys, the timed kernel's
+    roofline, and no pointer to a detail file it did not write."""
+    import json
+    b = _load_bench()
+    full = json.load(open(os.path.join(ROOT, "tests", "golden", "bench_full_record.json")))
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                                  "dtype", "data", "config", "roofline")}
+    _, line = b.compact_record(plain)
+    back = json.loads(line)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in back, k
+    assert back["metric"] == "tracker_iterations_per_sec" and back["higher_is_better"] is True and back["ms_per_step"] > 0
+    assert "detail" not in back and "cpu_baseline" not in back and "parity_max_se3" not in back
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_sample_under_the_limit(tmp_path):
+    """--dump-outputs: DIR/<name>.npy in float64; an output over the size limit becomes the same seeded sample of its rows every time."""
+    import numpy as np
+    b = _load_bench()
+    table = np.arange(4096 * 16, dtype=np.float64).reshape(4096, 16)
+    b.dump_outputs(str(tmp_path / "d"), {"results": table})
+    back = np.load(tmp_path / "d" / "results.npy")
+    assert back.dtype == np.float64 and np.array_equal(back, table)
+    limit = 1000 * 16 * 8
+    b.dump_outputs(str(tmp_path / "s1"), {"results": table}, limit=limit)
+    b.dump_outputs(str(tmp_path / "s2"), {"results": table}, limit=limit)
+    s1, s2 = np.load(tmp_path / "s1" / "results.npy"), np.load(tmp_path / "s2" / "results.npy")
+    assert s1.nbytes <= limit and s1.shape == (1000, 16) and np.array_equal(s1, s2)
+    rows = (s1[:, 0] // 16).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, table[rows])
+    assert b.DUMP_LIMIT == 64 << 20

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 TAG=${1:-r04}
 OUT=$R/gpurun_out/sq_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-ARGS="--steps 3 --warmup 2 --no-cpu --no-shared --no-configs --distinct 256 --gen-workers 0"
+ARGS="--full --steps 3 --warmup 2 --no-cpu --no-shared --no-configs --distinct 256 --gen-workers 0"
 cd /tmp
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d "$OUT/p1" --output-format csv -- python3 $R/bench.py $ARGS > "$OUT/b1.json" 2> "$OUT/b1.err"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU -d "$OUT/p2" --output-format csv -- python3 $R/bench.py $ARGS > "$OUT/b2.json" 2> "$OUT/b2.err"
