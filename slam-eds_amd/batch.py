@@ -155,6 +155,18 @@ class BatchTracker:
         if self.count > 0:
             self.handle.optimize_batch(level, 0, self.count, sync=sync)
 
+    def update_depth(self, coords=None, xy=None, kf_xy=None, T_kf_ef=None, init=None) -> list:
+        """Optional step after solve(): DepthPoints::update of this shard's seeds on the device (include/eds_hip_depth.h), by default
+        from getCoord's re-projection at the solved poses, so the next solve reads the filtered depths with no upload.  `init`: keyword
+        arguments of Handle.depth_init, to seed the shard first (a new keyframe).  Returns the per-alignment summaries."""
+        if self.count == 0:
+            return []
+        capi = self.capi
+        if init is not None:
+            self.handle.depth_init(0, self.count, **init)
+        coords = capi.DEPTH_REPROJECT if coords is None else coords
+        return self.handle.depth_update(0, self.count, coords, xy=xy, kf_xy=kf_xy, T_kf_ef=T_kf_ef)
+
     def local_results(self) -> np.ndarray:
         if self.count == 0:
             return np.zeros((0, RESULT_WIDTH))

@@ -47,6 +47,16 @@ EXPORTS = (
     "eds_pyr_get_residuals", "eds_pyr_create_batch", "eds_pyr_set_keyframe_slot", "eds_pyr_set_event_frame_slot", "eds_pyr_optimize_batch",
 )
 
+# every symbol include/eds_hip_depth.h declares: the inverse-depth filter (its own header and ABI version; EXPORTS stays eds_hip.h's)
+DEPTH_EXPORTS = (
+    "eds_depth_abi_version", "eds_depth_params_default", "eds_depth_init", "eds_depth_update", "eds_depth_get", "eds_depth_set",
+    "eds_depth_get_idepth", "eds_depth_stats",
+)
+# enums of include/eds_hip_depth.h
+DEPTH_INIT_CONSTANT, DEPTH_INIT_HOST, DEPTH_INIT_PLANE = 0, 1, 2
+DEPTH_TRACKS, DEPTH_EF_COORD, DEPTH_REPROJECT = 0, 1, 2
+DEPTH_VOGIATZIS, DEPTH_GAUSS = 0, 1
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -56,6 +66,21 @@ class KfSelect(C.Structure):
     """``eds_kf_select`` — the arguments of KeyFrame::create that steer the point set-up (KeyFrame.cpp:333-341)."""
     _fields_ = [("method", C.c_int32), ("cell", C.c_int32), ("num_points", C.c_int32), ("sobel_ksize", C.c_int32),
                 ("min_depth", C.c_double), ("max_depth", C.c_double), ("weight_threshold", C.c_double)]
+
+
+class DepthParams(C.Structure):
+    """``eds_depth_params`` — DepthPoints::init's scalars (DepthPoints.hpp:60-75)."""
+    _fields_ = [("min_depth", C.c_double), ("max_depth", C.c_double), ("threshold", C.c_double), ("init_a", C.c_double),
+                ("init_b", C.c_double)]
+
+
+class DepthSummary(C.Structure):
+    """``eds_depth_summary`` — what one eds_depth_update did to one alignment."""
+    _fields_ = [("updated", C.c_int32), ("skipped_nan", C.c_int32), ("sigma2_restored", C.c_int32), ("mu_reset", C.c_int32),
+                ("converged", C.c_int32), ("pad_", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
 class Cfg(C.Structure):
@@ -118,6 +143,7 @@ def build(force: bool = False) -> str:
     """Compile libeds_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_depth.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
@@ -228,6 +254,14 @@ def lib():
         L.eds_trk_set_knob.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.eds_trk_get_strips_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), _ip, _ip]
         L.eds_pyr_get_residuals.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.eds_depth_params_default.argtypes = [C.POINTER(DepthParams)]
+        L.eds_depth_params_default.restype = None
+        L.eds_depth_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(DepthParams), C.c_int, _dp, C.c_int]
+        L.eds_depth_update.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, C.POINTER(DepthSummary)]
+        L.eds_depth_get.argtypes = [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_uint8)]
+        L.eds_depth_set.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.eds_depth_get_idepth.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.eds_depth_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
         if L.eds_trk_cfg_size() != C.sizeof(Cfg) or L.eds_trk_info_size() != C.sizeof(Info):
             raise EdsError(ERR_INVALID, "ctypes struct layout disagrees with include/eds_hip.h")
         _lib = L
@@ -249,6 +283,21 @@ def _f64(a):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(_dp)
+
+
+def _rows(a, count, width):
+    """per-slot rows -> (contiguous count x stride [x width] float64 array, stride): an array is taken as it is, a list of
+    per-slot arrays of different lengths is padded to the longest"""
+    if isinstance(a, (list, tuple)):
+        stride = max(1, max(len(r) for r in a))
+        t = np.zeros((count, stride) + ((width,) if width > 1 else ()))
+        for b, r in enumerate(a):
+            t[b, :len(r)] = r
+        return t, stride
+    t = _f64(a)
+    if t.ndim == (1 if width == 1 else 2):
+        t = t[None]
+    return np.ascontiguousarray(t), int(t.shape[1])
 
 
 def default_config(**kw) -> Cfg:
@@ -556,6 +605,59 @@ class Handle:
             self._N[first + b] = int(n[b])
             out.append(dict(coord=coord[b, :n[b]] if want_points else None, tracks=tracks[b, :n[b]] if want_points else None,
                             kept=kept[b, :n[b]] if want_points else None, mean_sq_flow=float(flow[b]), n=int(n[b])))
+        return out
+
+    # -- inverse-depth filter (include/eds_hip_depth.h) -----------------------------------------
+    def depth_init(self, first=0, count=None, source=DEPTH_INIT_CONSTANT, idp=None, min_depth=1.0, max_depth=3.0, threshold=100.0,
+                   init_a=2.0, init_b=5.0):
+        """DepthPoints::init for slots first .. first + count - 1.  idp (DEPTH_INIT_HOST): one row of inverse depths per slot
+        (count x stride array, or a list of per-slot vectors)."""
+        count = self.batch - first if count is None else count
+        prm = DepthParams(float(min_depth), float(max_depth), float(threshold), float(init_a), float(init_b))
+        t, stride = (None, 1) if idp is None else _rows(idp, count, 1)
+        _check(lib().eds_depth_init(self._h, int(first), int(count), C.byref(prm), int(source), _p(t), int(stride)))
+
+    def depth_update(self, first=0, count=None, coords=DEPTH_REPROJECT, xy=None, kf_xy=None, T_kf_ef=None, filter=DEPTH_VOGIATZIS):
+        """DepthPoints::update for slots first .. first + count - 1.  xy / kf_xy: per slot N x 2 pixels (a count x stride x 2 array or a
+        list of N x 2 arrays); T_kf_ef: count x 7 (p, q_xyzw) or None (the inverse of each slot's pose).  Returns the summaries."""
+        count = self.batch - first if count is None else count
+        stride = 1
+        a = b = None
+        if xy is not None:
+            a, stride = _rows(xy, count, 2)
+        if kf_xy is not None:
+            b, stride2 = _rows(kf_xy, count, 2)
+            if a is not None and stride2 != stride:
+                raise EdsError(ERR_INVALID, "xy and kf_xy have different strides")
+            stride = stride2
+        T = None if T_kf_ef is None else _f64(T_kf_ef).reshape(count, 7)
+        out = (DepthSummary * count)()
+        _check(lib().eds_depth_update(self._h, int(first), int(count), int(coords), _p(a), _p(b), int(stride), _p(T), int(filter), out))
+        return [o.as_dict() for o in out]
+
+    def depth_get(self, slot):
+        """the seeds of a slot: (N x 4 [mu, sigma2, a, b], N converged flags)"""
+        N = self._N[slot]
+        seeds, conv = np.zeros((N, 4)), np.zeros(N, dtype=np.uint8)
+        _check(lib().eds_depth_get(self._h, int(slot), _p(seeds), conv.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return seeds, conv.astype(bool)
+
+    def depth_set(self, slot, seeds):
+        s = _f64(seeds)
+        if s.shape != (self._N[slot], 4):
+            raise EdsError(ERR_INVALID, "seeds must be N x 4")
+        _check(lib().eds_depth_set(self._h, int(slot), _p(s)))
+
+    def depth_get_idepth(self, slot):
+        mu = np.zeros(self._N[slot])
+        _check(lib().eds_depth_get_idepth(self._h, int(slot), _p(mu)))
+        return mu
+
+    def depth_stats(self, first=0, count=None):
+        """count x 4: mean, "std_dev" (the n-1 variance), median (n/2-th), "third_q" (n/3-th) of mu"""
+        count = self.batch - first if count is None else count
+        out = np.zeros((count, 4))
+        _check(lib().eds_depth_stats(self._h, int(first), int(count), _p(out)))
         return out
 
     # -- keyframe set-up on the device ------------------------------------------------------

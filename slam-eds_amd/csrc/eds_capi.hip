@@ -102,6 +102,7 @@ void free_all(eds_trk* h) {
     eds_strips_free(h);
     eds_frame_free(&h->frame_build);
     eds_points_free(&h->point_ops);
+    eds_depth_free(&h->depth);
     eds_keyframe_free(&h->kf_build);
     void* hptrs[] = {h->h_pose, h->h_part, h->h_G, h->h_f32, h->h_r, h->h_fstage, h->h_rmap, h->h_idp, h->h_fprog, h->h_bstage};
     for (hipEvent_t e : h->ev_bstage) hipEventDestroy(e);
@@ -546,7 +547,7 @@ int eds_trk_update_points(eds_trk* h, int slot, int delete_out_points, double* c
         s.residuals.clear();
         s.res_on_device = false;
         if (n > 0 && (rc = refresh_gram(h, slot))) return rc;
-        if (n == 0) s.has_kf = false;
+        if (n == 0) { s.has_kf = false; s.seeded = false; }     // (the seeds were compacted with the planes: eds_points_update)
     }
     return EDS_OK;
 }
@@ -574,7 +575,7 @@ int eds_trk_update_points_batch(eds_trk* h, int first, int count, int delete_out
             s.residuals.clear();
             s.res_on_device = false;
             if (n[b] > 0) { if ((rc = refresh_gram(h, first + b, false))) return rc; any = true; }
-            else s.has_kf = false;
+            else { s.has_kf = false; s.seeded = false; }
         }
     }
     if (any) { EDS_HIP_TRY(hipStreamSynchronize(h->st)); h->gram_pending = false; }

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/eds_hip.h"
+#include "eds_depth.hpp"
 #include "eds_fused.hpp"
 #include "eds_kernels.hpp"
 #include "eds_launch_rule.hpp"
@@ -33,6 +34,9 @@ struct Slot {
     bool res_on_device = false;     // residuals of the last solve still only in HBM
     bool res_in_hostmap = false;    // ... and mirrored in the handle's pinned h_rmap by the kernel that produced them (small launches)
     bool trace_on_device = false;   // trace of the last solve still only in HBM
+    // inverse-depth filter (include/eds_hip_depth.h): DepthPoints' scalars of this slot's seeds; set_keyframe / build_keyframe unseed
+    bool seeded = false;
+    double dp_mu_range = 0.0, dp_px_error_angle = 0.0, dp_threshold = 0.0;
 };
 
 
@@ -57,6 +61,7 @@ struct eds_trk {
     EdsFusedBuffers fused;
     EdsFrameBuffers frame_build;
     EdsPointBuffers point_ops;
+    EdsDepthBuffers depth;
     EdsKeyframeBuffers kf_build;
     // pinned host staging
     double *h_pose = nullptr, *h_part = nullptr, *h_G = nullptr;

@@ -37,9 +37,10 @@ __device__ __forceinline__ bool decode_wg(int first, int count, int nchunk, int&
 // new_rho (optional): the slot's inverse depths as the host just narrowed them into device-mapped pinned memory (set_idepth on the live
 // path: Tracker.cpp:167 re-reads the depths on every optimize) — every block stores its own points' values into the rho plane on its
 // way, block 0 the padding as well: the depth refresh is ONE launch, no copy call.
-__global__ __launch_bounds__(EDS_TPB) void eds_gram_kernel(EdsArrays A, int slot, const float* __restrict__ new_rho) {
-    // grid.x = residual block index k; fp64 accumulation of the 21 unique products
-    const int k = blockIdx.x;
+// (one workgroup = residual block k of `slot`: the body of eds_gram_kernel and of its batched form eds_gram_batch_kernel — one
+// arithmetic, so a slot's Gram matrices come out bit-identical whichever launched it)
+__device__ __forceinline__ void gram_block(const EdsArrays& A, int slot, int k, const float* __restrict__ new_rho) {
+    // fp64 accumulation of the 21 unique products
     const double* pb = A.pose + (size_t)slot * EDS_POSE_STRIDE;
     const int N = (int)pb[EDS_PB_N], nb = (int)pb[EDS_PB_NB], ne = (int)pb[EDS_PB_NE];
     const int start = k * ne;
@@ -78,6 +79,13 @@ __global__ __launch_bounds__(EDS_TPB) void eds_gram_kernel(EdsArrays A, int slot
         for (int p = 0; p < 6; ++p)
             for (int q = p; q < 6; ++q) { G[6 * p + q] = sh[0][c]; G[6 * q + p] = sh[0][c]; ++c; }
     }
+}
+__global__ __launch_bounds__(EDS_TPB) void eds_gram_kernel(EdsArrays A, int slot, const float* __restrict__ new_rho) {
+    gram_block(A, slot, blockIdx.x, new_rho);       // grid.x = residual block index k
+}
+// slots first .. first + count - 1 in one launch over a (nb, count) grid, from the rho planes as they are (eds_depth.hip writes them)
+__global__ __launch_bounds__(EDS_TPB) void eds_gram_batch_kernel(EdsArrays A, int first, int nb) {
+    gram_block(A, first + (int)(blockIdx.x / nb), (int)(blockIdx.x % nb), nullptr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -341,6 +349,9 @@ static inline int grid_for(int count, int per_slot) { return ((count + 7) / 8) *
 
 void eds_launch_gram(const EdsArrays& A, int slot, int nb, hipStream_t st, const float* new_rho) {
     hipLaunchKernelGGL(eds_gram_kernel, dim3(nb), dim3(EDS_TPB), 0, st, A, slot, new_rho);
+}
+void eds_launch_gram_batch(const EdsArrays& A, int first, int count, int nb, hipStream_t st) {
+    hipLaunchKernelGGL(eds_gram_batch_kernel, dim3((unsigned)nb * (unsigned)count), dim3(EDS_TPB), 0, st, A, first, nb);
 }
 void eds_launch_model(const EdsArrays& A, int first, int count, int nchunk, hipStream_t st) {
     hipLaunchKernelGGL(eds_model_kernel, dim3(grid_for(count, nchunk)), dim3(EDS_TPB), 0, st, A, first, count, nchunk);

@@ -39,6 +39,8 @@ struct EdsArrays {
 #define EDS_DONE_WORDS 32          // workgroups per alignment at most: teams x candidate groups (4 x 8, 8 x 4, 16 x 1)
 
 void eds_launch_gram(const EdsArrays& A, int slot, int nb, hipStream_t st, const float* new_rho = nullptr);
+// the same for slots first .. first + count - 1 in ONE launch (nb x count workgroups), each from its rho plane as it is
+void eds_launch_gram_batch(const EdsArrays& A, int first, int count, int nb, hipStream_t st);
 void eds_launch_model(const EdsArrays& A, int first, int count, int nchunk, hipStream_t st);
 void eds_launch_resjac(const EdsArrays& A, int sampling, int ncols, int first, int count, int nchunk, hipStream_t st);
 // PhotometricErrorNC (reference PhotometricErrorNC.hpp:124-192): block statistics of the sampled brightness, then the

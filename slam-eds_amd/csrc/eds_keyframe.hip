@@ -552,6 +552,7 @@ int eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int 
     s.N = N; s.K[0] = fx; s.K[1] = fy; s.K[2] = cx; s.K[3] = cy;
     if ((rc = eds_internal_refresh_gram(h, slot))) return rc;
     s.has_kf = true;
+    s.seeded = false;                       // as eds_trk_set_keyframe
     s.residuals.clear();
     s.res_on_device = false; s.trace_on_device = false; s.ntrace = 0;     // as eds_trk_set_keyframe
     kb.last_slot = slot;
