@@ -337,7 +337,7 @@ void eds_kf_select_default(eds_kf_select* sel);
 /* Replaces the tracker-facing part of KeyFrame::create (reference src/tracking/KeyFrame.cpp:333-463): grayscale image
  * (H x W of the handle, row-major, already undistorted) -> [0,1] -> log(img + 0.2) -> Sobel 3x3 -> gradient magnitude ->
  * per-cell point selection -> norm_coord, grad -> nearest depth-map point (n_depth points depth_xy (n x 2, pixels) with
- * inverse depth depth_idp; n_depth = 0: constant initial depth) -> weights -> cleanPoints.  The surviving points go
+ * inverse depth depth_idp; n_depth = 0: constant initial depth; found as the reference's k-d tree finds it, ties included) -> weights -> cleanPoints.  The surviving points go
  * straight into slot `slot` as by eds_trk_set_keyframe (same order as the reference pushes them); *n_points receives
  * their number (also when it exceeds the handle's max_points, which is an error). */
 int eds_trk_build_keyframe(eds_trk* h, int slot, int img_type, const void* img, const eds_kf_select* sel, int n_depth,

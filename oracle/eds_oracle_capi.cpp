@@ -4,11 +4,57 @@
 #include "eds_oracle.hpp"
 #include "eds_cpu_fast.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <limits>
+#include <numeric>
 #include <thread>
+#include <vector>
 
 using namespace eds_oracle;
+
+// KeyFrame::setDepthMap's nearest depth-map point (KeyFrame.cpp:1151-1158) through the reference's k-d tree (src/utils/KDTree.hpp),
+// restated node by node: build (:187-205) splits at mid = (n - 1) / 2 with std::nth_element on axis depth % 2; nnSearch (:263-284)
+// visits a node, replaces the guess on a strict < of the sqrt distance, recurses near side first, then the far side when
+// fabs(diff) < minDist.  A tie's winner is the first in that traversal; the tree's shape comes from libstdc++'s nth_element.
+namespace {
+struct KdTree {
+    struct Node { int idx = -1, axis = -1, next[2] = {-1, -1}; };
+    const double* xy;
+    std::vector<Node> nodes;
+    int build(int* idx, int n, int depth) {
+        if (n <= 0) return -1;
+        const int axis = depth % 2, mid = (n - 1) / 2;
+        std::nth_element(idx, idx + mid, idx + n, [&](int l, int r) { return xy[2 * (size_t)l + axis] < xy[2 * (size_t)r + axis]; });
+        const int id = (int)nodes.size();
+        nodes.push_back(Node());
+        nodes[id].idx = idx[mid]; nodes[id].axis = axis;
+        const int left = build(idx, mid, depth + 1);
+        const int right = build(idx + mid + 1, n - mid - 1, depth + 1);
+        nodes[id].next[0] = left; nodes[id].next[1] = right;
+        return id;
+    }
+    void search(const double* q, int node, int* guess, double* min_dist) const {
+        if (node < 0) return;
+        const Node& nd = nodes[node];
+        const double* t = xy + 2 * (size_t)nd.idx;
+        const double dist = distance(q, t);
+        if (dist < *min_dist) { *min_dist = dist; *guess = nd.idx; }
+        const int dir = q[nd.axis] < t[nd.axis] ? 0 : 1;
+        search(q, nd.next[dir], guess, min_dist);
+        const double diff = std::fabs(q[nd.axis] - t[nd.axis]);
+        if (diff < *min_dist) search(q, nd.next[!dir], guess, min_dist);
+    }
+    // (:253-259) every product and sum rounded on its own, as the reference's build (C++14, no -march) has no FMA: this library is
+    // built with -march=x86-64-v3, where GCC would contract them
+    __attribute__((noinline, optimize("fp-contract=off"))) static double distance(const double* p, const double* q) {
+        double dist = 0;
+        for (int i = 0; i < 2; i++) dist += (p[i] - q[i]) * (p[i] - q[i]);
+        return std::sqrt(dist);
+    }
+};
+}  // namespace
 
 extern "C" {
 
@@ -227,5 +273,21 @@ void eds_oracle_se3_log(const double* t, const double* q, double* xi) { se3_log(
 void eds_oracle_se3_left_update(const double* xi, double* t, double* q) { se3_left_update(xi, t, q); }
 double eds_oracle_se3_distance(const double* ta, const double* qa, const double* tb, const double* qb) { return se3_distance(ta, qa, tb, qb); }
 void eds_oracle_loss_eval(int type, double a, double s, double* rho3) { loss_eval(type, a, s, rho3); }
+
+// nearest of m depth-map points (xy: m x 2) for each of n queries (q: n x 2): nnSearch's index and minDist
+void eds_oracle_kdtree_nn(const double* xy, int m, const double* q, int n, int32_t* idx, double* min_dist) {
+    KdTree t;
+    t.xy = xy;
+    t.nodes.reserve(m);
+    std::vector<int> perm(m);
+    std::iota(perm.begin(), perm.end(), 0);
+    const int root = t.build(perm.data(), m, 0);
+    for (int i = 0; i < n; ++i) {
+        int guess = -1;
+        double best = std::numeric_limits<double>::max();
+        t.search(q + 2 * (size_t)i, root, &guess, &best);
+        idx[i] = guess; min_dist[i] = best;
+    }
+}
 
 }  // extern "C"

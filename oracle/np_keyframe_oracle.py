@@ -11,7 +11,8 @@ numpy restatement of what the reference does once per keyframe with OpenCV:
 
 PARITY UNPINNED: OpenCV is not available here and the reference has no tests; cv::Sobel (ksize 3, CV_64F,
 BORDER_REFLECT_101 default), cv::log, cv::minMaxLoc (first extremum in row-major order) and cv::cartToPolar
-(sqrt(x^2 + y^2)) are restated from their documented behaviour.
+(sqrt(x^2 + y^2)) are restated from their documented behaviour.  The depth association is pinned: it is the reference's own k-d
+tree (src/utils/KDTree.hpp), restated in the oracle library and compared with the real one (tests/test_kdtree_pin.py).
 """
 import numpy as np
 
@@ -152,18 +153,18 @@ def candidate_points(mag, cell=20, method=MEDIAN, num_points=0):
 
 
 def set_depth_map(coord, depth_xy, depth_idp, min_depth, max_depth):
-    """KeyFrame.cpp:1137-1198: idp of the nearest depth-map point and weight 1 - (d - min)/(max - min).
-    Exact ties in distance resolve to the lowest depth-map index (the reference's KD-tree order is unspecified)."""
+    """KeyFrame.cpp:1137-1198: idp of the nearest depth-map point and weight 1 - (d - min)/(max - min), d = cv::norm to that point.
+    The nearest point is the one the reference's k-d tree (src/utils/KDTree.hpp) returns: the oracle library restates its build
+    (std::nth_element at (n - 1)/2, axis depth % 2) and its search (near side first, strict < of the sqrt distance), so an exact tie
+    goes to the first point of the tree's traversal.  The tree's shape follows libstdc++'s nth_element; tests/test_kdtree_pin.py pins
+    it against the reference's own tree."""
+    import pyoracle
     n = len(coord)
     if depth_xy is None or len(depth_xy) == 0:
         return np.full(n, 1.0 / ((max_depth - min_depth) / 2.0)), np.ones(n)
     depth_xy = np.asarray(depth_xy, dtype=np.float64)
     c = np.asarray(coord, dtype=np.float64)
-    idx = np.empty(n, dtype=np.int64)
-    for s in range(0, n, 2048):                              # brute force, chunked
-        dx = c[s:s + 2048, None, 0] - depth_xy[None, :, 0]
-        dy = c[s:s + 2048, None, 1] - depth_xy[None, :, 1]
-        idx[s:s + 2048] = np.argmin(dx * dx + dy * dy, axis=1)
+    idx, _ = pyoracle.kdtree_nn(depth_xy, c)
     dx = depth_xy[idx, 0] - c[:, 0]
     dy = depth_xy[idx, 1] - c[:, 1]
     dist = np.sqrt(dx * dx + dy * dy)

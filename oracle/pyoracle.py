@@ -257,6 +257,17 @@ def unit_plus_jacobian(v):
     return J
 
 
+def kdtree_nn(depth_xy, queries):
+    """The nearest depth-map point of every query as the reference's k-d tree finds it (KeyFrame.cpp:1151-1158, KDTree.hpp):
+    (int64 index into depth_xy, float64 minDist).  Ties go to the first point of the tree's traversal, not the lowest index."""
+    d, q = _f64(depth_xy).reshape(-1, 2), _f64(queries).reshape(-1, 2)
+    if len(d) == 0:
+        raise ValueError("empty depth map")
+    idx, dist = np.zeros(len(q), dtype=np.int32), np.zeros(len(q))
+    lib().eds_oracle_kdtree_nn(_p(d), C.c_int(len(d)), _p(q), C.c_int(len(q)), idx.ctypes.data_as(C.POINTER(C.c_int32)), _p(dist))
+    return idx.astype(np.int64), dist
+
+
 def loss_eval(loss_type, a, s):
     rho = np.zeros(3)
     lib().eds_oracle_loss_eval(int(loss_type), C.c_double(a), C.c_double(s), _p(rho))

@@ -10,10 +10,31 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DRIVER = os.path.join(os.path.dirname(HERE), "_ref", "ref_driver")
+KDTREE = os.path.join(os.path.dirname(HERE), "_ref", "kdtree_nn")
 
 
 def available() -> bool:
     return os.path.isfile(DRIVER) and os.access(DRIVER, os.X_OK)
+
+
+def kdtree_available() -> bool:
+    """oracle/_ref/kdtree_nn: the reference's KDTree.hpp, unmodified, with the reference's flags (built wherever the tree exists)."""
+    return os.path.isfile(KDTREE) and os.access(KDTREE, os.X_OK)
+
+
+def kdtree_nn(depth_xy, queries):
+    """KDTree<Point2d>(depth_xy).nnSearch(query, &minDist) for every query (KeyFrame.cpp:1151-1158): (int64 index, float64 minDist)."""
+    d = np.ascontiguousarray(depth_xy, dtype=np.float64).reshape(-1, 2)
+    q = np.ascontiguousarray(queries, dtype=np.float64).reshape(-1, 2)
+    with tempfile.TemporaryDirectory() as t:
+        cin, cout = os.path.join(t, "case.bin"), os.path.join(t, "out.bin")
+        with open(cin, "wb") as f:
+            np.array([len(d)], dtype=np.int32).tofile(f); d.tofile(f)
+            np.array([len(q)], dtype=np.int32).tofile(f); q.tofile(f)
+        subprocess.run([KDTREE, cin, cout], check=True, stdout=subprocess.DEVNULL)
+        raw = open(cout, "rb").read()
+    n = len(q)
+    return np.frombuffer(raw[:4 * n], dtype=np.int32).astype(np.int64), np.frombuffer(raw[4 * n:], dtype=np.float64).copy()
 
 
 def build() -> str:

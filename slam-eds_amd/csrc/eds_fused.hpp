@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 struct eds_trk;
 
 struct EdsFusedIn {            // start state of a slot
@@ -190,7 +192,8 @@ struct EdsKeyframeBuffers {
     double *d_log = nullptr, *d_gx = nullptr, *d_gy = nullptr, *d_mag = nullptr, *d_partial = nullptr;
     int *d_cand = nullptr, *d_cnt = nullptr, *d_off = nullptr, *d_summary = nullptr;
     double *d_coord = nullptr, *d_grad = nullptr, *d_idp = nullptr, *d_w = nullptr;   // candidates, then the cleaned points (in place)
-    double *d_dxy = nullptr, *d_didp = nullptr;                              // depth map
+    double *d_dxy = nullptr, *d_didp = nullptr;                              // depth map, in its k-d tree's order (eds_kdtree.hpp)
+    std::vector<int> h_perm; std::vector<double> h_txy, h_tidp;              // host side of the tree: permutation, gathered xy and idp
     int cap_depth = 0, last_slot = -1, last_N = 0, last_candidates = 0;
     double K[4] = {0, 0, 0, 0};
 };

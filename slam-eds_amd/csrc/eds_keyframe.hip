@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "eds_handle.hpp"
+#include "eds_kdtree.hpp"
 
 #pragma clang fp contract(off)      // sums are formed exactly as written (the oracle states the same association)
 
@@ -305,47 +306,19 @@ __global__ __launch_bounds__(KF_T) void k_emit(const int* __restrict__ cand, con
     }
 }
 
-// Nearest depth-map point of every candidate (KeyFrame.cpp:1137-1166: a brute-force search; lowest index wins exact ties).
-// Two launches: the depth points are cut into gridDim.y chunks, workgroup (x, y) finds for its 64 candidates the nearest point of
-// chunk y (points staged through LDS, fp64 like the reference); the merge walks the chunks in order with a strict <, so the
-// winner is the one a single sequential scan would have found.  (One workgroup per 256 candidates scanning all m points: 95 us
-// for 886 candidates x 3 000 points — 4 workgroups on a 256-CU chip.)
-constexpr int NN_T = 64, NN_TILE = 512;
-__global__ __launch_bounds__(NN_T) void k_nearest_part(const double* __restrict__ coord, int n, const double* __restrict__ dxy, int m, int chunk,
-                                                       double* __restrict__ pd2, int* __restrict__ pidx) {
-    __shared__ double sx[NN_TILE], sy[NN_TILE];
-    const int i = blockIdx.x * NN_T + threadIdx.x;
-    const int lo = blockIdx.y * chunk, hi = min(m, lo + chunk);
-    const double qx = i < n ? coord[2 * (size_t)i] : 0.0, qy = i < n ? coord[2 * (size_t)i + 1] : 0.0;
-    double best = INFINITY;
-    int bi = 0;
-    for (int base = lo; base < hi; base += NN_TILE) {
-        const int len = min(NN_TILE, hi - base);
-        __syncthreads();
-        for (int j = threadIdx.x; j < len; j += NN_T) { sx[j] = dxy[2 * (size_t)(base + j)]; sy[j] = dxy[2 * (size_t)(base + j) + 1]; }
-        __syncthreads();
-        for (int j = 0; j < len; ++j) {
-            const double dx = qx - sx[j], dy = qy - sy[j];
-            const double d2 = dx * dx + dy * dy;
-            if (d2 < best) { best = d2; bi = base + j; }
-        }
-    }
-    if (i < n) { pd2[(size_t)blockIdx.y * n + i] = best; pidx[(size_t)blockIdx.y * n + i] = bi; }
-}
-__global__ __launch_bounds__(KF_T) void k_nearest_merge(const double* __restrict__ coord, int n, const double* __restrict__ dxy,
-                                                        const double* __restrict__ didp, int nchunk, const double* __restrict__ pd2,
-                                                        const int* __restrict__ pidx, double* __restrict__ idp, double* __restrict__ dist) {
+// Nearest depth-map point of every candidate (KeyFrame.cpp:1137-1166): the reference's k-d tree, built on the host with
+// std::nth_element (eds_kdtree.hpp), walked here one candidate per lane with an explicit stack.  The tree's nodes come in tree order
+// (txy, tidp), so the winner's position reads its idp directly.  Distances are fp64 sqrt of separately rounded squares and sum, and a
+// strict `<` in the reference's traversal order decides: an exact tie goes to the first point of that traversal, which depends on
+// libstdc++'s nth_element (pinned for this toolchain by tests/test_kdtree_pin.py).
+__global__ __launch_bounds__(KF_T) void k_nearest_tree(const double* __restrict__ coord, int n, const double* __restrict__ txy,
+                                                       const double* __restrict__ tidp, int m, double* __restrict__ idp, double* __restrict__ dist) {
     const int i = blockIdx.x * KF_T + threadIdx.x;
     if (i >= n) return;
-    double best = INFINITY;
-    int bi = 0;
-    for (int c = 0; c < nchunk; ++c) {
-        const double d2 = pd2[(size_t)c * n + i];
-        if (d2 < best) { best = d2; bi = pidx[(size_t)c * n + i]; }
-    }
     const double qx = coord[2 * (size_t)i], qy = coord[2 * (size_t)i + 1];
-    const double dx = dxy[2 * (size_t)bi] - qx, dy = dxy[2 * (size_t)bi + 1] - qy;     // cv::norm(dist)  (:1161-1162)
-    idp[i] = didp[bi];
+    const int k = edskd::nn(txy, m, qx, qy, nullptr);
+    const double dx = txy[2 * (size_t)k] - qx, dy = txy[2 * (size_t)k + 1] - qy;      // cv::norm(dist)  (:1161-1162)
+    idp[i] = tidp[k];
     dist[i] = sqrt(dx * dx + dy * dy);
 }
 
@@ -501,8 +474,6 @@ int eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int 
         else if (img_type == 1) hipLaunchKernelGGL(k_prepare<float>, g, b, 0, st, (const float*)kb.d_src, img_H, img_W, channels, (float*)kb.d_raw, H, W);
         else hipLaunchKernelGGL(k_prepare<double>, g, b, 0, st, (const double*)kb.d_src, img_H, img_W, channels, (double*)kb.d_raw, H, W);
     }
-    if (e == hipSuccess && n_depth > 0) e = hipMemcpyAsync(kb.d_dxy, depth_xy, (size_t)n_depth * 16, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_depth > 0) e = hipMemcpyAsync(kb.d_didp, depth_idp, (size_t)n_depth * 8, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
     const int NB = 256;
     hipLaunchKernelGGL(k_minmax, dim3(NB), dim3(KF_T), 0, st, kb.d_raw, img_type, n, kb.d_partial);
@@ -514,6 +485,19 @@ int eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int 
     hipLaunchKernelGGL(k_select, dim3(ncell), dim3(KF_T), 0, st, kb.d_mag, W, cell, ncx, (int)sel->method, k_per_cell, kb.d_cand, kb.d_cnt);
     hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(KF_T), 0, st, kb.d_cnt, ncell, kb.d_off);
     hipLaunchKernelGGL(k_emit, dim3(ncell), dim3(KF_T), 0, st, kb.d_cand, kb.d_cnt, kb.d_off, cell, ncx, W, kb.d_gx, kb.d_gy, kb.d_coord, kb.d_grad);
+    // the depth map's k-d tree, built on the host while the device works on the image; uploaded in tree order
+    if (n_depth > 0) {
+        kb.h_perm.resize(n_depth); kb.h_txy.resize(2 * (size_t)n_depth); kb.h_tidp.resize(n_depth);
+        edskd::build_tree(depth_xy, n_depth, kb.h_perm.data());
+        for (int k = 0; k < n_depth; ++k) {
+            const int j = kb.h_perm[k];
+            kb.h_txy[2 * (size_t)k] = depth_xy[2 * (size_t)j]; kb.h_txy[2 * (size_t)k + 1] = depth_xy[2 * (size_t)j + 1];
+            kb.h_tidp[k] = depth_idp[j];
+        }
+        e = hipMemcpyAsync(kb.d_dxy, kb.h_txy.data(), (size_t)n_depth * 16, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(kb.d_didp, kb.h_tidp.data(), (size_t)n_depth * 8, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
+    }
     int ncand = 0;
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&ncand, kb.d_off + ncell, 4, hipMemcpyDeviceToHost, st);
@@ -522,14 +506,8 @@ int eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int 
     if (ncand < 1) return eds_internal_fail(EDS_ERR_INVALID, "the selection produced no candidate point");
     const double const_idp = 1.0 / ((sel->max_depth - sel->min_depth) / 2.0);       // KeyFrame.cpp:1189
     if (n_depth > 0) {
-        // per-chunk winners go to two planes the selection no longer needs (|grad| and the log image: n doubles each)
-        int nchunk = (int)std::min<size_t>(16, n / (size_t)ncand);
-        nchunk = std::max(1, std::min(nchunk, (n_depth + 63) / 64));
-        const int chunk = (n_depth + nchunk - 1) / nchunk;
-        hipLaunchKernelGGL(k_nearest_part, dim3((ncand + NN_T - 1) / NN_T, nchunk), dim3(NN_T), 0, st, kb.d_coord, ncand, kb.d_dxy, n_depth, chunk,
-                           kb.d_mag, reinterpret_cast<int*>(kb.d_log));
-        hipLaunchKernelGGL(k_nearest_merge, dim3((ncand + KF_T - 1) / KF_T), dim3(KF_T), 0, st, kb.d_coord, ncand, kb.d_dxy, kb.d_didp, nchunk,
-                           kb.d_mag, reinterpret_cast<const int*>(kb.d_log), kb.d_idp, kb.d_w);
+        hipLaunchKernelGGL(k_nearest_tree, dim3((ncand + KF_T - 1) / KF_T), dim3(KF_T), 0, st, kb.d_coord, ncand, kb.d_dxy, kb.d_didp, n_depth,
+                           kb.d_idp, kb.d_w);
         hipLaunchKernelGGL(k_minmax, dim3(NB), dim3(KF_T), 0, st, (const void*)kb.d_w, 2, (size_t)ncand, kb.d_partial);
     }
     hipLaunchKernelGGL(k_weights_clean, dim3(1), dim3(1024), 0, st, kb.d_coord, kb.d_grad, kb.d_idp, kb.d_w, ncand, n_depth > 0 ? 1 : 0,

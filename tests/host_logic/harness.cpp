@@ -10,6 +10,7 @@
 #include "../../slam-eds_amd/csrc/eds_layout.hpp"
 #include "../../slam-eds_amd/csrc/eds_launch_rule.hpp"
 #include "../../slam-eds_amd/csrc/eds_solver.hpp"
+#include "../../slam-eds_amd/csrc/eds_kdtree.hpp"
 
 using namespace eds_oracle;
 
@@ -199,6 +200,16 @@ const char* hl_knobs_from_env(void) { EdsKnobs kn; return eds_knobs_from_env(&kn
 int hl_knob_set(const char* name, const char* value) { EdsKnobs kn; return eds_knobs_set(&kn, name, value); }
 int hl_strips_phases_for_budget(int wanted, long long slots, long long two_copies_bytes, long long free_bytes, int pct) {
     return eds_strips_phases_for_budget(wanted, (unsigned long long)slots, (unsigned long long)two_copies_bytes, (unsigned long long)free_bytes, pct);
+}
+
+// product k-d tree of the keyframe's depth association (eds_kdtree.hpp): the host build the library runs, then the walk the kernel
+// runs, compiled here for the CPU — nearest point index (into xy) and minDist of every query
+void hl_kdtree_nn(const double* xy, int m, const double* q, int n, int32_t* idx, double* min_dist) {
+    std::vector<int> perm(m);
+    edskd::build_tree(xy, m, perm.data());
+    std::vector<double> txy(2 * (size_t)m);
+    for (int k = 0; k < m; ++k) { txy[2 * (size_t)k] = xy[2 * (size_t)perm[k]]; txy[2 * (size_t)k + 1] = xy[2 * (size_t)perm[k] + 1]; }
+    for (int i = 0; i < n; ++i) idx[i] = perm[edskd::nn(txy.data(), m, q[2 * (size_t)i], q[2 * (size_t)i + 1], &min_dist[i])];
 }
 
 }  // extern "C"

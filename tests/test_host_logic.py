@@ -28,7 +28,7 @@ class _Pb(C.Structure):
 def hl():
     deps = [SRC] + [os.path.join(HERE, "..", p) for p in ("oracle/eds_oracle.hpp", "slam-eds_amd/csrc/eds_math.hpp",
                                                          "slam-eds_amd/csrc/eds_solver.hpp", "slam-eds_amd/csrc/eds_layout.hpp",
-                                                         "slam-eds_amd/csrc/eds_launch_rule.hpp")]
+                                                         "slam-eds_amd/csrc/eds_launch_rule.hpp", "slam-eds_amd/csrc/eds_kdtree.hpp")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-misleading-indentation", "-o", LIB, SRC])
     return C.CDLL(LIB)

@@ -257,3 +257,118 @@ def test_build_keyframe_from_camera_image(gpu, capi, dtype, src, channels):
     out = h.build_keyframe(0, img, K, method=0, num_points=1500, depth_xy=xy, depth_idp=di)
     _compare(out, ref)
     h.close()
+
+
+# ---- depth association: the reference's k-d tree, ties included (tests/test_kdtree_pin.py pins the oracle to it) -------------
+def _depth_image_map(seed, H, W, step):
+    """fromDepthmapImage's shape (Types.hpp:196-232): integer pixels column by column, NaN holes (15 % and one block) skipped."""
+    import kdtree_cases as kc
+    return kc.depth_image_map(np.random.default_rng(seed), H, W, 0.15, (H // 6, W // 5), step)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(480, 640), (181, 243)], ids=["vga", "odd"])
+@pytest.mark.parametrize("method,npts", [(0, 4000), (1, 0)], ids=["max4000", "median"])
+@pytest.mark.parametrize("dtype", [np.uint8, np.float32], ids=["u8", "f32"])
+@pytest.mark.parametrize("step", [1, 2], ids=["dense", "every_other"])
+def test_build_keyframe_depth_image_ties(gpu, capi, shape, method, npts, dtype, step):
+    import np_keyframe_oracle as ko
+    H, W = shape
+    img = make_image(41, H, W, dtype)
+    K = (0.78 * W, 0.78 * W, (W - 1) / 2, (H - 1) / 2)
+    xy, di = _depth_image_map(42 + step, H, W, step)
+    ref = ko.keyframe(img, K, method, npts, depth_xy=xy, depth_idp=di)
+    h = capi.Handle(capi.default_config(), 1, H * W, H, W)
+    out = h.build_keyframe(0, img, K, method=method, num_points=npts, depth_xy=xy, depth_idp=di)
+    _compare(out, ref)
+    h.close()
+
+
+def _golden_replay(capi, g, method=1, img=None):
+    """A keyframe at the golden's frame size with its depth map: every surviving candidate at (x, y) carries the idp of the point the
+    reference's tree returned for query (x, y); the survivors are the oracle's (cleanPoints drops the far ones)."""
+    import np_keyframe_oracle as ko
+    H, W = int(g["H"]), int(g["W"])
+    img = make_image(51, H, W) if img is None else img
+    K = (0.78 * W, 0.78 * W, (W - 1) / 2, (H - 1) / 2)
+    xy = g["depth_xy"]
+    di = 1.0 / (1.0 + np.arange(len(xy), dtype=np.float64))          # distinct per point: any other winner shows
+    ref = ko.keyframe(img, K, method, 0 if method else H * W // 8, cell=min(20, H // 2, W // 2), depth_xy=xy, depth_idp=di)
+    h = capi.Handle(capi.default_config(), 1, H * W, H, W)
+    out = h.build_keyframe(0, img, K, method=method, num_points=0 if method else H * W // 8, cell=min(20, H // 2, W // 2), depth_xy=xy, depth_idp=di)
+    h.close()
+    _compare(out, ref)
+    return out, di
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["dense_120x160", "dense_61x83", "every_other_120x160", "duplicates", "single_row", "single_column"])
+def test_build_keyframe_golden_replay(gpu, capi, name):
+    import kdtree_cases as kc
+    g = kc.load(f"ref_kdtree_{name}.npz")
+    W = int(g["W"])
+    out, di = _golden_replay(capi, g)
+    x, y = out["coord"][:, 0].astype(np.int64), out["coord"][:, 1].astype(np.int64)
+    assert len(x) >= (50 if min(g["H"], g["W"]) >= 60 else 5)      # the single column keeps the few pixels beside it
+    assert np.array_equal(out["idp"], di[g["ref_idx"][y * W + x]])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["fma", "sqrt", "swap"])
+def test_build_keyframe_near_ties(gpu, capi, kind):
+    """Real-valued near-tie pairs about lattice pixels: separate rounding of dx*dx + dy*dy and a strict < of the sqrt decide."""
+    import kdtree_cases as kc
+    g = kc.load(f"ref_kdtree_near_tie_{kind}.npz")
+    W = int(g["W"])
+    out, di = _golden_replay(capi, g)
+    site = {(int(a), int(b)): k for k, (a, b) in enumerate(g["queries"])}
+    hits = [(i, site[(int(cx), int(cy))]) for i, (cx, cy) in enumerate(out["coord"]) if (int(cx), int(cy)) in site]
+    assert len(hits) >= 20, len(hits)
+    assert all(out["idp"][i] == di[g["ref_idx"][k]] for i, k in hits)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("m", [1, 2, 3])
+def test_build_keyframe_tiny_depth_maps(gpu, capi, m):
+    import kdtree_cases as kc
+    for t in range(4):
+        g = kc.load(f"ref_kdtree_tiny_m{m}_{t}.npz")
+        g = {**g, "H": 40, "W": 40}
+        out, di = _golden_replay(capi, g)
+        ref_idx, _ = __import__("pyoracle").kdtree_nn(g["depth_xy"], out["coord"])
+        assert np.array_equal(out["idp"], di[ref_idx])
+
+
+@pytest.mark.gpu
+def test_build_keyframe_dense_vga_depth_map(gpu, capi):
+    """A dense VGA depth map, ~260 k points: the tree's depth (19 levels) and the upload size."""
+    import np_keyframe_oracle as ko
+    import kdtree_cases as kc
+    H, W = 480, 640
+    mask = np.random.default_rng(61).random((H, W)) >= 0.15
+    xy = kc.grid_points(mask)
+    di = np.random.default_rng(62).uniform(0.2, 1.0, len(xy))
+    assert len(xy) > 255_000
+    img = make_image(63, H, W)
+    K = (0.78 * W, 0.78 * W, (W - 1) / 2, (H - 1) / 2)
+    ref = ko.keyframe(img, K, 1, 0, depth_xy=xy, depth_idp=di)
+    h = capi.Handle(capi.default_config(), 1, H * W, H, W)
+    out = h.build_keyframe(0, img, K, method=1, depth_xy=xy, depth_idp=di)
+    _compare(out, ref)
+    h.close()
+
+
+@pytest.mark.gpu
+def test_build_keyframe_image_depth_ties(gpu, capi):
+    """eds_trk_build_keyframe_image (an RGB camera image at twice the size) takes the same tree."""
+    import np_keyframe_oracle as ko
+    H, W = 120, 160
+    base = make_image(71, 2 * H, 2 * W, np.float64)
+    img = np.round(np.stack([base, np.roll(base, 2, 1), base[::-1]], axis=2) * 255).astype(np.uint8)
+    K = (0.78 * W, 0.78 * W, (W - 1) / 2, (H - 1) / 2)
+    xy, di = _depth_image_map(72, H, W, 2)
+    ref = ko.keyframe(ko.prepare_image(img, H, W), K, 0, 1500, depth_xy=xy, depth_idp=di)
+    h = capi.Handle(capi.default_config(), 1, H * W, H, W)
+    out = h.build_keyframe(0, img, K, method=0, num_points=1500, depth_xy=xy, depth_idp=di)
+    _compare(out, ref)
+    h.close()
