@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define EDS_HIP_DEPTH_ABI_VERSION 1
+#define EDS_HIP_DEPTH_ABI_VERSION 2
 int eds_depth_abi_version(void);
 
 /* DepthPoints::init's scalar arguments (DepthPoints.hpp:60-75): the depth range gives mu_range = max - min; threshold is
@@ -60,8 +60,11 @@ int eds_depth_init(eds_trk* h, int first, int count, const eds_depth_params* prm
 enum eds_depth_coords {
     EDS_DEPTH_TRACKS = 0,           /* update(T_kf_ef, kf_coord, tracks) (:137-178): x_ef = x_kf + xy[i] */
     EDS_DEPTH_EF_COORD = 1,         /* update(T_kf_ef, kf_coord, ef_coord) (:101-135): x_ef = xy[i] */
-    EDS_DEPTH_REPROJECT = 2         /* x_ef = x_kf + the track Tracker::getCoord computes at the slot's current pose (Tracker.cpp:343-366,
+    EDS_DEPTH_REPROJECT = 2,        /* x_ef = x_kf + the track Tracker::getCoord computes at the slot's current pose (Tracker.cpp:343-366,
                                      * eds_trk_update_points' expression in fp64): the whole loop stays on the device; xy unused */
+    EDS_DEPTH_DEVICE_TRACKS = 3     /* x_ef = x_kf + the slot's device kf->tracks plane, as the KLT left it (include/eds_hip_klt.h;
+                                     * ABI 2): the photometric tracks without a host round trip; xy unused.  EDS_ERR_STATE while the
+                                     * handle has no such plane (no eds_klt_track_points* yet) */
 };
 /* eds::mapping::DEPTH_FILTER (DepthPoints.hpp:31): accepted and ignored, as in the reference (GAUSS runs VOGIATZIS) */
 enum eds_depth_filter { EDS_DEPTH_VOGIATZIS = 0, EDS_DEPTH_GAUSS = 1 };
@@ -77,7 +80,7 @@ typedef struct eds_depth_summary {
 /* DepthPoints::update for slots first .. first + count - 1 in one pass.  Point i of alignment b reads xy[2 * (b * stride + i)]
  * and kf_xy likewise (pixels, N x 2 per alignment, stride >= the largest point count).
  *   kf_xy   NULL: the keyframe pixels the slot holds (fp32 fraction of an integer cell: ~1e-7 px resolution).
- *   xy      NULL only with EDS_DEPTH_REPROJECT.
+ *   xy      NULL only with EDS_DEPTH_REPROJECT and EDS_DEPTH_DEVICE_TRACKS (ignored there).
  *   T_kf_ef count x 7 (p[3], q_xyzw[4]) or NULL: the inverse of each slot's current pose (the tracker's (p, q) is T_ef_kf;
  *           Tracker.cpp:220 hands on its inverse).  EDS_DEPTH_REPROJECT always re-projects at the slot's pose.
  *   filter  an eds_depth_filter, ignored like the reference's.

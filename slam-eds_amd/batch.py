@@ -167,6 +167,16 @@ class BatchTracker:
         coords = capi.DEPTH_REPROJECT if coords is None else coords
         return self.handle.depth_update(0, self.count, coords, xy=xy, kf_xy=kf_xy, T_kf_ef=T_kf_ef)
 
+    def track_points(self, patch_radius: int = 7, num_level=None) -> list:
+        """Optional step after solve(): the KLT point trackers of this shard on the device (include/eds_hip_klt.h) —
+        Tracker::trackPoints(patch_radius), or Tracker::trackPointsPyr(num_level) when num_level is given.  The tracks stay in HBM,
+        where update_depth(coords=capi.DEPTH_DEVICE_TRACKS) reads them.  Returns per alignment dict(coord, tracks, flow, kept, n)."""
+        if self.count == 0:
+            return []
+        if num_level is not None:
+            return self.handle.klt_track_points_pyr(0, self.count, num_level)
+        return self.handle.klt_track_points(0, self.count, patch_radius)
+
     def local_results(self) -> np.ndarray:
         if self.count == 0:
             return np.zeros((0, RESULT_WIDTH))

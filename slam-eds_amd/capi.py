@@ -54,8 +54,11 @@ DEPTH_EXPORTS = (
 )
 # enums of include/eds_hip_depth.h
 DEPTH_INIT_CONSTANT, DEPTH_INIT_HOST, DEPTH_INIT_PLANE = 0, 1, 2
-DEPTH_TRACKS, DEPTH_EF_COORD, DEPTH_REPROJECT = 0, 1, 2
+DEPTH_TRACKS, DEPTH_EF_COORD, DEPTH_REPROJECT, DEPTH_DEVICE_TRACKS = 0, 1, 2, 3
 DEPTH_VOGIATZIS, DEPTH_GAUSS = 0, 1
+
+# every symbol include/eds_hip_klt.h declares: the KLT point trackers (their own header and ABI version)
+KLT_EXPORTS = ("eds_klt_abi_version", "eds_klt_track_points", "eds_klt_track_points_pyr", "eds_klt_get")
 
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -144,6 +147,7 @@ def build(force: bool = False) -> str:
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_depth.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_klt.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
@@ -262,6 +266,9 @@ def lib():
         L.eds_depth_set.argtypes = [C.c_void_p, C.c_int, _dp]
         L.eds_depth_get_idepth.argtypes = [C.c_void_p, C.c_int, _dp]
         L.eds_depth_stats.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        for fn in (L.eds_klt_track_points, L.eds_klt_track_points_pyr):
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip]
+        L.eds_klt_get.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
         if L.eds_trk_cfg_size() != C.sizeof(Cfg) or L.eds_trk_info_size() != C.sizeof(Info):
             raise EdsError(ERR_INVALID, "ctypes struct layout disagrees with include/eds_hip.h")
         _lib = L
@@ -606,6 +613,36 @@ class Handle:
             out.append(dict(coord=coord[b, :n[b]] if want_points else None, tracks=tracks[b, :n[b]] if want_points else None,
                             kept=kept[b, :n[b]] if want_points else None, mean_sq_flow=float(flow[b]), n=int(n[b])))
         return out
+
+    # -- KLT point trackers (include/eds_hip_klt.h) -------------------------------------------
+    def _klt(self, fn, first, count, arg):
+        count = self.batch - first if count is None else count
+        stride = max(self._N[first:first + count] + [1])
+        coord, tracks, flow = np.zeros((count, stride, 2)), np.zeros((count, stride, 2)), np.zeros((count, stride, 2))
+        kept, n = np.zeros((count, stride), dtype=np.int32), np.zeros(count, dtype=np.int32)
+        _check(fn(self._h, int(first), int(count), int(arg), stride, _p(coord), _p(tracks), _p(flow), kept.ctypes.data_as(_ip),
+                  n.ctypes.data_as(_ip)))
+        out = []
+        for b in range(count):
+            self._N[first + b] = int(n[b])
+            out.append(dict(coord=coord[b, :n[b]], tracks=tracks[b, :n[b]], flow=flow[b, :n[b]], kept=kept[b, :n[b]], n=int(n[b])))
+        return out
+
+    def klt_track_points(self, first=0, count=None, patch_radius=7):
+        """Tracker::trackPoints for slots first .. first + count - 1: getCoord(true), then the KLT flow of every kept point against the
+        slot's event frame.  Returns per slot dict(coord, tracks, flow, kept, n) — tracks and flow as the device keeps them."""
+        return self._klt(lib().eds_klt_track_points, first, count, patch_radius)
+
+    def klt_track_points_pyr(self, first=0, count=None, num_level=3):
+        """Tracker::trackPointsPyr; returns as klt_track_points (flow accumulates over calls until the next keyframe)."""
+        return self._klt(lib().eds_klt_track_points_pyr, first, count, num_level)
+
+    def klt_get(self, slot):
+        """The device's kf->tracks and kf->flow of one slot: (N x 2, N x 2)."""
+        N = self._N[slot]
+        tracks, flow = np.zeros((N, 2)), np.zeros((N, 2))
+        _check(lib().eds_klt_get(self._h, int(slot), _p(tracks), _p(flow)))
+        return tracks, flow
 
     # -- inverse-depth filter (include/eds_hip_depth.h) -----------------------------------------
     def depth_init(self, first=0, count=None, source=DEPTH_INIT_CONSTANT, idp=None, min_depth=1.0, max_depth=3.0, threshold=100.0,

@@ -103,6 +103,7 @@ void free_all(eds_trk* h) {
     eds_frame_free(&h->frame_build);
     eds_points_free(&h->point_ops);
     eds_depth_free(&h->depth);
+    eds_klt_free(&h->klt);
     eds_keyframe_free(&h->kf_build);
     void* hptrs[] = {h->h_pose, h->h_part, h->h_G, h->h_f32, h->h_r, h->h_fstage, h->h_rmap, h->h_idp, h->h_fprog, h->h_bstage};
     for (hipEvent_t e : h->ev_bstage) hipEventDestroy(e);
@@ -563,8 +564,15 @@ int eds_trk_update_points_batch(eds_trk* h, int first, int count, int delete_out
     }
     if ((coord_xy || tracks_xy || kept_index) && stride < maxN) return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
     EDS_HIP_TRY(hipSetDevice(h->dev));
+    return update_points_range(h, first, count, delete_out_points, stride, coord_xy, tracks_xy, kept_index, n_kept, mean_sq_flow);
+}
+
+}  // extern "C"
+
+int edscapi::update_points_range(eds_trk* h, int first, int count, int delete_out_points, int stride, double* coord_xy, double* tracks_xy,
+                                 int32_t* kept_index, int* n_kept, double* mean_sq_flow, const EdsPointsDev* dev) {
     std::vector<int> n(count);
-    int rc = eds_points_update_batch(h, first, count, delete_out_points != 0, stride, coord_xy, tracks_xy, kept_index, n.data(), mean_sq_flow);
+    int rc = eds_points_update_batch(h, first, count, delete_out_points != 0, stride, coord_xy, tracks_xy, kept_index, n.data(), mean_sq_flow, dev);
     if (rc) return rc;
     bool any = false;
     for (int b = 0; b < count; ++b) {
@@ -581,6 +589,8 @@ int eds_trk_update_points_batch(eds_trk* h, int first, int count, int delete_out
     if (any) { EDS_HIP_TRY(hipStreamSynchronize(h->st)); h->gram_pending = false; }
     return EDS_OK;
 }
+
+extern "C" {
 
 /* ---- keyframe point set-up on the device ------------------------------------------ */
 void eds_kf_select_default(eds_kf_select* sel) {

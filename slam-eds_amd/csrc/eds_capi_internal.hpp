@@ -35,6 +35,9 @@ void fill_static(const eds_trk* h, int slot);
 void fill_pose(eds_trk* h, int slot, const double* p, const double* q, const double* v);
 int upload_pose(eds_trk* h, int first, int count);
 int max_points(const eds_trk* h, int first, int count);
+// eds_trk_update_points_batch after its argument checks; dev: see eds_points_update_batch
+int update_points_range(eds_trk* h, int first, int count, int delete_out_points, int stride, double* coord_xy, double* tracks_xy,
+                        int32_t* kept_index, int* n_kept, double* mean_sq_flow, const EdsPointsDev* dev = nullptr);
 // eds_capi_inputs.hip
 int refresh_gram(eds_trk* h, int slot, bool wait = true);
 // eds_capi_solve.hip

@@ -3,7 +3,7 @@
 //
 //   k_depth_init     DepthPoints::init, both overloads (DepthPoints.cpp:59-99), or the seeds as a caller hands them (operator[])
 //   k_depth_update   DepthPoints::update (:101-178) in ONE pass per point: keyframe pixel, event-frame pixel (host tracks, host
-//                    event-frame coordinates, or getCoord's re-projection at the slot's pose), triangulation (invDepthTwoPointsEucl,
+//                    event-frame coordinates, getCoord's re-projection at the slot's pose, or the KLT's device tracks), triangulation (invDepthTwoPointsEucl,
 //                    :368-397), depth uncertainty (computeTau, DepthPoints.hpp:165-182), the Vogiatzis update (filterVogiatzis,
 //                    :180-228), the seed write-back and the narrowed mu into the slot's inverse-depth plane
 //   k_depth_stats    meanIDepth / medianIDepth (:248-260): fp64 sums and two order statistics by radix select (eds_select.hpp)
@@ -89,7 +89,8 @@ __global__ __launch_bounds__(EDS_DEPTH_TPB) void k_depth_init(EdsArrays A, doubl
 // one lane per point; workgroup -> (alignment b, chunk of EDS_DEPTH_TPB points)
 __global__ __launch_bounds__(EDS_DEPTH_TPB) void k_depth_update(EdsArrays A, double* __restrict__ seeds, const double* __restrict__ par, int first,
                                                               int nchunk, int coords, const double* __restrict__ xy,
-                                                              const double* __restrict__ kfxy, int* __restrict__ sum) {
+                                                              const double* __restrict__ kfxy, const double* __restrict__ tpl,
+                                                              int* __restrict__ sum) {
     const int b = blockIdx.x / nchunk, i = (blockIdx.x % nchunk) * EDS_DEPTH_TPB + threadIdx.x;
     const int slot = first + b;
     if (i >= A.Np) return;              // (uniform per wavefront: Np is a multiple of 64)
@@ -107,6 +108,7 @@ __global__ __launch_bounds__(EDS_DEPTH_TPB) void k_depth_update(EdsArrays A, dou
         double uef, vef;
         if (coords == EDS_DEPTH_EF_COORD) { uef = xy[2 * k]; vef = xy[2 * k + 1]; }
         else if (coords == EDS_DEPTH_TRACKS) { uef = ukf + xy[2 * k]; vef = vkf + xy[2 * k + 1]; }
+        else if (coords == EDS_DEPTH_DEVICE_TRACKS) { uef = ukf + tpl[o]; vef = vkf + tpl[plane + o]; }      // the KLT's kf->tracks
         else {
             // Tracker::getCoord's track at the slot's pose with the raw inverse depth (Tracker.cpp:343-351; k_update_points' expression)
             const double x = (double)A.x[o], y = (double)A.y[o], r = (double)A.rho[o];
@@ -385,11 +387,14 @@ int eds_depth_update(eds_trk* h, int first, int count, int coords, const double*
                      int filter, eds_depth_summary* out) {
     int rc = check_common(h, first, count, true);
     if (rc) return rc;
-    if (coords < EDS_DEPTH_TRACKS || coords > EDS_DEPTH_REPROJECT) return fail(EDS_ERR_INVALID, "unknown coordinate source");
+    if (coords < EDS_DEPTH_TRACKS || coords > EDS_DEPTH_DEVICE_TRACKS) return fail(EDS_ERR_INVALID, "unknown coordinate source");
     if (filter != EDS_DEPTH_VOGIATZIS && filter != EDS_DEPTH_GAUSS) return fail(EDS_ERR_INVALID, "unknown depth filter");
-    if (!xy && coords != EDS_DEPTH_REPROJECT) return fail(EDS_ERR_INVALID, "null event-frame coordinates");
-    if (coords == EDS_DEPTH_REPROJECT) xy = nullptr;
+    const bool on_device = coords == EDS_DEPTH_REPROJECT || coords == EDS_DEPTH_DEVICE_TRACKS;
+    if (!xy && !on_device) return fail(EDS_ERR_INVALID, "null event-frame coordinates");
+    if (on_device) xy = nullptr;
     if ((xy || kf_xy) && stride < max_points(h, first, count)) return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
+    if (coords == EDS_DEPTH_DEVICE_TRACKS && !h->klt.tracks)
+        return fail(EDS_ERR_STATE, "no device tracks: eds_klt_track_points has not run on this handle (include/eds_hip_klt.h)");
     EDS_HIP_TRY(hipSetDevice(h->dev));
     EdsDepthBuffers& d = h->depth;
     const size_t half = 2 * (size_t)h->B * h->Np;
@@ -433,7 +438,7 @@ int eds_depth_update(eds_trk* h, int first, int count, int coords, const double*
     EDS_HIP_TRY(hipMemsetAsync(d.d_sum, 0, (size_t)count * EDS_DEPTH_SUM * 4, h->st));
     const int nchunk = (h->Np + EDS_DEPTH_TPB - 1) / EDS_DEPTH_TPB;
     hipLaunchKernelGGL(k_depth_update, dim3((unsigned)count * nchunk), dim3(EDS_DEPTH_TPB), 0, h->st, h->arrays(), d.seeds, d.d_par, first, nchunk,
-                       coords, xy ? d.d_in : nullptr, kf_xy ? d.d_in + half : nullptr, d.d_sum);
+                       coords, xy ? d.d_in : nullptr, kf_xy ? d.d_in + half : nullptr, h->klt.tracks, d.d_sum);
     EDS_HIP_TRY(hipGetLastError());
     if ((rc = finish_planes(h, first, count))) return rc;
     EDS_HIP_TRY(hipMemcpyAsync(d.h_sum, d.d_sum, (size_t)count * EDS_DEPTH_SUM * 4, hipMemcpyDeviceToHost, h->st));

@@ -181,8 +181,10 @@ bool eds_points_supported(const eds_trk* h, int first, int count);
 int  eds_points_loss_param(eds_trk* h, int first, int count, int method, double* tau_out);
 int  eds_points_update(eds_trk* h, int slot, int delete_out, double* coord_xy, double* tracks_xy, int32_t* kept_index, int* n_kept,
                        double* mean_sq_flow);
+struct EdsPointsDev;
+// dev (eds_klt.hpp): the coordinates and kept indices go to these HBM buffers (indexed by slot) instead of the pinned block
 int  eds_points_update_batch(eds_trk* h, int first, int count, int delete_out, int stride, double* coord_xy, double* tracks_xy,
-                             int32_t* kept_index, int* n_kept, double* mean_sq_flow);
+                             int32_t* kept_index, int* n_kept, double* mean_sq_flow, const EdsPointsDev* dev = nullptr);
 
 // ---- keyframe point set-up on device (eds_keyframe.hip) ------------------------------------------------------
 struct eds_kf_select;

@@ -6,6 +6,7 @@
 
 #include "../../include/eds_hip.h"
 #include "eds_depth.hpp"
+#include "eds_klt.hpp"
 #include "eds_fused.hpp"
 #include "eds_kernels.hpp"
 #include "eds_launch_rule.hpp"
@@ -62,6 +63,7 @@ struct eds_trk {
     EdsFrameBuffers frame_build;
     EdsPointBuffers point_ops;
     EdsDepthBuffers depth;
+    EdsKltBuffers klt;                  // KLT tracks / flow planes (include/eds_hip_klt.h), allocated by the first KLT call
     EdsKeyframeBuffers kf_build;
     // pinned host staging
     double *h_pose = nullptr, *h_part = nullptr, *h_G = nullptr;

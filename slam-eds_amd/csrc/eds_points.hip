@@ -66,10 +66,13 @@ __global__ __launch_bounds__(EDS_LP_THREADS) void k_loss_param(EdsArrays A, int 
 // One workgroup per alignment; per sweep lane t owns the CONTIGUOUS points [t*cppt, (t+1)*cppt) so that an exclusive scan of the
 // per-lane keep counts gives order-preserving destinations.
 // (blockIdx.x: alignment of a batch — slot first + blockIdx.x, its pose, outputs and summary at their blockIdx.x-th places; coord /
-// track / kept may be null: only the compaction, the count and the mean squared flow are wanted)
+// track / kept may be null: only the compaction, the count and the mean squared flow are wanted.  tplane / fplane: the KLT's fp64
+// kf->tracks / kf->flow planes [2][B][Np] (include/eds_hip_klt.h) once a KLT call allocated them, else null: the tracks go there
+// too, and the flow is compacted with the other planes)
 __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, int first, int ppt, int delete_out, const double* __restrict__ pose_in,
                                                                   double* __restrict__ coord, double* __restrict__ track,
-                                                                  int* __restrict__ kept, double* __restrict__ summary) {
+                                                                  int* __restrict__ kept, double* __restrict__ summary,
+                                                                  double* __restrict__ tplane, double* __restrict__ fplane) {
     const int tid = threadIdx.x;
     const int slot = first + (int)blockIdx.x;
     pose_in += 16 * (size_t)blockIdx.x; summary += 2 * (size_t)blockIdx.x;
@@ -78,7 +81,8 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
     if (kept) kept += (size_t)A.Np * blockIdx.x;
     double* pb = A.pose + (size_t)slot * EDS_POSE_STRIDE;
     const int N = (int)pb[EDS_PB_N];
-    const size_t base = (size_t)slot * A.Np;
+    const size_t base = (size_t)slot * A.Np, plane = (size_t)A.B * A.Np;
+    const bool move_flow = fplane && delete_out;
     __shared__ int s_cnt[EDS_PTS_THREADS];
     __shared__ double s_flow[EDS_PTS_THREADS / 64];
     __shared__ double s_pose[16];
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
         const int cppt = (nc + EDS_PTS_THREADS - 1) / EDS_PTS_THREADS;
         float fx_[MAXP], fy_[MAXP], frho[MAXP], fgx[MAXP], fgy[MAXP], fw[MAXP], ff0x[MAXP], ff0y[MAXP];
         int fcell[MAXP];
-        double xp[MAXP], yp[MAXP];
+        double xp[MAXP], yp[MAXP], fl0[MAXP], fl1[MAXP];
         bool keep[MAXP];
         int mine = 0;
 #pragma unroll
@@ -116,6 +120,7 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
                 const size_t o = base + i;
                 fx_[k] = A.x[o]; fy_[k] = A.y[o]; frho[k] = A.rho[o]; fgx[k] = A.gx[o]; fgy[k] = A.gy[o]; fw[k] = A.w[o];
                 ff0x[k] = A.f0x[o]; ff0y[k] = A.f0y[o]; fcell[k] = A.cell0[o];
+                if (move_flow) { fl0[k] = fplane[o]; fl1[k] = fplane[plane + o]; }
                 // p = R (x, y, 1)/mu + t with the RAW inverse depth (Tracker.cpp:343-347), projected (:350-351)
                 const float rho = frho[k];
                 const float d0 = ps.D[0] * fx_[k] + ps.D[1] * fy_[k] + ps.D[2] + ps.t[0] * rho;
@@ -151,6 +156,8 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
             if (coord) { coord[2 * dst] = xp[k]; coord[2 * dst + 1] = yp[k]; }
             const double u0 = (double)(short)(fcell[k] & 0xffff) + (double)ff0x[k], v0 = (double)(fcell[k] >> 16) + (double)ff0y[k];
             if (track) { track[2 * dst] = xp[k] - u0; track[2 * dst + 1] = yp[k] - v0; }
+            if (tplane) { tplane[o] = xp[k] - u0; tplane[plane + o] = yp[k] - v0; }
+            if (move_flow) { fplane[o] = fl0[k]; fplane[plane + o] = fl1[k]; }
             if (kept) kept[dst] = c0 + tid * cppt + k;
             ++dst;
         }
@@ -232,7 +239,7 @@ int eds_points_loss_param(eds_trk* h, int first, int count, int method, double* 
 // getCoord (+ culling) of slots [first, first + count) — one workgroup per alignment, EDS_PTS_BATCH alignments per launch.  Outputs of
 // alignment b start at index b * stride of the caller's arrays (points) resp. b (n_kept, mean_sq_flow).
 int eds_points_update_batch(eds_trk* h, int first, int count, int delete_out, int stride, double* coord_xy, double* tracks_xy, int32_t* kept_index,
-                            int* n_kept, double* mean_sq_flow) {
+                            int* n_kept, double* mean_sq_flow, const EdsPointsDev* dev) {
     int rc = ensure(h, std::min(count, EDS_PTS_BATCH));
     if (rc) return rc;
     EdsPointBuffers& pb = h->point_ops;
@@ -253,19 +260,21 @@ int eds_points_update_batch(eds_trk* h, int first, int count, int delete_out, in
         // indices, and the seed gather reads them behind it on the stream.  Without seeds the launch is what it always was.
         bool seeded = false;
         for (int b = 0; b < cn && delete_out; ++b) seeded |= h->slots[first + c0 + b].seeded;
+        // the KLT (dev) keeps coordinates and kept indices in HBM for its own kernels (eds_klt.hip)
+        double* dcoord = dev ? dev->coord + 2 * Np * (size_t)(first + c0) : (coord_xy ? pb.d_coord : nullptr);
+        int* dkept = dev ? dev->kept + Np * (size_t)(first + c0) : ((kept_index || seeded) ? pb.d_kept : nullptr);
         hipLaunchKernelGGL(k_update_points, dim3(cn), dim3(EDS_PTS_THREADS), 0, h->st, h->arrays(), first + c0, ppt, delete_out, pb.d_pose,
-                           coord_xy ? pb.d_coord : nullptr, tracks_xy ? pb.d_track : nullptr, (kept_index || seeded) ? pb.d_kept : nullptr,
-                           pb.d_summary);
-        if (seeded) eds_depth_compact(h, first + c0, cn, pb.d_kept);
+                           dcoord, tracks_xy ? pb.d_track : nullptr, dkept, pb.d_summary, h->klt.tracks, h->klt.flow);
+        if (seeded) eds_depth_compact(h, first + c0, cn, dkept);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(h->st);
         if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
         for (int b = 0; b < cn; ++b) {
             const int n = (int)pb.h_summary[2 * b];
             const size_t o = (size_t)(c0 + b) * stride;
-            if (coord_xy && n > 0) std::memcpy(coord_xy + 2 * o, pb.h_coord + 2 * Np * b, (size_t)n * 16);
+            if (coord_xy && !dev && n > 0) std::memcpy(coord_xy + 2 * o, pb.h_coord + 2 * Np * b, (size_t)n * 16);
             if (tracks_xy && n > 0) std::memcpy(tracks_xy + 2 * o, pb.h_track + 2 * Np * b, (size_t)n * 16);
-            if (kept_index && n > 0) std::memcpy(kept_index + o, pb.h_kept + Np * b, (size_t)n * 4);
+            if (kept_index && !dev && n > 0) std::memcpy(kept_index + o, pb.h_kept + Np * b, (size_t)n * 4);
             if (n_kept) n_kept[c0 + b] = n;
             if (mean_sq_flow) mean_sq_flow[c0 + b] = pb.h_summary[2 * b + 1];
         }

@@ -1,8 +1,9 @@
 """Python mirror of ``eds::tracking::Tracker`` (reference src/tracking/Tracker.hpp:36-114) over the
 C ABI — same member names, argument meaning and error behaviour for the alignment path
-(``optimize``, ``getLossParams``, ``getTransform``, ``set``/``reset``, ``getInfo``).  The KLT /
-epipolar helpers of the reference class (Tracker.cpp:378-654) are outside the hot path and are
-not mirrored.  The C++ twin with the reference's exact signatures is ``csrc/Tracker.hpp``.
+(``optimize``, ``getLossParams``, ``getTransform``, ``set``/``reset``, ``getInfo``) and the KLT point
+trackers ``trackPoints`` / ``trackPointsPyr`` (Tracker.cpp:378-488, include/eds_hip_klt.h).  The epipolar
+helpers (trackPointsAlongEpiline, getEMatrix / getFMatrix) are not mirrored.  The C++ twin with the
+reference's exact signatures is ``csrc/Tracker.hpp``.
 """
 from __future__ import annotations
 
@@ -61,6 +62,8 @@ class KeyFrame:
     cols: int                       # kf->img.cols
     residuals: np.ndarray = field(default_factory=lambda: np.zeros(0))
     coord: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))   # pixel coordinates (KeyFrame.hpp:80)
+    tracks: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))  # kf->tracks: getCoord's track (+ the KLT flow)
+    flow: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))    # kf->flow: the KLT flow (zero after KeyFrame::create)
 
     @classmethod
     def create(cls, img, K_ref, depth_xy=None, depth_idp=None, points_selection_method: int = SELECT_MEDIAN,
@@ -259,6 +262,40 @@ class Tracker:
         self.tracks = out["tracks"]                                  # kf->tracks (Tracker.cpp:365)
         self.squared_norm_flow = out["mean_sq_flow"]                 # :372
         return out["coord"]
+
+    def _klt(self, event_frame, pyr: bool, arg: int):
+        """getCoord(true) + the KLT flow on the device (include/eds_hip_klt.h), then kf updated as the reference's members leave it.
+        The handle's keyframe is re-uploaded on every call, which zeroes the device flow: the accumulated kf.flow is kept here."""
+        self._ensure_handle()
+        kf, h = self.kf, self._h
+        K = np.asarray(kf.K_ref, dtype=np.float64)
+        N = len(kf.inv_depth)
+        flow = np.asarray(kf.flow, dtype=np.float64) if len(kf.flow) == N else np.zeros((N, 2))
+        h.set_keyframe(0, kf.norm_coord, kf.grad, kf.inv_depth, kf.weights, K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        h.set_event_frame(0, event_frame)
+        h.set_state(0, self.px, self.qx, self.vx)
+        out = (h.klt_track_points_pyr(0, 1, arg) if pyr else h.klt_track_points(0, 1, arg))[0]
+        keep = out["kept"]
+        if len(keep) != N:                                            # KeyFrame::erasePoint of the points that left the frame
+            for name in ("norm_coord", "grad", "weights", "inv_depth"):
+                setattr(kf, name, np.ascontiguousarray(np.asarray(getattr(kf, name))[keep]))
+            if len(kf.coord) == N:
+                kf.coord = np.ascontiguousarray(np.asarray(kf.coord)[keep])
+            if len(kf.residuals) != len(keep):
+                kf.residuals = np.zeros(0)
+            flow = flow[keep]
+        kf.flow = flow + out["flow"] if pyr else out["flow"]          # Tracker.cpp:479 (+=) / :413 (=)
+        kf.tracks = out["tracks"]                                     # getCoord's track + f (:365, :417, :481)
+        self.tracks = kf.tracks
+        return out["coord"]
+
+    def trackPoints(self, event_frame, patch_radius: int = 7):
+        """Tracker::trackPoints (Tracker.cpp:378-434): getCoord(true), then kf.flow = f and kf.tracks += f per point."""
+        self._klt(event_frame, False, patch_radius)
+
+    def trackPointsPyr(self, event_frame, num_level: int = 3):
+        """Tracker::trackPointsPyr (Tracker.cpp:436-488): as trackPoints over num_level pyrDown levels, kf.flow += f."""
+        self._klt(event_frame, True, num_level)
 
     def needNewKeyframe(self, weight_factor: float = 0.03) -> bool:
         """Tracker::needNewKeyframe (Tracker.cpp:650-654)."""

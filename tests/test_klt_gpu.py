@@ -1,0 +1,316 @@
+"""The KLT point trackers on the device (include/eds_hip_klt.h) against the numpy restatement of Tracker::trackPoints /
+trackPointsPyr (tests/np_klt_oracle.py).  The oracle is fed the coordinates the call returned, the fp32-narrowed gradients the slot
+holds and the event frame as the slot stores it: what is checked is the KLT, not getCoord's fp32 geometry."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import np_klt_oracle as ko
+
+pytestmark = pytest.mark.gpu
+
+REL, ABS, COND = 1e-9, 1e-12, 1e5
+
+
+def _grad32(g):
+    return np.asarray(g, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def _check(got, ref, ms):
+    """flows agree within REL relative or ABS px on points whose M (every level) has cond <= COND; inf / NaN at the same points.
+    A window without any gradient in x or in y (a zero row of M) gives inf / NaN on both sides whatever the rounding; a rank-1 window
+    (one point's splat) has a determinant of rounding noise on both sides, so whether it comes out 0 is not judged."""
+    ms = ms if isinstance(ms, list) else [ms]
+    c = np.max(np.stack([ko.cond(m) for m in ms]), axis=0)
+    zero = np.any(np.stack([(m[:, 0] == 0) | (m[:, 1] == 0) for m in ms]), axis=0)
+    bad_ref, bad_got = ~np.isfinite(ref).all(1), ~np.isfinite(got).all(1)
+    judged = (c <= COND) | zero
+    assert np.array_equal(bad_ref[judged], bad_got[judged])
+    assert bad_ref[zero].all()
+    sel = (c <= COND) & ~bad_ref
+    assert sel.sum() > 0
+    err = np.abs(got[sel] - ref[sel])
+    assert (err <= np.maximum(REL * np.abs(ref[sel]), ABS)).all(), float(np.max(err / np.maximum(np.abs(ref[sel]), 1e-300)))
+    return sel
+
+
+def _handle(capi, als, H, W):
+    cfg = capi.default_config(solver=capi.SOLVER_LM6, exec=capi.EXEC_DEVICE, max_num_iterations=4)
+    h = capi.Handle(cfg, len(als), max(a.N for a in als), H, W)
+    for b, a in enumerate(als):
+        h.set_alignment(b, a)
+    return h
+
+
+def _oracle(h, slot, al, out, radius=None, num_level=None):
+    frame = h.get_event_frame(slot)
+    g = _grad32(al.grad)[out["kept"]]
+    if num_level is None:
+        return ko.track_points(out["coord"], g, frame, radius)
+    return ko.track_points_pyr(out["coord"], g, frame, num_level)
+
+
+def _kf_pixels(al):
+    return np.column_stack([al.fx * al.norm_coord[:, 0] + al.cx, al.fy * al.norm_coord[:, 1] + al.cy])
+
+
+@pytest.mark.parametrize("layout", ["uniform", "edges"])
+@pytest.mark.parametrize("radius", [1, 3, 7, 11])
+def test_track_points_vga(gpu, capi, synth, layout, radius):
+    al = synth.make_alignment(100 + radius, H=480, W=640, N=2000, layout=layout)
+    h = _handle(capi, [al], 480, 640)
+    out = h.klt_track_points(0, 1, radius)[0]
+    ref, m = _oracle(h, 0, al, out, radius=radius)
+    _check(out["flow"], ref, m)
+    # kf->tracks = getCoord's track + f (the keyframe pixel as the slot holds it: fp32 fraction of an integer cell)
+    kf = _kf_pixels(al)[out["kept"]]
+    ok = np.isfinite(out["flow"]).all(1)
+    assert np.allclose(out["tracks"][ok] - out["flow"][ok], out["coord"][ok] - kf[ok], rtol=0, atol=1e-4)
+    t, f = h.klt_get(0)
+    assert np.array_equal(t, out["tracks"], equal_nan=True) and np.array_equal(f, out["flow"], equal_nan=True)
+
+
+@pytest.mark.parametrize("layout", ["uniform", "edges"])
+@pytest.mark.parametrize("num_level", [1, 2, 3, 4, 5])
+def test_track_points_pyr_vga(gpu, capi, synth, layout, num_level):
+    al = synth.make_alignment(200 + num_level, H=480, W=640, N=2000, layout=layout)
+    h = _handle(capi, [al], 480, 640)
+    out = h.klt_track_points_pyr(0, 1, num_level)[0]
+    ref, ms = _oracle(h, 0, al, out, num_level=num_level)
+    _check(out["flow"], ref, ms)
+
+
+def _edge_keyframe(capi, H, W, px, rng, grad=None):
+    """a keyframe whose points sit at the pixels `px` under the identity pose (getCoord returns them as the slot holds them)"""
+    fx, fy, cx, cy = 0.9 * W, 0.9 * W, W / 2.0, H / 2.0
+    n = len(px)
+    norm = np.column_stack([(px[:, 0] - cx) / fx, (px[:, 1] - cy) / fy])
+    g = rng.normal(size=(n, 2)) if grad is None else grad
+    idp = rng.uniform(0.3, 1.0, size=n)
+    cfg = capi.default_config(solver=capi.SOLVER_LM6, exec=capi.EXEC_DEVICE, max_num_iterations=4)
+    h = capi.Handle(cfg, 1, n, H, W)
+    h.set_keyframe(0, norm, g, idp, np.ones(n), fx, fy, cx, cy)
+    h.set_event_frame(0, rng.normal(size=(H, W)))
+    h.set_state(0, np.zeros(3), np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(6))
+    return h, g
+
+
+def _edge_pixels(H, W, rng, n_inner=300):
+    pts = [(0, 0), (W, 0), (0, H), (W, H), (W - 1, H - 1), (W - 0.5, H - 0.5), (3.999, 4.0), (4.0, 3.999), (4.0, 4.0)]
+    for t in np.linspace(0, 1, 9):
+        pts += [(t * W, 0), (t * W, H), (0, t * H), (W, t * H), (t * W, 0.25), (0.25, t * H), (W - 0.25, t * H), (t * W, H - 0.25)]
+    pts += [(float(a), float(b)) for a, b in zip(rng.integers(0, W, 40), rng.integers(0, H, 40))]      # integer coordinates
+    pts += list(zip(rng.uniform(0, W, n_inner), rng.uniform(0, H, n_inner)))
+    return np.array(pts, dtype=np.float64)
+
+
+@pytest.mark.parametrize("H,W,radius,num_level", [(120, 160, 7, None), (120, 160, 3, None), (120, 160, None, 3), (48, 64, 26, None),
+                                                  (48, 64, None, 5)])
+def test_edges_corners_and_repeated_reflection(gpu, capi, H, W, radius, num_level):
+    rng = np.random.default_rng(H + (radius or 0) + 10 * (num_level or 0))
+    px = _edge_pixels(H, W, rng)
+    h, g = _edge_keyframe(capi, H, W, px, rng)
+    out = (h.klt_track_points(0, 1, radius) if num_level is None else h.klt_track_points_pyr(0, 1, num_level))[0]
+    assert out["n"] == len(px)                      # nothing left the frame: x == cols / y == rows are kept
+    ref, m = ko.track_points(out["coord"], _grad32(g), h.get_event_frame(0), radius) if num_level is None else \
+        ko.track_points_pyr(out["coord"], _grad32(g), h.get_event_frame(0), num_level)
+    _check(out["flow"], ref, m)
+
+
+def test_isolated_zero_gradient_point(gpu, capi):
+    H, W = 120, 160
+    rng = np.random.default_rng(7)
+    px = np.vstack([rng.uniform(0, 70, size=(200, 2)) * [1, 1.5], [[140.3, 100.6]]])
+    g = rng.normal(size=(len(px), 2))
+    g[-1] = 0.0
+    h, _ = _edge_keyframe(capi, H, W, px, rng, grad=g)
+    out = h.klt_track_points(0, 1, 7)[0]
+    assert np.isnan(out["flow"][-1]).all()
+    assert np.isfinite(out["flow"][:-1]).all()
+    ref, m = ko.track_points(out["coord"], _grad32(g), h.get_event_frame(0), 7)
+    _check(out["flow"], ref, m)
+
+
+def _ragged(synth, n=64, H=120, W=160):
+    Ns = [1, 2, 5, 64, 300, 1000] + [int(x) for x in np.random.default_rng(3).integers(1, 1000, size=n - 6)]
+    return [synth.make_alignment(500 + b, H=H, W=W, N=Ns[b], layout="edges" if b % 3 == 0 else "uniform") for b in range(n)]
+
+
+def _load_shared(capi, als, H, W):
+    h = _handle(capi, als, H, W)
+    for b in range(1, len(als), 5):             # some alignments sample another slot's frame
+        h.share_event_frame(b, b - 1)
+    return h
+
+
+@pytest.mark.parametrize("pyr", [False, True])
+def test_batch_equals_singles_and_repeats(gpu, capi, synth, pyr):
+    H, W = 120, 160
+    als = _ragged(synth)
+    runs = []
+    for mode in ("batch", "batch", "singles"):
+        h = _load_shared(capi, als, H, W)
+        call = (lambda f, c: h.klt_track_points_pyr(f, c, 3)) if pyr else (lambda f, c: h.klt_track_points(f, c, 7))
+        outs = call(0, len(als)) if mode == "batch" else [call(b, 1)[0] for b in range(len(als))]
+        runs.append(outs)
+        h.close()
+    for b in range(len(als)):
+        for k in ("coord", "tracks", "flow", "kept"):
+            assert np.array_equal(runs[0][b][k], runs[1][b][k], equal_nan=True), (b, k)
+            assert np.array_equal(runs[0][b][k], runs[2][b][k], equal_nan=True), (b, k)
+    # and the shared frames are the ones sampled: parity of a sharing slot against its source's frame
+    h = _load_shared(capi, als, H, W)
+    out = h.klt_track_points(0, 7, 7)[6]             # slot 6 samples slot 5's frame
+    ref, m = ko.track_points(out["coord"], _grad32(als[6].grad)[out["kept"]], h.get_event_frame(5), 7)
+    assert np.array_equal(h.get_event_frame(6), h.get_event_frame(5))
+    _check(out["flow"], ref, m)
+
+
+def test_erasure_matches_get_coord_and_compacts_seeds(gpu, capi, synth):
+    H, W = 120, 160
+    al = synth.make_alignment(77, H=H, W=W, N=800)
+    p = np.array([1.0, -0.5, 0.0])                   # pushes part of the points out of the frame
+    twins = []
+    for _ in range(2):
+        h = _handle(capi, [al], H, W)
+        h.set_state(0, p, al.q0, al.v0)
+        h.depth_init(0, 1, min_depth=0.5, max_depth=6.0)
+        twins.append(h)
+    ref = twins[1].update_points(0, True)
+    out = twins[0].klt_track_points(0, 1, 5)[0]
+    assert 0 < out["n"] < al.N
+    assert np.array_equal(out["kept"], ref["kept"])
+    assert np.array_equal(out["coord"], ref["coord"])
+    assert np.array_equal(twins[0].depth_get(0)[0], twins[1].depth_get(0)[0])
+    # tracks before the KLT step are getCoord's: tracks - flow == update_points' tracks
+    ok = np.isfinite(out["flow"]).all(1)
+    assert np.array_equal((out["tracks"] - out["flow"])[ok], ref["tracks"][ok]) or \
+        np.allclose((out["tracks"] - out["flow"])[ok], ref["tracks"][ok], rtol=0, atol=1e-9)
+
+
+def test_pyr_flow_accumulates_and_new_keyframe_zeroes(gpu, capi, synth):
+    H, W = 120, 160
+    al = synth.make_alignment(88, H=H, W=W, N=600)
+    h = _handle(capi, [al], H, W)
+    o1 = h.klt_track_points_pyr(0, 1, 3)[0]
+    o2 = h.klt_track_points_pyr(0, 1, 3)[0]
+    assert np.array_equal(o1["coord"], o2["coord"])         # same pose, same frame: the same f again
+    assert np.array_equal(o2["flow"], o1["flow"] + o1["flow"], equal_nan=True)
+    assert np.array_equal(o2["tracks"], o1["tracks"], equal_nan=True)      # tracks restart from getCoord's on every call
+    # trackPoints assigns the flow
+    o3 = h.klt_track_points(0, 1, 7)[0]
+    assert np.array_equal(h.klt_get(0)[1], o3["flow"], equal_nan=True)
+    h.set_alignment(0, al)                                  # a new keyframe: tracks and flow back to zero
+    t, f = h.klt_get(0)
+    assert not t.any() and not f.any()
+
+
+def test_device_tracks_equal_host_tracks(gpu, capi, synth):
+    H, W = 120, 160
+    als = [synth.make_alignment(900 + b, H=H, W=W, N=400 + 50 * b) for b in range(4)]
+    hs = []
+    for _ in range(2):
+        h = _handle(capi, als, H, W)
+        h.klt_track_points(0, len(als), 7)
+        h.depth_init(0, len(als), min_depth=0.5, max_depth=6.0)
+        hs.append(h)
+    s_dev = hs[0].depth_update(0, len(als), capi.DEPTH_DEVICE_TRACKS)
+    tr = [hs[1].klt_get(b)[0] for b in range(len(als))]
+    s_host = hs[1].depth_update(0, len(als), capi.DEPTH_TRACKS, xy=tr)
+    assert s_dev == s_host
+    for b in range(len(als)):
+        assert np.array_equal(hs[0].depth_get(b)[0], hs[1].depth_get(b)[0], equal_nan=True)
+
+
+def test_4096_alignments(gpu, capi, synth):
+    H, W = 480, 640
+    base = [synth.make_alignment(1000 + k, H=H, W=W, N=2000, layout="edges" if k % 2 else "uniform") for k in range(8)]
+    cfg = capi.default_config(solver=capi.SOLVER_LM6, exec=capi.EXEC_DEVICE, max_num_iterations=4)
+    B = 4096
+    h = capi.Handle(cfg, B, 2000, H, W)
+    rng = np.random.default_rng(4)
+    for b in range(B):
+        a = base[b % 8]
+        h.set_keyframe(b, a.norm_coord, a.grad, a.idp, a.weights, a.fx, a.fy, a.cx, a.cy)
+        if b < 8:
+            h.set_event_frame(b, a.frame)
+        else:
+            h.share_event_frame(b, b % 8)
+        h.set_state(b, a.p0 + rng.normal(scale=1e-3, size=3), a.q0, a.v0)
+    outs = h.klt_track_points(0, B, 7)
+    for b in sorted(set([0, 1, 7, 8, 1000, 2047, 3001, 4095])):
+        a, out = base[b % 8], outs[b]
+        ref, m = ko.track_points(out["coord"], _grad32(a.grad)[out["kept"]], h.get_event_frame(b), 7)
+        _check(out["flow"], ref, m)
+
+
+def test_errors_leave_state_alone(gpu, capi, synth):
+    H, W = 120, 160
+    al = synth.make_alignment(31, H=H, W=W, N=300)
+    cfg = capi.default_config(solver=capi.SOLVER_LM6, exec=capi.EXEC_DEVICE, max_num_iterations=4)
+    h = capi.Handle(cfg, 3, 300, H, W)
+    h.set_alignment(0, al)
+    h.set_keyframe(1, al.norm_coord, al.grad, al.idp, al.weights, al.fx, al.fy, al.cx, al.cy)    # no event frame
+    L = capi.lib()
+
+    def code(fn, *a):
+        with pytest.raises(capi.EdsError) as e:
+            fn(*a)
+        return e.value.code
+
+    # no KLT yet: no device tracks
+    assert code(h.klt_get, 0) == capi.ERR_STATE
+    h.depth_init(0, 1)
+    assert code(h.depth_update, 0, 1, capi.DEPTH_DEVICE_TRACKS) == capi.ERR_STATE
+    for r in (-1, 32):
+        assert code(h.klt_track_points, 0, 1, r) == capi.ERR_INVALID
+    for lv in (0, 6):
+        assert code(h.klt_track_points_pyr, 0, 1, lv) == capi.ERR_INVALID
+    assert code(h.klt_track_points, 2, 2, 7) == capi.ERR_INVALID            # range past the handle
+    assert code(h.klt_track_points, -1, 1, 7) == capi.ERR_INVALID
+    assert code(h.klt_track_points, 1, 1, 7) == capi.ERR_STATE              # keyframe, no frame
+    assert code(h.klt_track_points, 2, 1, 7) == capi.ERR_STATE              # nothing at all
+    buf = np.zeros((1, 10, 2))
+    rc = L.eds_klt_track_points(h._h, 0, 1, 7, 10, buf.ctypes.data_as(C.POINTER(C.c_double)), None, None, None, None)
+    assert rc == capi.ERR_INVALID                                             # stride below the point count
+    assert L.eds_klt_get(h._h, 0, None, None) == capi.ERR_INVALID
+    assert h._N[0] == 300 and h.update_points(0, False)["coord"].shape == (300, 2)   # nothing was erased by the failed calls
+    out = h.klt_track_points(0, 1, 7)[0]
+    assert out["n"] >= 1
+    t, f = h.klt_get(0)
+    assert t.shape == (out["n"], 2)
+    assert code(h.depth_update, 0, 1, 7) == capi.ERR_INVALID                  # unknown sources stay invalid
+    assert code(h.depth_update, 0, 1, capi.DEPTH_TRACKS) == capi.ERR_INVALID  # TRACKS without xy stays invalid
+    h.depth_update(0, 1, capi.DEPTH_DEVICE_TRACKS)
+    # an optimize_batch in flight: STATE
+    h.optimize_batch(0, 0, 1, sync=False)
+    assert code(h.klt_track_points, 0, 1, 7) == capi.ERR_STATE
+    assert code(h.klt_get, 0) == capi.ERR_STATE
+    h.sync()
+    h.klt_track_points(0, 1, 7)
+
+
+def test_tracker_mirror(gpu, capi, synth):
+    import importlib
+    trk = importlib.import_module("slam-eds_amd.tracker")
+    H, W = 120, 160
+    al = synth.make_alignment(61, H=H, W=W, N=500)
+    K = np.array([[al.fx, 0, al.cx], [0, al.fy, al.cy], [0, 0, 1.0]])
+    kf = trk.KeyFrame(al.norm_coord.copy(), al.grad.copy(), al.weights.copy(), al.idp.copy(), K, H, W,
+                      coord=_kf_pixels(al))
+    t = trk.Tracker(kf, trk.Config(solver=capi.SOLVER_LM6, options=trk.SolverOptions(max_num_iterations=[4])))
+    t.px, t.qx = al.p0.copy(), al.q0.copy()
+    t.trackPointsPyr(al.frame, 3)
+    f1 = kf.flow.copy()
+    t.trackPointsPyr(al.frame, 3)
+    assert np.array_equal(kf.flow, f1 + f1, equal_nan=True)                 # the mirror keeps kf.flow across its re-uploads
+    # the same points on a handle of our own
+    h = _handle(capi, [al], H, W)
+    o = h.klt_track_points_pyr(0, 1, 3)[0]
+    assert np.array_equal(o["flow"], f1, equal_nan=True)
+    t.trackPoints(al.frame, 7)
+    o = h.klt_track_points(0, 1, 7)[0]
+    assert np.array_equal(kf.flow, o["flow"], equal_nan=True) and np.array_equal(kf.tracks, o["tracks"], equal_nan=True)
+    assert len(kf.inv_depth) == o["n"]
+    t.close()
