@@ -177,6 +177,14 @@ class BatchTracker:
             return self.handle.klt_track_points_pyr(0, self.count, num_level)
         return self.handle.klt_track_points(0, self.count, patch_radius)
 
+    def track_points_along_epiline(self, patch_radius: int = 7, border_type: int = 4, border_value: int = 255, erase: bool = True) -> list:
+        """Optional step after solve(): Tracker::trackPointsAlongEpiline of this shard on the device (include/eds_hip_epiline.h)
+        against each alignment's event frame.  The kept points' p_ssd stay in HBM, where handle.epi_depth_update reads them.
+        Returns per alignment dict(ssd, ncc, scores, ef, kept, n)."""
+        if self.count == 0:
+            return []
+        return self.handle.epi_track_points(0, self.count, patch_radius, border_type, border_value, erase)
+
     def local_results(self) -> np.ndarray:
         if self.count == 0:
             return np.zeros((0, RESULT_WIDTH))

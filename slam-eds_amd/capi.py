@@ -60,6 +60,11 @@ DEPTH_VOGIATZIS, DEPTH_GAUSS = 0, 1
 # every symbol include/eds_hip_klt.h declares: the KLT point trackers (their own header and ABI version)
 KLT_EXPORTS = ("eds_klt_abi_version", "eds_klt_track_points", "eds_klt_track_points_pyr", "eds_klt_get")
 
+# every symbol include/eds_hip_epiline.h declares: the epiline tracker (its own header and ABI version)
+EPI_EXPORTS = ("eds_epi_abi_version", "eds_epi_track_points", "eds_epi_get", "eds_epi_get_model", "eds_epi_depth_update")
+# enum eds_epi_border: cv::BORDER_* (BORDER_DEFAULT = REFLECT_101)
+EPI_BORDER_CONSTANT, EPI_BORDER_REPLICATE, EPI_BORDER_REFLECT, EPI_BORDER_REFLECT_101 = 0, 1, 2, 4
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -148,6 +153,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_depth.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_klt.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_epiline.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
@@ -269,6 +275,11 @@ def lib():
         for fn in (L.eds_klt_track_points, L.eds_klt_track_points_pyr):
             fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip]
         L.eds_klt_get.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.eds_epi_track_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp,
+                                           _ip, _ip]
+        L.eds_epi_get.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.eds_epi_get_model.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.eds_epi_depth_update.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(DepthSummary)]
         if L.eds_trk_cfg_size() != C.sizeof(Cfg) or L.eds_trk_info_size() != C.sizeof(Info):
             raise EdsError(ERR_INVALID, "ctypes struct layout disagrees with include/eds_hip.h")
         _lib = L
@@ -643,6 +654,46 @@ class Handle:
         tracks, flow = np.zeros((N, 2)), np.zeros((N, 2))
         _check(lib().eds_klt_get(self._h, int(slot), _p(tracks), _p(flow)))
         return tracks, flow
+
+    # -- epiline tracker (include/eds_hip_epiline.h) -------------------------------------------
+    def epi_track_points(self, first=0, count=None, patch_radius=7, border_type=EPI_BORDER_REFLECT_101, border_value=255, erase=True):
+        """Tracker::trackPointsAlongEpiline for slots first .. first + count - 1.  Returns per slot dict(ssd, ncc, scores) for every
+        ORIGINAL point (int pixel pairs, the two fp32 scores), and dict(ef, kept, n) for the points the cull kept."""
+        count = self.batch - first if count is None else count
+        stride = max(self._N[first:first + count] + [1])
+        ssd, ncc = np.zeros((count, stride, 2), dtype=np.int32), np.zeros((count, stride, 2), dtype=np.int32)
+        scores, ef = np.zeros((count, stride, 2)), np.zeros((count, stride, 2))
+        kept, n = np.zeros((count, stride), dtype=np.int32), np.zeros(count, dtype=np.int32)
+        n0 = list(self._N[first:first + count])
+        _check(lib().eds_epi_track_points(self._h, int(first), int(count), int(patch_radius), int(border_type), int(border_value),
+                                          int(bool(erase)), stride, ssd.ctypes.data_as(_ip), ncc.ctypes.data_as(_ip), _p(scores), _p(ef),
+                                          kept.ctypes.data_as(_ip), n.ctypes.data_as(_ip)))
+        out = []
+        for b in range(count):
+            self._N[first + b] = int(n[b])
+            out.append(dict(ssd=ssd[b, :n0[b]], ncc=ncc[b, :n0[b]], scores=scores[b, :n0[b]], ef=ef[b, :n[b]], kept=kept[b, :n[b]],
+                            n=int(n[b])))
+        return out
+
+    def epi_get(self, slot):
+        """the device ef plane of one slot, N x 2"""
+        ef = np.zeros((self._N[slot], 2))
+        _check(lib().eds_epi_get(self._h, int(slot), _p(ef)))
+        return ef
+
+    def epi_get_model(self, slot):
+        """getModel(v, w, "bilinear", 0.5) at the slot's velocity and points, H x W fp64"""
+        m = np.zeros((self.H, self.W))
+        _check(lib().eds_epi_get_model(self._h, int(slot), _p(m)))
+        return m
+
+    def epi_depth_update(self, first=0, count=None, T_kf_ef=None, filter=DEPTH_VOGIATZIS):
+        """DepthPoints::update(T_kf_ef, kf->coord, ef_coord) with ef_coord = the device ef plane; returns the summaries"""
+        count = self.batch - first if count is None else count
+        T = None if T_kf_ef is None else _f64(T_kf_ef).reshape(count, 7)
+        out = (DepthSummary * count)()
+        _check(lib().eds_epi_depth_update(self._h, int(first), int(count), _p(T), int(filter), out))
+        return [o.as_dict() for o in out]
 
     # -- inverse-depth filter (include/eds_hip_depth.h) -----------------------------------------
     def depth_init(self, first=0, count=None, source=DEPTH_INIT_CONSTANT, idp=None, min_depth=1.0, max_depth=3.0, threshold=100.0,

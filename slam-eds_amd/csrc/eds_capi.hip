@@ -104,6 +104,7 @@ void free_all(eds_trk* h) {
     eds_points_free(&h->point_ops);
     eds_depth_free(&h->depth);
     eds_klt_free(&h->klt);
+    eds_epi_free(&h->epi);
     eds_keyframe_free(&h->kf_build);
     void* hptrs[] = {h->h_pose, h->h_part, h->h_G, h->h_f32, h->h_r, h->h_fstage, h->h_rmap, h->h_idp, h->h_fprog, h->h_bstage};
     for (hipEvent_t e : h->ev_bstage) hipEventDestroy(e);
@@ -542,6 +543,7 @@ int eds_trk_update_points(eds_trk* h, int slot, int delete_out_points, double* c
     EDS_HIP_TRY(hipSetDevice(h->dev));
     int n = 0;
     if ((rc = eds_points_update(h, slot, delete_out_points != 0, coord_xy, tracks_xy, kept_index, &n, mean_sq_flow))) return rc;
+    if (delete_out_points) s.epi_valid = false;     // the point set may have changed: the epiline's ef plane is stale
     if (n_kept) *n_kept = n;
     if (n != s.N) {                      // points were erased: every index-aligned plane was compacted on the device
         s.N = n;
@@ -577,6 +579,7 @@ int edscapi::update_points_range(eds_trk* h, int first, int count, int delete_ou
     bool any = false;
     for (int b = 0; b < count; ++b) {
         Slot& s = h->slots[first + b];
+        if (delete_out_points) s.epi_valid = false;     // the point set may have changed: the epiline's ef plane is stale
         if (n_kept) n_kept[b] = n[b];
         if (n[b] != s.N) {                  // points were erased: every index-aligned plane was compacted on the device
             s.N = n[b];

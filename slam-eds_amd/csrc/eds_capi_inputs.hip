@@ -309,6 +309,7 @@ int eds_trk_set_keyframe(eds_trk* h, int slot, int N, const double* norm_xy, con
     s.has_kf = true;
     s.seeded = false;                   // a new keyframe: its DepthPoints are seeded again (KeyFrame::setDepthMap, KeyFrame.cpp:1197)
     eds_klt_reset_slot(h, slot);        // ... and its tracks and flow start at zero (KeyFrame::create, KeyFrame.cpp:447-448)
+    s.epi_valid = false;                // ... and it has no epiline correspondences yet
     // residuals and trace of an earlier solve belong to the previous keyframe: drop the host copy AND the "still in HBM" marks,
     // so that get_residuals / loss_param before the next optimize report EDS_ERR_STATE instead of another keyframe's plane
     s.residuals.clear();

@@ -385,12 +385,19 @@ int eds_depth_init(eds_trk* h, int first, int count, const eds_depth_params* prm
 
 int eds_depth_update(eds_trk* h, int first, int count, int coords, const double* xy, const double* kf_xy, int stride, const double* T_kf_ef,
                      int filter, eds_depth_summary* out) {
+    return eds_depth_update_impl(h, first, count, coords, xy, kf_xy, stride, T_kf_ef, filter, out, nullptr);
+}
+
+}  // extern "C"
+
+int eds_depth_update_impl(eds_trk* h, int first, int count, int coords, const double* xy, const double* kf_xy, int stride,
+                          const double* T_kf_ef, int filter, eds_depth_summary* out, const double* dev_ef) {
     int rc = check_common(h, first, count, true);
     if (rc) return rc;
     if (coords < EDS_DEPTH_TRACKS || coords > EDS_DEPTH_DEVICE_TRACKS) return fail(EDS_ERR_INVALID, "unknown coordinate source");
     if (filter != EDS_DEPTH_VOGIATZIS && filter != EDS_DEPTH_GAUSS) return fail(EDS_ERR_INVALID, "unknown depth filter");
     const bool on_device = coords == EDS_DEPTH_REPROJECT || coords == EDS_DEPTH_DEVICE_TRACKS;
-    if (!xy && !on_device) return fail(EDS_ERR_INVALID, "null event-frame coordinates");
+    if (!xy && !dev_ef && !on_device) return fail(EDS_ERR_INVALID, "null event-frame coordinates");
     if (on_device) xy = nullptr;
     if ((xy || kf_xy) && stride < max_points(h, first, count)) return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
     if (coords == EDS_DEPTH_DEVICE_TRACKS && !h->klt.tracks)
@@ -438,7 +445,7 @@ int eds_depth_update(eds_trk* h, int first, int count, int coords, const double*
     EDS_HIP_TRY(hipMemsetAsync(d.d_sum, 0, (size_t)count * EDS_DEPTH_SUM * 4, h->st));
     const int nchunk = (h->Np + EDS_DEPTH_TPB - 1) / EDS_DEPTH_TPB;
     hipLaunchKernelGGL(k_depth_update, dim3((unsigned)count * nchunk), dim3(EDS_DEPTH_TPB), 0, h->st, h->arrays(), d.seeds, d.d_par, first, nchunk,
-                       coords, xy ? d.d_in : nullptr, kf_xy ? d.d_in + half : nullptr, h->klt.tracks, d.d_sum);
+                       coords, dev_ef ? dev_ef : (xy ? d.d_in : nullptr), kf_xy ? d.d_in + half : nullptr, h->klt.tracks, d.d_sum);
     EDS_HIP_TRY(hipGetLastError());
     if ((rc = finish_planes(h, first, count))) return rc;
     EDS_HIP_TRY(hipMemcpyAsync(d.h_sum, d.d_sum, (size_t)count * EDS_DEPTH_SUM * 4, hipMemcpyDeviceToHost, h->st));
@@ -446,6 +453,8 @@ int eds_depth_update(eds_trk* h, int first, int count, int coords, const double*
     if (out) std::memcpy(out, d.h_sum, (size_t)count * sizeof(eds_depth_summary));
     return EDS_OK;
 }
+
+extern "C" {
 
 int eds_depth_get(eds_trk* h, int slot, double* mu_s2_a_b, uint8_t* converged) {
     int rc = check_common(h, slot, 1, true);

@@ -24,3 +24,8 @@ void eds_depth_free(EdsDepthBuffers* db);
 // getCoord's compaction of slots first .. first + count - 1 has just been launched with its kept indices in `kept` ([count][Np],
 // device view): gather the seeds of those slots the same way, on the same stream (eds_points.hip)
 void eds_depth_compact(eds_trk* h, int first, int count, const int* kept);
+struct eds_depth_summary;
+// eds_depth_update's body.  dev_ef (or null): EDS_DEPTH_EF_COORD's coordinates already in HBM, [count][Np][2] (b relative to
+// first) — the epiline's ef plane (eds_epiline.hip); xy is then not read
+int eds_depth_update_impl(eds_trk* h, int first, int count, int coords, const double* xy, const double* kf_xy, int stride,
+                          const double* T_kf_ef, int filter, eds_depth_summary* out, const double* dev_ef);

@@ -1,0 +1,633 @@
+// The epiline tracker of EDS on the device (include/eds_hip_epiline.h): Tracker::trackPointsAlongEpiline (reference
+// src/tracking/Tracker.cpp:490-553) for the points of a tracker slot.
+//
+//   k_epi_values     one workgroup per alignment: getSparseModel (KeyFrame.cpp:1358-1403) — the keyframe pixel the slot holds, the
+//                    flow compute_flow(norm_coord, v, w, mu) (Utils.hpp:165-173), m = -(g . f), then m / sqrt(1e-3 + sum m^2) with
+//                    the sum in point order
+//   k_klt_bin        (eds_klt.hip) the keyframe pixels binned by splat row: keys (y0, x0, i), no per-pixel scratch
+//   k_epi_model      drawValuesPoints (Utils.cpp:124-193), bilinear, every pixel summing its contributions in point order, then the
+//                    3 x 3 Gaussian blur (sigma 0.5, reflect-101), per 32 x 8 tile: the model image [B][H][W] in fp64
+//   k_epi_templates  one wavefront per point: splitImageInPatches (Utils.cpp:608-633) at the TRUNCATED keyframe pixel, the patch in
+//                    fp32, S = sum T^2 exactly in fp64, and the non-zero taps compacted in row-major order as (LDS offset, value)
+//   k_epi_pad        copyMakeBorder(event_frame, r, border) in fp32 (Tracker.cpp:505-506)
+//   k_epi_rowsq / k_epi_energy   E = the window sums of P^2 in fp64 (separable), kept as fp32 (E, sqrt E) per position
+//   k_epi_match      the hot path.  One workgroup per (64 x 32 tile of positions, 32 templates, alignment): the tile's padded image
+//                    in LDS, per template C = sum_taps P T over its NON-ZERO taps in fp32 (8 positions per lane), the two normed scores
+//                    and their arg-extrema fused behind it; one 64-bit atomicMin per wavefront and method on a (orderable fp32 score,
+//                    row-major index) key.  No (position, template) value is ever stored, no float atomics.
+//   k_epi_finish     per point: the locations and scores from the keys, the cull |‖p_ssd‖ - ‖p_ncc‖| > 5 in fp64
+//   then getCoord's compaction (k_update_points, eds_points.hip) erases the culled points by flag, with the seeds and the KLT's
+//   tracks and flow; k_epi_gather writes the kept points' p_ssd into the ef plane.
+//
+// The model image and templates are fp64 without FMA contraction: this translation unit is compiled with -ffp-contract=off (Makefile);
+// the correlation's fp32 multiply-adds are explicit fmaf.  Every sum has a fixed order and the cross-workgroup combine is an integer
+// min, so a batch equals its singles bit for bit and runs repeat exactly.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/eds_hip_epiline.h"
+#include "../../include/eds_hip_depth.h"
+#include "eds_capi_internal.hpp"
+#include "eds_depth.hpp"
+#include "eds_device.hpp"
+
+using namespace edscapi;
+using namespace edsd;
+
+#define EDS_EPI_MAX_RADIUS 15
+#define EDS_EPI_PAR 16              // per slot: fx fy cx cy, v[6], seeded
+#define EDS_EPI_VAL_THREADS 1024
+#define EDS_EPI_MODEL_TW 32         // k_epi_model tile
+#define EDS_EPI_MODEL_TH 8
+#define EDS_EPI_TW 64               // k_epi_match tile: one column per lane ...
+#define EDS_EPI_ROWS 8              // ... EDS_EPI_ROWS rows per lane ...
+#define EDS_EPI_TH (4 * EDS_EPI_ROWS)   // ... four wavefronts
+#define EDS_EPI_GROUP 32            // templates per workgroup
+#define EDS_EPI_CHUNK 16            // alignments per pass of the per-radius work buffers
+
+namespace {
+
+// cv::borderInterpolate(p, len, type) for REPLICATE, REFLECT and REFLECT_101, repeated while p is outside
+__device__ __forceinline__ int border_map(int p, int len, int type) {
+    if ((unsigned)p < (unsigned)len) return p;
+    if (type == EDS_EPI_BORDER_REPLICATE) return p < 0 ? 0 : len - 1;
+    if (len == 1) return 0;
+    const int delta = type == EDS_EPI_BORDER_REFLECT_101 ? 1 : 0;
+    do {
+        if (p < 0) p = -p - 1 + delta;
+        else p = len - 1 - (p - len) - delta;
+    } while ((unsigned)p >= (unsigned)len);
+    return p;
+}
+
+__device__ __forceinline__ int reflect101(int p, int len) { return border_map(p, len, EDS_EPI_BORDER_REFLECT_101); }
+
+__device__ __forceinline__ int key_x0(uint64_t k) { return (int)((k >> 32) & 0xffffu); }
+__device__ __forceinline__ unsigned key_i(uint64_t k) { return (unsigned)(k & 0xffffffffu); }
+
+__device__ __forceinline__ int lower_x(const uint64_t* __restrict__ K, int lo, int hi, int xv) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key_x0(K[mid]) < xv) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// fp32 score -> unsigned key ascending with the score; -0 and +0 map to the same key
+__device__ __forceinline__ unsigned ord_key(float s) {
+    const unsigned u = __float_as_uint(s + 0.0f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord_val(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(EDS_EPI_VAL_THREADS) void k_epi_values(EdsArrays A, int first, const double* __restrict__ par,
+                                                                    const double* __restrict__ seeds_mu, double* __restrict__ kpix,
+                                                                    double* __restrict__ mval) {
+    __shared__ double s_sq[EDS_EPI_VAL_THREADS];
+    __shared__ double s_norm;
+    const int slot = first + blockIdx.x, tid = threadIdx.x;
+    const int N = (int)A.pose[(size_t)slot * EDS_POSE_STRIDE + EDS_PB_N];
+    const double* P = par + (size_t)slot * EDS_EPI_PAR;
+    const double fx = P[0], fy = P[1], cx = P[2], cy = P[3];
+    const double v0 = P[4], v1 = P[5], v2 = P[6], w0 = P[7], w1 = P[8], w2 = P[9];
+    const bool seeded = P[10] != 0.0;
+    const size_t base = (size_t)slot * A.Np;
+    for (int i = tid; i < N; i += EDS_EPI_VAL_THREADS) {
+        const size_t o = base + i;
+        const int c = A.cell0[o];
+        const double u = (double)(short)(c & 0xffff) + (double)A.f0x[o], v = (double)(c >> 16) + (double)A.f0y[o];
+        kpix[2 * o] = u; kpix[2 * o + 1] = v;
+        const double xp = (u - cx) / fx, yp = (v - cy) / fy;                  // KeyFrame.cpp:1373-1374
+        const double idp = seeded ? seeds_mu[o] : (double)A.rho[o];           // mu(inv_depth)
+        // compute_flow, left to right as written (Utils.hpp:165-173); std::pow(x, 2) is x * x correctly rounded
+        const double f0 = (-idp * v0) + (xp * idp * v2) + (xp * yp * w0) - (1.0 + xp * xp) * w1 + (yp * w2);
+        const double f1 = (-idp * v1) + (yp * idp * v2) + (1.0 + yp * yp) * w0 - (xp * yp * w1) - (xp * w2);
+        mval[o] = -((double)A.gx[o] * f0 + (double)A.gy[o] * f1);
+    }
+    // model_norm_sq = 1e-3 + sum m^2 in point order (:1386-1394): squares staged per chunk, one lane adds them in order
+    double acc = 1e-03;
+    for (int c0 = 0; c0 < N; c0 += EDS_EPI_VAL_THREADS) {
+        const int i = c0 + tid;
+        if (i < N) { const double m = mval[base + i]; s_sq[tid] = m * m; }      // (this lane wrote mval[base + i] above)
+        __syncthreads();
+        if (tid == 0) {
+            const int n = min(EDS_EPI_VAL_THREADS, N - c0);
+            for (int j = 0; j < n; ++j) acc += s_sq[j];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) s_norm = sqrt(acc);
+    __syncthreads();
+    const double norm = s_norm;
+    for (int i = tid; i < N; i += EDS_EPI_VAL_THREADS) mval[base + i] = mval[base + i] / norm;
+}
+
+// drawValuesPoints + GaussianBlur 3 x 3 of one 32 x 8 tile of alignment blockIdx.y
+__global__ __launch_bounds__(256) void k_epi_model(EdsArrays A, int first, double k0, double k1, double k2, const double* __restrict__ kpix,
+                                                   const double* __restrict__ mval, const uint64_t* __restrict__ keys,
+                                                   const int* __restrict__ row_start, double* __restrict__ model) {
+    __shared__ double s_box[(EDS_EPI_MODEL_TW + 2) * (EDS_EPI_MODEL_TH + 2)];
+    const int slot = first + blockIdx.y, tid = threadIdx.x, H = A.H, W = A.W;
+    const int ntx = (W + EDS_EPI_MODEL_TW - 1) / EDS_EPI_MODEL_TW;
+    const int tx0 = (blockIdx.x % ntx) * EDS_EPI_MODEL_TW, ty0 = (blockIdx.x / ntx) * EDS_EPI_MODEL_TH;
+    const size_t base = (size_t)slot * A.Np;
+    const double* __restrict__ Cd = kpix + 2 * base;
+    const double* __restrict__ V = mval + base;
+    const uint64_t* __restrict__ K = keys + base;
+    const int* __restrict__ RS = row_start + (size_t)slot * (H + 2);
+    // the splat pixels the blurred tile reads: its pixels +- 1, inside the image (reflect-101 of -1 / W lands inside this box)
+    const int bx0 = max(0, tx0 - 1), bx1 = min(W - 1, tx0 + EDS_EPI_MODEL_TW), by0 = max(0, ty0 - 1), by1 = min(H - 1, ty0 + EDS_EPI_MODEL_TH);
+    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
+    for (int p = tid; p < bw * bh; p += 256) {
+        const int jy = p / bw, py = by0 + jy, px = bx0 + p - jy * bw;
+        // the points whose footprint corner lands on (py, px): (y0, x0) = (py-1, px-1) [wd], (py-1, px) [wb], (py, px-1) [wc],
+        // (py, px) [wa] — four runs of keys ascending in i, merged so that the pixel sums in point order (as k_klt_window)
+        int g[4][2];
+        for (int h2 = 0; h2 < 2; ++h2) {
+            const int yy = py - 1 + h2;
+            int lo = 0, hi = 0;
+            if (yy >= 0) { lo = RS[yy]; hi = RS[yy + 1]; lo = lower_x(K, lo, hi, px - 1); }
+            int q = lo;
+            g[2 * h2][0] = q;
+            while (q < hi && key_x0(K[q]) == px - 1) ++q;
+            g[2 * h2][1] = q; g[2 * h2 + 1][0] = q;
+            while (q < hi && key_x0(K[q]) == px) ++q;
+            g[2 * h2 + 1][1] = q;
+        }
+        double s = 0.0;
+        while (true) {
+            unsigned m = UINT_MAX;
+            int which = -1;
+            for (int c = 0; c < 4; ++c)
+                if (g[c][0] < g[c][1]) {
+                    const unsigned ic = key_i(K[g[c][0]]);
+                    if (ic < m) { m = ic; which = c; }
+                }
+            if (which < 0) break;
+            ++g[which][0];
+            const double xj = Cd[2 * m], yj = Cd[2 * m + 1];
+            const double x0 = floor(xj), y0 = floor(yj), x1 = x0 + 1.0, y1 = y0 + 1.0;
+            double w;
+            if (which == 0) w = (xj - x0) * (yj - y0);
+            else if (which == 1) w = (x1 - xj) * (yj - y0);
+            else if (which == 2) w = (xj - x0) * (y1 - yj);
+            else w = (x1 - xj) * (y1 - yj);
+            s = s + w * V[m];
+        }
+        s_box[p] = s;
+    }
+    __syncthreads();
+    const int ly = tid / EDS_EPI_MODEL_TW, lx = tid - ly * EDS_EPI_MODEL_TW;
+    const int y = ty0 + ly, x = tx0 + lx;
+    if (y >= H || x >= W) return;
+    const int xl = reflect101(x - 1, W) - bx0, xc = x - bx0, xr = reflect101(x + 1, W) - bx0;
+    const int yu = reflect101(y - 1, H) - by0, yc = y - by0, yd = reflect101(y + 1, H) - by0;
+    const double ru = k0 * s_box[yu * bw + xl] + k1 * s_box[yu * bw + xc] + k2 * s_box[yu * bw + xr];
+    const double rc = k0 * s_box[yc * bw + xl] + k1 * s_box[yc * bw + xc] + k2 * s_box[yc * bw + xr];
+    const double rd = k0 * s_box[yd * bw + xl] + k1 * s_box[yd * bw + xc] + k2 * s_box[yd * bw + xr];
+    model[(size_t)slot * H * W + (size_t)y * W + x] = k0 * ru + k1 * rc + k2 * rd;
+}
+
+// one wavefront per point i = blockIdx.x of chunk alignment blockIdx.y (slot first + blockIdx.y)
+__global__ __launch_bounds__(64) void k_epi_templates(EdsArrays A, int first, int r, int border, double bval, int pitch,
+                                                      const double* __restrict__ kpix, const double* __restrict__ model,
+                                                      int2* __restrict__ taps, float4* __restrict__ tmeta) {
+    const int i = blockIdx.x, b = blockIdx.y, slot = first + b, lane = threadIdx.x, H = A.H, W = A.W;
+    const int N = (int)A.pose[(size_t)slot * EDS_POSE_STRIDE + EDS_PB_N];
+    if (i >= N) return;
+    const int S = 2 * r + 1, K = S * S;
+    const size_t o = (size_t)slot * A.Np + i, t = (size_t)b * A.Np + i;
+    // cv::Rect of a Point2d: the coordinates TRUNCATED.  The slot's pixel is cell + fp32 fraction, so a pixel that fx ((u - cx) / fx) + cx
+    // put 1e-13 below an integer u holds the fraction 1.0f and comes back as u exactly
+    const int tx = (int)kpix[2 * o], ty = (int)kpix[2 * o + 1];
+    const double* __restrict__ M = model + (size_t)slot * H * W;
+    int2* __restrict__ T = taps + t * K;
+    int cnt = 0;
+    double ss = 0.0;
+    for (int j0 = 0; j0 < K; j0 += 64) {
+        const int j = j0 + lane;
+        float v = 0.0f;
+        int off = 0;
+        if (j < K) {
+            const int ky = j / S, kx = j - ky * S;
+            const int my = ty - r + ky, mx = tx - r + kx;           // the padded model's (ty + ky, tx + kx)
+            double mv;
+            if (border == EDS_EPI_BORDER_CONSTANT && ((unsigned)my >= (unsigned)H || (unsigned)mx >= (unsigned)W)) mv = bval;
+            else mv = M[(size_t)border_map(my, H, border) * W + border_map(mx, W, border)];
+            v = (float)mv;                                           // convertTo(CV_32FC1) (Tracker.cpp:524)
+            off = ky * pitch + kx;
+            ss += (double)v * (double)v;
+        }
+        const bool nz = j < K && v != 0.0f;
+        const unsigned long long m = __ballot(nz);
+        if (nz) {
+            const int pos = cnt + __popcll(m & ((1ull << lane) - 1ull));
+            T[pos] = make_int2(off, __float_as_int(v));
+        }
+        cnt += __popcll(m);
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off, 64);
+    if (lane == 0) tmeta[t] = make_float4(__int_as_float(cnt), (float)ss, (float)sqrt(ss), 0.0f);
+}
+
+// copyMakeBorder(event_frame, r, border, bval) in fp32, [chunk][(H + 2r) (W + 2r)]
+__global__ __launch_bounds__(256) void k_epi_pad(EdsArrays A, int first, int r, int border, float bval, float* __restrict__ pad) {
+    const int b = blockIdx.y, slot = first + b, H = A.H, W = A.W, Wp2 = W + 2 * r, Hp2 = H + 2 * r;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Hp2 * Wp2) return;
+    const int py = q / Wp2, px = q - py * Wp2, iy = py - r, ix = px - r;
+    float v;
+    if (border == EDS_EPI_BORDER_CONSTANT && ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W)) v = bval;
+    else {
+        const FrameView fv = make_frame_view(A.frame, (int)A.pose[(size_t)slot * EDS_POSE_STRIDE + EDS_PB_FRAME], H, W, A.Hp, A.Wp, A.tiled);
+        v = fv.base[frame_index(fv, border_map(iy, H, border), border_map(ix, W, border))];
+    }
+    pad[(size_t)b * Hp2 * Wp2 + q] = v;
+}
+
+// row sums of P^2 over 2r + 1 columns, [chunk][(H + 2r) W] fp64
+__global__ __launch_bounds__(256) void k_epi_rowsq(int H, int W, int r, const float* __restrict__ pad, double* __restrict__ rowsq) {
+    const int b = blockIdx.y, Wp2 = W + 2 * r, Hp2 = H + 2 * r;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Hp2 * W) return;
+    const int py = q / W, x = q - py * W;
+    const float* P = pad + (size_t)b * Hp2 * Wp2 + (size_t)py * Wp2 + x;
+    double s = 0.0;
+    for (int k = 0; k <= 2 * r; ++k) s += (double)P[k] * (double)P[k];
+    rowsq[(size_t)b * Hp2 * W + q] = s;
+}
+
+// E of every position = the column sums of the row sums; kept as fp32 (E, sqrt E)
+__global__ __launch_bounds__(256) void k_epi_energy(int H, int W, int r, const double* __restrict__ rowsq, float2* __restrict__ energy) {
+    const int b = blockIdx.y, Hp2 = H + 2 * r;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= H * W) return;
+    const int y = q / W, x = q - y * W;
+    const double* R = rowsq + (size_t)b * Hp2 * W + (size_t)y * W + x;
+    double e = 0.0;
+    for (int k = 0; k <= 2 * r; ++k) e += R[(size_t)k * W];
+    energy[(size_t)b * H * W + q] = make_float2((float)e, (float)sqrt(e));
+}
+
+// The correlation with fused scores and arg-extrema.  Workgroup (tile blockIdx.x, template group blockIdx.y, chunk alignment
+// blockIdx.z); lane = column, wavefront w = rows 8w .. 8w + 7 of the tile.  LDS: the tile's padded image, (TH + 2r) x pitch.
+__global__ __launch_bounds__(256) void k_epi_match(EdsArrays A, int first, int r, int pitch, const float* __restrict__ pad,
+                                                   const float2* __restrict__ energy, const int2* __restrict__ taps,
+                                                   const float4* __restrict__ tmeta, unsigned long long* __restrict__ best) {
+    extern __shared__ float s_img[];
+    const int b = blockIdx.z, slot = first + b, tid = threadIdx.x, H = A.H, W = A.W;
+    const int N = (int)A.pose[(size_t)slot * EDS_POSE_STRIDE + EDS_PB_N];
+    const int g0 = blockIdx.y * EDS_EPI_GROUP;
+    if (g0 >= N) return;
+    const int g1 = min(N, g0 + EDS_EPI_GROUP);
+    const int ntx = (W + EDS_EPI_TW - 1) / EDS_EPI_TW;
+    const int tx0 = (blockIdx.x % ntx) * EDS_EPI_TW, ty0 = (blockIdx.x / ntx) * EDS_EPI_TH;
+    const int Wp2 = W + 2 * r, Hp2 = H + 2 * r, K = (2 * r + 1) * (2 * r + 1);
+    const float* __restrict__ P = pad + (size_t)b * Hp2 * Wp2;
+    const int rows = EDS_EPI_TH + 2 * r;
+    for (int q = tid; q < rows * pitch; q += 256) {
+        const int ly = q / pitch, lx = q - ly * pitch;
+        const int gy = ty0 + ly, gx = tx0 + lx;
+        s_img[q] = (gy < Hp2 && gx < Wp2) ? P[(size_t)gy * Wp2 + gx] : 0.0f;
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+    const int x = tx0 + lane, yb = ty0 + wave * EDS_EPI_ROWS;
+    float e[EDS_EPI_ROWS], se[EDS_EPI_ROWS];
+    const float2* __restrict__ En = energy + (size_t)b * H * W;
+#pragma unroll
+    for (int k = 0; k < EDS_EPI_ROWS; ++k) {
+        const bool ok = x < W && yb + k < H;
+        const float2 v = ok ? En[(size_t)(yb + k) * W + x] : make_float2(0.0f, 0.0f);
+        e[k] = v.x; se[k] = v.y;
+    }
+    __syncthreads();
+    const float* __restrict__ L = s_img + wave * EDS_EPI_ROWS * pitch + lane;
+    for (int t = g0; t < g1; ++t) {
+        const size_t tt = (size_t)b * A.Np + t;
+        const float4 mt = tmeta[tt];
+        const int nnz = __float_as_int(mt.x);
+        const float S = mt.y, sS = mt.z;
+        const int2* __restrict__ T = taps + tt * K;
+        float acc[EDS_EPI_ROWS];
+#pragma unroll
+        for (int k = 0; k < EDS_EPI_ROWS; ++k) acc[k] = 0.0f;
+        for (int j = 0; j < nnz; ++j) {
+            const int2 tv = T[j];
+            const float v = __int_as_float(tv.y);
+            const float* __restrict__ Lp = L + tv.x;
+#pragma unroll
+            for (int k = 0; k < EDS_EPI_ROWS; ++k) acc[k] = fmaf(Lp[k * pitch], v, acc[k]);
+        }
+        // the normed scores (OpenCV's common_matchTemplate rule) and this lane's arg-extrema, first index on a tie
+        unsigned long long kssd = ~0ull, kncc = ~0ull;
+#pragma unroll
+        for (int k = 0; k < EDS_EPI_ROWS; ++k) {
+            if (x >= W || yb + k >= H) continue;
+            const float C = acc[k], tn = se[k] * sS;
+            const float rt = __builtin_amdgcn_rcpf(tn);
+            const float aC = fabsf(C);
+            const float cc = aC < tn ? C * rt : (aC < 1.125f * tn ? (C > 0.0f ? 1.0f : -1.0f) : 0.0f);
+            float num = (e[k] - 2.0f * C) + S;
+            num = num < 0.0f ? 0.0f : num;                  // MAX(num, 0): a NaN stays NaN
+            const float sd = num < tn ? num * rt : 1.0f;
+            const unsigned long long idx = (unsigned long long)((yb + k) * W + x);
+            if (isfinite(sd)) { const unsigned long long kk = ((unsigned long long)ord_key(sd) << 32) | idx; kssd = kk < kssd ? kk : kssd; }
+            if (isfinite(cc)) { const unsigned long long kk = ((unsigned long long)(~ord_key(cc)) << 32) | idx; kncc = kk < kncc ? kk : kncc; }
+        }
+        kssd = wave_min64(kssd);
+        kncc = wave_min64(kncc);
+        if (lane == 0) {
+            unsigned long long* dst = best + 2 * ((size_t)slot * A.Np + t);
+            if (kssd != ~0ull) atomicMin(dst, kssd);
+            if (kncc != ~0ull) atomicMin(dst + 1, kncc);
+        }
+    }
+}
+
+// per original point: locations and scores from the keys, the cull in fp64 (Tracker.cpp:532)
+__global__ __launch_bounds__(256) void k_epi_finish(EdsArrays A, int first, const unsigned long long* __restrict__ best, int32_t* __restrict__ loc,
+                                                    double* __restrict__ score, double* __restrict__ ef_tmp, unsigned char* __restrict__ erase) {
+    const int slot = first + blockIdx.y, i = blockIdx.x * 256 + threadIdx.x, W = A.W;
+    const int N = (int)A.pose[(size_t)slot * EDS_POSE_STRIDE + EDS_PB_N];
+    if (i >= N) return;
+    const size_t o = (size_t)slot * A.Np + i;
+    const unsigned long long ks = best[2 * o], kn = best[2 * o + 1];
+    int sx = -1, sy = -1, nx = -1, ny = -1;
+    double ssd = __builtin_nan(""), ncc = __builtin_nan("");
+    if (ks != ~0ull) { const unsigned id = (unsigned)ks; sx = (int)(id % (unsigned)W); sy = (int)(id / (unsigned)W); ssd = ord_val((unsigned)(ks >> 32)); }
+    if (kn != ~0ull) { const unsigned id = (unsigned)kn; nx = (int)(id % (unsigned)W); ny = (int)(id / (unsigned)W); ncc = ord_val(~(unsigned)(kn >> 32)); }
+    loc[4 * o] = sx; loc[4 * o + 1] = sy; loc[4 * o + 2] = nx; loc[4 * o + 3] = ny;
+    score[2 * o] = ssd; score[2 * o + 1] = ncc;
+    ef_tmp[2 * o] = (double)sx; ef_tmp[2 * o + 1] = (double)sy;
+    // cv::norm(Point2d) = sqrt(x x + y y)
+    const double ds = sqrt((double)sx * sx + (double)sy * sy), dn = sqrt((double)nx * nx + (double)ny * ny);
+    erase[o] = (fabs(ds - dn) > 5.0 || ks == ~0ull || kn == ~0ull) ? 1 : 0;
+}
+
+// the ef plane of the kept points (kept == null: every point, in place)
+__global__ __launch_bounds__(256) void k_epi_gather(EdsArrays A, int first, const int* __restrict__ kept, const double* __restrict__ ef_tmp,
+                                                    double* __restrict__ ef) {
+    const int slot = first + blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    const int N = (int)A.pose[(size_t)slot * EDS_POSE_STRIDE + EDS_PB_N];
+    if (k >= N) return;
+    const size_t base = (size_t)slot * A.Np, plane = (size_t)A.B * A.Np;
+    const int src = kept ? kept[base + k] : k;
+    ef[base + k] = ef_tmp[2 * (base + src)];
+    ef[plane + base + k] = ef_tmp[2 * (base + src) + 1];
+}
+
+// the ef plane as eds_depth_update's EF_COORD input: [count][Np][2], b relative to first
+__global__ __launch_bounds__(256) void k_epi_to_aos(EdsArrays A, int first, const double* __restrict__ ef, double* __restrict__ out) {
+    const int b = blockIdx.y, slot = first + b, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= A.Np) return;
+    const size_t o = (size_t)slot * A.Np + k, plane = (size_t)A.B * A.Np, d = (size_t)b * A.Np + k;
+    out[2 * d] = ef[o];
+    out[2 * d + 1] = ef[plane + o];
+}
+
+template <typename T>
+int grow(T*& p, size_t& cap, size_t n) {
+    if (cap >= n) return EDS_OK;
+    if (p) hipFree(p);
+    p = nullptr; cap = 0;
+    if (hipMalloc((void**)&p, n * sizeof(T)) != hipSuccess) { p = nullptr; return fail(EDS_ERR_HIP, "allocation of the epiline work buffers failed"); }
+    cap = n;
+    return EDS_OK;
+}
+
+int ensure(eds_trk* h) {
+    EdsEpiBuffers& e = h->epi;
+    if (e.ef) return EDS_OK;
+    const size_t B = (size_t)h->B, Np = (size_t)h->Np, H = (size_t)h->H, W = (size_t)h->W;
+    if (hipMalloc((void**)&e.ef, 2 * B * Np * 8) != hipSuccess || hipMalloc((void**)&e.kpix, 2 * B * Np * 8) != hipSuccess ||
+        hipMalloc((void**)&e.mval, B * Np * 8) != hipSuccess || hipMalloc((void**)&e.keys_tmp, B * Np * 8) != hipSuccess ||
+        hipMalloc((void**)&e.keys, B * Np * 8) != hipSuccess || hipMalloc((void**)&e.row_start, B * (H + 2) * 4) != hipSuccess ||
+        hipMalloc((void**)&e.model, B * H * W * 8) != hipSuccess || hipMalloc((void**)&e.par, B * EDS_EPI_PAR * 8) != hipSuccess ||
+        hipHostMalloc((void**)&e.h_par, B * EDS_EPI_PAR * 8, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc((void**)&e.best, 2 * B * Np * 8) != hipSuccess || hipMalloc((void**)&e.ef_tmp, 2 * B * Np * 8) != hipSuccess ||
+        hipMalloc((void**)&e.loc, 4 * B * Np * 4) != hipSuccess || hipMalloc((void**)&e.score, 2 * B * Np * 8) != hipSuccess ||
+        hipMalloc((void**)&e.erase, B * Np) != hipSuccess || hipMalloc((void**)&e.coord, 2 * B * Np * 8) != hipSuccess ||
+        hipMalloc((void**)&e.kept, B * Np * 4) != hipSuccess || hipMalloc((void**)&e.ef_aos, 2 * B * Np * 8) != hipSuccess) {
+        eds_epi_free(&e);
+        return fail(EDS_ERR_HIP, "allocation of the epiline buffers failed");
+    }
+    EDS_HIP_TRY(hipMemsetAsync(e.ef, 0, 2 * B * Np * 8, h->st));
+    return EDS_OK;
+}
+
+// getModel of slots first .. first + count - 1 into the model plane
+int build_model(eds_trk* h, int first, int count) {
+    EdsEpiBuffers& e = h->epi;
+    for (int s = first; s < first + count; ++s) {
+        const Slot& sl = h->slots[s];
+        double* P = e.h_par + (size_t)s * EDS_EPI_PAR;
+        for (int j = 0; j < 4; ++j) P[j] = sl.K[j];
+        for (int j = 0; j < 6; ++j) P[4 + j] = sl.v[j];          // linearVelocity = vx[0:3], angularVelocity = vx[3:6]
+        P[10] = sl.seeded ? 1.0 : 0.0;
+    }
+    EDS_HIP_TRY(hipMemcpyAsync(e.par + (size_t)first * EDS_EPI_PAR, e.h_par + (size_t)first * EDS_EPI_PAR, (size_t)count * EDS_EPI_PAR * 8,
+                               hipMemcpyHostToDevice, h->st));
+    hipLaunchKernelGGL(k_epi_values, dim3(count), dim3(EDS_EPI_VAL_THREADS), 0, h->st, h->arrays(), first, e.par, h->depth.seeds, e.kpix, e.mval);
+    EDS_HIP_TRY(hipGetLastError());
+    int rc = eds_klt_bin_launch(h, first, count, e.kpix, e.keys_tmp, e.keys, e.row_start);
+    if (rc) return rc;
+    const double t = std::exp(-0.5 / (0.5 * 0.5));          // cv::getGaussianKernel(3, 0.5, CV_64F): [t, 1, t] / (1 + 2t)
+    const double k0 = t / (1.0 + 2.0 * t), k1 = 1.0 / (1.0 + 2.0 * t);
+    const int tiles = ((h->W + EDS_EPI_MODEL_TW - 1) / EDS_EPI_MODEL_TW) * ((h->H + EDS_EPI_MODEL_TH - 1) / EDS_EPI_MODEL_TH);
+    hipLaunchKernelGGL(k_epi_model, dim3(tiles, count), dim3(256), 0, h->st, h->arrays(), first, k0, k1, k0, e.kpix, e.mval, e.keys, e.row_start,
+                       e.model);
+    EDS_HIP_TRY(hipGetLastError());
+    return EDS_OK;
+}
+
+int check_slots(eds_trk* h, int first, int count) {
+    int rc = check_range(h, first, count);
+    if (rc) return rc;
+    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
+    for (int s = first; s < first + count; ++s)
+        if (!h->slots[s].has_kf || h->slots[s].N < 1) return fail(EDS_ERR_STATE, "keyframe not set");
+    return EDS_OK;
+}
+
+int track(eds_trk* h, int first, int count, int r, int border, int bval, int erase, int stride, int32_t* ssd_xy, int32_t* ncc_xy,
+          double* scores, double* ef_xy, int32_t* kept_index, int* n_kept) {
+    if (!h) return fail(EDS_ERR_INVALID, "null handle");
+    if (count < 1 || first < 0 || first + count > h->B) return fail(EDS_ERR_INVALID, "slot range out of bounds");
+    if (r < 0 || r > EDS_EPI_MAX_RADIUS) return fail(EDS_ERR_INVALID, "patch_radius outside 0 .. 15");
+    if (border != EDS_EPI_BORDER_CONSTANT && border != EDS_EPI_BORDER_REPLICATE && border != EDS_EPI_BORDER_REFLECT &&
+        border != EDS_EPI_BORDER_REFLECT_101)
+        return fail(EDS_ERR_INVALID, "unknown border type");
+    if (bval < 0 || bval > 255) return fail(EDS_ERR_INVALID, "border_value outside 0 .. 255");
+    if (erase != 0 && erase != 1) return fail(EDS_ERR_INVALID, "erase must be 0 or 1");
+    if ((ssd_xy || ncc_xy || scores || ef_xy || kept_index) && stride < max_points(h, first, count))
+        return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
+    int rc = check_slots(h, first, count);
+    if (rc) return rc;
+    for (int s = first; s < first + count; ++s)
+        if (!h->slots[s].has_frame) return fail(EDS_ERR_STATE, "event frame not set");
+    const int pitch = EDS_EPI_TW + 2 * r;
+    const size_t match_lds = (size_t)(EDS_EPI_TH + 2 * r) * pitch * 4;
+    int max_lds = 0;
+    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, h->dev));
+    if (2 * ((size_t)h->H + 2) * 4 > (size_t)max_lds || match_lds > (size_t)max_lds || h->W > 65535 || h->H > 65535 ||
+        (size_t)h->H * h->W >= (1ull << 32))
+        return fail(EDS_ERR_NOT_USABLE, "the row bins or the match tile of this frame size do not fit the workgroup's LDS");
+    if ((rc = ensure(h))) return rc;
+    EdsEpiBuffers& e = h->epi;
+    const int H = h->H, W = h->W, K = (2 * r + 1) * (2 * r + 1);
+    const size_t Np = (size_t)h->Np, Hp2 = (size_t)H + 2 * r, Wp2 = (size_t)W + 2 * r;
+    const int cap = std::min(count, EDS_EPI_CHUNK);
+    if ((rc = grow(e.pad, e.pad_cap, cap * Hp2 * Wp2)) || (rc = grow(e.rowsq, e.rowsq_cap, cap * Hp2 * W)) ||
+        (rc = grow(e.energy, e.energy_cap, (size_t)cap * H * W)) || (rc = grow(e.taps, e.taps_cap, cap * Np * K)) ||
+        (rc = grow(e.tmeta, e.tmeta_cap, cap * Np)))
+        return rc;
+    int maxN = 0;
+    for (int s = first; s < first + count; ++s) maxN = std::max(maxN, h->slots[s].N);
+    // 1. the model images
+    if ((rc = build_model(h, first, count))) return rc;
+    EDS_HIP_TRY(hipMemsetAsync(e.best + 2 * Np * first, 0xff, 2 * Np * count * 8, h->st));
+    // 2 .. 4, a chunk of alignments at a time
+    const int ntiles = ((W + EDS_EPI_TW - 1) / EDS_EPI_TW) * ((H + EDS_EPI_TH - 1) / EDS_EPI_TH);
+    const int ngroups = (maxN + EDS_EPI_GROUP - 1) / EDS_EPI_GROUP;
+    for (int c0 = 0; c0 < count; c0 += cap) {
+        const int cn = std::min(cap, count - c0), f = first + c0;
+        hipLaunchKernelGGL(k_epi_templates, dim3(maxN, cn), dim3(64), 0, h->st, h->arrays(), f, r, border, (double)bval, pitch, e.kpix, e.model,
+                           e.taps, e.tmeta);
+        hipLaunchKernelGGL(k_epi_pad, dim3((unsigned)((Hp2 * Wp2 + 255) / 256), cn), dim3(256), 0, h->st, h->arrays(), f, r, border, (float)bval,
+                           e.pad);
+        hipLaunchKernelGGL(k_epi_rowsq, dim3((unsigned)((Hp2 * W + 255) / 256), cn), dim3(256), 0, h->st, H, W, r, e.pad, e.rowsq);
+        hipLaunchKernelGGL(k_epi_energy, dim3((unsigned)(((size_t)H * W + 255) / 256), cn), dim3(256), 0, h->st, H, W, r, e.rowsq, e.energy);
+        hipLaunchKernelGGL(k_epi_match, dim3(ntiles, ngroups, cn), dim3(256), match_lds, h->st, h->arrays(), f, r, pitch, e.pad, e.energy, e.taps,
+                           e.tmeta, reinterpret_cast<unsigned long long*>(e.best));
+        EDS_HIP_TRY(hipGetLastError());
+    }
+    const unsigned nchunk = (unsigned)((maxN + 255) / 256);
+    hipLaunchKernelGGL(k_epi_finish, dim3(nchunk, count), dim3(256), 0, h->st, h->arrays(), first,
+                       reinterpret_cast<const unsigned long long*>(e.best), e.loc, e.score, e.ef_tmp, e.erase);
+    EDS_HIP_TRY(hipGetLastError());
+    // the per-original-point outputs, before the compaction
+    std::vector<int32_t> vloc;
+    std::vector<double> vsc;
+    if (ssd_xy || ncc_xy) { vloc.resize(4 * Np * count); EDS_HIP_TRY(hipMemcpyAsync(vloc.data(), e.loc + 4 * Np * first, vloc.size() * 4, hipMemcpyDeviceToHost, h->st)); }
+    if (scores) { vsc.resize(2 * Np * count); EDS_HIP_TRY(hipMemcpyAsync(vsc.data(), e.score + 2 * Np * first, vsc.size() * 8, hipMemcpyDeviceToHost, h->st)); }
+    std::vector<int> n0(count);
+    for (int b = 0; b < count; ++b) n0[b] = h->slots[first + b].N;
+    // 5. the cull: getCoord's compaction, erasing by flag
+    if (erase) {
+        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        const EdsPointsDev dev = {e.coord, e.kept, e.erase};
+        if ((rc = update_points_range(h, first, count, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dev))) return rc;
+    }
+    hipLaunchKernelGGL(k_epi_gather, dim3(nchunk, count), dim3(256), 0, h->st, h->arrays(), first, erase ? e.kept : nullptr, e.ef_tmp, e.ef);
+    EDS_HIP_TRY(hipGetLastError());
+    std::vector<double> vef;
+    std::vector<int32_t> vk;
+    const size_t plane = (size_t)h->B * Np;
+    if (ef_xy) {
+        vef.resize(2 * Np * count);
+        EDS_HIP_TRY(hipMemcpyAsync(vef.data(), e.ef + Np * first, Np * count * 8, hipMemcpyDeviceToHost, h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(vef.data() + Np * count, e.ef + plane + Np * first, Np * count * 8, hipMemcpyDeviceToHost, h->st));
+    }
+    if (kept_index && erase) { vk.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), e.kept + Np * first, Np * count * 4, hipMemcpyDeviceToHost, h->st)); }
+    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    for (int b = 0; b < count; ++b) {
+        Slot& sl = h->slots[first + b];
+        sl.epi_valid = sl.has_kf && sl.N > 0;
+        const int nk = sl.N;
+        const size_t o = (size_t)b * stride, src = Np * b;
+        if (n_kept) n_kept[b] = nk;
+        for (int i = 0; i < n0[b]; ++i) {
+            if (ssd_xy) { ssd_xy[2 * (o + i)] = vloc[4 * (src + i)]; ssd_xy[2 * (o + i) + 1] = vloc[4 * (src + i) + 1]; }
+            if (ncc_xy) { ncc_xy[2 * (o + i)] = vloc[4 * (src + i) + 2]; ncc_xy[2 * (o + i) + 1] = vloc[4 * (src + i) + 3]; }
+            if (scores) { scores[2 * (o + i)] = vsc[2 * (src + i)]; scores[2 * (o + i) + 1] = vsc[2 * (src + i) + 1]; }
+        }
+        for (int k = 0; k < nk; ++k) {
+            if (ef_xy) { ef_xy[2 * (o + k)] = vef[src + k]; ef_xy[2 * (o + k) + 1] = vef[Np * count + src + k]; }
+            if (kept_index) kept_index[o + k] = erase ? vk[src + k] : k;
+        }
+    }
+    return EDS_OK;
+}
+
+}  // namespace
+
+void eds_epi_free(EdsEpiBuffers* eb) {
+    void* dp[] = {eb->ef, eb->kpix, eb->mval, eb->keys_tmp, eb->keys, eb->row_start, eb->model, eb->par, eb->best, eb->ef_tmp, eb->loc,
+                  eb->score, eb->erase, eb->coord, eb->kept, eb->ef_aos, eb->pad, eb->rowsq, eb->energy, eb->taps, eb->tmeta};
+    for (void* p : dp) if (p) hipFree(p);
+    if (eb->h_par) hipHostFree(eb->h_par);
+    *eb = EdsEpiBuffers();
+}
+
+extern "C" {
+
+int eds_epi_abi_version(void) { return EDS_HIP_EPILINE_ABI_VERSION; }
+
+int eds_epi_track_points(eds_trk* h, int first, int count, int patch_radius, int border_type, int border_value, int erase, int stride,
+                         int32_t* ssd_xy, int32_t* ncc_xy, double* scores, double* ef_xy, int32_t* kept_index, int* n_kept) {
+    return track(h, first, count, patch_radius, border_type, border_value, erase, stride, ssd_xy, ncc_xy, scores, ef_xy, kept_index, n_kept);
+}
+
+int eds_epi_get(eds_trk* h, int slot, double* ef_xy) {
+    int rc = check_slot(h, slot);
+    if (rc) return rc;
+    if (!ef_xy) return fail(EDS_ERR_INVALID, "null output");
+    if ((rc = check_slots(h, slot, 1))) return rc;
+    if (!h->epi.ef || !h->slots[slot].epi_valid) return fail(EDS_ERR_STATE, "the slot's ef plane is not current: run eds_epi_track_points");
+    EDS_HIP_TRY(hipSetDevice(h->dev));
+    const size_t Np = (size_t)h->Np, plane = (size_t)h->B * Np, o = (size_t)slot * Np, N = (size_t)h->slots[slot].N;
+    std::vector<double> v(2 * N);
+    EDS_HIP_TRY(hipMemcpyAsync(v.data(), h->epi.ef + o, N * 8, hipMemcpyDeviceToHost, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(v.data() + N, h->epi.ef + plane + o, N * 8, hipMemcpyDeviceToHost, h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    for (size_t k = 0; k < N; ++k) { ef_xy[2 * k] = v[k]; ef_xy[2 * k + 1] = v[N + k]; }
+    return EDS_OK;
+}
+
+int eds_epi_get_model(eds_trk* h, int slot, double* model) {
+    int rc = check_slot(h, slot);
+    if (rc) return rc;
+    if (!model) return fail(EDS_ERR_INVALID, "null output");
+    if ((rc = check_slots(h, slot, 1))) return rc;
+    if (2 * ((size_t)h->H + 2) * 4 > 65536 || h->W > 65535 || h->H > 65535)
+        return fail(EDS_ERR_NOT_USABLE, "the row bins of this frame size do not fit the workgroup's LDS");
+    EDS_HIP_TRY(hipSetDevice(h->dev));
+    if ((rc = ensure(h)) || (rc = build_model(h, slot, 1))) return rc;
+    const size_t n = (size_t)h->H * h->W;
+    EDS_HIP_TRY(hipMemcpyAsync(model, h->epi.model + n * slot, n * 8, hipMemcpyDeviceToHost, h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    return EDS_OK;
+}
+
+int eds_epi_depth_update(eds_trk* h, int first, int count, const double* T_kf_ef, int filter, eds_depth_summary* out) {
+    int rc = check_range(h, first, count);
+    if (rc) return rc;
+    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
+    for (int s = first; s < first + count; ++s)
+        if (!h->epi.ef || !h->slots[s].epi_valid || !h->slots[s].has_kf)
+            return fail(EDS_ERR_STATE, "the slot's ef plane is not current: run eds_epi_track_points");
+    EDS_HIP_TRY(hipSetDevice(h->dev));
+    hipLaunchKernelGGL(k_epi_to_aos, dim3((h->Np + 255) / 256, count), dim3(256), 0, h->st, h->arrays(), first, h->epi.ef, h->epi.ef_aos);
+    EDS_HIP_TRY(hipGetLastError());
+    return eds_depth_update_impl(h, first, count, EDS_DEPTH_EF_COORD, nullptr, nullptr, 0, T_kf_ef, filter, out, h->epi.ef_aos);
+}
+
+}  // extern "C"

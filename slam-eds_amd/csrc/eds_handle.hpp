@@ -6,6 +6,7 @@
 
 #include "../../include/eds_hip.h"
 #include "eds_depth.hpp"
+#include "eds_epiline.hpp"
 #include "eds_klt.hpp"
 #include "eds_fused.hpp"
 #include "eds_kernels.hpp"
@@ -38,6 +39,9 @@ struct Slot {
     // inverse-depth filter (include/eds_hip_depth.h): DepthPoints' scalars of this slot's seeds; set_keyframe / build_keyframe unseed
     bool seeded = false;
     double dp_mu_range = 0.0, dp_px_error_angle = 0.0, dp_threshold = 0.0;
+    // epiline tracker (include/eds_hip_epiline.h): the ef plane is index-aligned with this slot's points.  Cleared by everything
+    // that changes the point set or the keyframe (set_keyframe, build_keyframe, an erasing update_points, the KLT)
+    bool epi_valid = false;
 };
 
 
@@ -64,6 +68,7 @@ struct eds_trk {
     EdsPointBuffers point_ops;
     EdsDepthBuffers depth;
     EdsKltBuffers klt;                  // KLT tracks / flow planes (include/eds_hip_klt.h), allocated by the first KLT call
+    EdsEpiBuffers epi;                  // epiline ef plane and work buffers (include/eds_hip_epiline.h), allocated by the first eds_epi_* call
     EdsKeyframeBuffers kf_build;
     // pinned host staging
     double *h_pose = nullptr, *h_part = nullptr, *h_G = nullptr;

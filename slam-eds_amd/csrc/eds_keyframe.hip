@@ -532,6 +532,7 @@ int eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int 
     s.has_kf = true;
     s.seeded = false;                       // as eds_trk_set_keyframe
     eds_klt_reset_slot(h, slot);
+    s.epi_valid = false;
     s.residuals.clear();
     s.res_on_device = false; s.trace_on_device = false; s.ntrace = 0;     // as eds_trk_set_keyframe
     kb.last_slot = slot;

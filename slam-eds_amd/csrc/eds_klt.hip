@@ -401,6 +401,12 @@ void eds_klt_free(EdsKltBuffers* kb) {
     *kb = EdsKltBuffers();
 }
 
+int eds_klt_bin_launch(eds_trk* h, int first, int count, const double* coord, uint64_t* keys_tmp, uint64_t* keys, int* row_start) {
+    hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), 2 * ((size_t)h->H + 2) * 4, h->st, h->arrays(), first, coord, keys_tmp,
+                       keys, row_start);
+    return hipGetLastError() == hipSuccess ? EDS_OK : fail(EDS_ERR_HIP, "launch of k_klt_bin failed");
+}
+
 void eds_klt_reset_slot(eds_trk* h, int slot) {
     if (!h->klt.tracks) return;
     const size_t Np = (size_t)h->Np, plane = (size_t)h->B * Np, o = (size_t)slot * Np;

@@ -17,12 +17,18 @@ struct EdsKltBuffers {
     int* row_start = nullptr;       // [B][H + 2] first key of splat row y0 = 0 .. H, then the number of binned points
 };
 
-// device outputs of getCoord for the KLT, indexed by slot, in HBM (eds_points.hip writes them instead of the pinned block)
+// device outputs of getCoord for the KLT, indexed by slot, in HBM (eds_points.hip writes them instead of the pinned block).
+// erase ([B][Np], indexed by slot, or null): the points to erase are those flagged non-zero instead of those that left the frame,
+// and the KLT's tracks plane is compacted like the flow instead of being rewritten (the epiline cull, eds_epiline.hip)
 struct EdsPointsDev {
     double* coord;
     int* kept;
+    const unsigned char* erase = nullptr;
 };
 
 void eds_klt_free(EdsKltBuffers* kb);
 // a new keyframe: zero the slot's tracks and flow (KeyFrame::create, KeyFrame.cpp:447-448), on the handle's stream
 void eds_klt_reset_slot(eds_trk* h, int slot);
+// k_klt_bin for slots first .. first + count - 1 over the pixel coordinates `coord` ([B][Np][2], indexed by slot): keys and row starts
+// as the KLT's window kernel reads them (the epiline model image splats with them, eds_epiline.hip)
+int eds_klt_bin_launch(eds_trk* h, int first, int count, const double* coord, uint64_t* keys_tmp, uint64_t* keys, int* row_start);

@@ -72,17 +72,20 @@ __global__ __launch_bounds__(EDS_LP_THREADS) void k_loss_param(EdsArrays A, int 
 __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, int first, int ppt, int delete_out, const double* __restrict__ pose_in,
                                                                   double* __restrict__ coord, double* __restrict__ track,
                                                                   int* __restrict__ kept, double* __restrict__ summary,
-                                                                  double* __restrict__ tplane, double* __restrict__ fplane) {
+                                                                  double* __restrict__ tplane, double* __restrict__ fplane,
+                                                                  const unsigned char* __restrict__ erase) {
     const int tid = threadIdx.x;
     const int slot = first + (int)blockIdx.x;
     pose_in += 16 * (size_t)blockIdx.x; summary += 2 * (size_t)blockIdx.x;
     if (coord) coord += 2 * (size_t)A.Np * blockIdx.x;
     if (track) track += 2 * (size_t)A.Np * blockIdx.x;
     if (kept) kept += (size_t)A.Np * blockIdx.x;
+    if (erase) erase += (size_t)A.Np * blockIdx.x;
     double* pb = A.pose + (size_t)slot * EDS_POSE_STRIDE;
     const int N = (int)pb[EDS_PB_N];
     const size_t base = (size_t)slot * A.Np, plane = (size_t)A.B * A.Np;
     const bool move_flow = fplane && delete_out;
+    const bool move_tracks = tplane && erase;       // the epiline cull erases by flag: kf->tracks are compacted, not re-projected
     __shared__ int s_cnt[EDS_PTS_THREADS];
     __shared__ double s_flow[EDS_PTS_THREADS / 64];
     __shared__ double s_pose[16];
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
         const int cppt = (nc + EDS_PTS_THREADS - 1) / EDS_PTS_THREADS;
         float fx_[MAXP], fy_[MAXP], frho[MAXP], fgx[MAXP], fgy[MAXP], fw[MAXP], ff0x[MAXP], ff0y[MAXP];
         int fcell[MAXP];
-        double xp[MAXP], yp[MAXP], fl0[MAXP], fl1[MAXP];
+        double xp[MAXP], yp[MAXP], fl0[MAXP], fl1[MAXP], tl0[MAXP], tl1[MAXP];
         bool keep[MAXP];
         int mine = 0;
 #pragma unroll
@@ -121,6 +124,7 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
                 fx_[k] = A.x[o]; fy_[k] = A.y[o]; frho[k] = A.rho[o]; fgx[k] = A.gx[o]; fgy[k] = A.gy[o]; fw[k] = A.w[o];
                 ff0x[k] = A.f0x[o]; ff0y[k] = A.f0y[o]; fcell[k] = A.cell0[o];
                 if (move_flow) { fl0[k] = fplane[o]; fl1[k] = fplane[plane + o]; }
+                if (move_tracks) { tl0[k] = tplane[o]; tl1[k] = tplane[plane + o]; }
                 // p = R (x, y, 1)/mu + t with the RAW inverse depth (Tracker.cpp:343-347), projected (:350-351)
                 const float rho = frho[k];
                 const float d0 = ps.D[0] * fx_[k] + ps.D[1] * fy_[k] + ps.D[2] + ps.t[0] * rho;
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
                 const double u0 = (double)(short)(fcell[k] & 0xffff) + (double)ff0x[k], v0 = (double)(fcell[k] >> 16) + (double)ff0y[k];
                 xp[k] = u0 + du; yp[k] = v0 + dv;
                 const bool outlier = (xp[k] < 0.0 || xp[k] > cols) || (yp[k] < 0.0 || yp[k] > rows);      // Tracker.cpp:354
-                keep[k] = !(delete_out && outlier);
+                keep[k] = erase ? erase[i] == 0 : !(delete_out && outlier);
                 if (keep[k]) { ++mine; flow += du * du + dv * dv; }                                     // track = new - old pixel (:364-366)
             }
         }
@@ -156,7 +160,8 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
             if (coord) { coord[2 * dst] = xp[k]; coord[2 * dst + 1] = yp[k]; }
             const double u0 = (double)(short)(fcell[k] & 0xffff) + (double)ff0x[k], v0 = (double)(fcell[k] >> 16) + (double)ff0y[k];
             if (track) { track[2 * dst] = xp[k] - u0; track[2 * dst + 1] = yp[k] - v0; }
-            if (tplane) { tplane[o] = xp[k] - u0; tplane[plane + o] = yp[k] - v0; }
+            if (move_tracks) { tplane[o] = tl0[k]; tplane[plane + o] = tl1[k]; }
+            else if (tplane) { tplane[o] = xp[k] - u0; tplane[plane + o] = yp[k] - v0; }
             if (move_flow) { fplane[o] = fl0[k]; fplane[plane + o] = fl1[k]; }
             if (kept) kept[dst] = c0 + tid * cppt + k;
             ++dst;
@@ -264,7 +269,8 @@ int eds_points_update_batch(eds_trk* h, int first, int count, int delete_out, in
         double* dcoord = dev ? dev->coord + 2 * Np * (size_t)(first + c0) : (coord_xy ? pb.d_coord : nullptr);
         int* dkept = dev ? dev->kept + Np * (size_t)(first + c0) : ((kept_index || seeded) ? pb.d_kept : nullptr);
         hipLaunchKernelGGL(k_update_points, dim3(cn), dim3(EDS_PTS_THREADS), 0, h->st, h->arrays(), first + c0, ppt, delete_out, pb.d_pose,
-                           dcoord, tracks_xy ? pb.d_track : nullptr, dkept, pb.d_summary, h->klt.tracks, h->klt.flow);
+                           dcoord, tracks_xy ? pb.d_track : nullptr, dkept, pb.d_summary, h->klt.tracks, h->klt.flow,
+                           dev && dev->erase ? dev->erase + Np * (size_t)(first + c0) : nullptr);
         if (seeded) eds_depth_compact(h, first + c0, cn, dkept);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(h->st);

@@ -1,9 +1,9 @@
 """Python mirror of ``eds::tracking::Tracker`` (reference src/tracking/Tracker.hpp:36-114) over the
 C ABI — same member names, argument meaning and error behaviour for the alignment path
 (``optimize``, ``getLossParams``, ``getTransform``, ``set``/``reset``, ``getInfo``) and the KLT point
-trackers ``trackPoints`` / ``trackPointsPyr`` (Tracker.cpp:378-488, include/eds_hip_klt.h).  The epipolar
-helpers (trackPointsAlongEpiline, getEMatrix / getFMatrix) are not mirrored.  The C++ twin with the
-reference's exact signatures is ``csrc/Tracker.hpp``.
+trackers ``trackPoints`` / ``trackPointsPyr`` (Tracker.cpp:378-488, include/eds_hip_klt.h) and the template
+matcher ``trackPointsAlongEpiline`` (Tracker.cpp:490-553, include/eds_hip_epiline.h).  getEMatrix / getFMatrix
+are not mirrored.  The C++ twin with the reference's exact signatures is ``csrc/Tracker.hpp``.
 """
 from __future__ import annotations
 
@@ -288,6 +288,29 @@ class Tracker:
         kf.tracks = out["tracks"]                                     # getCoord's track + f (:365, :417, :481)
         self.tracks = kf.tracks
         return out["coord"]
+
+    def trackPointsAlongEpiline(self, event_frame, patch_radius: int = 7, border_type: int = 4, border_value: int = 255):
+        """Tracker::trackPointsAlongEpiline (Tracker.cpp:490-553) on the device (include/eds_hip_epiline.h): both normed template
+        matches of every point against the padded event frame; the points whose two matches disagree by more than 5 px are erased
+        from every index-aligned KeyFrame vector.  Returns the kept points' p_ssd (N x 2 event-frame pixels)."""
+        self._ensure_handle()
+        kf, h = self.kf, self._h
+        K = np.asarray(kf.K_ref, dtype=np.float64)
+        N = len(kf.inv_depth)
+        h.set_keyframe(0, kf.norm_coord, kf.grad, kf.inv_depth, kf.weights, K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        h.set_event_frame(0, event_frame)
+        h.set_state(0, self.px, self.qx, self.vx)
+        out = h.epi_track_points(0, 1, patch_radius, border_type, border_value)[0]
+        keep = out["kept"]
+        if len(keep) != N:                                            # KeyFrame::erasePoint of the culled points
+            for name in ("norm_coord", "grad", "weights", "inv_depth"):
+                setattr(kf, name, np.ascontiguousarray(np.asarray(getattr(kf, name))[keep]))
+            for name in ("coord", "flow", "tracks"):
+                if len(getattr(kf, name)) == N:
+                    setattr(kf, name, np.ascontiguousarray(np.asarray(getattr(kf, name))[keep]))
+            if len(kf.residuals) != len(keep):
+                kf.residuals = np.zeros(0)
+        return out["ef"]
 
     def trackPoints(self, event_frame, patch_radius: int = 7):
         """Tracker::trackPoints (Tracker.cpp:378-434): getCoord(true), then kf.flow = f and kf.tracks += f per point."""
