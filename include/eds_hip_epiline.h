@@ -5,7 +5,9 @@
  * One call, per slot:
  *  1. the model image kf->getModel(linearVelocity(), angularVelocity(), "bilinear") (KeyFrame.cpp:1358-1423): per point
  *     f = compute_flow(norm_coord, v, w, mu) (Utils.hpp:165-173), m = -(g . f) / sqrt(1e-3 + sum m^2), splatted bilinearly at the
- *     keyframe pixels in point order (drawValuesPoints, Utils.cpp:124-193), blurred 3 x 3 with sigma 0.5 (reflect-101);
+ *     keyframe pixels in point order (drawValuesPoints, Utils.cpp:124-193), blurred 3 x 3 with sigma 0.5 (reflect-101).  A keyframe
+ *     pixel outside the frame is splatted as there: a corner outside carries weight 0, so a pixel with x in (-1, 0) adds its x1
+ *     corners to column 0 (y likewise to row 0), and one with x <= -1, x >= cols, y <= -1 or y >= rows adds nothing;
  *  2. the templates: splitImageInPatches(model, kf->coord, r, border_type, border_value) (Utils.cpp:608-633), each (2r+1)^2 patch
  *     in fp32, placed at the TRUNCATED keyframe pixel;
  *  3. the search image: copyMakeBorder(event_frame, r, border_type, border_value) in fp32;

@@ -4,7 +4,9 @@
 //   k_epi_values     one workgroup per alignment: getSparseModel (KeyFrame.cpp:1358-1403) — the keyframe pixel the slot holds, the
 //                    flow compute_flow(norm_coord, v, w, mu) (Utils.hpp:165-173), m = -(g . f), then m / sqrt(1e-3 + sum m^2) with
 //                    the sum in point order
-//   k_klt_bin        (eds_klt.hip) the keyframe pixels binned by splat row: keys (y0, x0, i), no per-pixel scratch
+//   k_klt_bin        (eds_klt.hip) the keyframe pixels binned by splat row: keys (y0 + 1, x0 + 1, i), no per-pixel scratch.  The bias
+//                    of one keeps the points with x or y in (-1, 0): their x1 / y1 corners land on column / row 0 with the
+//                    reference's weights (Utils.cpp:164-178); no getCoord has erased them, as it has for the KLT
 //   k_epi_model      drawValuesPoints (Utils.cpp:124-193), bilinear, every pixel summing its contributions in point order, then the
 //                    3 x 3 Gaussian blur (sigma 0.5, reflect-101), per 32 x 8 tile: the model image [B][H][W] in fp64
 //   k_epi_templates  one wavefront per point: splitImageInPatches (Utils.cpp:608-633) at the TRUNCATED keyframe pixel, the patch in
@@ -157,17 +159,17 @@ __global__ __launch_bounds__(256) void k_epi_model(EdsArrays A, int first, doubl
     for (int p = tid; p < bw * bh; p += 256) {
         const int jy = p / bw, py = by0 + jy, px = bx0 + p - jy * bw;
         // the points whose footprint corner lands on (py, px): (y0, x0) = (py-1, px-1) [wd], (py-1, px) [wb], (py, px-1) [wc],
-        // (py, px) [wa] — four runs of keys ascending in i, merged so that the pixel sums in point order (as k_klt_window)
+        // (py, px) [wa] — four runs of keys ascending in i, merged so that the pixel sums in point order (as k_klt_window).
+        // The keys and row starts carry a bias of one: y0 = -1 and x0 = -1 are row 0 and key column 0
         int g[4][2];
         for (int h2 = 0; h2 < 2; ++h2) {
-            const int yy = py - 1 + h2;
-            int lo = 0, hi = 0;
-            if (yy >= 0) { lo = RS[yy]; hi = RS[yy + 1]; lo = lower_x(K, lo, hi, px - 1); }
-            int q = lo;
+            const int yy = py + h2;                             // y0 + 1 of y0 = py - 1, py
+            const int hi = RS[yy + 1];
+            int q = lower_x(K, RS[yy], hi, px);
             g[2 * h2][0] = q;
-            while (q < hi && key_x0(K[q]) == px - 1) ++q;
+            while (q < hi && key_x0(K[q]) == px) ++q;           // x0 = px - 1
             g[2 * h2][1] = q; g[2 * h2 + 1][0] = q;
-            while (q < hi && key_x0(K[q]) == px) ++q;
+            while (q < hi && key_x0(K[q]) == px + 1) ++q;       // x0 = px
             g[2 * h2 + 1][1] = q;
         }
         double s = 0.0;
@@ -446,7 +448,7 @@ int build_model(eds_trk* h, int first, int count) {
                                hipMemcpyHostToDevice, h->st));
     hipLaunchKernelGGL(k_epi_values, dim3(count), dim3(EDS_EPI_VAL_THREADS), 0, h->st, h->arrays(), first, e.par, h->depth.seeds, e.kpix, e.mval);
     EDS_HIP_TRY(hipGetLastError());
-    int rc = eds_klt_bin_launch(h, first, count, e.kpix, e.keys_tmp, e.keys, e.row_start);
+    int rc = eds_klt_bin_launch(h, first, count, e.kpix, e.keys_tmp, e.keys, e.row_start, 1);
     if (rc) return rc;
     const double t = std::exp(-0.5 / (0.5 * 0.5));          // cv::getGaussianKernel(3, 0.5, CV_64F): [t, 1, t] / (1 + 2t)
     const double k0 = t / (1.0 + 2.0 * t), k1 = 1.0 / (1.0 + 2.0 * t);

@@ -14,7 +14,7 @@ struct EdsEpiBuffers {
     double* mval = nullptr;             // [B][Np] getSparseModel's normalised values
     uint64_t* keys_tmp = nullptr;       // [B][Np] splat keys (k_klt_bin)
     uint64_t* keys = nullptr;
-    int* row_start = nullptr;           // [B][H + 2]
+    int* row_start = nullptr;           // [B][H + 2], biased by one: entry y0 + 1 is the first key of splat row y0 = -1 .. H - 1
     double* model = nullptr;            // [B][H][W] the blurred model image
     double* par = nullptr;              // [B][EDS_EPI_PAR] per-alignment parameters (device) ...
     double* h_par = nullptr;            // ... and their pinned staging

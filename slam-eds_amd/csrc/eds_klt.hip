@@ -50,13 +50,18 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 
 // getCoord(true) keeps 0 <= x <= cols, 0 <= y <= rows (and lets NaN through): only such points are binned
 __device__ __forceinline__ bool binned(double x, double y, int W, int H) { return x >= 0.0 && x <= (double)W && y >= 0.0 && y <= (double)H; }
+// bias 1 (the epiline model, whose keyframe pixels no getCoord has erased): every point whose footprint touches the image,
+// -1 < x < cols, -1 < y < rows, keyed (y0 + 1, x0 + 1) so that the row and column left of the frame fit the unsigned key
+__device__ __forceinline__ bool binned(double x, double y, int W, int H, int bias) {
+    return bias ? (x > -1.0 && x < (double)W && y > -1.0 && y < (double)H) : binned(x, y, W, H);
+}
 
 __device__ __forceinline__ int key_x0(uint64_t k) { return (int)((k >> 32) & 0xffffu); }
 __device__ __forceinline__ unsigned key_i(uint64_t k) { return (unsigned)(k & 0xffffffffu); }
 
 __global__ __launch_bounds__(EDS_KLT_BIN_THREADS) void k_klt_bin(EdsArrays A, int first, const double* __restrict__ coord,
                                                                 uint64_t* __restrict__ keys_tmp, uint64_t* __restrict__ keys,
-                                                                int* __restrict__ row_start) {
+                                                                int* __restrict__ row_start, int bias) {
     extern __shared__ int s_bin[];          // [H + 2] row starts, [H + 2] cursors
     const int slot = first + blockIdx.x, tid = threadIdx.x, H = A.H, W = A.W;
     const int N = (int)A.pose[(size_t)slot * EDS_POSE_STRIDE + EDS_PB_N];
@@ -67,7 +72,7 @@ __global__ __launch_bounds__(EDS_KLT_BIN_THREADS) void k_klt_bin(EdsArrays A, in
     __syncthreads();
     for (int i = tid; i < N; i += EDS_KLT_BIN_THREADS) {
         const double x = coord[2 * i], y = coord[2 * i + 1];
-        if (binned(x, y, W, H)) atomicAdd(&s_bin[(int)floor(y)], 1);         // (integer counts: the same in any order)
+        if (binned(x, y, W, H, bias)) atomicAdd(&s_bin[(int)floor(y) + bias], 1);         // (integer counts: the same in any order)
     }
     __syncthreads();
     if (tid == 0) {
@@ -79,8 +84,8 @@ __global__ __launch_bounds__(EDS_KLT_BIN_THREADS) void k_klt_bin(EdsArrays A, in
     for (int y = tid; y < H + 2; y += EDS_KLT_BIN_THREADS) row_start[y] = s_bin[y];
     for (int i = tid; i < N; i += EDS_KLT_BIN_THREADS) {
         const double x = coord[2 * i], y = coord[2 * i + 1];
-        if (!binned(x, y, W, H)) continue;
-        const int y0 = (int)floor(y), x0 = (int)floor(x);
+        if (!binned(x, y, W, H, bias)) continue;
+        const int y0 = (int)floor(y) + bias, x0 = (int)floor(x) + bias;
         const int pos = atomicAdd(&s_cur[y0], 1);                             // arrival order; the rank sort below fixes it
         keys_tmp[pos] = ((uint64_t)y0 << 48) | ((uint64_t)x0 << 32) | (uint64_t)i;
     }
@@ -349,7 +354,7 @@ int run(eds_trk* h, int first, int count, int r, int L, bool pyr, int stride, do
     for (int s = first; s < first + count; ++s) maxN = std::max(maxN, h->slots[s].N);
     // 2. bins, 3. windows
     hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), bin_lds, h->st, h->arrays(), first, kb.coord, kb.keys_tmp, kb.keys,
-                       kb.row_start);
+                       kb.row_start, 0);
     EDS_HIP_TRY(hipGetLastError());
     const double t = std::exp(-0.5 / (0.5 * 0.5));          // cv::getGaussianKernel(3, 0.5, CV_64F): [t, 1, t] / (1 + 2t)
     const double k0 = t / (1.0 + 2.0 * t), k1 = 1.0 / (1.0 + 2.0 * t);
@@ -401,9 +406,9 @@ void eds_klt_free(EdsKltBuffers* kb) {
     *kb = EdsKltBuffers();
 }
 
-int eds_klt_bin_launch(eds_trk* h, int first, int count, const double* coord, uint64_t* keys_tmp, uint64_t* keys, int* row_start) {
+int eds_klt_bin_launch(eds_trk* h, int first, int count, const double* coord, uint64_t* keys_tmp, uint64_t* keys, int* row_start, int bias) {
     hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), 2 * ((size_t)h->H + 2) * 4, h->st, h->arrays(), first, coord, keys_tmp,
-                       keys, row_start);
+                       keys, row_start, bias);
     return hipGetLastError() == hipSuccess ? EDS_OK : fail(EDS_ERR_HIP, "launch of k_klt_bin failed");
 }
 

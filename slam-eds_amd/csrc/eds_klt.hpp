@@ -30,5 +30,6 @@ void eds_klt_free(EdsKltBuffers* kb);
 // a new keyframe: zero the slot's tracks and flow (KeyFrame::create, KeyFrame.cpp:447-448), on the handle's stream
 void eds_klt_reset_slot(eds_trk* h, int slot);
 // k_klt_bin for slots first .. first + count - 1 over the pixel coordinates `coord` ([B][Np][2], indexed by slot): keys and row starts
-// as the KLT's window kernel reads them (the epiline model image splats with them, eds_epiline.hip)
-int eds_klt_bin_launch(eds_trk* h, int first, int count, const double* coord, uint64_t* keys_tmp, uint64_t* keys, int* row_start);
+// as the KLT's window kernel reads them (bias 0: the points getCoord(true) keeps).  bias 1 is the epiline model image's
+// (eds_epiline.hip): every point with -1 < x < W, -1 < y < H, keyed and binned by (y0 + 1, x0 + 1)
+int eds_klt_bin_launch(eds_trk* h, int first, int count, const double* coord, uint64_t* keys_tmp, uint64_t* keys, int* row_start, int bias);

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import np_epiline_oracle as eo
+import np_klt_oracle as ko
+import subpixel_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -17,9 +19,9 @@ BORDERS = [(eo.BORDER_CONSTANT, 0), (eo.BORDER_CONSTANT, 255), (eo.BORDER_REPLIC
            (eo.BORDER_REFLECT_101, 0)]
 
 
-def _handle(capi, als, vel=VEL, solver=None):
+def _handle(capi, als, vel=VEL, solver=None, max_points=None):
     cfg = capi.default_config(solver=capi.SOLVER_LM6 if solver is None else solver, exec=capi.EXEC_DEVICE, max_num_iterations=4)
-    h = capi.Handle(cfg, len(als), max(a.N for a in als), als[0].H, als[0].W)
+    h = capi.Handle(cfg, len(als), max(a.N for a in als) if max_points is None else max_points, als[0].H, als[0].W)
     for b, a in enumerate(als):
         h.set_alignment(b, a)
         h.set_state(b, a.p0, a.q0, vel)
@@ -78,12 +80,14 @@ def _model_frame(h, slot, al, dx=2, dy=-1, noise=0.05, base=None, seed=0):
     return f
 
 
-def _check(out, ref, r, idx=None, min_strict=0.5):
+def _check(out, ref, r, idx=None, min_strict=0.5, min_strict_ncc=None):
     idx = np.arange(len(out["ssd"])) if idx is None else np.asarray(idx)
-    ssd, ncc, sc = out["ssd"][idx], out["ncc"][idx], out["scores"][idx]
-    s1 = _judge(ssd, sc[:, 0], ref["ssd_map"], ref["ssd"], ref["s_ssd"], r, False)
-    s2 = _judge(ncc, sc[:, 1], ref["ncc_map"], ref["ncc"], ref["s_ncc"], r, True)
+    ssd, ncc, scr = out["ssd"][idx], out["ncc"][idx], out["scores"][idx]
+    s1 = _judge(ssd, scr[:, 0], ref["ssd_map"], ref["ssd"], ref["s_ssd"], r, False)
+    s2 = _judge(ncc, scr[:, 1], ref["ncc_map"], ref["ncc"], ref["s_ncc"], r, True)
     assert s1.mean() >= min_strict, s1.mean()
+    if min_strict_ncc is not None:
+        assert s2.mean() >= min_strict_ncc, s2.mean()
     same = np.all(ssd == ref["ssd"], axis=1) & np.all(ncc == ref["ncc"], axis=1)
     assert np.array_equal(eo.cull(ssd, ncc)[same], ref["keep"][same])
     return same
@@ -344,3 +348,190 @@ def test_python_mirrors_agree_with_handle(gpu, capi, synth):
     for k in ("ssd", "ncc", "scores", "ef", "kept"):
         assert np.array_equal(b[k], ref[k])
     bt.handle.close()
+
+
+# -- keyframes off the pixel grid, frames that are no multiple of a tile, slot ranges that start above zero (tests/subpixel_cases.py) --
+
+def _seed(h, capi, al, slot=0):
+    h.depth_init(slot, 1, capi.DEPTH_INIT_HOST, idp=[np.asarray(al.idp) * 1.1])
+
+
+def _model_parity(h, al, seeded):
+    got = h.epi_get_model(0)
+    kp, idp = _kpix(al), _idp(h, 0, al, seeded)
+    K = (al.fx, al.fy, al.cx, al.cy)
+    ref = eo.model_image(kp, _grad(al), idp, VEL, K, al.H, al.W)
+    assert np.abs(ref).max() > 0
+    err = np.abs(got - ref).max()
+    print(f"model image {al.H}x{al.W} N={al.N} seeded={seeded}: max|got - ref| = {err:.3e}, max|ref| = {np.abs(ref).max():.3e}")
+    assert err <= 1e-12 * np.abs(ref).max()
+    return ko.draw_values_points(kp, eo.sparse_model(kp, _grad(al), idp, VEL, K), al.H, al.W, 0)       # the un-blurred splat
+
+
+@pytest.mark.parametrize("H,W,N", [(H, W, 200) for H, W in sc.FRAMES] + [(480, 640, 2000)])
+@pytest.mark.parametrize("seeded", [False, True])
+def test_model_image_subpixel(gpu, capi, H, W, N, seeded):
+    """all four bilinear weights at work, footprints across the seams of the 32 x 8 tiles and into their halos, partial tiles"""
+    assert np.array_equal(sc.VEL, VEL)
+    al = sc.subpixel_alignment(11 + H, H, W, N, extra=sc.SEAMS(H, W) + sc.LAST(H, W) + sc.EXACT)
+    fr = _kpix(al) - np.floor(_kpix(al))
+    assert ((fr > 0.05) & (fr < 0.95)).all(axis=1).mean() > 0.6
+    h = _handle(capi, [al])
+    if seeded:
+        _seed(h, capi, al)
+    _model_parity(h, al, seeded)
+    h.close()
+
+
+@pytest.mark.parametrize("H,W", sc.FRAMES)
+@pytest.mark.parametrize("only", [False, True])
+@pytest.mark.parametrize("seeded", [False, True])
+def test_model_image_points_just_outside(gpu, capi, H, W, only, seeded):
+    """keyframe pixels with x or y in (-1, 0): drawValuesPoints puts their x1 / y1 corners on column / row 0 (Utils.cpp:164-178).
+    On the commit before this test the device left such points out of the image (its bins began at 0, as the KLT's, whose points
+    getCoord has erased): max|got - ref| was of the order of max|ref| itself."""
+    out = sc.JUST_OUTSIDE(H, W)
+    al = sc.subpixel_alignment(23 + H, H, W, 0 if only else 150, extra=out if only else sc.SEAMS(H, W) + sc.LAST(H, W) + sc.EXACT + out)
+    h = _handle(capi, [al])
+    if seeded:
+        _seed(h, capi, al)
+    splat = _model_parity(h, al, seeded)
+    assert np.abs(splat[0, :]).max() > 0 and np.abs(splat[:, 0]).max() > 0 and splat[0, 0] != 0      # not vacuous
+    if only:
+        assert not splat[1:, 1:].any()
+    h.close()
+
+
+@pytest.mark.parametrize("H,W,r,border,value", sc.PARITY_CASES)
+def test_parity_subpixel_odd_frames(gpu, capi, H, W, r, border, value):
+    al = sc.parity_alignment(H, W)
+    h = _handle(capi, [al])
+    _model_frame(h, 0, al, seed=r)
+    ref = _oracle(h, 0, al, r, border, value)
+    out = h.epi_track_points(0, 1, r, border, value, erase=False)[0]
+    _check(out, ref, r, min_strict_ncc=0.5 if r >= 1 else None)
+    h.close()
+
+
+@pytest.mark.parametrize("N", [1, 31, 32, 33, 1023, 1024, 1025])
+def test_point_count_edges(gpu, capi, N):
+    """one point, the template group of 32 and the 1 024-point chunks of the ordered norm, each at and around its size, N < Np"""
+    H, W, r = 37, 45, 3
+    al = sc.subpixel_alignment(300 + N, H, W, N)
+    h = _handle(capi, [al], max_points=1100)
+    _model_parity(h, al, False)
+    _model_frame(h, 0, al, seed=N)
+    sample = None if N <= 33 else np.random.default_rng(N).choice(N, 64, replace=False)
+    ref = _oracle(h, 0, al, r, sample=sample)
+    out = h.epi_track_points(0, 1, r, erase=False)[0]
+    assert len(out["ssd"]) == N and out["n"] == N
+    _check(out, ref, r, idx=sample)
+    h.close()
+
+
+@pytest.mark.parametrize("r", [1, 3, 0])
+def test_negative_best_ncc(gpu, capi, r):
+    """one blob of a single sign against a frame strictly of the other sign: the best CCORR score is negative (the other branch of the
+    orderable key), every SQDIFF score clamps to 1 (first index over a frame of several workgroups)"""
+    H, W = 37, 45
+    al = sc.subpixel_alignment(1, H, W, 0, extra=[(20.3, 15.6)])
+    h = _handle(capi, [al])
+    model = h.epi_get_model(0)
+    assert (model >= 0).all() or (model <= 0).all()
+    sign = 1.0 if model.sum() > 0 else -1.0
+    h.set_event_frame(0, -sign * (1.0 + np.abs(np.random.default_rng(r).normal(size=(H, W)))))
+    h.set_state(0, al.p0, al.q0, VEL)
+    ref = _oracle(h, 0, al, r)
+    assert ref["s_ncc"][0] < 0 and ref["s_ssd"][0] == 1.0 and tuple(ref["ssd"][0]) == (0, 0)
+    out = h.epi_track_points(0, 1, r, erase=False)[0]
+    print(f"r={r}: oracle ncc {ref['s_ncc'][0]:.6f} at {tuple(ref['ncc'][0])}, device {out['scores'][0, 1]:.6f} at {tuple(out['ncc'][0])}")
+    _judge(out["ncc"], out["scores"][:, 1], ref["ncc_map"], ref["ncc"], ref["s_ncc"], r, True)
+    assert abs(out["scores"][0, 1] - ref["s_ncc"][0]) <= eo.tol(r)
+    assert tuple(out["ssd"][0]) == (0, 0) and out["scores"][0, 0] == 1.0
+    if r == 0:
+        assert ref["s_ncc"][0] == -1.0 and tuple(ref["ncc"][0]) == (0, 0)
+        assert out["scores"][0, 1] == -1.0 and tuple(out["ncc"][0]) == (0, 0)
+    else:
+        assert not ref["keep"][0] and not eo.cull(out["ssd"], out["ncc"])[0]
+        assert h.epi_track_points(0, 1, r)[0]["n"] == 0                           # ... and the device erases it
+    h.close()
+
+
+def _range_handle(capi, pairs, slots):
+    """the slots `slots` of tests/subpixel_cases.range_alignments on a handle of their own: seeded, KLT planes allocated and filled"""
+    als = [pairs[b][0] for b in slots]
+    h = _handle(capi, als)
+    for k, b in enumerate(slots):
+        if pairs[b][1] != b and len(als) > 1:                                    # (on its own, a sharing slot's alignment carries its
+            assert slots[k - 1] == pairs[b][1]                                    # source's frame)
+            h.share_event_frame(k, k - 1)
+    h.depth_init(0, len(als), capi.DEPTH_INIT_HOST, idp=[np.asarray(a.idp) for a in als])
+    outs = h.klt_track_points(0, len(als), 3)
+    assert [o["n"] for o in outs] == [a.N for a in als]                           # identity pose: nothing left the frame
+    for k, a in enumerate(als):
+        h.set_state(k, a.p0, a.q0, VEL)
+    return h
+
+
+def test_sub_range_equals_singles_and_leaves_the_rest(gpu, capi):
+    pairs = sc.range_alignments()
+    B, keys = sc.RANGE_B, ("ssd", "ncc", "scores", "ef", "kept")
+    assert pairs[4][0].N >= 64 and pairs[24][0].N >= 64 and min(p[0].N for p in pairs) == 1 and max(p[0].N for p in pairs) == 300
+    h, twin = _range_handle(capi, pairs, range(B)), _range_handle(capi, pairs, range(B))
+    rng = np.random.default_rng(8)
+    T = np.column_stack([rng.normal(scale=0.02, size=(19, 3)), np.zeros((19, 3)), np.ones(19)])
+
+    def single(b):
+        g = _range_handle(capi, pairs, [b])                                      # a sharing slot's alignment carries its source's frame
+        return g, g.epi_track_points(0, 1, 5)[0]
+
+    def same_as_single(b, out, g, s):
+        for k in keys:
+            assert np.array_equal(out[k], s[k]), (b, k)
+        assert out["n"] == s["n"] and h._N[b] == s["n"]
+        for x, y in zip(h.depth_get(b) + h.klt_get(b), g.depth_get(0) + g.klt_get(0)):
+            assert np.array_equal(x, y, equal_nan=True), b
+        assert np.array_equal(h.epi_get(b), s["ef"])
+
+    outs = h.epi_track_points(5, 19, 5)                                           # one chunk of 16 and a tail of 3, starting above zero
+    assert 0 < sum(o["n"] for o in outs) < sum(pairs[b][0].N for b in range(5, 24))      # the cull kept some and erased some
+    singles = {}
+    for b in range(5, 24):
+        singles[b] = single(b)
+        same_as_single(b, outs[b - 5], *singles[b])
+    # (b) the slots outside the range
+    for b in list(range(5)) + list(range(24, B)):
+        assert h._N[b] == twin._N[b] == pairs[b][0].N
+        for x, y in zip(h.depth_get(b) + h.klt_get(b), twin.depth_get(b) + twin.klt_get(b)):
+            assert np.array_equal(x, y, equal_nan=True), b
+        with pytest.raises(capi.EdsError) as e:
+            h.epi_get(b)
+        assert e.value.code == capi.ERR_STATE
+    for b in (4, 24):
+        al = pairs[b][0]
+        x, y = h.optimize(b, p=al.p0, q=al.q0, v=al.v0), twin.optimize(b, p=al.p0, q=al.q0, v=al.v0)
+        for u, w in zip(x[:3], y[:3]):
+            assert np.array_equal(u, w), b
+        h.set_state(b, al.p0, al.q0, VEL)
+    # (c) the depth hook over the same range
+    live = [b for b in range(5, 24) if outs[b - 5]["n"] > 0]
+    assert len(live) == 19, "every slot of the range must keep a point for the hook to run: " + str([o["n"] for o in outs])
+    summ = h.epi_depth_update(5, 19, T)
+    for b in range(5, 24):
+        g, s = singles[b]
+        assert summ[b - 5] == g.depth_update(0, 1, capi.DEPTH_EF_COORD, xy=[s["ef"]], T_kf_ef=T[b - 5:b - 4])[0], b
+        for x, y in zip(h.depth_get(b), g.depth_get(0)):
+            assert np.array_equal(x, y, equal_nan=True), b
+        g.close()
+    # (d) a range that ends at the handle's last slot
+    outs = h.epi_track_points(24, 16, 5)
+    for b in range(24, B):
+        g, s = single(b)
+        same_as_single(b, outs[b - 24], g, s)
+        g.close()
+    for b in range(5):
+        assert h._N[b] == pairs[b][0].N
+        for x, y in zip(h.depth_get(b) + h.klt_get(b), twin.depth_get(b) + twin.klt_get(b)):
+            assert np.array_equal(x, y, equal_nan=True), b
+    h.close()
+    twin.close()

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import np_epiline_oracle as eo
+import subpixel_cases as sc
 
 
 def _maps(img, tmpl, r, border=eo.BORDER_CONSTANT, value=0):
@@ -161,3 +162,119 @@ def test_sparse_model_normalisation_and_order():
     raw = -(g[:, 0] * f0 + g[:, 1] * f1)
     assert np.allclose(m, raw / np.sqrt(1e-3 + (raw * raw).sum()), rtol=1e-14, atol=0)
     assert np.array_equal(eo.sparse_model(kp, g, np.ones(3), np.zeros(6), K), np.zeros(3))
+
+
+# -- the inputs of the sub-pixel GPU tests (tests/subpixel_cases.py), checked before they reach a GPU ----------------------------------
+
+def test_subpixel_helper_promises():
+    for H, W in sc.FRAMES + [(480, 640)]:
+        al = sc.subpixel_alignment(3, H, W, 400)
+        kp = eo.slot_pixels(al.norm_coord, al.fx, al.fy, al.cx, al.cy)
+        assert np.abs(kp - al.coord).max() < 1e-4
+        assert (kp[:, 0] >= 1).all() and (kp[:, 0] <= W - 2).all() and (kp[:, 1] >= 1).all() and (kp[:, 1] <= H - 2).all()
+        fr = kp - np.floor(kp)
+        off_grid = ((fr >= 0.05) & (fr <= 0.95)).all(axis=1)
+        assert off_grid.mean() >= 0.7, (H, W, off_grid.mean())
+        for name in ("SEAMS", "LAST", "JUST_OUTSIDE"):
+            pts = np.array(getattr(sc, name)(H, W))
+            assert len(pts) > 0, (name, H, W)
+        s = np.array(sc.SEAMS(H, W))
+        assert set(np.floor(s[:, 0])) >= {v for v in (31, 32, 63, 64) if v < W} and (s[:, 0] < W).all() and (s[:, 1] < H).all()
+        assert set(np.floor(s[:, 1])) >= {v for v in (7, 8, 15, 16, 31, 32) if v < H}
+        assert set((s - np.floor(s)).ravel()) <= {0.25, 0.5, 0.75}
+        la = np.array(sc.LAST(H, W))
+        assert {(W - 1.0, H - 1.0), (W - 0.5, H - 0.5), (W - 1.0, H - 0.5), (W - 0.5, H - 1.0)} <= set(map(tuple, la))
+        jo = np.array(sc.JUST_OUTSIDE(H, W))
+        assert ((jo[:, 0] > -1) & (jo[:, 0] < 0) & (jo[:, 1] > 0) & (jo[:, 1] < H - 1)).any()
+        assert ((jo[:, 1] > -1) & (jo[:, 1] < 0) & (jo[:, 0] > 0) & (jo[:, 0] < W - 1)).any()
+        assert ((jo[:, 0] < 0) & (jo[:, 1] < 0)).any() and (jo[:, 0] > W).any() and (jo[:, 1] > H).any()
+        # `extra` is appended verbatim, and EXACT holds a pixel the slot stores as cell k - 1 with the fp32 fraction 1.0f
+        al = sc.subpixel_alignment(4, H, W, 10, extra=sc.EXACT)
+        assert al.N == 10 + len(sc.EXACT) and np.array_equal(al.coord[10:], np.array(sc.EXACT))
+        ex = np.array(sc.EXACT)
+        assert (ex[:, 0] < W - 1).all() and (ex[:, 1] < H - 1).all()
+        u = np.column_stack([al.fx * al.norm_coord[10:, 0] + al.cx, al.fy * al.norm_coord[10:, 1] + al.cy])
+        kp = eo.slot_pixels(al.norm_coord[10:], al.fx, al.fy, al.cx, al.cy)
+        below = (u < np.rint(u)) & (kp == np.rint(u))
+        assert below.any(), (H, W)
+        assert (kp == np.rint(kp)).all(axis=1).sum() >= 3
+    assert sc.subpixel_alignment(5, 37, 45, 0, extra=sc.JUST_OUTSIDE(37, 45)).N == len(sc.JUST_OUTSIDE(37, 45))
+
+
+def _parity_case_oracle(H, W, r, border, value):
+    """the oracle alone on the construction of test_parity_subpixel_odd_frames (tests/test_epiline_gpu.py): its own model image,
+    shifted by (2, -1), 5 % noise with seed r, as the fp32 frame a slot holds"""
+    al = sc.parity_alignment(H, W)
+    frame = sc.f32(sc.shifted_frame(sc.oracle_model(al), seed=r))
+    kp = eo.slot_pixels(al.norm_coord, al.fx, al.fy, al.cx, al.cy)
+    return eo.track_points_along_epiline(kp, sc.f32(al.grad), sc.f32(al.idp), sc.VEL, (al.fx, al.fy, al.cx, al.cy), frame, r, border,
+                                         value, with_maps=True)
+
+
+def test_parity_case_table_is_the_issue_s():
+    cases = set(sc.PARITY_CASES)
+    assert len(cases) == len(sc.PARITY_CASES) == 3 * 4 * 3 + (3 + 4) * 2
+    for H, W in sc.ODD_FRAMES:
+        for r in (0, 3, 7, 15):
+            for b in (eo.BORDER_REPLICATE, eo.BORDER_REFLECT, eo.BORDER_REFLECT_101):
+                assert (H, W, r, b, 0) in cases
+            for v in (0, 255):
+                assert ((H, W, r, eo.BORDER_CONSTANT, v) in cases) == ((H, W) == (37, 45) or ((H, W) == (61, 83) and r <= 7))
+
+
+@pytest.mark.parametrize("H,W,r,border,value", sc.PARITY_CASES)
+def test_parity_case_table_strict_shares(H, W, r, border, value):
+    """every committed case leaves at least half of its points with a strict best match, so the device is judged on the location of
+    those (at r = 0 every CCORR score is +-1: nothing is strict, only the tie rule applies)"""
+    ref = _parity_case_oracle(H, W, r, border, value)
+    assert len(ref["ssd"]) == sc.PARITY_N
+    s_ssd = sc.strict_share(ref["ssd_map"], ref["ssd"], r, False)
+    s_ncc = sc.strict_share(ref["ncc_map"], ref["ncc"], r, True)
+    print(f"strict shares {H}x{W} r={r} border={border}/{value}: ssd {s_ssd:.3f} ncc {s_ncc:.3f}")
+    assert s_ssd >= 0.5
+    if r >= 1:
+        assert s_ncc >= 0.5
+
+
+# -- the oracle against independent restatements of its padding and its correlation ---------------------------------------------------
+
+@pytest.mark.parametrize("shape", [(1, 6), (5, 7), (9, 70), (37, 45)])
+@pytest.mark.parametrize("r", [0, 1, 3, 7, 15])
+def test_copy_make_border_equals_np_pad(shape, r):
+    img = np.random.default_rng(shape[0] + r).normal(size=shape)
+    for border, mode, kw in ((eo.BORDER_REPLICATE, "edge", {}), (eo.BORDER_REFLECT, "symmetric", {}), (eo.BORDER_REFLECT_101, "reflect", {}),
+                             (eo.BORDER_CONSTANT, "constant", dict(constant_values=255.0)), (eo.BORDER_CONSTANT, "constant", dict(constant_values=0.0))):
+        got = eo.copy_make_border(img, r, border, kw.get("constant_values", 0))
+        assert got.shape == (shape[0] + 2 * r, shape[1] + 2 * r)
+        assert np.array_equal(got, np.pad(img, r, mode=mode, **kw)), (border, kw)
+
+
+@pytest.mark.parametrize("r", [0, 1, 3, 7])
+def test_score_maps_against_scipy_correlate2d(r):
+    sig = pytest.importorskip("scipy.signal")
+    rng = np.random.default_rng(20 + r)
+    P = rng.normal(size=(19 + 2 * r, 23 + 2 * r)).astype(np.float32)
+    T = rng.normal(size=(3, 2 * r + 1, 2 * r + 1)).astype(np.float32)
+    ssd, ncc = eo.score_maps(P, T)
+    P64 = P.astype(np.float64)
+    E = sig.correlate2d(P64 * P64, np.ones((2 * r + 1, 2 * r + 1)), mode="valid")
+    worst = 0.0
+    for i in range(3):
+        T64 = T[i].astype(np.float64)
+        C = sig.correlate2d(P64, T64, mode="valid")
+        S = float((T64 * T64).sum())
+        t = np.sqrt(E) * np.sqrt(S)
+        num = np.maximum(E - 2.0 * C + S, 0.0)
+        if r >= 1:
+            # no clamp branch is near its threshold: |C| < t and num >= t (or num < t) with room to spare
+            assert (np.abs(C) < t * (1 - 1e-6)).all() and (np.abs(num - t) > 1e-6 * t).all()
+            want_ncc = C / t
+        else:
+            # one pixel: |C| = |P||T| = t up to rounding, the +-1 branch (|C| < 1.125 t) with room to spare
+            assert (np.abs(np.abs(C) - t) <= 1e-12 * t).all() and (np.abs(num - t) > 1e-6 * t).all()
+            want_ncc = np.sign(C)
+        want_ssd = np.where(num < t, num / t, 1.0)
+        assert (np.abs(want_ncc) <= 1).all() and (want_ssd >= 0).all() and (want_ssd <= 1).all()
+        worst = max(worst, np.abs(ncc[i].astype(np.float64) - want_ncc).max(), np.abs(ssd[i].astype(np.float64) - want_ssd).max())
+    print(f"score_maps vs correlate2d, r={r}: {worst:.3e}")
+    assert worst <= 2.0 ** -24 + 1e-12

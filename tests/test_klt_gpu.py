@@ -314,3 +314,68 @@ def test_tracker_mirror(gpu, capi, synth):
     assert np.array_equal(kf.flow, o["flow"], equal_nan=True) and np.array_equal(kf.tracks, o["tracks"], equal_nan=True)
     assert len(kf.inv_depth) == o["n"]
     t.close()
+
+
+# -- frames that are no multiple of a tile or narrower than one, slot ranges that start above zero ------------------------------------
+
+@pytest.mark.parametrize("H,W,radius,num_level", [(H, W, r, None) for H, W in ((61, 83), (37, 45)) for r in (3, 7, 26)] +
+                         [(H, W, None, lv) for H, W in ((61, 83), (37, 45)) for lv in (3, 5)] + [(9, 70, 3, None), (9, 70, 7, None)])
+def test_odd_frames(gpu, capi, H, W, radius, num_level):
+    rng = np.random.default_rng(H + (radius or 0) + 10 * (num_level or 0))
+    px = _edge_pixels(H, W, rng)
+    h, g = _edge_keyframe(capi, H, W, px, rng)
+    out = (h.klt_track_points(0, 1, radius) if num_level is None else h.klt_track_points_pyr(0, 1, num_level))[0]
+    assert out["n"] == len(px)
+    ref, m = ko.track_points(out["coord"], _grad32(g), h.get_event_frame(0), radius) if num_level is None else \
+        ko.track_points_pyr(out["coord"], _grad32(g), h.get_event_frame(0), num_level)
+    _check(out["flow"], ref, m)
+    h.close()
+
+
+def test_sub_range_equals_singles_and_leaves_the_rest(gpu, capi, synth):
+    H, W, B, first, count = 120, 160, 40, 7, 18
+    als = _ragged(synth, n=B)
+    keys = ("coord", "tracks", "flow", "kept")
+
+    def load():
+        h = _load_shared(capi, als, H, W)
+        h.depth_init(0, B, min_depth=0.5, max_depth=6.0)
+        return h
+
+    h, twin, idle = load(), load(), load()                   # idle never runs the KLT
+    a1, b1 = h.klt_track_points(first, count, 5), twin.klt_track_points(first, count, 5)
+    a2, b2 = h.klt_track_points_pyr(first, count, 3), twin.klt_track_points_pyr(first, count, 3)
+    for b in range(first, first + count):
+        al = als[b] if (b - 1) % 5 else type(als[b])(**{**als[b].__dict__, "frame": als[b - 1].frame})      # the frame the slot samples
+        g = _handle(capi, [al], H, W)
+        g.depth_init(0, 1, min_depth=0.5, max_depth=6.0)
+        s1, s2 = g.klt_track_points(0, 1, 5)[0], g.klt_track_points_pyr(0, 1, 3)[0]
+        for k in keys:
+            assert np.array_equal(a1[b - first][k], s1[k], equal_nan=True), (b, k)
+            assert np.array_equal(a2[b - first][k], s2[k], equal_nan=True), (b, k)
+        assert h._N[b] == s2["n"] and a2[b - first]["n"] == s2["n"]
+        for x, y in zip(h.klt_get(b) + h.depth_get(b), g.klt_get(0) + g.depth_get(0)):
+            assert np.array_equal(x, y, equal_nan=True), b
+        g.close()
+    outside = list(range(first)) + list(range(first + count, B))
+    for b in outside:
+        assert h._N[b] == als[b].N
+        t, f = h.klt_get(b)
+        assert t.shape == (als[b].N, 2) and not t.any() and not f.any()
+        x, y = h.update_points(b, False), idle.update_points(b, False)        # (getCoord: it writes the slot's tracks, so it comes last)
+        assert x["coord"].shape == (als[b].N, 2)
+        for k in ("coord", "tracks", "kept"):
+            assert np.array_equal(x[k], y[k]), (b, k)
+    # the device's tracks of the range as the depth filter's input, against the same tracks passed from the host
+    s_dev = h.depth_update(first, count, capi.DEPTH_DEVICE_TRACKS)
+    s_host = twin.depth_update(first, count, capi.DEPTH_TRACKS, xy=[o["tracks"] for o in b2])
+    assert s_dev == s_host
+    for b in range(first, first + count):
+        assert np.array_equal(a2[b - first]["tracks"], b2[b - first]["tracks"], equal_nan=True)
+        for x, y in zip(h.depth_get(b), twin.depth_get(b)):
+            assert np.array_equal(x, y, equal_nan=True), b
+    for b in outside:
+        for x, y in zip(h.depth_get(b), idle.depth_get(b)):
+            assert np.array_equal(x, y, equal_nan=True), b
+    for x in (h, twin, idle):
+        x.close()

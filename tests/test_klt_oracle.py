@@ -127,3 +127,17 @@ def test_cv_sum_order():
     m = np.array([[1e16, 1.0, 1.0, 1.0, -1e16, 1.0]])
     # (((1e16 + 1) + 1) + 1) then + ((-1e16) alone) then + 1
     assert ko.cv_sum(m)[0] == ((0.0 + (((1e16 + 1.0) + 1.0) + 1.0)) + -1e16) + 1.0
+
+
+@pytest.mark.parametrize("shape", [(1, 6), (5, 7), (9, 70), (37, 45), (2, 2)])
+def test_gaussian_blur_3x3_against_scipy_correlate1d(shape):
+    """the blur every splat goes through against two separable scipy passes with the same taps and reflect-101 ("mirror") borders"""
+    ndi = pytest.importorskip("scipy.ndimage")
+    img = np.random.default_rng(shape[1]).normal(size=shape)
+    t = np.exp(-0.5 / (0.5 * 0.5))
+    k = np.array([t, 1.0, t]) / (1.0 + 2.0 * t)
+    want = ndi.correlate1d(ndi.correlate1d(img, k, axis=1, mode="mirror"), k, axis=0, mode="mirror")
+    got = ko.gaussian_blur_3x3(img, 0.5)
+    err = np.abs(got - want).max()
+    print(f"gaussian_blur_3x3 vs correlate1d {shape}: {err:.3e}")
+    assert err <= 4 * np.spacing(np.abs(want).max())
