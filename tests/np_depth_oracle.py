@@ -91,9 +91,29 @@ def projection_matrices(K, R, t):
     return P_kf, P_ef
 
 
-def inv_depth_two_points_eucl(x1, x2, P1, P2):
-    """invDepthTwoPointsEucl (DepthPoints.cpp:368-397), literally: homogeneous 3-vectors x1 (keyframe), x2 (event frame)"""
+def closed_form_K_inverse(K):
+    """K^-1 as the device's host code and `update` form it: entry by entry, no SVD"""
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    return np.array([[1.0 / fx, 0.0, -cx / fx], [0.0, 1.0 / fy, -cy / fy], [0.0, 0.0, 1.0]])
+
+
+def _rows_times(M, x):
+    """M x, each row summed left to right (no BLAS: its order and contraction are not ours to know)"""
+    return np.array([M[r, 0] * x[0] + M[r, 1] * x[1] + M[r, 2] * x[2] for r in range(3)])
+
+
+def inv_depth_two_points_eucl(x1, x2, P1, P2, inv_M1=None):
+    """invDepthTwoPointsEucl (DepthPoints.cpp:368-397), literally: homogeneous 3-vectors x1 (keyframe), x2 (event frame).
+    inv_M1: the inverse to use in place of pinv(M1) — with `closed_form_K_inverse` and row-wise products the triangulation rounds as
+    `update`'s does, to the last bit (what decides skip against update where the exact inverse depth is 0)"""
     M1, M2 = P1[:, :3], P2[:, :3]
+    if inv_M1 is not None:
+        x1p = _rows_times(M2, _rows_times(inv_M1, x1))
+        e2 = P2[:, 3]                               # C1 = (0, 0, 0, 1): P1's last column is zero
+        aux1 = np.array([x1p[1] * x2[2] - x1p[2] * x2[1], x1p[2] * x2[0] - x1p[0] * x2[2], x1p[0] * x2[1] - x1p[1] * x2[0]])
+        aux2 = np.array([x2[1] * e2[2] - x2[2] * e2[1], x2[2] * e2[0] - x2[0] * e2[2], x2[0] * e2[1] - x2[1] * e2[0]])
+        with np.errstate(all="ignore"):
+            return float((aux1[0] * aux2[0] + aux1[1] * aux2[1] + aux1[2] * aux2[2]) / (aux2[0] * aux2[0] + aux2[1] * aux2[1] + aux2[2] * aux2[2]))
     invM1 = np.linalg.pinv(M1)
     C1 = np.ones(4)
     C1[:3] = -invM1 @ P1[:, 3]
@@ -135,7 +155,8 @@ def _acos(x):
 def sigma2_from_depth_sigma(depth, depth_sigma):
     """getSigma2FromDepthSigma (DepthPoints.hpp:184-189); std::max(1e-12, d) is (1e-12 < d) ? d : 1e-12 (NaN -> 1e-12)"""
     d = depth - depth_sigma
-    sigma = 0.5 * (1.0 / (d if 1e-12 < d else 1e-12) - 1.0 / (depth + depth_sigma))
+    with np.errstate(all="ignore"):                 # IEEE division: 1 / 0 is inf, as in C++ (a Python float raises)
+        sigma = 0.5 * (1.0 / (d if 1e-12 < d else 1e-12) - float(np.float64(1.0) / np.float64(depth + depth_sigma)))
     return sigma * sigma
 
 
@@ -187,16 +208,19 @@ def is_converged(state, mu_range, threshold):
     return state[1] < thresh * thresh
 
 
-def update_literal(prm: Params, seeds, kf_coord, ef_coord, R, t, t_kf_ef):
+def update_literal(prm: Params, seeds, kf_coord, ef_coord, R, t, t_kf_ef, closed_form_inverse=False):
     """DepthPoints::update (ef_coord overload, DepthPoints.cpp:101-135), one point at a time; seeds N x 4 in place.
-    Returns the summary counts."""
+    Returns the summary counts.  closed_form_inverse: K^-1 and P_ef entry by entry as `update` forms them, instead of pinv and BLAS."""
     P_kf, P_ef = projection_matrices(prm.K, R, t)
+    inv_M1 = None
+    if closed_form_inverse:
+        P_ef, inv_M1 = projection_rows(prm.K, R, t), closed_form_K_inverse(prm.K)
     cnt = dict(updated=0, skipped_nan=0, sigma2_restored=0, mu_reset=0, converged=0)
     for i in range(len(seeds)):
         x_kf = np.array([kf_coord[i][0], kf_coord[i][1], 1.0])
         x_ef = np.array([ef_coord[i][0], ef_coord[i][1], 1.0])
         with np.errstate(all="ignore"):
-            inv_depth = inv_depth_two_points_eucl(x_kf, x_ef, P_kf, P_ef)
+            inv_depth = inv_depth_two_points_eucl(x_kf, x_ef, P_kf, P_ef, inv_M1)
             depth = 1.0 / inv_depth if inv_depth != 0 else math.copysign(math.inf, inv_depth)
             x_norm = ((x_ef[0] - prm.cx) / prm.fx, (x_ef[1] - prm.cy) / prm.fy)
             try:
@@ -214,76 +238,110 @@ def update_literal(prm: Params, seeds, kf_coord, ef_coord, R, t, t_kf_ef):
 
 
 # ---- vectorised: the same operations in the same order over arrays ------------------------------------------------------------
-def update(prm: Params, seeds, kf_coord, ef_coord, R, t, t_kf_ef):
-    """seeds N x 4 (updated in place), kf_coord / ef_coord N x 2 pixels.  Returns the summary counts."""
+def projection_rows(K, R, t, T=np.float64):
+    """P_ef = K [R | t] with the products and sums in the order the device's host code forms them (csrc/eds_depth.hip)"""
+    K, R, t = np.asarray(K, dtype=T), np.asarray(R, dtype=T), np.asarray(t, dtype=T)
+    Pe = np.empty((3, 4), dtype=T)
+    for r in range(3):
+        for c in range(3):
+            Pe[r, c] = K[r, 0] * R[0, c] + K[r, 1] * R[1, c] + K[r, 2] * R[2, c]
+        Pe[r, 3] = K[r, 0] * t[0] + K[r, 1] * t[1] + K[r, 2] * t[2]
+    return Pe
+
+
+def evaluate(prm: Params, seeds, kf_coord, ef_coord, R, t, t_kf_ef, T=np.float64):
+    """DepthPoints::update per point, nothing written: every operation of `update` in its order, in the number format T.  The inputs
+    (fp64 pixels, seeds, K, R, t, px_error_angle and the reference's fp64 constant pi) are the same numbers in every format;
+    T = np.longdouble is the extended-precision evaluation of the same formulas.  Returns a dict of length-N arrays:
+      run                          filterVogiatzis ran (not the NaN skip)
+      restored, reset, converged   the branches taken, and isConverged of the seed the point ends with
+      mu_new, sigma2_new           BEFORE the sigma2 < 0 / mu < 0 branches
+      a_new, b_new, m, C1, C2      the other updated values and the terms of mu_new = C1 m + C2 mu
+      f, e, inv_depth, tau2        the Beta moments behind a_new / b_new, the triangulated inverse depth and its variance
+      seeds                        N x 4, the seeds after the update (input rows where run is False)"""
     with np.errstate(all="ignore"):
-        K = prm.K
-        Ki = np.array([[1.0 / prm.fx, 0.0, -prm.cx / prm.fx], [0.0, 1.0 / prm.fy, -prm.cy / prm.fy], [0.0, 0.0, 1.0]])
-        Pe = np.empty((3, 4))
-        for r in range(3):
-            for c in range(3):
-                Pe[r, c] = K[r, 0] * R[0, c] + K[r, 1] * R[1, c] + K[r, 2] * R[2, c]
-            Pe[r, 3] = K[r, 0] * t[0] + K[r, 1] * t[1] + K[r, 2] * t[2]
+        c = lambda x: np.asarray(x, dtype=T)
+        one, two, half = T(1.0), T(2.0), T(0.5)
+        fx, fy, cx, cy = T(prm.fx), T(prm.fy), T(prm.cx), T(prm.cy)
+        pi = T(math.pi)
+        zero = T(0.0)
+        Ki = [[one / fx, zero, -cx / fx], [zero, one / fy, -cy / fy], [zero, zero, one]]
+        Pe = projection_rows(prm.K, R, t, T)
+        kf_coord, ef_coord, seeds = c(kf_coord), c(ef_coord), c(seeds)
         u, v = kf_coord[:, 0], kf_coord[:, 1]
         ue, ve = ef_coord[:, 0], ef_coord[:, 1]
-        y0 = Ki[0, 0] * u + Ki[0, 1] * v + Ki[0, 2]
-        y1 = Ki[1, 0] * u + Ki[1, 1] * v + Ki[1, 2]
-        y2 = Ki[2, 0] * u + Ki[2, 1] * v + Ki[2, 2]
+        y0 = Ki[0][0] * u + Ki[0][1] * v + Ki[0][2]
+        y1 = Ki[1][0] * u + Ki[1][1] * v + Ki[1][2]
+        y2 = Ki[2][0] * u + Ki[2][1] * v + Ki[2][2]
         p0 = Pe[0, 0] * y0 + Pe[0, 1] * y1 + Pe[0, 2] * y2
         p1 = Pe[1, 0] * y0 + Pe[1, 1] * y1 + Pe[1, 2] * y2
         p2 = Pe[2, 0] * y0 + Pe[2, 1] * y1 + Pe[2, 2] * y2
         e0, e1, e2 = Pe[0, 3], Pe[1, 3], Pe[2, 3]
-        a1x, a1y, a1z = p1 * 1.0 - p2 * ve, p2 * ue - p0 * 1.0, p0 * ve - p1 * ue
-        a2x, a2y, a2z = ve * e2 - 1.0 * e1, 1.0 * e0 - ue * e2, ue * e1 - ve * e0
+        a1x, a1y, a1z = p1 * one - p2 * ve, p2 * ue - p0 * one, p0 * ve - p1 * ue
+        a2x, a2y, a2z = ve * e2 - one * e1, one * e0 - ue * e2, ue * e1 - ve * e0
         inv_depth = (a1x * a2x + a1y * a2y + a1z * a2z) / (a2x * a2x + a2y * a2y + a2z * a2z)
-        depth = 1.0 / inv_depth
-        xn, yn = (ue - prm.cx) / prm.fx, (ve - prm.cy) / prm.fy
-        bn = np.sqrt(xn * xn + yn * yn + 1.0 * 1.0)
-        bx, by, bz = xn / bn, yn / bn, 1.0 / bn
-        tx, ty, tz = t_kf_ef
+        depth = one / inv_depth
+        xn, yn = (ue - cx) / fx, (ve - cy) / fy
+        bn = np.sqrt(xn * xn + yn * yn + one * one)
+        bx, by, bz = xn / bn, yn / bn, one / bn
+        tx, ty, tz = (T(x) for x in t_kf_ef)
         ax, ay, az = bx * depth - tx, by * depth - ty, bz * depth - tz
-        t_norm = math.sqrt(tx * tx + ty * ty + tz * tz)
+        t_norm = np.sqrt(tx * tx + ty * ty + tz * tz)
         a_norm = np.sqrt(ax * ax + ay * ay + az * az)
         alpha = np.arccos((bx * tx + by * ty + bz * tz) / t_norm)
         beta = np.arccos((ax * -tx + ay * -ty + az * -tz) / (t_norm * a_norm))
-        beta_plus = beta + prm.px_error_angle
-        gamma_plus = math.pi - alpha - beta_plus
+        beta_plus = beta + T(prm.px_error_angle)
+        gamma_plus = pi - alpha - beta_plus
         z_plus = t_norm * np.sin(beta_plus) / np.sin(gamma_plus)
         tau = z_plus - depth
         dm = depth - tau
-        sg = 0.5 * (1.0 / np.where(1e-12 < dm, dm, 1e-12) - 1.0 / (depth + tau))
+        sg = half * (one / np.where(T(1e-12) < dm, dm, T(1e-12)) - one / (depth + tau))
         tau2 = sg * sg
-        mu, sigma2, a, b = (seeds[:, c].copy() for c in range(4))
+        mu, sigma2, a, b = (seeds[:, k].copy() for k in range(4))
         norm_scale = np.sqrt(sigma2 + tau2)
         run = ~np.isnan(norm_scale)
         z = inv_depth
-        s2 = 1.0 / (1.0 / sigma2 + 1.0 / tau2)
+        s2 = one / (one / sigma2 + one / tau2)
         m = s2 * (mu / sigma2 + z / tau2)
-        uniform_x = 1.0 / prm.mu_range
+        uniform_x = one / T(prm.mu_range)
         ex = z - mu
         ex = ex * -ex
-        ex = ex / (2 * norm_scale * norm_scale)
-        pdf = np.exp(ex) / (norm_scale * math.sqrt(2 * math.pi))
+        ex = ex / (two * norm_scale * norm_scale)
+        pdf = np.exp(ex) / (norm_scale * np.sqrt(two * pi))
         C1 = a / (a + b) * pdf
         C2 = b / (a + b) * uniform_x
         nc = C1 + C2
         C1 = C1 / nc
         C2 = C2 / nc
-        f = C1 * (a + 1.0) / (a + b + 1.0) + C2 * a / (a + b + 1.0)
-        e = C1 * (a + 1.0) * (a + 2.0) / ((a + b + 1.0) * (a + b + 2.0)) + C2 * a * (a + 1.0) / ((a + b + 1.0) * (a + b + 2.0))
+        f = C1 * (a + one) / (a + b + one) + C2 * a / (a + b + one)
+        e = C1 * (a + one) * (a + two) / ((a + b + one) * (a + b + two)) + C2 * a * (a + one) / ((a + b + one) * (a + b + two))
         mu_new = C1 * m + C2 * mu
         sigma2_new = C1 * (s2 + m * m) + C2 * (sigma2 + mu * mu) - mu_new * mu_new
         a_new = (e - f) / (f - e / f)
-        b_new = a_new * (1.0 - f) / f
-        restored = run & (sigma2_new < 0.0)
-        sigma2_new = np.where(sigma2_new < 0.0, sigma2, sigma2_new)
-        reset = run & (mu_new < 0.0)
-        mu_new = np.where(mu_new < 0.0, 1.0, mu_new)
-        seeds[run, 0], seeds[run, 1], seeds[run, 2], seeds[run, 3] = mu_new[run], sigma2_new[run], a_new[run], b_new[run]
-        th = prm.mu_range / prm.convergence_sigma2_thresh
-        conv = seeds[:, 1] < th * th
-    return dict(updated=int(run.sum()), skipped_nan=int((~run).sum()), sigma2_restored=int(restored.sum()), mu_reset=int(reset.sum()),
-                converged=int(conv.sum()))
+        b_new = a_new * (one - f) / f
+        restored = run & (sigma2_new < zero)
+        reset = run & (mu_new < zero)
+        out = seeds.copy()
+        out[run, 0] = np.where(mu_new < zero, one, mu_new)[run]
+        out[run, 1] = np.where(sigma2_new < zero, sigma2, sigma2_new)[run]
+        out[run, 2], out[run, 3] = a_new[run], b_new[run]
+        th = T(prm.mu_range) / T(prm.convergence_sigma2_thresh)
+        conv = out[:, 1] < th * th
+    return dict(run=run, restored=restored, reset=reset, converged=conv, mu_new=mu_new, sigma2_new=sigma2_new, a_new=a_new, b_new=b_new,
+                m=m, C1=C1, C2=C2, f=f, e=e, seeds=out, inv_depth=inv_depth, tau2=tau2, thresh2=th * th)
+
+
+def update(prm: Params, seeds, kf_coord, ef_coord, R, t, t_kf_ef):
+    """seeds N x 4 (updated in place), kf_coord / ef_coord N x 2 pixels.  Returns the summary counts."""
+    ev = evaluate(prm, seeds, np.asarray(kf_coord, dtype=np.float64), np.asarray(ef_coord, dtype=np.float64), R, t, t_kf_ef)
+    seeds[:] = ev["seeds"]
+    return summary_of(ev)
+
+
+def summary_of(ev):
+    run = ev["run"]
+    return dict(updated=int(run.sum()), skipped_nan=int((~run).sum()), sigma2_restored=int(ev["restored"].sum()),
+                mu_reset=int(ev["reset"].sum()), converged=int(ev["converged"].sum()))
 
 
 def reproject_tracks(norm_xy, rho, K4, p, q):
