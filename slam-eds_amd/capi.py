@@ -65,6 +65,13 @@ EPI_EXPORTS = ("eds_epi_abi_version", "eds_epi_track_points", "eds_epi_get", "ed
 # enum eds_epi_border: cv::BORDER_* (BORDER_DEFAULT = REFLECT_101)
 EPI_BORDER_CONSTANT, EPI_BORDER_REPLICATE, EPI_BORDER_REFLECT, EPI_BORDER_REFLECT_101 = 0, 1, 2, 4
 
+# every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
+DEV_EXPORTS = (
+    "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
+    "eds_dev_wait_stream", "eds_dev_signal_stream", "eds_dev_set_event_frames", "eds_dev_build_event_frames", "eds_dev_set_keyframes",
+    "eds_dev_set_idepths",
+)
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -154,6 +161,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_depth.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_klt.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_epiline.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_device.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
@@ -280,6 +288,18 @@ def lib():
         L.eds_epi_get.argtypes = [C.c_void_p, C.c_int, _dp]
         L.eds_epi_get_model.argtypes = [C.c_void_p, C.c_int, _dp]
         L.eds_epi_depth_update.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(DepthSummary)]
+        L.eds_dev_check_range.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
+        L.eds_dev_malloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.eds_dev_free.argtypes = [C.c_void_p]
+        L.eds_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.eds_dev_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.eds_dev_wait_stream.argtypes = [C.c_void_p, C.c_void_p]
+        L.eds_dev_signal_stream.argtypes = [C.c_void_p, C.c_void_p]
+        L.eds_dev_set_event_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64]
+        L.eds_dev_build_event_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                                 C.c_int, _dp]
+        L.eds_dev_set_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, _dp]
+        L.eds_dev_set_idepths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int]
         if L.eds_trk_cfg_size() != C.sizeof(Cfg) or L.eds_trk_info_size() != C.sizeof(Info):
             raise EdsError(ERR_INVALID, "ctypes struct layout disagrees with include/eds_hip.h")
         _lib = L
@@ -316,6 +336,169 @@ def _rows(a, count, width):
     if t.ndim == (1 if width == 1 else 2):
         t = t[None]
     return np.ascontiguousarray(t), int(t.shape[1])
+
+
+# -- arrays in device memory (include/eds_hip_device.h) --------------------------------------------------------------------------
+# Everything below up to DeviceArray is pure Python: it reads ``__cuda_array_interface__`` (torch device tensors on ROCm have it,
+# DeviceArray has it) or a raw ``(ptr, shape, strides, dtype)`` tuple and raises ValueError before the library is called.
+def is_device_array(obj) -> bool:
+    return hasattr(obj, "__cuda_array_interface__")
+
+
+def device_array_info(obj):
+    """``(ptr, shape, strides in ELEMENTS, numpy dtype)`` of an object with ``__cuda_array_interface__`` or of a raw
+    ``(ptr, shape, strides in bytes or None, dtype)`` tuple.  ValueError: no pointer, or a byte stride that is no whole number of
+    elements."""
+    if isinstance(obj, tuple) and len(obj) == 4 and not hasattr(obj, "__cuda_array_interface__"):
+        ptr, shape, strides, dtype = obj
+        dt = np.dtype(dtype)
+    else:
+        try:
+            cai = obj.__cuda_array_interface__
+        except AttributeError:
+            raise ValueError("not a device array: no __cuda_array_interface__ (and not a (ptr, shape, strides, dtype) tuple)") from None
+        ptr, shape, strides = cai["data"][0], cai["shape"], cai.get("strides")
+        dt = np.dtype(cai["typestr"])
+    shape = tuple(int(n) for n in shape)
+    if dt.byteorder == ">":
+        raise ValueError("big-endian device array")
+    if not ptr and int(np.prod(shape, dtype=np.int64)) > 0:
+        raise ValueError("device array without a pointer")
+    if strides is None:                     # C-contiguous
+        st, acc = [], 1
+        for n in reversed(shape):
+            st.append(acc)
+            acc *= max(n, 1)
+        est = tuple(reversed(st))
+    else:
+        if len(strides) != len(shape):
+            raise ValueError("strides and shape have different lengths")
+        for b in strides:
+            if int(b) % dt.itemsize:
+                raise ValueError(f"a stride of {int(b)} bytes is no whole number of {dt.name} elements")
+        est = tuple(int(b) // dt.itemsize for b in strides)
+    return int(ptr or 0), shape, est, dt
+
+
+def device_frames_args(obj, H, W):
+    """Arguments of eds_dev_set_event_frames for `obj`: ``(ptr, count, dtype code, frame_stride, row_stride)``, strides in elements.
+    `obj`: count x H x W (or H x W: one frame), float32 or float64, last dimension contiguous, rows and frames not overlapping."""
+    ptr, shape, est, dt = device_array_info(obj)
+    if len(shape) == 2:
+        shape, est = (1,) + shape, (0,) + est
+    if len(shape) != 3:
+        raise ValueError(f"event frames must be count x H x W (or H x W), not {len(shape)}-dimensional")
+    if dt == np.float32:
+        code = IMG_F32
+    elif dt == np.float64:
+        code = IMG_F64
+    else:
+        raise ValueError(f"event frames must be float32 or float64, not {dt.name}")
+    count = shape[0]
+    if shape[1:] != (int(H), int(W)):
+        raise ValueError(f"frames of {shape[1]} x {shape[2]} do not fit a handle of {H} x {W}")
+    if count < 1:
+        raise ValueError("no frame")
+    if est[2] != 1:
+        raise ValueError("the last dimension must be contiguous (a stride of one element)")
+    row = est[1]
+    if row < W:
+        raise ValueError("rows overlap or run backwards (row stride < W)")
+    need = (H - 1) * row + W
+    frame = est[0] if count > 1 else need
+    if frame < need:
+        raise ValueError("frames overlap or run backwards (frame stride < (H - 1) * row stride + W)")
+    return ptr, count, code, frame, row
+
+
+def _device_rows(obj, count, width, name):
+    """(ptr, points per row, point stride between rows) of a float64 device array count x S [x width] whose rows are dense"""
+    ptr, shape, est, dt = device_array_info(obj)
+    if dt != np.float64:
+        raise ValueError(f"{name} must be float64, not {dt.name}")
+    want = 2 if width == 1 else 3
+    if len(shape) == want - 1:
+        shape, est = (1,) + shape, (0,) + est
+    if len(shape) != want or shape[0] != count or (width > 1 and shape[2] != width):
+        raise ValueError(f"{name} must be count x S" + (f" x {width}" if width > 1 else "") + f" with count = {count}, not {shape}")
+    if est[-1] != 1 or (width > 1 and est[1] != width):
+        raise ValueError(f"the rows of {name} must be contiguous")
+    S = shape[1]
+    if count > 1 and (est[0] % width or est[0] // width < S):
+        raise ValueError(f"the rows of {name} overlap or are not a whole number of points apart")
+    return ptr, S, (est[0] // width if count > 1 else S)
+
+
+def _stream_ptr(stream):
+    """a hipStream_t as an integer: None / 0 is the null stream; an int, or an object with ``.cuda_stream`` (torch.cuda.Stream)"""
+    if stream is None:
+        return None
+    v = int(getattr(stream, "cuda_stream", stream))
+    return v or None
+
+
+class DeviceArray:
+    """A dense array in device memory, owned through ``eds_dev_malloc`` (the HIP runtime libeds_hip.so itself is bound to), for
+    callers without a HIP binding and for the tests.  Has ``__cuda_array_interface__``; ``view`` describes a strided window of it."""
+
+    def __init__(self, shape, dtype, device=0):
+        self.shape = tuple(int(n) for n in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+        self.dtype = np.dtype(dtype)
+        self.device = int(device)
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        p = C.c_void_p()
+        _check(lib().eds_dev_malloc(self.device, max(self.nbytes, 1), C.byref(p)))
+        self.ptr = int(p.value)
+
+    @classmethod
+    def from_numpy(cls, a, device=0):
+        a = np.ascontiguousarray(a)
+        d = cls(a.shape, a.dtype, device)
+        if d.nbytes:
+            _check(lib().eds_dev_upload(C.c_void_p(d.ptr), a.ctypes.data_as(C.c_void_p), d.nbytes))
+        return d
+
+    def numpy(self):
+        out = np.empty(self.shape, dtype=self.dtype)
+        if self.nbytes:
+            _check(lib().eds_dev_download(out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr), self.nbytes))
+        return out
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": self.shape, "typestr": self.dtype.str, "data": (self.ptr, False), "strides": None, "version": 3}
+
+    def view(self, shape, strides=None, offset=0):
+        """A window of this buffer: `shape`, `strides` in BYTES (None: dense), starting `offset` bytes in.  Keeps the buffer alive."""
+        return DeviceView(self, tuple(int(n) for n in shape), None if strides is None else tuple(int(b) for b in strides), int(offset))
+
+    def free(self):
+        if getattr(self, "ptr", 0):
+            lib().eds_dev_free(C.c_void_p(self.ptr))
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceView:
+    """What DeviceArray.view returns: ``__cuda_array_interface__`` of a strided window; owns nothing."""
+
+    def __init__(self, base, shape, strides, offset):
+        self.base, self.shape, self.strides, self.offset = base, shape, strides, offset
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": self.shape, "typestr": self.base.dtype.str, "data": (self.base.ptr + self.offset, False), "strides": self.strides,
+                "version": 3}
+
+
+def check_range(ptr, nbytes, device=0) -> int:
+    """``eds_dev_check_range``: EDS_OK or ERR_INVALID (the reason: last_error()).  Launches nothing."""
+    return int(lib().eds_dev_check_range(int(device), C.c_void_p(int(ptr) or None), int(nbytes)))
 
 
 def default_config(**kw) -> Cfg:
@@ -406,6 +589,79 @@ class Handle:
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         fn = lib().eds_trk_set_event_frames_f32 if f32 else lib().eds_trk_set_event_frames
         _check(fn(self._h, int(first), len(arrs), ptrs))
+
+    # -- inputs that already live in device memory (include/eds_hip_device.h) -----------------------------------------------
+    def wait_stream(self, stream=None):
+        """The handle's stream waits for everything queued on `stream` so far (an int, an object with ``.cuda_stream``, None: the null stream)."""
+        _check(lib().eds_dev_wait_stream(self._h, _stream_ptr(stream)))
+
+    def signal_stream(self, stream=None):
+        """`stream` waits for everything queued on the handle's stream so far: a source buffer may be reused behind this."""
+        _check(lib().eds_dev_signal_stream(self._h, _stream_ptr(stream)))
+
+    def set_event_frames_device(self, first, frames):
+        """count x H x W (or H x W) float32 / float64 frames in device memory -> slots first .. first + count - 1, one launch on the
+        handle's stream (eds_dev_set_event_frames).  `frames`: anything with ``__cuda_array_interface__``, or (ptr, shape, strides, dtype)."""
+        ptr, count, code, fs, rs = device_frames_args(frames, self.H, self.W)
+        _check(lib().eds_dev_set_event_frames(self._h, int(first), count, code, C.c_void_p(ptr), fs, rs))
+
+    def build_event_frames_device(self, first_slot, offsets, x, y, polarity, level=0, blur_sigma=0.5, use_exp_weights=True):
+        """build_event_frame_batch with the concatenated event arrays (uint16 x, y, uint8 polarity) in device memory; slice b is
+        events offsets[b] .. offsets[b + 1] - 1.  Returns the norms."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int32)
+        if offs.ndim != 1 or offs.shape[0] < 2:
+            raise ValueError("offsets: count + 1 integers")
+        ptrs = []
+        for a, dt, name in ((x, np.uint16, "x"), (y, np.uint16, "y"), (polarity, np.uint8, "polarity")):
+            ptr, shape, est, d = device_array_info(a)
+            if d != dt or len(shape) != 1 or est[0] != 1:
+                raise ValueError(f"{name} must be a contiguous 1-D {np.dtype(dt).name} device array")
+            if shape[0] < int(offs[-1]):
+                raise ValueError(f"{name} holds {shape[0]} events, the offsets ask for {int(offs[-1])}")
+            ptrs.append(C.c_void_p(ptr or None))
+        norms = np.zeros(offs.shape[0] - 1)
+        _check(lib().eds_dev_build_event_frames(self._h, int(first_slot), offs.shape[0] - 1, offs.ctypes.data_as(_ip), *ptrs, int(level),
+                                                float(blur_sigma), int(bool(use_exp_weights)), _p(norms)))
+        return norms
+
+    def set_keyframes_device(self, first, N, norm_coord, grad, idp, weights, K):
+        """set_keyframe for slots first .. first + len(N) - 1 from float64 device arrays: norm_coord, grad count x S x 2, idp, weights
+        count x S (rows the same number of points apart in all four), N[b] points used of row b, K count x (fx, fy, cx, cy)."""
+        n = np.ascontiguousarray(N, dtype=np.int32).reshape(-1)
+        count = int(n.shape[0])
+        k = _f64(K).reshape(-1)
+        if k.shape[0] != 4 * count:
+            raise ValueError("K must be count x 4 (fx, fy, cx, cy)")
+        rows = [_device_rows(a, count, w, name) for a, w, name in ((norm_coord, 2, "norm_coord"), (grad, 2, "grad"), (idp, 1, "idp"),
+                                                                   (weights, 1, "weights"))]
+        if len({r[2] for r in rows}) != 1:
+            raise ValueError("the four keyframe arrays must have the same point stride between alignments")
+        if count and int(n.max()) > min(r[1] for r in rows):
+            raise ValueError("N exceeds the points per row of the arrays")
+        if count and (int(n.min()) < 1 or int(n.max()) > self.max_points):
+            raise ValueError("N out of range for this handle")
+        _check(lib().eds_dev_set_keyframes(self._h, int(first), count, n.ctypes.data_as(_ip), *[C.c_void_p(r[0] or None) for r in rows],
+                                           rows[0][2], _p(k)))
+        for b in range(count):
+            self._N[int(first) + b] = int(n[b])
+
+    def set_idepths_device(self, first, idp):
+        """set_idepth for slots first .. first + count - 1 from a float64 device array count x S (or count x S x k: column 0 of an
+        S x k table per slot, as set_idepth_strided)."""
+        ptr, shape, est, dt = device_array_info(idp)
+        if dt != np.float64:
+            raise ValueError(f"idp must be float64, not {dt.name}")
+        if len(shape) == 3:
+            shape, est = shape[:2], est[:2]
+        if len(shape) != 2:
+            raise ValueError("idp must be count x S (or count x S x k)")
+        count, S = shape
+        es = est[1]
+        if count < 1 or es < 1 or (count > 1 and (est[0] % es or est[0] // es < S)):
+            raise ValueError("idp: rows must be a whole, non-overlapping number of points apart")
+        if max(self._N[int(first):int(first) + count] + [0]) > S:
+            raise ValueError("idp holds fewer points per row than the slots do")
+        _check(lib().eds_dev_set_idepths(self._h, int(first), count, C.c_void_p(ptr or None), est[0] // es if count > 1 else S, es))
 
     def set_undistort_map(self, mapx=None, mapy=None):
         if mapx is None:

@@ -114,6 +114,8 @@ void free_all(eds_trk* h) {
     if (h->ev_stage) hipEventDestroy(h->ev_stage);
     if (h->ev_idp) hipEventDestroy(h->ev_idp);
     if (h->ev_up) hipEventDestroy(h->ev_up);
+    if (h->ev_dev_in) hipEventDestroy(h->ev_dev_in);
+    if (h->ev_dev_out) hipEventDestroy(h->ev_dev_out);
     if (h->st_up) hipStreamDestroy(h->st_up);
     if (h->st) hipStreamDestroy(h->st);
     delete h;

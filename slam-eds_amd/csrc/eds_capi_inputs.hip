@@ -25,7 +25,7 @@ using namespace edscapi;
 // (Round 1 built the tiled, margin-padded image element by element on one host thread: 300 us for 640x480, more than the solve;
 // chunked hipMemcpyAsync into HBM + one tiling launch: 80 us, 30 of them after the host had finished.)
 // slots that are about to receive a frame of their own stop sampling somebody else's
-static int unshare_frames(eds_trk* h, int first, int count) {
+int edscapi::unshare_frames(eds_trk* h, int first, int count) {
     for (int s = first; s < first + count; ++s) {
         if (h->slots[s].frame_slot < 0) continue;
         h->slots[s].frame_slot = -1;

@@ -40,6 +40,7 @@ int update_points_range(eds_trk* h, int first, int count, int delete_out_points,
                         int32_t* kept_index, int* n_kept, double* mean_sq_flow, const EdsPointsDev* dev = nullptr);
 // eds_capi_inputs.hip
 int refresh_gram(eds_trk* h, int slot, bool wait = true);
+int unshare_frames(eds_trk* h, int first, int count);       // slots about to receive a frame of their own stop sampling somebody else's
 // eds_capi_solve.hip
 int solve_host(eds_trk* h, int level, int first, int count);
 int materialise_residuals(eds_trk* h, int slot);

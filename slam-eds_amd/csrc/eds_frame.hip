@@ -510,8 +510,9 @@ int eds_frame_build_levels(eds_trk* h, int first_slot, int level0, int nlevels, 
 // over all slices of a chunk, one blur, one level + sum-of-squares launch, one normalise + tile launch (blockIdx.z = image).  Same
 // arithmetic per image as eds_frame_build_levels.
 #define EDS_FRAME_BATCH 32
+// (dev_events: ex / ey / pol are device memory — include/eds_hip_device.h — and the vote reads them where they are: no staging, no copy)
 int eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offsets, const uint16_t* ex, const uint16_t* ey, const uint8_t* pol,
-                          int level, double blur_sigma, int use_exp_weights, double* norms_out) {
+                          int level, double blur_sigma, int use_exp_weights, double* norms_out, bool dev_events) {
     EdsFrameBuffers& fb = h->frame_build;
     const int H = h->H, W = h->W;
     const size_t n = (size_t)H * W;
@@ -558,7 +559,7 @@ int eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offs
         int* h_off = reinterpret_cast<int*>(fb.h_bmeta + (size_t)fb.meta_cap * 8);     // [meta_cap + 1] event offsets relative to the group
         double* d_tot = reinterpret_cast<double*>(fb.d_bmeta);
         int* d_off = reinterpret_cast<int*>(fb.d_bmeta + (size_t)fb.meta_cap * 8);
-        if (gev > fb.cap_events) {           // the mapped staging of the single-slice builder, grown
+        if (!dev_events && gev > fb.cap_events) {           // the mapped staging of the single-slice builder, grown
             if (fb.h_events) hipHostFree(fb.h_events);
             fb.h_events = nullptr; fb.d_ex = fb.d_ey = nullptr; fb.d_pol = nullptr;
             fb.cap_events = (int)((gev + gev / 4 + 1024 + 7) & ~7ll);
@@ -578,7 +579,7 @@ int eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offs
             const int e0 = h_off[c0], ne = h_off[c0 + cn] - e0;
             int maxn = 0;
             for (int b = 0; b < cn; ++b) maxn = std::max(maxn, h_off[c0 + b + 1] - h_off[c0 + b]);
-            if (ne > 0) {
+            if (ne > 0 && !dev_events) {
                 std::memcpy(fb.h_events + (size_t)e0 * 2, ex + ge0 + e0, (size_t)ne * 2);
                 std::memcpy(fb.h_events + cap * 2 + (size_t)e0 * 2, ey + ge0 + e0, (size_t)ne * 2);
                 std::memcpy(fb.h_events + cap * 4 + (size_t)e0, pol + ge0 + e0, (size_t)ne);
@@ -587,8 +588,8 @@ int eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offs
             if (e == hipSuccess) e = hipMemsetAsync(fb.b_norm, 0, (size_t)cn * EDS_SUMSQ_WAYS * 8, st);
             if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
             if (maxn > 0)
-                hipLaunchKernelGGL(k_vote_batch, dim3((maxn + 255) / 256, cn), dim3(256), 0, st, fb.d_ex, fb.d_ey, fb.d_pol, d_off + c0, fb.d_mapx,
-                                   fb.d_mapy, H, W, use_exp_weights, fb.b_img);
+                hipLaunchKernelGGL(k_vote_batch, dim3((maxn + 255) / 256, cn), dim3(256), 0, st, dev_events ? ex + ge0 : fb.d_ex, dev_events ? ey + ge0 : fb.d_ey,
+                                   dev_events ? pol + ge0 : fb.d_pol, d_off + c0, fb.d_mapx, fb.d_mapy, H, W, use_exp_weights, fb.b_img);
             double* cur = fb.b_img;
             const bool fused0 = blur_sigma > 0.0 && level == 0;       // the blurred image is the level: blur + plane + sum of squares in one launch
             if (blur_sigma > 0.0) {

@@ -149,7 +149,7 @@ struct EdsFrameBuffers {
 };
 void eds_frame_free(EdsFrameBuffers* fb);
 int  eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offsets, const uint16_t* ex, const uint16_t* ey, const uint8_t* pol,
-                           int level, double blur_sigma, int use_exp_weights, double* norms_out);
+                           int level, double blur_sigma, int use_exp_weights, double* norms_out, bool dev_events = false);
 // few alignments per launch: one more (tiny) launch writes the kept residuals into pinned host memory as well, so that reading
 // them back (Tracker.cpp:223-230) costs no copy call and no second wait; false: not mirrored (fetch as usual)
 bool eds_mirror_residuals(eds_trk* h, int first, int count);

@@ -97,6 +97,7 @@ struct eds_trk {
     int bstage_slots = 0;
     bool bstage_busy = false;           // the last batch's store kernels may still read the ring
     std::vector<hipEvent_t> ev_bstage;  // one per staging slot: recorded behind the kernel that read it
+    hipEvent_t ev_dev_in = nullptr, ev_dev_out = nullptr;   // eds_dev_wait_stream / eds_dev_signal_stream (include/eds_hip_device.h), created at their first call
     void* d_probe = nullptr;            // scratch of the measurement helpers (eds_trk_hbm_probe, eds_trk_bench_kernel_cold): allocated at their first call
     size_t probe_bytes = 0;
     std::vector<Slot> slots;

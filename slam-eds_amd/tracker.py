@@ -207,6 +207,10 @@ class Tracker:
 
         Returns ``(ok, T_kf_ef)``; on ``ok == False`` nothing is updated (T_kf_ef is returned
         unchanged), exactly like the reference's ``return false`` branch.
+
+        ``event_frame`` may live in device memory (anything with ``__cuda_array_interface__``, e.g. a torch tensor on the GPU,
+        H x W float32 / float64): it is then read where it is (include/eds_hip_device.h).  The handle's stream is ordered against no
+        other stream: the frame must be complete before the call and stay untouched until it returns (the solve waits for the read).
         """
         if px is not None:
             self.px = np.asarray(px, dtype=np.float64).copy()
@@ -219,7 +223,10 @@ class Tracker:
         K = np.asarray(kf.K_ref, dtype=np.float64)
         # the reference re-reads every vector on each call (Tracker.cpp:164-167,189-191)
         h.set_keyframe(0, kf.norm_coord, kf.grad, kf.inv_depth, kf.weights, K[0, 0], K[1, 1], K[0, 2], K[1, 2])
-        h.set_event_frame(0, event_frame)
+        if capi.is_device_array(event_frame):
+            h.set_event_frames_device(0, event_frame)
+        else:
+            h.set_event_frame(0, event_frame)
         try:
             p, q, v, info = h.optimize(0, level=id, p=self.px, q=self.qx, v=self.vx)
         except capi.EdsError as e:
