@@ -32,8 +32,13 @@ def test_shim_compiles_against_c_abi_only(capi):
 @pytest.mark.gpu
 @pytest.mark.parametrize("nb,loss", [(1, 0), (4, 1)])
 def test_shim_optimize_matches_oracle(gpu, capi, synth, po, tmp_path, nb, loss):
+    shim_case(capi, synth, po, tmp_path, synth.make_alignment(808, H=240, W=320, N=700, start="ctor"), nb, loss)
+
+
+def shim_case(capi, synth, po, tmp_path, al, nb, loss):
+    """One run of tests/cpp/shim_demo.cpp on `al` (its camera goes into the input file), checked against the oracles.  Also the body of
+    tests/test_intrinsics_gpu.py's shim case."""
     exe = build_demo(capi)
-    al = synth.make_alignment(808, H=240, W=320, N=700, start="ctor")
     path = tmp_path / "al.bin"
     with open(path, "wb") as f:
         f.write(struct.pack("3i", al.N, al.H, al.W))
