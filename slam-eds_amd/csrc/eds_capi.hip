@@ -87,6 +87,47 @@ int check_range(const eds_trk* h, int first, int count) {
     return EDS_OK;
 }
 
+int check_idle_slots(const eds_trk* h, int first, int count, int need) {
+    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
+    for (int s = first; s < first + count; ++s) {
+        const Slot& sl = h->slots[s];
+        if ((need & EDS_NEED_KF) && (!sl.has_kf || sl.N < 1)) return fail(EDS_ERR_STATE, "keyframe not set");
+        if ((need & EDS_NEED_FRAME) && !sl.has_frame) return fail(EDS_ERR_STATE, "event frame not set");
+        if ((need & EDS_NEED_SEEDS) && !sl.seeded) return fail(EDS_ERR_STATE, "depth seeds not initialised (eds_depth_init)");
+    }
+    return EDS_OK;
+}
+
+int read_xy_planes(eds_trk* h, const double* plane, int first, int count, int stride, double* dst) {
+    const size_t Np = (size_t)h->Np, n = (size_t)count * Np;
+    std::vector<double> v(2 * n);
+    EDS_HIP_TRY(hipMemcpyAsync(v.data(), plane + Np * first, n * 8, hipMemcpyDeviceToHost, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(v.data() + n, plane + (size_t)h->B * Np + Np * first, n * 8, hipMemcpyDeviceToHost, h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    for (int b = 0; b < count; ++b) {
+        const double* x = v.data() + Np * b;
+        double* d = dst + 2 * (size_t)b * stride;
+        for (int k = 0; k < h->slots[first + b].N; ++k) { d[2 * k] = x[k]; d[2 * k + 1] = x[n + k]; }
+    }
+    return EDS_OK;
+}
+
+int workgroup_lds_limit(const eds_trk* h, size_t* bytes) {
+    int v = 0;
+    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->dev));
+    *bytes = (size_t)v;
+    return EDS_OK;
+}
+
+bool row_bins_fit(const eds_trk* h, size_t limit) { return 2 * ((size_t)h->H + 2) * 4 <= limit && h->W <= 65535 && h->H <= 65535; }
+
+bool device_alloc(std::initializer_list<DevAlloc> table) {
+    for (const DevAlloc& a : table)
+        if (hipMalloc(a.p, a.bytes) != hipSuccess) return false;
+    return true;
+}
+
 }  // namespace edscapi
 using namespace edscapi;
 

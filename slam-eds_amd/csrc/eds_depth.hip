@@ -292,17 +292,6 @@ int upload_rows(eds_trk* h, int first, int count, const double* src, int stride,
     return EDS_OK;
 }
 
-int check_common(eds_trk* h, int first, int count, bool need_seeds) {
-    int rc = check_range(h, first, count);
-    if (rc) return rc;
-    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
-    for (int s = first; s < first + count; ++s) {
-        if (!h->slots[s].has_kf || h->slots[s].N < 1) return fail(EDS_ERR_STATE, "keyframe not set");
-        if (need_seeds && !h->slots[s].seeded) return fail(EDS_ERR_STATE, "depth seeds not initialised (eds_depth_init)");
-    }
-    return EDS_OK;
-}
-
 // the slots' planes were just written: Gram matrices as eds_trk_set_idepth refreshes them, on the device only (fill_pose fetches h_G
 // for a host-side reader); the caller waits for the stream
 int finish_planes(eds_trk* h, int first, int count) {
@@ -358,8 +347,8 @@ void eds_depth_params_default(eds_depth_params* prm) {
 }
 
 int eds_depth_init(eds_trk* h, int first, int count, const eds_depth_params* prm, int source, const double* idp, int stride) {
-    int rc = check_common(h, first, count, false);
-    if (rc) return rc;
+    int rc = check_range(h, first, count);
+    if (rc || (rc = check_idle_slots(h, first, count, EDS_NEED_KF))) return rc;
     if (!prm) return fail(EDS_ERR_INVALID, "null parameters");
     if (source < EDS_DEPTH_INIT_CONSTANT || source > EDS_DEPTH_INIT_PLANE) return fail(EDS_ERR_INVALID, "unknown init source");
     if (source == EDS_DEPTH_INIT_HOST) {
@@ -392,8 +381,8 @@ int eds_depth_update(eds_trk* h, int first, int count, int coords, const double*
 
 int eds_depth_update_impl(eds_trk* h, int first, int count, int coords, const double* xy, const double* kf_xy, int stride,
                           const double* T_kf_ef, int filter, eds_depth_summary* out, const double* dev_ef) {
-    int rc = check_common(h, first, count, true);
-    if (rc) return rc;
+    int rc = check_range(h, first, count);
+    if (rc || (rc = check_idle_slots(h, first, count, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (coords < EDS_DEPTH_TRACKS || coords > EDS_DEPTH_DEVICE_TRACKS) return fail(EDS_ERR_INVALID, "unknown coordinate source");
     if (filter != EDS_DEPTH_VOGIATZIS && filter != EDS_DEPTH_GAUSS) return fail(EDS_ERR_INVALID, "unknown depth filter");
     const bool on_device = coords == EDS_DEPTH_REPROJECT || coords == EDS_DEPTH_DEVICE_TRACKS;
@@ -457,8 +446,8 @@ int eds_depth_update_impl(eds_trk* h, int first, int count, int coords, const do
 extern "C" {
 
 int eds_depth_get(eds_trk* h, int slot, double* mu_s2_a_b, uint8_t* converged) {
-    int rc = check_common(h, slot, 1, true);
-    if (rc) return rc;
+    int rc = check_range(h, slot, 1);
+    if (rc || (rc = check_idle_slots(h, slot, 1, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!mu_s2_a_b && !converged) return fail(EDS_ERR_INVALID, "null output");
     EDS_HIP_TRY(hipSetDevice(h->dev));
     const Slot& s = h->slots[slot];
@@ -476,8 +465,8 @@ int eds_depth_get(eds_trk* h, int slot, double* mu_s2_a_b, uint8_t* converged) {
 }
 
 int eds_depth_set(eds_trk* h, int slot, const double* mu_s2_a_b) {
-    int rc = check_common(h, slot, 1, true);
-    if (rc) return rc;
+    int rc = check_range(h, slot, 1);
+    if (rc || (rc = check_idle_slots(h, slot, 1, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!mu_s2_a_b) return fail(EDS_ERR_INVALID, "null seeds");
     EDS_HIP_TRY(hipSetDevice(h->dev));
     if ((rc = ensure_input(h))) return rc;
@@ -486,16 +475,16 @@ int eds_depth_set(eds_trk* h, int slot, const double* mu_s2_a_b) {
 }
 
 int eds_depth_get_idepth(eds_trk* h, int slot, double* mu) {
-    int rc = check_common(h, slot, 1, true);
-    if (rc) return rc;
+    int rc = check_range(h, slot, 1);
+    if (rc || (rc = check_idle_slots(h, slot, 1, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!mu) return fail(EDS_ERR_INVALID, "null output");
     EDS_HIP_TRY(hipSetDevice(h->dev));
     return read_plane(h, slot, 0, mu);
 }
 
 int eds_depth_stats(eds_trk* h, int first, int count, double* out4) {
-    int rc = check_common(h, first, count, true);
-    if (rc) return rc;
+    int rc = check_range(h, first, count);
+    if (rc || (rc = check_idle_slots(h, first, count, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!out4) return fail(EDS_ERR_INVALID, "null output");
     EDS_HIP_TRY(hipSetDevice(h->dev));
     EdsDepthBuffers& d = h->depth;

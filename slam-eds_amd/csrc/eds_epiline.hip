@@ -7,8 +7,8 @@
 //   k_klt_bin        (eds_klt.hip) the keyframe pixels binned by splat row: keys (y0 + 1, x0 + 1, i), no per-pixel scratch.  The bias
 //                    of one keeps the points with x or y in (-1, 0): their x1 / y1 corners land on column / row 0 with the
 //                    reference's weights (Utils.cpp:164-178); no getCoord has erased them, as it has for the KLT
-//   k_epi_model      drawValuesPoints (Utils.cpp:124-193), bilinear, every pixel summing its contributions in point order, then the
-//                    3 x 3 Gaussian blur (sigma 0.5, reflect-101), per 32 x 8 tile: the model image [B][H][W] in fp64
+//   k_epi_model      the splat of those keys and its 3 x 3 Gaussian blur (both eds_splat.hpp) per 32 x 8 tile: the model image
+//                    [B][H][W] in fp64
 //   k_epi_templates  one wavefront per point: splitImageInPatches (Utils.cpp:608-633) at the TRUNCATED keyframe pixel, the patch in
 //                    fp32, S = sum T^2 exactly in fp64, and the non-zero taps compacted in row-major order as (LDS offset, value)
 //   k_epi_pad        copyMakeBorder(event_frame, r, border) in fp32 (Tracker.cpp:505-506)
@@ -37,9 +37,11 @@
 #include "eds_capi_internal.hpp"
 #include "eds_depth.hpp"
 #include "eds_device.hpp"
+#include "eds_splat.hpp"
 
 using namespace edscapi;
 using namespace edsd;
+using namespace edssplat;
 
 #define EDS_EPI_MAX_RADIUS 15
 #define EDS_EPI_PAR 16              // per slot: fx fy cx cy, v[6], seeded
@@ -54,49 +56,12 @@ using namespace edsd;
 
 namespace {
 
-// cv::borderInterpolate(p, len, type) for REPLICATE, REFLECT and REFLECT_101, repeated while p is outside
-__device__ __forceinline__ int border_map(int p, int len, int type) {
-    if ((unsigned)p < (unsigned)len) return p;
-    if (type == EDS_EPI_BORDER_REPLICATE) return p < 0 ? 0 : len - 1;
-    if (len == 1) return 0;
-    const int delta = type == EDS_EPI_BORDER_REFLECT_101 ? 1 : 0;
-    do {
-        if (p < 0) p = -p - 1 + delta;
-        else p = len - 1 - (p - len) - delta;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
-
-__device__ __forceinline__ int reflect101(int p, int len) { return border_map(p, len, EDS_EPI_BORDER_REFLECT_101); }
-
-__device__ __forceinline__ int key_x0(uint64_t k) { return (int)((k >> 32) & 0xffffu); }
-__device__ __forceinline__ unsigned key_i(uint64_t k) { return (unsigned)(k & 0xffffffffu); }
-
-__device__ __forceinline__ int lower_x(const uint64_t* __restrict__ K, int lo, int hi, int xv) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key_x0(K[mid]) < xv) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // fp32 score -> unsigned key ascending with the score; -0 and +0 map to the same key
 __device__ __forceinline__ unsigned ord_key(float s) {
     const unsigned u = __float_as_uint(s + 0.0f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float ord_val(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-__device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, off, 64), hi = __shfl_xor((unsigned)(v >> 32), off, 64);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(EDS_EPI_VAL_THREADS) void k_epi_values(EdsArrays A, int first, const double* __restrict__ par,
                                                                     const double* __restrict__ seeds_mu, double* __restrict__ kpix,
@@ -150,7 +115,7 @@ __global__ __launch_bounds__(256) void k_epi_model(EdsArrays A, int first, doubl
     const int tx0 = (blockIdx.x % ntx) * EDS_EPI_MODEL_TW, ty0 = (blockIdx.x / ntx) * EDS_EPI_MODEL_TH;
     const size_t base = (size_t)slot * A.Np;
     const double* __restrict__ Cd = kpix + 2 * base;
-    const double* __restrict__ V = mval + base;
+    const double* const V[1] = {mval + base};
     const uint64_t* __restrict__ K = keys + base;
     const int* __restrict__ RS = row_start + (size_t)slot * (H + 2);
     // the splat pixels the blurred tile reads: its pixels +- 1, inside the image (reflect-101 of -1 / W lands inside this box)
@@ -158,52 +123,22 @@ __global__ __launch_bounds__(256) void k_epi_model(EdsArrays A, int first, doubl
     const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
     for (int p = tid; p < bw * bh; p += 256) {
         const int jy = p / bw, py = by0 + jy, px = bx0 + p - jy * bw;
-        // the points whose footprint corner lands on (py, px): (y0, x0) = (py-1, px-1) [wd], (py-1, px) [wb], (py, px-1) [wc],
-        // (py, px) [wa] — four runs of keys ascending in i, merged so that the pixel sums in point order (as k_klt_window).
-        // The keys and row starts carry a bias of one: y0 = -1 and x0 = -1 are row 0 and key column 0
+        // The keys and row starts carry a bias of one: y0 = -1 and x0 = -1 are row 0 and key column 0, so the runs of rows
+        // y0 = py - 1, py at x0 = px - 1, px are those of key rows py, py + 1 at key columns px, px + 1
         int g[4][2];
         for (int h2 = 0; h2 < 2; ++h2) {
-            const int yy = py + h2;                             // y0 + 1 of y0 = py - 1, py
-            const int hi = RS[yy + 1];
-            int q = lower_x(K, RS[yy], hi, px);
-            g[2 * h2][0] = q;
-            while (q < hi && key_x0(K[q]) == px) ++q;           // x0 = px - 1
-            g[2 * h2][1] = q; g[2 * h2 + 1][0] = q;
-            while (q < hi && key_x0(K[q]) == px + 1) ++q;       // x0 = px
-            g[2 * h2 + 1][1] = q;
+            const int hi = RS[py + h2 + 1];
+            splat_runs(K, lower_x(K, RS[py + h2], hi, px), hi, px, g + 2 * h2);
         }
-        double s = 0.0;
-        while (true) {
-            unsigned m = UINT_MAX;
-            int which = -1;
-            for (int c = 0; c < 4; ++c)
-                if (g[c][0] < g[c][1]) {
-                    const unsigned ic = key_i(K[g[c][0]]);
-                    if (ic < m) { m = ic; which = c; }
-                }
-            if (which < 0) break;
-            ++g[which][0];
-            const double xj = Cd[2 * m], yj = Cd[2 * m + 1];
-            const double x0 = floor(xj), y0 = floor(yj), x1 = x0 + 1.0, y1 = y0 + 1.0;
-            double w;
-            if (which == 0) w = (xj - x0) * (yj - y0);
-            else if (which == 1) w = (x1 - xj) * (yj - y0);
-            else if (which == 2) w = (xj - x0) * (y1 - yj);
-            else w = (x1 - xj) * (y1 - yj);
-            s = s + w * V[m];
-        }
-        s_box[p] = s;
+        double s[1];
+        splat_merge(K, g, Cd, V, s);
+        s_box[p] = s[0];
     }
     __syncthreads();
     const int ly = tid / EDS_EPI_MODEL_TW, lx = tid - ly * EDS_EPI_MODEL_TW;
     const int y = ty0 + ly, x = tx0 + lx;
     if (y >= H || x >= W) return;
-    const int xl = reflect101(x - 1, W) - bx0, xc = x - bx0, xr = reflect101(x + 1, W) - bx0;
-    const int yu = reflect101(y - 1, H) - by0, yc = y - by0, yd = reflect101(y + 1, H) - by0;
-    const double ru = k0 * s_box[yu * bw + xl] + k1 * s_box[yu * bw + xc] + k2 * s_box[yu * bw + xr];
-    const double rc = k0 * s_box[yc * bw + xl] + k1 * s_box[yc * bw + xc] + k2 * s_box[yc * bw + xr];
-    const double rd = k0 * s_box[yd * bw + xl] + k1 * s_box[yd * bw + xc] + k2 * s_box[yd * bw + xr];
-    model[(size_t)slot * H * W + (size_t)y * W + x] = k0 * ru + k1 * rc + k2 * rd;
+    model[(size_t)slot * H * W + (size_t)y * W + x] = blur3_at(s_box, bw, bx0, by0, x, y, W, H, k0, k1, k2);
 }
 
 // one wavefront per point i = blockIdx.x of chunk alignment blockIdx.y (slot first + blockIdx.y)
@@ -244,8 +179,7 @@ __global__ __launch_bounds__(64) void k_epi_templates(EdsArrays A, int first, in
         }
         cnt += __popcll(m);
     }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) ss += __shfl_xor(ss, off, 64);
+    ss = wave_sum(ss);
     if (lane == 0) tmeta[t] = make_float4(__int_as_float(cnt), (float)ss, (float)sqrt(ss), 0.0f);
 }
 
@@ -418,15 +352,13 @@ int ensure(eds_trk* h) {
     EdsEpiBuffers& e = h->epi;
     if (e.ef) return EDS_OK;
     const size_t B = (size_t)h->B, Np = (size_t)h->Np, H = (size_t)h->H, W = (size_t)h->W;
-    if (hipMalloc((void**)&e.ef, 2 * B * Np * 8) != hipSuccess || hipMalloc((void**)&e.kpix, 2 * B * Np * 8) != hipSuccess ||
-        hipMalloc((void**)&e.mval, B * Np * 8) != hipSuccess || hipMalloc((void**)&e.keys_tmp, B * Np * 8) != hipSuccess ||
-        hipMalloc((void**)&e.keys, B * Np * 8) != hipSuccess || hipMalloc((void**)&e.row_start, B * (H + 2) * 4) != hipSuccess ||
-        hipMalloc((void**)&e.model, B * H * W * 8) != hipSuccess || hipMalloc((void**)&e.par, B * EDS_EPI_PAR * 8) != hipSuccess ||
-        hipHostMalloc((void**)&e.h_par, B * EDS_EPI_PAR * 8, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void**)&e.best, 2 * B * Np * 8) != hipSuccess || hipMalloc((void**)&e.ef_tmp, 2 * B * Np * 8) != hipSuccess ||
-        hipMalloc((void**)&e.loc, 4 * B * Np * 4) != hipSuccess || hipMalloc((void**)&e.score, 2 * B * Np * 8) != hipSuccess ||
-        hipMalloc((void**)&e.erase, B * Np) != hipSuccess || hipMalloc((void**)&e.coord, 2 * B * Np * 8) != hipSuccess ||
-        hipMalloc((void**)&e.kept, B * Np * 4) != hipSuccess || hipMalloc((void**)&e.ef_aos, 2 * B * Np * 8) != hipSuccess) {
+    if (!device_alloc({{(void**)&e.ef, 2 * B * Np * 8}, {(void**)&e.kpix, 2 * B * Np * 8}, {(void**)&e.mval, B * Np * 8},
+                       {(void**)&e.keys_tmp, B * Np * 8}, {(void**)&e.keys, B * Np * 8}, {(void**)&e.row_start, B * (H + 2) * 4},
+                       {(void**)&e.model, B * H * W * 8}, {(void**)&e.par, B * EDS_EPI_PAR * 8}, {(void**)&e.best, 2 * B * Np * 8},
+                       {(void**)&e.ef_tmp, 2 * B * Np * 8}, {(void**)&e.loc, 4 * B * Np * 4}, {(void**)&e.score, 2 * B * Np * 8},
+                       {(void**)&e.erase, B * Np}, {(void**)&e.coord, 2 * B * Np * 8}, {(void**)&e.kept, B * Np * 4},
+                       {(void**)&e.ef_aos, 2 * B * Np * 8}}) ||
+        hipHostMalloc((void**)&e.h_par, B * EDS_EPI_PAR * 8, hipHostMallocDefault) != hipSuccess) {
         eds_epi_free(&e);
         return fail(EDS_ERR_HIP, "allocation of the epiline buffers failed");
     }
@@ -450,8 +382,8 @@ int build_model(eds_trk* h, int first, int count) {
     EDS_HIP_TRY(hipGetLastError());
     int rc = eds_klt_bin_launch(h, first, count, e.kpix, e.keys_tmp, e.keys, e.row_start, 1);
     if (rc) return rc;
-    const double t = std::exp(-0.5 / (0.5 * 0.5));          // cv::getGaussianKernel(3, 0.5, CV_64F): [t, 1, t] / (1 + 2t)
-    const double k0 = t / (1.0 + 2.0 * t), k1 = 1.0 / (1.0 + 2.0 * t);
+    double k0, k1;
+    gauss3_sigma_half(k0, k1);
     const int tiles = ((h->W + EDS_EPI_MODEL_TW - 1) / EDS_EPI_MODEL_TW) * ((h->H + EDS_EPI_MODEL_TH - 1) / EDS_EPI_MODEL_TH);
     hipLaunchKernelGGL(k_epi_model, dim3(tiles, count), dim3(256), 0, h->st, h->arrays(), first, k0, k1, k0, e.kpix, e.mval, e.keys, e.row_start,
                        e.model);
@@ -459,19 +391,10 @@ int build_model(eds_trk* h, int first, int count) {
     return EDS_OK;
 }
 
-int check_slots(eds_trk* h, int first, int count) {
-    int rc = check_range(h, first, count);
-    if (rc) return rc;
-    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
-    for (int s = first; s < first + count; ++s)
-        if (!h->slots[s].has_kf || h->slots[s].N < 1) return fail(EDS_ERR_STATE, "keyframe not set");
-    return EDS_OK;
-}
-
 int track(eds_trk* h, int first, int count, int r, int border, int bval, int erase, int stride, int32_t* ssd_xy, int32_t* ncc_xy,
           double* scores, double* ef_xy, int32_t* kept_index, int* n_kept) {
-    if (!h) return fail(EDS_ERR_INVALID, "null handle");
-    if (count < 1 || first < 0 || first + count > h->B) return fail(EDS_ERR_INVALID, "slot range out of bounds");
+    int rc = check_range(h, first, count);
+    if (rc) return rc;
     if (r < 0 || r > EDS_EPI_MAX_RADIUS) return fail(EDS_ERR_INVALID, "patch_radius outside 0 .. 15");
     if (border != EDS_EPI_BORDER_CONSTANT && border != EDS_EPI_BORDER_REPLICATE && border != EDS_EPI_BORDER_REFLECT &&
         border != EDS_EPI_BORDER_REFLECT_101)
@@ -480,17 +403,12 @@ int track(eds_trk* h, int first, int count, int r, int border, int bval, int era
     if (erase != 0 && erase != 1) return fail(EDS_ERR_INVALID, "erase must be 0 or 1");
     if ((ssd_xy || ncc_xy || scores || ef_xy || kept_index) && stride < max_points(h, first, count))
         return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
-    int rc = check_slots(h, first, count);
-    if (rc) return rc;
-    for (int s = first; s < first + count; ++s)
-        if (!h->slots[s].has_frame) return fail(EDS_ERR_STATE, "event frame not set");
+    if ((rc = check_idle_slots(h, first, count, EDS_NEED_KF | EDS_NEED_FRAME))) return rc;
     const int pitch = EDS_EPI_TW + 2 * r;
     const size_t match_lds = (size_t)(EDS_EPI_TH + 2 * r) * pitch * 4;
-    int max_lds = 0;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, h->dev));
-    if (2 * ((size_t)h->H + 2) * 4 > (size_t)max_lds || match_lds > (size_t)max_lds || h->W > 65535 || h->H > 65535 ||
-        (size_t)h->H * h->W >= (1ull << 32))
+    size_t max_lds = 0;
+    if ((rc = workgroup_lds_limit(h, &max_lds))) return rc;
+    if (!row_bins_fit(h, max_lds) || match_lds > max_lds || (size_t)h->H * h->W >= (1ull << 32))
         return fail(EDS_ERR_NOT_USABLE, "the row bins or the match tile of this frame size do not fit the workgroup's LDS");
     if ((rc = ensure(h))) return rc;
     EdsEpiBuffers& e = h->epi;
@@ -501,8 +419,7 @@ int track(eds_trk* h, int first, int count, int r, int border, int bval, int era
         (rc = grow(e.energy, e.energy_cap, (size_t)cap * H * W)) || (rc = grow(e.taps, e.taps_cap, cap * Np * K)) ||
         (rc = grow(e.tmeta, e.tmeta_cap, cap * Np)))
         return rc;
-    int maxN = 0;
-    for (int s = first; s < first + count; ++s) maxN = std::max(maxN, h->slots[s].N);
+    const int maxN = max_points(h, first, count);
     // 1. the model images
     if ((rc = build_model(h, first, count))) return rc;
     EDS_HIP_TRY(hipMemsetAsync(e.best + 2 * Np * first, 0xff, 2 * Np * count * 8, h->st));
@@ -540,15 +457,9 @@ int track(eds_trk* h, int first, int count, int r, int border, int bval, int era
     }
     hipLaunchKernelGGL(k_epi_gather, dim3(nchunk, count), dim3(256), 0, h->st, h->arrays(), first, erase ? e.kept : nullptr, e.ef_tmp, e.ef);
     EDS_HIP_TRY(hipGetLastError());
-    std::vector<double> vef;
     std::vector<int32_t> vk;
-    const size_t plane = (size_t)h->B * Np;
-    if (ef_xy) {
-        vef.resize(2 * Np * count);
-        EDS_HIP_TRY(hipMemcpyAsync(vef.data(), e.ef + Np * first, Np * count * 8, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(vef.data() + Np * count, e.ef + plane + Np * first, Np * count * 8, hipMemcpyDeviceToHost, h->st));
-    }
     if (kept_index && erase) { vk.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), e.kept + Np * first, Np * count * 4, hipMemcpyDeviceToHost, h->st)); }
+    if (ef_xy && (rc = read_xy_planes(h, e.ef, first, count, stride, ef_xy))) return rc;
     EDS_HIP_TRY(hipStreamSynchronize(h->st));
     for (int b = 0; b < count; ++b) {
         Slot& sl = h->slots[first + b];
@@ -561,10 +472,7 @@ int track(eds_trk* h, int first, int count, int r, int border, int bval, int era
             if (ncc_xy) { ncc_xy[2 * (o + i)] = vloc[4 * (src + i) + 2]; ncc_xy[2 * (o + i) + 1] = vloc[4 * (src + i) + 3]; }
             if (scores) { scores[2 * (o + i)] = vsc[2 * (src + i)]; scores[2 * (o + i) + 1] = vsc[2 * (src + i) + 1]; }
         }
-        for (int k = 0; k < nk; ++k) {
-            if (ef_xy) { ef_xy[2 * (o + k)] = vef[src + k]; ef_xy[2 * (o + k) + 1] = vef[Np * count + src + k]; }
-            if (kept_index) kept_index[o + k] = erase ? vk[src + k] : k;
-        }
+        for (int k = 0; kept_index && k < nk; ++k) kept_index[o + k] = erase ? vk[src + k] : k;
     }
     return EDS_OK;
 }
@@ -592,26 +500,20 @@ int eds_epi_get(eds_trk* h, int slot, double* ef_xy) {
     int rc = check_slot(h, slot);
     if (rc) return rc;
     if (!ef_xy) return fail(EDS_ERR_INVALID, "null output");
-    if ((rc = check_slots(h, slot, 1))) return rc;
+    if ((rc = check_idle_slots(h, slot, 1, EDS_NEED_KF))) return rc;
     if (!h->epi.ef || !h->slots[slot].epi_valid) return fail(EDS_ERR_STATE, "the slot's ef plane is not current: run eds_epi_track_points");
     EDS_HIP_TRY(hipSetDevice(h->dev));
-    const size_t Np = (size_t)h->Np, plane = (size_t)h->B * Np, o = (size_t)slot * Np, N = (size_t)h->slots[slot].N;
-    std::vector<double> v(2 * N);
-    EDS_HIP_TRY(hipMemcpyAsync(v.data(), h->epi.ef + o, N * 8, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(v.data() + N, h->epi.ef + plane + o, N * 8, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    for (size_t k = 0; k < N; ++k) { ef_xy[2 * k] = v[k]; ef_xy[2 * k + 1] = v[N + k]; }
-    return EDS_OK;
+    return read_xy_planes(h, h->epi.ef, slot, 1, h->slots[slot].N, ef_xy);
 }
 
 int eds_epi_get_model(eds_trk* h, int slot, double* model) {
     int rc = check_slot(h, slot);
     if (rc) return rc;
     if (!model) return fail(EDS_ERR_INVALID, "null output");
-    if ((rc = check_slots(h, slot, 1))) return rc;
-    if (2 * ((size_t)h->H + 2) * 4 > 65536 || h->W > 65535 || h->H > 65535)
-        return fail(EDS_ERR_NOT_USABLE, "the row bins of this frame size do not fit the workgroup's LDS");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    if ((rc = check_idle_slots(h, slot, 1, EDS_NEED_KF))) return rc;
+    size_t max_lds = 0;
+    if ((rc = workgroup_lds_limit(h, &max_lds))) return rc;
+    if (!row_bins_fit(h, max_lds)) return fail(EDS_ERR_NOT_USABLE, "the row bins of this frame size do not fit the workgroup's LDS");
     if ((rc = ensure(h)) || (rc = build_model(h, slot, 1))) return rc;
     const size_t n = (size_t)h->H * h->W;
     EDS_HIP_TRY(hipMemcpyAsync(model, h->epi.model + n * slot, n * 8, hipMemcpyDeviceToHost, h->st));
@@ -622,7 +524,7 @@ int eds_epi_get_model(eds_trk* h, int slot, double* model) {
 int eds_epi_depth_update(eds_trk* h, int first, int count, const double* T_kf_ef, int filter, eds_depth_summary* out) {
     int rc = check_range(h, first, count);
     if (rc) return rc;
-    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
+    if ((rc = check_idle_slots(h, first, count, 0))) return rc;
     for (int s = first; s < first + count; ++s)
         if (!h->epi.ef || !h->slots[s].epi_valid || !h->slots[s].has_kf)
             return fail(EDS_ERR_STATE, "the slot's ef plane is not current: run eds_epi_track_points");

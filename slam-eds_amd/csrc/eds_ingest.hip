@@ -167,10 +167,8 @@ int check_named(int device, const void* p, size_t bytes, const char* what) {
 
 // the checks every ingest call starts with, in this order: handle and slot range, then "no batch in flight"
 int check_call(eds_trk* h, int first, int count) {
-    int rc = check_range(h, first, count);
-    if (rc) return rc;
-    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
-    return EDS_OK;
+    const int rc = check_range(h, first, count);
+    return rc ? rc : check_idle_slots(h, first, count, 0);
 }
 
 }  // namespace

@@ -3,15 +3,13 @@
 //
 //   k_update_points  getCoord(true) (eds_points.hip) with its coordinates and kept indices in HBM, the re-projection tracks in the
 //                    tracks plane and the flow plane compacted behind the kept indices
-//   k_klt_bin        one workgroup per alignment: the points binned by splat row.  Key (y0, x0, i) of every point, y0 / x0 the
-//                    floor of its coordinates = the top-left corner of its bilinear footprint; a counting sort by y0, then a rank
-//                    sort inside each row, so that each row's keys ascend in (x0, i).  [B][Np] keys and [B][H + 2] row starts: no
-//                    per-pixel scratch
+//   k_klt_bin        one workgroup per alignment: the points binned by splat row.  One key (eds_splat.hpp) per point; a counting
+//                    sort by y0, then a rank sort inside each row, so that each row's keys ascend in (x0, i).  [B][Np] keys and
+//                    [B][H + 2] row starts: no per-pixel scratch
 //   k_klt_window     one wavefront per point: its window's reflect-101 positions (splitImageInPatches, Utils.cpp:608-633), the splat
-//                    values of the box they and the blur reach (drawValuesPoints, Utils.cpp:124-193: the keys of the rows above and
-//                    at each pixel, merged in ascending point index, so every pixel sums in the reference's order), the 3 x 3
-//                    Gaussian blur (sigma 0.5, reflect-101), pyrDown levels (pyramidPatches, Utils.cpp:662-673), kltTracker's five
-//                    sums (Utils.cpp:735-759) as shuffle reductions and the 2 x 2 solve in Eigen's closed form; then flow / tracks
+//                    values of the box they and the blur reach and the 3 x 3 Gaussian blur (both eds_splat.hpp), pyrDown levels
+//                    (pyramidPatches, Utils.cpp:662-673), kltTracker's five sums (Utils.cpp:735-759) as shuffle reductions and
+//                    the 2 x 2 solve in Eigen's closed form; then flow / tracks
 //
 // fp64 throughout, and this translation unit is compiled WITHOUT fp contraction (Makefile).  No float atomics: every sum has a
 // fixed order, so a batch equals its singles bit for bit and runs repeat exactly.
@@ -26,9 +24,11 @@
 #include "../../include/eds_hip_klt.h"
 #include "eds_capi_internal.hpp"
 #include "eds_device.hpp"
+#include "eds_splat.hpp"
 
 using namespace edscapi;
 using namespace edsd;
+using namespace edssplat;
 
 #define EDS_KLT_BIN_THREADS 1024
 #define EDS_KLT_MAX_RADIUS 31
@@ -37,17 +37,6 @@ using namespace edsd;
 
 namespace {
 
-// cv::borderInterpolate(p, len, BORDER_REFLECT_101), repeated while p is outside (a window wider than the image)
-__device__ __forceinline__ int reflect101(int p, int len) {
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        if (p < 0) p = -p;
-        else p = 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
-
 // getCoord(true) keeps 0 <= x <= cols, 0 <= y <= rows (and lets NaN through): only such points are binned
 __device__ __forceinline__ bool binned(double x, double y, int W, int H) { return x >= 0.0 && x <= (double)W && y >= 0.0 && y <= (double)H; }
 // bias 1 (the epiline model, whose keyframe pixels no getCoord has erased): every point whose footprint touches the image,
@@ -55,9 +44,6 @@ __device__ __forceinline__ bool binned(double x, double y, int W, int H) { retur
 __device__ __forceinline__ bool binned(double x, double y, int W, int H, int bias) {
     return bias ? (x > -1.0 && x < (double)W && y > -1.0 && y < (double)H) : binned(x, y, W, H);
 }
-
-__device__ __forceinline__ int key_x0(uint64_t k) { return (int)((k >> 32) & 0xffffu); }
-__device__ __forceinline__ unsigned key_i(uint64_t k) { return (unsigned)(k & 0xffffffffu); }
 
 __global__ __launch_bounds__(EDS_KLT_BIN_THREADS) void k_klt_bin(EdsArrays A, int first, const double* __restrict__ coord,
                                                                 uint64_t* __restrict__ keys_tmp, uint64_t* __restrict__ keys,
@@ -87,35 +73,19 @@ __global__ __launch_bounds__(EDS_KLT_BIN_THREADS) void k_klt_bin(EdsArrays A, in
         if (!binned(x, y, W, H, bias)) continue;
         const int y0 = (int)floor(y) + bias, x0 = (int)floor(x) + bias;
         const int pos = atomicAdd(&s_cur[y0], 1);                             // arrival order; the rank sort below fixes it
-        keys_tmp[pos] = ((uint64_t)y0 << 48) | ((uint64_t)x0 << 32) | (uint64_t)i;
+        keys_tmp[pos] = splat_key(y0, x0, i);
     }
     __threadfence_block();
     __syncthreads();
     const int nb = s_bin[H + 1];
     for (int p = tid; p < nb; p += EDS_KLT_BIN_THREADS) {
         const uint64_t k = keys_tmp[p];
-        const int y0 = (int)(k >> 48);
+        const int y0 = key_y0(k);
         const int lo = s_bin[y0], hi = s_bin[y0 + 1];
         int rank = 0;
         for (int q = lo; q < hi; ++q) rank += keys_tmp[q] < k ? 1 : 0;
         keys[lo + rank] = k;
     }
-}
-
-// first q in [lo, hi) whose key has x0 >= xv (the keys of one row ascend in x0)
-__device__ __forceinline__ int lower_x(const uint64_t* __restrict__ K, int lo, int hi, int xv) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key_x0(K[mid]) < xv) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {      // xor butterfly: every lane ends with the same, fixed-order total
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // kltTracker's return value -M^-1 b with Eigen's 2 x 2 inverse (invdet = 1 / (m00 m11 - m10 m01), cofactors times invdet)
@@ -176,64 +146,31 @@ __global__ __launch_bounds__(64) void k_klt_window(EdsArrays A, int first, int r
             s_rlo[j] = lo; s_rhi[j] = hi;
         }
         __syncthreads();
-        // drawValuesPoints' bilinear splat of both gradients at each box pixel (py, px): the points whose footprint corner lands there
-        // are those with (y0, x0) = (py-1, px-1) [wd], (py-1, px) [wb], (py, px-1) [wc], (py, px) [wa] — four runs of keys, each
-        // ascending in i, merged so that the sum runs in point order.  Corners outside the image carry weight 0 in the reference and
-        // land on a clipped pixel: adding +-0 to a sum that starts at +0 changes nothing, so they are left out.
+        // drawValuesPoints' bilinear splat of both gradients at each box pixel (py, px), py = by0 + jy: the runs of rows py - 1 (range
+        // index jy) and py (jy + 1), each scanned forward from the row's pre-bisected start
         const int nbox = bw * bh;
-        const float* __restrict__ gxp = A.gx + base;
-        const float* __restrict__ gyp = A.gy + base;
+        const float* const G[2] = {A.gx + base, A.gy + base};
         for (int p = lane; p < nbox; p += 64) {
             const int jy = p / bw, px = bx0 + p - jy * bw;
-            int g[4][2];    // [wd, wb] from row py - 1 (range index jy), [wc, wa] from row py (jy + 1)
+            int g[4][2];
             for (int h2 = 0; h2 < 2; ++h2) {
-                const int lo = s_rlo[jy + h2], hi = s_rhi[jy + h2];
-                int q = lo;
+                const int hi = s_rhi[jy + h2];
+                int q = s_rlo[jy + h2];
                 while (q < hi && key_x0(K[q]) < px - 1) ++q;
-                g[2 * h2][0] = q;
-                while (q < hi && key_x0(K[q]) == px - 1) ++q;
-                g[2 * h2][1] = q; g[2 * h2 + 1][0] = q;
-                while (q < hi && key_x0(K[q]) == px) ++q;
-                g[2 * h2 + 1][1] = q;
+                splat_runs(K, q, hi, px - 1, g + 2 * h2);
             }
-            double sx = 0.0, sy = 0.0;
-            while (true) {
-                unsigned m = UINT_MAX;
-                int which = -1;
-                for (int c = 0; c < 4; ++c)
-                    if (g[c][0] < g[c][1]) {
-                        const unsigned ic = key_i(K[g[c][0]]);
-                        if (ic < m) { m = ic; which = c; }
-                    }
-                if (which < 0) break;
-                ++g[which][0];
-                const double xj = C[2 * m], yj = C[2 * m + 1];
-                const double x0 = floor(xj), y0 = floor(yj), x1 = x0 + 1.0, y1 = y0 + 1.0;
-                double w;
-                if (which == 0) w = (xj - x0) * (yj - y0);            // wd at (y1, x1)
-                else if (which == 1) w = (x1 - xj) * (yj - y0);       // wb at (y1, x0)
-                else if (which == 2) w = (xj - x0) * (y1 - yj);       // wc at (y0, x1)
-                else w = (x1 - xj) * (y1 - yj);                       // wa at (y0, x0)
-                sx = sx + w * (double)gxp[m];
-                sy = sy + w * (double)gyp[m];
-            }
-            s_box[p] = sx;
-            s_box[nbox + p] = sy;
+            double s[2];
+            splat_merge(K, g, C, G, s);
+            s_box[p] = s[0];
+            s_box[nbox + p] = s[1];
         }
         __syncthreads();
         const FrameView fv = make_frame_view(A.frame, (int)pbk[EDS_PB_FRAME], H, W, A.Hp, A.Wp, A.tiled);
-        // level-0 window value of channel ch (0: blurred grad_x, 1: blurred grad_y, 2: event frame) at window row kr, column kc.
-        // cv::GaussianBlur 3 x 3: rows first, then columns, each k0 a + k1 b + k2 c on reflect-101 neighbours
+        // level-0 window value of channel ch (0: blurred grad_x, 1: blurred grad_y, 2: event frame) at window row kr, column kc
         auto level0 = [&](int ch, int kr, int kc) -> double {
             const int oy = s_oy[kr], ox = s_ox[kc];
             if (ch == 2) return (double)fv.base[frame_index(fv, oy, ox)];
-            const double* Sb = s_box + ch * nbox;
-            const int xl = reflect101(ox - 1, W) - bx0, xc = ox - bx0, xr = reflect101(ox + 1, W) - bx0;
-            const int yu = reflect101(oy - 1, H) - by0, yc = oy - by0, yd = reflect101(oy + 1, H) - by0;
-            const double ru = k0 * Sb[yu * bw + xl] + k1 * Sb[yu * bw + xc] + k2 * Sb[yu * bw + xr];
-            const double rc = k0 * Sb[yc * bw + xl] + k1 * Sb[yc * bw + xc] + k2 * Sb[yc * bw + xr];
-            const double rd = k0 * Sb[yd * bw + xl] + k1 * Sb[yd * bw + xc] + k2 * Sb[yd * bw + xr];
-            return k0 * ru + k1 * rc + k2 * rd;
+            return blur3_at(s_box + ch * nbox, bw, bx0, by0, ox, oy, W, H, k0, k1, k2);
         };
         double kl[EDS_KLT_MAX_LEVEL][2];
         if (PYR && L > 1) {
@@ -302,10 +239,9 @@ int ensure(eds_trk* h) {
     EdsKltBuffers& k = h->klt;
     if (k.tracks) return EDS_OK;
     const size_t B = (size_t)h->B, Np = (size_t)h->Np, H = (size_t)h->H;
-    if (hipMalloc((void**)&k.tracks, 2 * B * Np * 8) != hipSuccess || hipMalloc((void**)&k.flow, 2 * B * Np * 8) != hipSuccess ||
-        hipMalloc((void**)&k.coord, 2 * B * Np * 8) != hipSuccess || hipMalloc((void**)&k.kept, B * Np * 4) != hipSuccess ||
-        hipMalloc((void**)&k.keys_tmp, B * Np * 8) != hipSuccess || hipMalloc((void**)&k.keys, B * Np * 8) != hipSuccess ||
-        hipMalloc((void**)&k.row_start, B * (H + 2) * 4) != hipSuccess) {
+    if (!device_alloc({{(void**)&k.tracks, 2 * B * Np * 8}, {(void**)&k.flow, 2 * B * Np * 8}, {(void**)&k.coord, 2 * B * Np * 8},
+                       {(void**)&k.kept, B * Np * 4}, {(void**)&k.keys_tmp, B * Np * 8}, {(void**)&k.keys, B * Np * 8},
+                       {(void**)&k.row_start, B * (H + 2) * 4}})) {
         eds_klt_free(&k);
         return fail(EDS_ERR_HIP, "allocation of the KLT buffers failed");
     }
@@ -327,37 +263,30 @@ size_t window_lds(const eds_trk* h, int r, int L, bool pyr) {
 
 int run(eds_trk* h, int first, int count, int r, int L, bool pyr, int stride, double* coord_xy, double* tracks_xy, double* flow_xy,
         int32_t* kept_index, int* n_kept) {
-    if (!h) return fail(EDS_ERR_INVALID, "null handle");
-    if (count < 1 || first < 0 || first + count > h->B) return fail(EDS_ERR_INVALID, "slot range out of bounds");
+    int rc = check_range(h, first, count);
+    if (rc) return rc;
     if (pyr ? (L < 1 || L > EDS_KLT_MAX_LEVEL) : (r < 0 || r > EDS_KLT_MAX_RADIUS))
         return fail(EDS_ERR_INVALID, pyr ? "num_level outside 1 .. 5" : "patch_radius outside 0 .. 31");
     if ((coord_xy || tracks_xy || flow_xy || kept_index) && stride < max_points(h, first, count))
         return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
-    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
-    for (int s = first; s < first + count; ++s) {
-        if (!h->slots[s].has_kf || h->slots[s].N < 1) return fail(EDS_ERR_STATE, "keyframe not set");
-        if (!h->slots[s].has_frame) return fail(EDS_ERR_STATE, "event frame not set");
-    }
+    if ((rc = check_idle_slots(h, first, count, EDS_NEED_KF | EDS_NEED_FRAME))) return rc;
     const size_t bin_lds = 2 * ((size_t)h->H + 2) * 4, win_lds = window_lds(h, r, L, pyr);
-    int max_lds = 0;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, h->dev));
-    if (bin_lds > (size_t)max_lds || win_lds > (size_t)max_lds || h->W > 65535 || h->H > 65535)
+    size_t max_lds = 0;
+    if ((rc = workgroup_lds_limit(h, &max_lds))) return rc;
+    if (!row_bins_fit(h, max_lds) || win_lds > max_lds)
         return fail(EDS_ERR_NOT_USABLE, "the KLT windows or the row bins of this frame size do not fit the workgroup's LDS");
-    int rc = ensure(h);
-    if (rc) return rc;
+    if ((rc = ensure(h))) return rc;
     EdsKltBuffers& kb = h->klt;
     // 1. getCoord(true): coordinates and kept indices into HBM, tracks into the plane, seeds and flow compacted
     const EdsPointsDev dev = {kb.coord, kb.kept};
     if ((rc = update_points_range(h, first, count, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dev))) return rc;
-    int maxN = 0;
-    for (int s = first; s < first + count; ++s) maxN = std::max(maxN, h->slots[s].N);
+    const int maxN = max_points(h, first, count);
     // 2. bins, 3. windows
     hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), bin_lds, h->st, h->arrays(), first, kb.coord, kb.keys_tmp, kb.keys,
                        kb.row_start, 0);
     EDS_HIP_TRY(hipGetLastError());
-    const double t = std::exp(-0.5 / (0.5 * 0.5));          // cv::getGaussianKernel(3, 0.5, CV_64F): [t, 1, t] / (1 + 2t)
-    const double k0 = t / (1.0 + 2.0 * t), k1 = 1.0 / (1.0 + 2.0 * t);
+    double k0, k1;
+    gauss3_sigma_half(k0, k1);
     if (maxN > 0) {
         if (pyr)
             hipLaunchKernelGGL(k_klt_window<true>, dim3(maxN, count), dim3(64), win_lds, h->st, h->arrays(), first, r, L, k0, k1, k0, kb.coord,
@@ -368,8 +297,8 @@ int run(eds_trk* h, int first, int count, int r, int L, bool pyr, int stride, do
         EDS_HIP_TRY(hipGetLastError());
     }
     // 4. what the caller asked for
-    const size_t Np = (size_t)h->Np, plane = (size_t)h->B * Np, n = (size_t)count * Np;
-    std::vector<double> va, vb;
+    const size_t Np = (size_t)h->Np, n = (size_t)count * Np;
+    std::vector<double> va;
     std::vector<int32_t> vk;
     if (coord_xy) { va.resize(2 * n); EDS_HIP_TRY(hipMemcpyAsync(va.data(), kb.coord + 2 * Np * first, 2 * n * 8, hipMemcpyDeviceToHost, h->st)); }
     if (kept_index) { vk.resize(n); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), kb.kept + Np * first, n * 4, hipMemcpyDeviceToHost, h->st)); }
@@ -381,20 +310,8 @@ int run(eds_trk* h, int first, int count, int r, int L, bool pyr, int stride, do
         if (coord_xy && nk > 0) std::memcpy(coord_xy + 2 * o, va.data() + 2 * Np * b, (size_t)nk * 16);
         if (kept_index && nk > 0) std::memcpy(kept_index + o, vk.data() + Np * b, (size_t)nk * 4);
     }
-    double* outs[2] = {tracks_xy, flow_xy};
-    const double* planes[2] = {kb.tracks, kb.flow};
-    for (int c = 0; c < 2; ++c) {
-        if (!outs[c]) continue;
-        va.resize(n); vb.resize(n);
-        EDS_HIP_TRY(hipMemcpyAsync(va.data(), planes[c] + Np * first, n * 8, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(vb.data(), planes[c] + plane + Np * first, n * 8, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
-        for (int b = 0; b < count; ++b) {
-            const int nk = h->slots[first + b].N;
-            double* dst = outs[c] + 2 * (size_t)b * stride;
-            for (int k = 0; k < nk; ++k) { dst[2 * k] = va[Np * b + k]; dst[2 * k + 1] = vb[Np * b + k]; }
-        }
-    }
+    if (tracks_xy && (rc = read_xy_planes(h, kb.tracks, first, count, stride, tracks_xy))) return rc;
+    if (flow_xy && (rc = read_xy_planes(h, kb.flow, first, count, stride, flow_xy))) return rc;
     return EDS_OK;
 }
 
@@ -441,22 +358,12 @@ int eds_klt_get(eds_trk* h, int slot, double* tracks_xy, double* flow_xy) {
     int rc = check_slot(h, slot);
     if (rc) return rc;
     if (!tracks_xy && !flow_xy) return fail(EDS_ERR_INVALID, "null output");
-    if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
-    const Slot& s = h->slots[slot];
-    if (!s.has_kf || s.N < 1) return fail(EDS_ERR_STATE, "keyframe not set");
+    if ((rc = check_idle_slots(h, slot, 1, EDS_NEED_KF))) return rc;
     if (!h->klt.tracks) return fail(EDS_ERR_STATE, "no device tracks: eds_klt_track_points has not run on this handle");
     EDS_HIP_TRY(hipSetDevice(h->dev));
-    const size_t Np = (size_t)h->Np, plane = (size_t)h->B * Np, o = (size_t)slot * Np, N = (size_t)s.N;
-    std::vector<double> v(2 * N);
-    double* outs[2] = {tracks_xy, flow_xy};
-    const double* planes[2] = {h->klt.tracks, h->klt.flow};
-    for (int c = 0; c < 2; ++c) {
-        if (!outs[c]) continue;
-        EDS_HIP_TRY(hipMemcpyAsync(v.data(), planes[c] + o, N * 8, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(v.data() + N, planes[c] + plane + o, N * 8, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
-        for (size_t k = 0; k < N; ++k) { outs[c][2 * k] = v[k]; outs[c][2 * k + 1] = v[N + k]; }
-    }
+    const int N = h->slots[slot].N;
+    if (tracks_xy && (rc = read_xy_planes(h, h->klt.tracks, slot, 1, N, tracks_xy))) return rc;
+    if (flow_xy && (rc = read_xy_planes(h, h->klt.flow, slot, 1, N, flow_xy))) return rc;
     return EDS_OK;
 }
 

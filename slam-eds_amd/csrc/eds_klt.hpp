@@ -12,7 +12,7 @@ struct EdsKltBuffers {
     double* flow = nullptr;         // [2][B][Np] fp64 SoA: kf->flow
     double* coord = nullptr;        // [B][Np][2] the warped coordinates getCoord(true) left for the window kernel
     int* kept = nullptr;            // [B][Np] the kept indices of that getCoord
-    uint64_t* keys_tmp = nullptr;   // [B][Np] (y0 << 48 | x0 << 32 | i) in arrival order (binning scratch)
+    uint64_t* keys_tmp = nullptr;   // [B][Np] splat_key(y0, x0, i) (eds_splat.hpp) in arrival order (binning scratch)
     uint64_t* keys = nullptr;       // [B][Np] the same keys sorted by (y0, x0, i)
     int* row_start = nullptr;       // [B][H + 2] first key of splat row y0 = 0 .. H, then the number of binned points
 };
