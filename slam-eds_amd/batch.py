@@ -185,6 +185,31 @@ class BatchTracker:
             return []
         return self.handle.epi_track_points(0, self.count, patch_radius, border_type, border_value, erase)
 
+    def refine_points(self, event_diff: float = 1.0, patch_radius: int = 11, border_type: int = 4, border_value: int = 255,
+                      erase: bool = True) -> list:
+        """KeyFrame::pointsRefinement of this shard on the device (include/eds_hip_kfpoints.h); per alignment dict(range, kept, n)"""
+        if self.count == 0:
+            return []
+        return self.handle.refine_points(0, self.count, event_diff, patch_radius, border_type, border_value, erase)
+
+    def clean_points(self, w_norm_thr: float = 0.2) -> list:
+        """KeyFrame::cleanPoints of this shard; per alignment dict(kept, n)"""
+        if self.count == 0:
+            return []
+        return self.handle.clean_points(0, self.count, w_norm_thr)
+
+    def erase_points(self, which) -> list:
+        """KeyFrame::erasePoint of this shard: one boolean mask or index list per alignment; per alignment dict(kept, n)"""
+        if self.count == 0:
+            return []
+        return self.handle.erase_points(which, 0, self.count)
+
+    def project_depth_maps(self, T=None, K=None, size=None) -> list:
+        """The next keyframes' depth maps of this shard (eds_kfp_project_depth_map); per alignment dict(xy, idp, src, n)"""
+        if self.count == 0:
+            return []
+        return self.handle.project_depth_map(0, self.count, T, K, size)
+
     def local_results(self) -> np.ndarray:
         if self.count == 0:
             return np.zeros((0, RESULT_WIDTH))

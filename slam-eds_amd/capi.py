@@ -65,6 +65,10 @@ EPI_EXPORTS = ("eds_epi_abi_version", "eds_epi_track_points", "eds_epi_get", "ed
 # enum eds_epi_border: cv::BORDER_* (BORDER_DEFAULT = REFLECT_101)
 EPI_BORDER_CONSTANT, EPI_BORDER_REPLICATE, EPI_BORDER_REFLECT, EPI_BORDER_REFLECT_101 = 0, 1, 2, 4
 
+# every symbol include/eds_hip_kfpoints.h declares: refine / clean / erase a keyframe's points, its counts, the next keyframe's depth map
+KFP_EXPORTS = ("eds_kfp_abi_version", "eds_kfp_refine_points", "eds_kfp_clean_points", "eds_kfp_erase_points", "eds_kfp_counts",
+               "eds_kfp_project_depth_map")
+
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
     "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
@@ -162,6 +166,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_klt.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_epiline.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_device.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfpoints.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
@@ -288,6 +293,11 @@ def lib():
         L.eds_epi_get.argtypes = [C.c_void_p, C.c_int, _dp]
         L.eds_epi_get_model.argtypes = [C.c_void_p, C.c_int, _dp]
         L.eds_epi_depth_update.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(DepthSummary)]
+        L.eds_kfp_refine_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip, _ip]
+        L.eds_kfp_clean_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, _ip, _ip]
+        L.eds_kfp_erase_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _ip, _ip]
+        L.eds_kfp_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip]
+        L.eds_kfp_project_depth_map.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip]
         L.eds_dev_check_range.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
         L.eds_dev_malloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
         L.eds_dev_free.argtypes = [C.c_void_p]
@@ -950,6 +960,88 @@ class Handle:
         out = (DepthSummary * count)()
         _check(lib().eds_epi_depth_update(self._h, int(first), int(count), _p(T), int(filter), out))
         return [o.as_dict() for o in out]
+
+    # -- the keyframe's own point set (include/eds_hip_kfpoints.h) --------------------------------
+    def _kfp_kept(self, first, count, kept, n):
+        out = []
+        for b in range(count):
+            self._N[first + b] = int(n[b])
+            out.append(dict(kept=kept[b, :n[b]].copy(), n=int(n[b])))
+        return out
+
+    def refine_points(self, first=0, count=None, event_diff=1.0, patch_radius=11, border_type=EPI_BORDER_REFLECT_101, border_value=255,
+                      erase=True):
+        """KeyFrame::pointsRefinement for slots first .. first + count - 1 on the frame each slot's solve reads.  Returns per slot
+        dict(range, kept, n): max - min of every ORIGINAL point's window, and the kept points' original indices."""
+        count = self.batch - first if count is None else count
+        n0 = list(self._N[first:first + count])
+        stride = max(n0 + [1])
+        rng = np.zeros((count, stride))
+        kept, n = np.zeros((count, stride), dtype=np.int32), np.zeros(count, dtype=np.int32)
+        _check(lib().eds_kfp_refine_points(self._h, int(first), int(count), float(event_diff), int(patch_radius), int(border_type),
+                                           int(border_value), int(bool(erase)), stride, _p(rng), kept.ctypes.data_as(_ip),
+                                           n.ctypes.data_as(_ip)))
+        out = self._kfp_kept(first, count, kept, n)
+        for b in range(count):
+            out[b]["range"] = rng[b, :n0[b]].copy()
+        return out
+
+    def clean_points(self, first=0, count=None, w_norm_thr=0.2):
+        """KeyFrame::cleanPoints(w_norm_thr) on the slots' weight planes; per slot dict(kept, n)"""
+        count = self.batch - first if count is None else count
+        stride = max(self._N[first:first + count] + [1])
+        kept, n = np.zeros((count, stride), dtype=np.int32), np.zeros(count, dtype=np.int32)
+        _check(lib().eds_kfp_clean_points(self._h, int(first), int(count), float(w_norm_thr), stride, kept.ctypes.data_as(_ip),
+                                          n.ctypes.data_as(_ip)))
+        return self._kfp_kept(first, count, kept, n)
+
+    def erase_points(self, which, first=0, count=None):
+        """KeyFrame::erasePoint: `which` holds per slot either a boolean mask over its points or a list of indices (one such entry
+        alone means one slot); per slot dict(kept, n)"""
+        count = self.batch - first if count is None else count
+        if count == 1 and not (isinstance(which, (list, tuple)) and len(which) == 1 and np.ndim(which[0]) == 1):
+            which = [which]
+        if len(which) != count:
+            raise EdsError(ERR_INVALID, "one mask or index list per slot")
+        stride = max(self._N[first:first + count] + [1])
+        flags = np.zeros((count, stride), dtype=np.uint8)
+        for b in range(count):
+            w, N = np.asarray(which[b]), self._N[first + b]
+            if w.dtype == np.bool_:
+                if w.shape != (N,):
+                    raise EdsError(ERR_INVALID, "an erase mask has one entry per point of its slot")
+                flags[b, :N] = w
+            else:
+                w = w.astype(np.int64).ravel()
+                if w.size and (w.min() < 0 or w.max() >= N):
+                    raise EdsError(ERR_INVALID, "an erase index lies outside its slot's points")
+                flags[b, w] = 1
+        kept, n = np.zeros((count, stride), dtype=np.int32), np.zeros(count, dtype=np.int32)
+        _check(lib().eds_kfp_erase_points(self._h, int(first), int(count), stride, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          kept.ctypes.data_as(_ip), n.ctypes.data_as(_ip)))
+        return self._kfp_kept(first, count, kept, n)
+
+    def point_counts(self, first=0, count=None):
+        """(KeyFrame::num_points, coord.size()) per slot, two int arrays"""
+        count = self.batch - first if count is None else count
+        num, cur = np.zeros(count, dtype=np.int32), np.zeros(count, dtype=np.int32)
+        _check(lib().eds_kfp_counts(self._h, int(first), int(count), num.ctypes.data_as(_ip), cur.ctypes.data_as(_ip)))
+        return num, cur
+
+    def project_depth_map(self, first=0, count=None, T=None, K=None, size=None):
+        """getDepthMap() -> T_dst_src -> IDepthMap::fromPoints: the depth map the next keyframe's build_keyframe takes.  T: count x 7
+        (p, q_xyzw) or None (each slot's state); K: count x 4 or None (the slot's own); size: (dst_H, dst_W) or None (the handle's).
+        Returns per slot dict(xy, idp, src, n)."""
+        count = self.batch - first if count is None else count
+        stride = max(self._N[first:first + count] + [1])
+        T = None if T is None else _f64(T).reshape(count, 7)
+        K = None if K is None else _f64(K).reshape(count, 4)
+        dH, dW = (0, 0) if size is None else (int(size[0]), int(size[1]))
+        xy, idp = np.zeros((count, stride, 2)), np.zeros((count, stride))
+        src, n = np.zeros((count, stride), dtype=np.int32), np.zeros(count, dtype=np.int32)
+        _check(lib().eds_kfp_project_depth_map(self._h, int(first), int(count), _p(T), _p(K), dH, dW, stride, _p(xy), _p(idp),
+                                               src.ctypes.data_as(_ip), n.ctypes.data_as(_ip)))
+        return [dict(xy=xy[b, :n[b]].copy(), idp=idp[b, :n[b]].copy(), src=src[b, :n[b]].copy(), n=int(n[b])) for b in range(count)]
 
     # -- inverse-depth filter (include/eds_hip_depth.h) -----------------------------------------
     def depth_init(self, first=0, count=None, source=DEPTH_INIT_CONSTANT, idp=None, min_depth=1.0, max_depth=3.0, threshold=100.0,

@@ -304,6 +304,7 @@ int eds_trk_set_keyframe(eds_trk* h, int slot, int N, const double* norm_xy, con
     EDS_HIP_TRY(hipSetDevice(h->dev));
     Slot& s = h->slots[slot];
     s.N = N; s.K[0] = fx; s.K[1] = fy; s.K[2] = cx; s.K[3] = cy;
+    s.num_points = N;                   // KeyFrame::num_points of a keyframe that arrives with its points
     if ((rc = upload_points(h, slot, N, norm_xy, grad_xy, idp, w))) return rc;
     if ((rc = refresh_gram(h, slot))) return rc;
     s.has_kf = true;

@@ -8,6 +8,7 @@
 #include "eds_depth.hpp"
 #include "eds_epiline.hpp"
 #include "eds_klt.hpp"
+#include "eds_kfpoints.hpp"
 #include "eds_fused.hpp"
 #include "eds_kernels.hpp"
 #include "eds_launch_rule.hpp"
@@ -42,6 +43,9 @@ struct Slot {
     // epiline tracker (include/eds_hip_epiline.h): the ef plane is index-aligned with this slot's points.  Cleared by everything
     // that changes the point set or the keyframe (set_keyframe, build_keyframe, an erasing update_points, the KLT)
     bool epi_valid = false;
+    // KeyFrame::num_points (include/eds_hip_kfpoints.h): N of an uploaded keyframe, the candidate count of a built one, the kept count
+    // of eds_kfp_refine_points(erase = 1); nothing else changes it
+    int num_points = 0;
 };
 
 
@@ -69,6 +73,7 @@ struct eds_trk {
     EdsDepthBuffers depth;
     EdsKltBuffers klt;                  // KLT tracks / flow planes (include/eds_hip_klt.h), allocated by the first KLT call
     EdsEpiBuffers epi;                  // epiline ef plane and work buffers (include/eds_hip_epiline.h), allocated by the first eds_epi_* call
+    EdsKfpBuffers kfp;                  // refine / clean / erase / project (include/eds_hip_kfpoints.h), allocated by the first eds_kfp_* call that needs them
     EdsKeyframeBuffers kf_build;
     // pinned host staging
     double *h_pose = nullptr, *h_part = nullptr, *h_G = nullptr;

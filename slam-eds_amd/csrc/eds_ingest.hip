@@ -294,6 +294,7 @@ int eds_dev_set_keyframes(eds_trk* h, int first, int count, const int* N, const 
     for (int b = 0; b < count; ++b) {                   // N and K reach the kernels through the slots' pose blocks
         Slot& s = h->slots[first + b];
         s.N = N[b];
+        s.num_points = N[b];
         for (int k = 0; k < 4; ++k) s.K[k] = K[4 * b + k];
         fill_static(h, first + b);
     }

@@ -528,6 +528,7 @@ int eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int 
     if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
     Slot& s = h->slots[slot];
     s.N = N; s.K[0] = fx; s.K[1] = fy; s.K[2] = cx; s.K[3] = cy;
+    s.num_points = ncand;                   // candidatePoints assigns it (KeyFrame.cpp:820); cleanPoints does not touch it
     if ((rc = eds_internal_refresh_gram(h, slot))) return rc;
     s.has_kf = true;
     s.seeded = false;                       // as eds_trk_set_keyframe

@@ -64,6 +64,11 @@ class KeyFrame:
     coord: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))   # pixel coordinates (KeyFrame.hpp:80)
     tracks: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))  # kf->tracks: getCoord's track (+ the KLT flow)
     flow: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))    # kf->flow: the KLT flow (zero after KeyFrame::create)
+    num_points: Optional[int] = None   # KeyFrame::num_points (KeyFrame.hpp:74); None: the number of points given
+
+    def __post_init__(self):
+        if self.num_points is None:
+            self.num_points = int(np.asarray(self.inv_depth).shape[0])
 
     @classmethod
     def create(cls, img, K_ref, depth_xy=None, depth_idp=None, points_selection_method: int = SELECT_MEDIAN,
@@ -80,9 +85,10 @@ class KeyFrame:
         try:
             out = h.build_keyframe(0, img, (K[0, 0], K[1, 1], K[0, 2], K[1, 2]), method=method, num_points=num,
                                    depth_xy=depth_xy, depth_idp=depth_idp, min_depth=min_depth, max_depth=max_depth)
+            num = int(h.point_counts(0, 1)[0][0])        # the candidates BEFORE cleanPoints (KeyFrame.cpp:820)
         finally:
             h.close()
-        return cls(out["norm_coord"], out["grad"], out["weights"], out["idp"], K, rows, cols, coord=out["coord"])
+        return cls(out["norm_coord"], out["grad"], out["weights"], out["idp"], K, rows, cols, coord=out["coord"], num_points=num)
 
 
 @dataclass
@@ -318,6 +324,75 @@ class Tracker:
             if len(kf.residuals) != len(keep):
                 kf.residuals = np.zeros(0)
         return out["ef"]
+
+    # -- the keyframe's own point set (include/eds_hip_kfpoints.h) ----------------------------
+    def _upload(self, event_frame=None):
+        self._ensure_handle()
+        kf, h = self.kf, self._h
+        K = np.asarray(kf.K_ref, dtype=np.float64)
+        h.set_keyframe(0, kf.norm_coord, kf.grad, kf.inv_depth, kf.weights, K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        if event_frame is not None:
+            h.set_event_frame(0, event_frame)
+        h.set_state(0, self.px, self.qx, self.vx)
+        return kf, h
+
+    def _erase(self, keep, N):
+        """KeyFrame::erasePoint of everything but `keep`, on every index-aligned vector"""
+        kf = self.kf
+        if len(keep) != N:
+            for name in ("norm_coord", "grad", "weights", "inv_depth"):
+                setattr(kf, name, np.ascontiguousarray(np.asarray(getattr(kf, name))[keep]))
+            for name in ("coord", "flow", "tracks"):
+                if len(getattr(kf, name)) == N:
+                    setattr(kf, name, np.ascontiguousarray(np.asarray(getattr(kf, name))[keep]))
+            if len(kf.residuals) != len(keep):
+                kf.residuals = np.zeros(0)
+
+    def pointsRefinement(self, event_frame, event_diff: float = 1.0, patch_radius: int = 11, border_type: int = 4,
+                         border_value: int = 255):
+        """KeyFrame::pointsRefinement (KeyFrame.cpp:1031-1058) on the device: the points whose (2r+1)^2 window of the event frame
+        is flatter than event_diff are erased, and num_points becomes the number left.  The handle stores the frame divided by
+        its Frobenius norm unless config.nc: event_diff is compared against THAT frame.  Returns every original point's range."""
+        N = len(self.kf.inv_depth)
+        kf, h = self._upload(event_frame)
+        out = h.refine_points(0, 1, event_diff, patch_radius, border_type, border_value)[0]
+        self._erase(out["kept"], N)
+        kf.num_points = out["n"]
+        return out["range"]
+
+    def cleanPoints(self, w_norm_thr: float = 0.2):
+        """KeyFrame::cleanPoints (KeyFrame.cpp:1566-1587); returns the kept indices"""
+        N = len(self.kf.inv_depth)
+        kf, h = self._upload()
+        out = h.clean_points(0, 1, w_norm_thr)[0]
+        self._erase(out["kept"], N)
+        return out["kept"]
+
+    def erasePoints(self, idx):
+        """KeyFrame::erasePoint (KeyFrame.cpp:1060-1106) for a boolean mask or a list of indices; returns the kept indices"""
+        N = len(self.kf.inv_depth)
+        kf, h = self._upload()
+        out = h.erase_points(idx, 0, 1)[0]
+        self._erase(out["kept"], N)
+        return out["kept"]
+
+    def needNewKF(self, percent_thr: float = 0.1) -> bool:
+        """KeyFrame::needNewKF (KeyFrame.cpp:1552-1557): unsigned num_points - size_t coord.size(), which wraps when the keyframe
+        holds more points than num_points"""
+        num, cur = int(self.kf.num_points), len(self.kf.inv_depth)
+        return bool(float((num - cur) % (1 << 64)) > percent_thr * float(num))
+
+    def needNewKFImageCriteria(self, percent: float) -> bool:
+        """KeyFrame::needNewKFImageCriteria (KeyFrame.cpp:1559-1564)"""
+        return bool(float(len(self.kf.inv_depth)) < float(self.kf.cols * self.kf.rows) * percent)
+
+    def getDepthMap(self, T=None, K=None, size=None):
+        """kf->getDepthMap() (KeyFrame.cpp:1220-1237) moved by T (p, q_xyzw of T_dst_src; None: the tracker's T_ef_kf) and pushed
+        through IDepthMap::fromPoints with K (fx, fy, cx, cy; None: the keyframe's) and size (rows, cols; None: the keyframe's):
+        (xy, idp, src) of the points that land inside — what the next KeyFrame.create takes as depth_xy, depth_idp."""
+        kf, h = self._upload()
+        out = h.project_depth_map(0, 1, None if T is None else [T], None if K is None else [K], size)[0]
+        return out["xy"], out["idp"], out["src"]
 
     def trackPoints(self, event_frame, patch_radius: int = 7):
         """Tracker::trackPoints (Tracker.cpp:378-434): getCoord(true), then kf.flow = f and kf.tracks += f per point."""
