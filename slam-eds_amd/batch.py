@@ -210,6 +210,16 @@ class BatchTracker:
             return []
         return self.handle.project_depth_map(0, self.count, T, K, size)
 
+    def switch_keyframes(self, images, T=None, K=None, **select) -> list:
+        """The keyframe switch of this shard without leaving the device (include/eds_hip_kfswitch.h): every alignment's points are
+        projected by T (count x 7 T_newkf_kf; None: the solved state) and K (count x 4, the new keyframes' intrinsics; None: unchanged)
+        into the new keyframe's depth map, its k-d tree is built on the device, and KeyFrame::create runs on `images` (count x H x W,
+        numpy or a device array) into the same slots.  `select`: method, num_points, cell, ... of Handle.build_keyframes.
+        Returns per alignment dict(status, n, tree_on_host, coord, norm_coord, grad, idp, weights)."""
+        if self.count == 0:
+            return []
+        return self.handle.build_keyframes(images, K, first=0, depth="slots", src_first=0, T=T, K_dst=K, **select)
+
     def local_results(self) -> np.ndarray:
         if self.count == 0:
             return np.zeros((0, RESULT_WIDTH))

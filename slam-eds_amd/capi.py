@@ -69,6 +69,11 @@ EPI_BORDER_CONSTANT, EPI_BORDER_REPLICATE, EPI_BORDER_REFLECT, EPI_BORDER_REFLEC
 KFP_EXPORTS = ("eds_kfp_abi_version", "eds_kfp_refine_points", "eds_kfp_clean_points", "eds_kfp_erase_points", "eds_kfp_counts",
                "eds_kfp_project_depth_map")
 
+# every symbol include/eds_hip_kfswitch.h declares: the depth k-d tree built on the device, KeyFrame::create for a range of slots
+KFS_EXPORTS = ("eds_kfs_abi_version", "eds_kfs_tree_capacity", "eds_kfs_chunk_size", "eds_kfs_build_tree", "eds_kfs_build_keyframes",
+               "eds_kfs_build_keyframes_dev")
+KFS_DEPTH_NONE, KFS_DEPTH_HOST, KFS_DEPTH_DEVICE, KFS_DEPTH_SLOTS = 0, 1, 2, 3      # enum eds_kfs_depth_source
+
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
     "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
@@ -85,6 +90,18 @@ class KfSelect(C.Structure):
     """``eds_kf_select`` — the arguments of KeyFrame::create that steer the point set-up (KeyFrame.cpp:333-341)."""
     _fields_ = [("method", C.c_int32), ("cell", C.c_int32), ("num_points", C.c_int32), ("sobel_ksize", C.c_int32),
                 ("min_depth", C.c_double), ("max_depth", C.c_double), ("weight_threshold", C.c_double)]
+
+
+class KfsDepth(C.Structure):
+    """``eds_kfs_depth`` — where the depth maps of eds_kfs_build_keyframes come from (include/eds_hip_kfswitch.h)."""
+    _fields_ = [("source", C.c_int32), ("src_first", C.c_int32), ("n", C.c_void_p), ("depth_xy", C.c_void_p), ("depth_idp", C.c_void_p),
+                ("stride", C.c_int64), ("T7", C.c_void_p), ("K_dst", C.c_void_p)]
+
+
+class KfsOut(C.Structure):
+    """``eds_kfs_out`` — the optional host outputs of eds_kfs_build_keyframes."""
+    _fields_ = [("n_points", C.c_void_p), ("status", C.c_void_p), ("tree_on_host", C.c_void_p), ("stride", C.c_int64),
+                ("coord_xy", C.c_void_p), ("norm_xy", C.c_void_p), ("grad_xy", C.c_void_p), ("idp", C.c_void_p), ("weights", C.c_void_p)]
 
 
 class DepthParams(C.Structure):
@@ -167,6 +184,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_epiline.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_device.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfpoints.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfswitch.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
@@ -298,6 +316,11 @@ def lib():
         L.eds_kfp_erase_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), _ip, _ip]
         L.eds_kfp_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip]
         L.eds_kfp_project_depth_map.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip]
+        L.eds_kfs_build_tree.argtypes = [C.c_void_p, C.c_int, _ip, C.c_void_p, C.c_int64, _ip, C.POINTER(C.c_uint8)]
+        L.eds_kfs_build_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(KfSelect), _dp,
+                                              C.POINTER(KfsDepth), C.POINTER(KfsOut)]
+        L.eds_kfs_build_keyframes_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(KfSelect), _dp,
+                                                  C.POINTER(KfsDepth), C.POINTER(KfsOut)]
         L.eds_dev_check_range.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
         L.eds_dev_malloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
         L.eds_dev_free.argtypes = [C.c_void_p]
@@ -439,6 +462,26 @@ def _device_rows(obj, count, width, name):
     return ptr, S, (est[0] // width if count > 1 else S)
 
 
+def _kfs_device_images(obj, H, W):
+    """Arguments of eds_kfs_build_keyframes_dev for `obj`: ``(ptr, count, dtype code, frame_stride, row_stride)``, strides in elements.
+    `obj`: count x H x W (or H x W), uint8 / float32 / float64, last dimension contiguous, rows and frames not overlapping."""
+    ptr, shape, est, dt = device_array_info(obj)
+    if len(shape) == 2:
+        shape, est = (1,) + shape, (0,) + est
+    codes = {np.dtype(np.uint8): IMG_U8, np.dtype(np.float32): IMG_F32, np.dtype(np.float64): IMG_F64}
+    if dt not in codes:
+        raise ValueError(f"keyframe images must be uint8, float32 or float64, not {dt.name}")
+    if len(shape) != 3 or shape[0] < 1 or shape[1:] != (int(H), int(W)):
+        raise ValueError(f"keyframe images must be count x {H} x {W}, not {shape}")
+    if est[2] != 1 or est[1] < W:
+        raise ValueError("the last dimension must be contiguous and rows must not overlap")
+    need = (H - 1) * est[1] + W
+    frame = est[0] if shape[0] > 1 else need
+    if frame < need:
+        raise ValueError("frames overlap or run backwards")
+    return ptr, shape[0], codes[dt], frame, est[1]
+
+
 def _stream_ptr(stream):
     """a hipStream_t as an integer: None / 0 is the null stream; an int, or an object with ``.cuda_stream`` (torch.cuda.Stream)"""
     if stream is None:
@@ -504,6 +547,16 @@ class DeviceView:
     def __cuda_array_interface__(self):
         return {"shape": self.shape, "typestr": self.base.dtype.str, "data": (self.base.ptr + self.offset, False), "strides": self.strides,
                 "version": 3}
+
+
+def tree_capacity() -> int:
+    """``eds_kfs_tree_capacity``: points per depth map the device builds the k-d tree of; larger maps take the host build."""
+    return int(lib().eds_kfs_tree_capacity())
+
+
+def kfs_chunk_size() -> int:
+    """``eds_kfs_chunk_size``: slots that build_keyframes queues between two waits on the stream."""
+    return int(lib().eds_kfs_chunk_size())
 
 
 def check_range(ptr, nbytes, device=0) -> int:
@@ -1042,6 +1095,126 @@ class Handle:
         _check(lib().eds_kfp_project_depth_map(self._h, int(first), int(count), _p(T), _p(K), dH, dW, stride, _p(xy), _p(idp),
                                                src.ctypes.data_as(_ip), n.ctypes.data_as(_ip)))
         return [dict(xy=xy[b, :n[b]].copy(), idp=idp[b, :n[b]].copy(), src=src[b, :n[b]].copy(), n=int(n[b])) for b in range(count)]
+
+    # -- the keyframe switch for a range of slots (include/eds_hip_kfswitch.h) ----------------------
+    def build_tree(self, maps):
+        """``eds_kfs_build_tree``: the k-d tree's index array of every depth map.  `maps`: a list of m x 2 arrays (numpy: uploaded
+        here), or a float64 device array count x S x 2 with a list of sizes, as ``(device_array, n)``.  Returns
+        ``(list of int32 index arrays, on_host flags)``; on_host[b] is True where the map was ambiguous or beyond
+        ``tree_capacity()`` and the host build made the array."""
+        keep = None
+        if isinstance(maps, tuple) and len(maps) == 2 and is_device_array(maps[0]):
+            n = np.ascontiguousarray(maps[1], dtype=np.int32)
+            count = int(n.shape[0])
+            ptr, S, stride = _device_rows(maps[0], count, 2, "maps")
+            if count and int(n.max()) > S:
+                raise EdsError(ERR_INVALID, "a map has more points than its row holds")
+        else:
+            maps = [_f64(m).reshape(-1, 2) for m in maps]
+            count = len(maps)
+            n = np.array([m.shape[0] for m in maps], dtype=np.int32)
+            stride = max(1, int(n.max()) if count else 1)
+            t = np.zeros((max(count, 1), stride, 2))
+            for b, m in enumerate(maps):
+                t[b, :m.shape[0]] = m
+            keep = DeviceArray.from_numpy(t)
+            ptr = keep.ptr
+        perm, on_host = np.zeros((max(count, 1), stride), dtype=np.int32), np.zeros(max(count, 1), dtype=np.uint8)
+        _check(lib().eds_kfs_build_tree(self._h, count, n.ctypes.data_as(_ip), C.c_void_p(ptr or None), int(stride), perm.ctypes.data_as(_ip),
+                                        on_host.ctypes.data_as(C.POINTER(C.c_uint8))))
+        del keep
+        return [perm[b, :n[b]].copy() for b in range(count)], on_host[:count].astype(bool)
+
+    def build_keyframes(self, images, K, first=0, depth=None, depth_idp=None, depth_n=None, src_first=None, T=None, K_dst=None, method=KF_MEDIAN,
+                        num_points=0, cell=20, min_depth=1.0, max_depth=3.0, weight_threshold=0.7, sobel_ksize=3, vectors=True, check=True):
+        """``eds_kfs_build_keyframes[_dev]``: KeyFrame::create for slots first .. first + count - 1 in one call.
+
+        images: count grey H x W images — a numpy array count x H x W (or a list of H x W arrays) of uint8 / float32 / float64, or
+        anything with ``__cuda_array_interface__`` of that shape (strided frames and rows are fine).  K: count x 4.
+        depth: None (the constant initial depth); ``"slots"`` — each map is the projection of slot ``src_first + b`` (default: in place)
+        by T (count x 7, None: the solved state) and K_dst (count x 4, None: the slot's own); a list of m x 2 arrays (None or empty: that
+        slot has no map) with `depth_idp` a list of m-vectors; or device arrays count x S x 2 / count x S with `depth_n` sizes.
+        Returns per slot dict(status, n, tree_on_host[, coord, norm_coord, grad, idp, weights]).  check: raise EdsError at the first
+        failing slot's code after all slots were tried (False: look at status)."""
+        if is_device_array(images):
+            ptr, count, ty, fstride, rstride = _kfs_device_images(images, self.H, self.W)
+            host_imgs = None
+        else:
+            host_imgs = [np.ascontiguousarray(im) for im in images]
+            count = len(host_imgs)
+            dts = {im.dtype for im in host_imgs}
+            if count < 1 or len(dts) != 1 or any(im.shape != (self.H, self.W) for im in host_imgs):
+                raise EdsError(ERR_INVALID, "images must be count x H x W of one dtype")
+            dt = dts.pop()
+            ty = IMG_U8 if dt == np.uint8 else (IMG_F32 if dt == np.float32 else IMG_F64)
+            if ty == IMG_F64:
+                host_imgs = [np.ascontiguousarray(im, dtype=np.float64) for im in host_imgs]
+        K = None if K is None else _f64(K).reshape(count, 4)          # None: the source slots' own (depth="slots" only)
+        sel = KfSelect()
+        lib().eds_kf_select_default(C.byref(sel))
+        sel.method, sel.cell, sel.num_points, sel.sobel_ksize = int(method), int(cell), int(num_points), int(sobel_ksize)
+        sel.min_depth, sel.max_depth, sel.weight_threshold = float(min_depth), float(max_depth), float(weight_threshold)
+        d, keep = KfsDepth(), []
+        if depth is None:
+            d.source = KFS_DEPTH_NONE
+        elif isinstance(depth, str):
+            if depth != "slots":
+                raise EdsError(ERR_INVALID, 'depth is None, "slots", a list of maps or device arrays')
+            d.source, d.src_first = KFS_DEPTH_SLOTS, int(first if src_first is None else src_first)
+            if T is not None:
+                keep.append(_f64(T).reshape(count, 7)); d.T7 = keep[-1].ctypes.data
+            if K_dst is not None:
+                keep.append(_f64(K_dst).reshape(count, 4)); d.K_dst = keep[-1].ctypes.data
+        elif is_device_array(depth):
+            n = np.ascontiguousarray(depth_n, dtype=np.int32).reshape(count)
+            pxy, S, stride = _device_rows(depth, count, 2, "depth")
+            pidp, S2, stride2 = _device_rows(depth_idp, count, 1, "depth_idp")
+            if stride2 != stride or int(n.max()) > min(S, S2):
+                raise EdsError(ERR_INVALID, "depth and depth_idp have different strides, or a map has more points than its row holds")
+            keep.append(n)
+            d.source, d.n, d.depth_xy, d.depth_idp, d.stride = KFS_DEPTH_DEVICE, n.ctypes.data, pxy, pidp, stride
+        else:
+            maps = [np.zeros((0, 2)) if m is None else _f64(m).reshape(-1, 2) for m in depth]
+            idps = [np.zeros(0) if m is None else _f64(m).reshape(-1) for m in (depth_idp if depth_idp is not None else [None] * count)]
+            if len(maps) != count or len(idps) != count or any(a.shape[0] != b.shape[0] for a, b in zip(maps, idps)):
+                raise EdsError(ERR_INVALID, "one depth map and one inverse-depth vector of the same length per slot")
+            n = np.array([m.shape[0] for m in maps], dtype=np.int32)
+            stride = max(1, int(n.max()))
+            txy, tidp = np.zeros((count, stride, 2)), np.zeros((count, stride))
+            for b in range(count):
+                txy[b, :n[b]], tidp[b, :n[b]] = maps[b], idps[b]
+            keep += [n, txy, tidp]
+            d.source, d.n, d.depth_xy, d.depth_idp, d.stride = KFS_DEPTH_HOST, n.ctypes.data, txy.ctypes.data, tidp.ctypes.data, stride
+        o = KfsOut()
+        n_points, status, on_host = np.full(count, -1, dtype=np.int32), np.zeros(count, dtype=np.int32), np.zeros(count, dtype=np.uint8)
+        o.n_points, o.status, o.tree_on_host = n_points.ctypes.data, status.ctypes.data, on_host.ctypes.data
+        vec = {}
+        if vectors:
+            S = self.max_points
+            vec = dict(coord=np.zeros((count, S, 2)), norm_coord=np.zeros((count, S, 2)), grad=np.zeros((count, S, 2)), idp=np.zeros((count, S)),
+                       weights=np.zeros((count, S)))
+            o.stride = S
+            o.coord_xy, o.norm_xy, o.grad_xy = vec["coord"].ctypes.data, vec["norm_coord"].ctypes.data, vec["grad"].ctypes.data
+            o.idp, o.weights = vec["idp"].ctypes.data, vec["weights"].ctypes.data
+        if host_imgs is None:
+            rc = lib().eds_kfs_build_keyframes_dev(self._h, int(first), count, ty, C.c_void_p(ptr or None), fstride, rstride, C.byref(sel), _p(K),
+                                                   C.byref(d), C.byref(o))
+        else:
+            ptrs = (C.c_void_p * count)(*[im.ctypes.data for im in host_imgs])
+            rc = lib().eds_kfs_build_keyframes(self._h, int(first), count, ty, ptrs, C.byref(sel), _p(K), C.byref(d), C.byref(o))
+        if rc != EDS_OK and not status.any():       # refused as a whole: nothing was tried
+            _check(rc)
+        out = []
+        for b in range(count):
+            r = dict(status=int(status[b]), n=int(n_points[b]), tree_on_host=bool(on_host[b]))
+            if status[b] == EDS_OK:
+                self._N[first + b] = r["n"]
+                for k_, v in vec.items():
+                    r[k_] = v[b, :r["n"]].copy()
+            out.append(r)
+        if check:
+            _check(rc)
+        return out
 
     # -- inverse-depth filter (include/eds_hip_depth.h) -----------------------------------------
     def depth_init(self, first=0, count=None, source=DEPTH_INIT_CONSTANT, idp=None, min_depth=1.0, max_depth=3.0, threshold=100.0,

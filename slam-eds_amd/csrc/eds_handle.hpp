@@ -9,6 +9,7 @@
 #include "eds_epiline.hpp"
 #include "eds_klt.hpp"
 #include "eds_kfpoints.hpp"
+#include "eds_kfswitch.hpp"
 #include "eds_fused.hpp"
 #include "eds_kernels.hpp"
 #include "eds_launch_rule.hpp"
@@ -75,6 +76,7 @@ struct eds_trk {
     EdsEpiBuffers epi;                  // epiline ef plane and work buffers (include/eds_hip_epiline.h), allocated by the first eds_epi_* call
     EdsKfpBuffers kfp;                  // refine / clean / erase / project (include/eds_hip_kfpoints.h), allocated by the first eds_kfp_* call that needs them
     EdsKeyframeBuffers kf_build;
+    EdsKfsBuffers kfs;                  // the batched keyframe switch (include/eds_hip_kfswitch.h), allocated by the first eds_kfs_* call that needs them
     // pinned host staging
     double *h_pose = nullptr, *h_part = nullptr, *h_G = nullptr;
     float *h_f32 = nullptr, *h_r = nullptr;

@@ -238,6 +238,44 @@ void eds_kfp_free(EdsKfpBuffers* kb) {
     *kb = EdsKfpBuffers();
 }
 
+int eds_kfp_check_transforms(int count, const double* T7, const double* K_dst) {
+    for (int b = 0; b < count; ++b) {
+        if (T7) {
+            const double* q = T7 + 7 * (size_t)b + 3;
+            if (!finite_all(T7 + 7 * (size_t)b, 7)) return fail(EDS_ERR_INVALID, "T7 is not finite");
+            if (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] == 0.0) return fail(EDS_ERR_INVALID, "T7 holds a zero quaternion");
+        }
+        if (K_dst) {
+            const double* K = K_dst + 4 * (size_t)b;
+            if (!finite_all(K, 4) || K[0] == 0.0 || K[1] == 0.0) return fail(EDS_ERR_INVALID, "K_dst is not finite or has a zero focal length");
+        }
+    }
+    return EDS_OK;
+}
+
+int eds_kfp_project_queue(eds_trk* h, int first, int cn, const double* T7, const double* K_dst, double dW, double dH, double* h_par,
+                      const double* d_par, int* d_n, double* d_xy, double* d_idp, int* d_src) {
+    for (int b = 0; b < cn; ++b) {
+        const Slot& sl = h->slots[first + b];
+        const double* p = T7 ? T7 + 7 * (size_t)b : sl.p;
+        const double* qq = T7 ? T7 + 7 * (size_t)b + 3 : sl.q;
+        double* P = h_par + (size_t)b * EDS_KFP_PAR;
+        // R of the normalised quaternion (x, y, z, w), each entry as written, in fp64
+        const double n = std::sqrt(qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
+        const double x = qq[0] / n, y = qq[1] / n, z = qq[2] / n, w = qq[3] / n;
+        P[0] = 1.0 - 2.0 * (y * y + z * z); P[1] = 2.0 * (x * y - z * w);       P[2] = 2.0 * (x * z + y * w);
+        P[3] = 2.0 * (x * y + z * w);       P[4] = 1.0 - 2.0 * (x * x + z * z); P[5] = 2.0 * (y * z - x * w);
+        P[6] = 2.0 * (x * z - y * w);       P[7] = 2.0 * (y * z + x * w);       P[8] = 1.0 - 2.0 * (x * x + y * y);
+        for (int j = 0; j < 3; ++j) P[9 + j] = p[j];
+        for (int j = 0; j < 4; ++j) { P[12 + j] = sl.K[j]; P[16 + j] = K_dst ? K_dst[4 * (size_t)b + j] : sl.K[j]; }
+        P[20] = dW; P[21] = dH; P[22] = sl.seeded ? 1.0 : 0.0; P[23] = 0.0;
+    }
+    hipLaunchKernelGGL(k_kfp_project, dim3(cn), dim3(EDS_KFP_PROJ_THREADS), 0, h->st, h->arrays(), first, d_par, h->depth.seeds, d_n,
+                       d_xy, d_idp, d_src);
+    EDS_HIP_TRY(hipGetLastError());
+    return EDS_OK;
+}
+
 extern "C" {
 
 int eds_kfp_abi_version(void) { return EDS_HIP_KFPOINTS_ABI_VERSION; }
@@ -318,17 +356,7 @@ int eds_kfp_project_depth_map(eds_trk* h, int first, int count, const double* T7
                               double* depth_xy, double* depth_idp, int32_t* src_index, int* n_out) {
     int rc = check_range(h, first, count);
     if (rc) return rc;
-    for (int b = 0; b < count; ++b) {
-        if (T7) {
-            const double* q = T7 + 7 * (size_t)b + 3;
-            if (!finite_all(T7 + 7 * (size_t)b, 7)) return fail(EDS_ERR_INVALID, "T7 is not finite");
-            if (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] == 0.0) return fail(EDS_ERR_INVALID, "T7 holds a zero quaternion");
-        }
-        if (K_dst) {
-            const double* K = K_dst + 4 * (size_t)b;
-            if (!finite_all(K, 4) || K[0] == 0.0 || K[1] == 0.0) return fail(EDS_ERR_INVALID, "K_dst is not finite or has a zero focal length");
-        }
-    }
+    if ((rc = eds_kfp_check_transforms(count, T7, K_dst))) return rc;
     if ((rc = common_checks(h, first, count, depth_xy || depth_idp || src_index, stride, EDS_NEED_KF))) return rc;
     EDS_HIP_TRY(hipSetDevice(h->dev));
     if ((rc = ensure_project(h, std::min(count, EDS_KFP_BATCH)))) return rc;
@@ -337,24 +365,8 @@ int eds_kfp_project_depth_map(eds_trk* h, int first, int count, const double* T7
     const double dW = (double)(dst_W > 0 ? dst_W : h->W), dH = (double)(dst_H > 0 ? dst_H : h->H);
     for (int c0 = 0; c0 < count; c0 += k.cap) {
         const int cn = std::min(k.cap, count - c0);
-        for (int b = 0; b < cn; ++b) {
-            const Slot& sl = h->slots[first + c0 + b];
-            const double* p = T7 ? T7 + 7 * (size_t)(c0 + b) : sl.p;
-            const double* qq = T7 ? T7 + 7 * (size_t)(c0 + b) + 3 : sl.q;
-            double* P = k.h_par + (size_t)b * EDS_KFP_PAR;
-            // R of the normalised quaternion (x, y, z, w), each entry as written, in fp64
-            const double n = std::sqrt(qq[0] * qq[0] + qq[1] * qq[1] + qq[2] * qq[2] + qq[3] * qq[3]);
-            const double x = qq[0] / n, y = qq[1] / n, z = qq[2] / n, w = qq[3] / n;
-            P[0] = 1.0 - 2.0 * (y * y + z * z); P[1] = 2.0 * (x * y - z * w);       P[2] = 2.0 * (x * z + y * w);
-            P[3] = 2.0 * (x * y + z * w);       P[4] = 1.0 - 2.0 * (x * x + z * z); P[5] = 2.0 * (y * z - x * w);
-            P[6] = 2.0 * (x * z - y * w);       P[7] = 2.0 * (y * z + x * w);       P[8] = 1.0 - 2.0 * (x * x + y * y);
-            for (int j = 0; j < 3; ++j) P[9 + j] = p[j];
-            for (int j = 0; j < 4; ++j) { P[12 + j] = sl.K[j]; P[16 + j] = K_dst ? K_dst[4 * (size_t)(c0 + b) + j] : sl.K[j]; }
-            P[20] = dW; P[21] = dH; P[22] = sl.seeded ? 1.0 : 0.0; P[23] = 0.0;
-        }
-        hipLaunchKernelGGL(k_kfp_project, dim3(cn), dim3(EDS_KFP_PROJ_THREADS), 0, h->st, h->arrays(), first + c0, k.d_par, h->depth.seeds, k.d_n,
-                           k.d_xy, k.d_idp, k.d_src);
-        EDS_HIP_TRY(hipGetLastError());
+        if ((rc = eds_kfp_project_queue(h, first + c0, cn, T7 ? T7 + 7 * (size_t)c0 : nullptr, K_dst ? K_dst + 4 * (size_t)c0 : nullptr, dW, dH, k.h_par,
+                                        k.d_par, k.d_n, k.d_xy, k.d_idp, k.d_src))) return rc;
         EDS_HIP_TRY(hipStreamSynchronize(h->st));
         for (int b = 0; b < cn; ++b) {
             const int n = k.h_n[b];

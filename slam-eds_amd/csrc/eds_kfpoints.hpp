@@ -27,3 +27,9 @@ struct EdsKfpBuffers {
 };
 
 void eds_kfp_free(EdsKfpBuffers* kb);
+// eds_kfp_project_depth_map's checks of T7 (count x 7) and K_dst (count x 4), either may be NULL
+int eds_kfp_check_transforms(int count, const double* T7, const double* K_dst);
+// fills the projection blocks of slots first .. first + cn - 1 (h_par / d_par: the two views of mapped pinned memory, EDS_KFP_PAR doubles
+// per slot) and queues k_kfp_project on the handle's stream: slot first + b writes d_n[b] and, at b * Np, d_xy, d_idp and d_src
+int eds_kfp_project_queue(eds_trk* h, int first, int cn, const double* T7, const double* K_dst, double dW, double dH, double* h_par,
+                          const double* d_par, int* d_n, double* d_xy, double* d_idp, int* d_src);
