@@ -187,6 +187,74 @@ __device__ __forceinline__ void shift_patch_row3(const float4& a, const float4& 
 // quad index so that the 16 lanes one ds_read_b128 / ds_write_b128 services together hit 16 different bank groups.
 __device__ __forceinline__ int patch_unit(int point, int row) { return ((point << 2) + row) ^ (((point >> 2) & 3) << 2); }
 
+// ---------------------------------------------------------------------------------------
+// Toroidal patch cache with incremental refetch (EDS_TILE_REFETCH; DESIGN §3.1, policy P6).  The [point][row] unit of quad lane jr
+// holds the patch row whose frame row is = jr (mod 4), and position k of a unit holds the tap whose frame column is = k (mod 4).
+// A 4x4 patch covers every residue once per axis, so the taps two overlapping patches share have ONE address: a patch that moved
+// by (dr, dc) with |dr|, |dc| <= 3 fetches only its new rows and columns, and a lane asks only for the tile pieces they lie in.
+// Two words go round the quad.  The origin (torus_origin): allocation row of patch row 0 in bits 16-28, allocation column of patch
+// column 0 in bits 0-15, both of the CLAMPED patch — what is really read; this is also what s_cell remembers.  The refetch word
+// (torus_refetch): two halves of the same shape, the low one for a lane whose row is new, the high one for a lane whose row stays:
+//   bits 0-3  taps to take from piece a (the tile that holds patch column 0)      bits 4-6  taps to take from piece b (the next tile)
+//   bits 8-9  (column of patch column 0) & 3: where patch order starts in a unit   bits 10-11 the same for the rows, among the units
+//   bits 12-15 rows that are new, by residue
+// ---------------------------------------------------------------------------------------
+static_assert(EDS_FRAME_MARGIN % 4 == 0, "toroidal cache: allocation and frame coordinates share their residues mod 4");
+typedef short short2v __attribute__((ext_vector_type(2)));
+typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
+typedef float float3v __attribute__((ext_vector_type(3)));   // piece b of a row: tap 3 of a unit never comes from it, 12 bytes are fetched
+// (min / max, not clampi: that compiles to compare + select here, whose constant arm occupies a register for the whole solve)
+__device__ __forceinline__ int torus_origin(const FrameView& f, int r0, int c0) {
+    const int r = max(min(r0, f.H), -2), c = max(min(c0, f.W), -2);
+    return (r << 16) + c + (((EDS_FRAME_MARGIN - 1) << 16) | (EDS_FRAME_MARGIN - 1));
+}
+// `old`: the origin cached for this point, 0x7fffffff: none.  Along an axis the new lines of a patch that moved by d are a cyclic run
+// of min(|d|, 4) residues that starts at the smaller of the two origins; 4 on either axis means no overlap, and everything is fetched.
+// Both axes at once, as two 16-bit halves (columns low, rows high).
+__device__ __forceinline__ int torus_refetch(int cur, int old) {
+    const short2v c = __builtin_bit_cast(short2v, cur), o = __builtin_bit_cast(short2v, old);
+    const short2v d = c - o;
+    const short2v len = __builtin_elementwise_min(__builtin_elementwise_max(d, -d), (short2v)(4));
+    const short2v start = __builtin_elementwise_min(c, o) & (short2v)(3);
+    const ushort2v below = ~((ushort2v)(15) << __builtin_bit_cast(ushort2v, len)) & (ushort2v)(15);      // the low `len` bits
+    const unsigned run = __builtin_bit_cast(unsigned, (ushort2v)(below << __builtin_bit_cast(ushort2v, start)));
+    const unsigned m2 = (run | (run >> 4)) & 0x000f000fu;                                                  // new columns in bits 0-3, new rows in bits 16-19
+    // nothing cached: every row is new, so every lane fetches all it owns.  (The sentinel's row field, 0x7fff, is further than 3 from
+    // any row of a frame, but the no-overlap case does not rest on that.)
+    // (old + 1 is negative for the sentinel alone; spelled as a compare and select the mask would occupy a register for the whole solve)
+    const unsigned none = (unsigned)((int)((unsigned)old + 1u) >> 31) & 0xf000u;
+    const unsigned s = (unsigned)cur & 3u;
+    const unsigned F = 0xfu << s;                        // residues >= s come from piece a (bits 0-3), residues < s from piece b (bits 4-6)
+    const unsigned common = (s << 8) | ((((unsigned)cur >> 16) & 3u) << 10) | ((m2 >> 4) & 0xf000u) | none;
+    return (int)((((F & ((m2 & 0xfu) * 0x11u)) | common) << 16) | F | common);
+}
+// the half of a refetch word that holds for the lane of row residue jr, in bits 16-31 (rowbit = 12 + jr)
+__device__ __forceinline__ int torus_lane_mask(int w, int rowbit) {
+    const int rn = (int)__builtin_amdgcn_sbfe(w, rowbit, 1);
+    return __builtin_amdgcn_bitop3_b32(rn, w << 16, w, 0xCA);
+}
+// The row of residue jr of the patch at origin `org`: byte offset of its piece a from row jr of the allocation's first tile (piece b:
+// + 64).  rowc = (3 - jr) << 16: the row sits in tile row (row of patch row 0 + 3 - jr) >> 2, at row jr of that tile.
+__device__ __forceinline__ unsigned torus_row_offset(int org, unsigned rowc, unsigned tile_row_bytes) {
+    return __umul24(((unsigned)org + rowc) >> 18, tile_row_bytes) + (((unsigned)org & 0xfffcu) << 4);
+}
+// Merge what was fetched into the cached unit (taps stay where they are), then the unit in patch order: a rotation by bits 24-25 of m.
+__device__ __forceinline__ void torus_merge(const float4& a, const float3v& b, float4& c, int m) {
+    const int a0 = __builtin_amdgcn_sbfe(m, 16, 1), a1 = __builtin_amdgcn_sbfe(m, 17, 1), a2 = __builtin_amdgcn_sbfe(m, 18, 1), a3 = __builtin_amdgcn_sbfe(m, 19, 1);
+    const int b0 = __builtin_amdgcn_sbfe(m, 20, 1), b1 = __builtin_amdgcn_sbfe(m, 21, 1), b2 = __builtin_amdgcn_sbfe(m, 22, 1);
+    c.x = mask_select(a0, a.x, mask_select(b0, b.x, c.x));
+    c.y = mask_select(a1, a.y, mask_select(b1, b.y, c.y));
+    c.z = mask_select(a2, a.z, mask_select(b2, b.z, c.z));
+    c.w = mask_select(a3, a.w, c.w);
+}
+// t[i] = u[(i + s) & 3], s in bits `bit`, `bit` + 1 of m
+template <int BIT>
+__device__ __forceinline__ void torus_rotate(float u0, float u1, float u2, float u3, int m, float (&t)[4]) {
+    const int m2 = __builtin_amdgcn_sbfe(m, BIT + 1, 1), m1 = __builtin_amdgcn_sbfe(m, BIT, 1);
+    const float v0 = mask_select(m2, u2, u0), v1 = mask_select(m2, u3, u1), v2 = mask_select(m2, u0, u2), v3 = mask_select(m2, u1, u3);
+    t[0] = mask_select(m1, v1, v0); t[1] = mask_select(m1, v2, v1); t[2] = mask_select(m1, v3, v2); t[3] = mask_select(m1, v0, v3);
+}
+
 // Bicubic value and derivatives from a register-resident 4x4 patch (ay: row phase, ax: col phase).
 __device__ __forceinline__ void bicubic_patch(const float (&p)[16], float ay, float ax, float& E, float& Erow, float& Ecol) {
     float f[4], d[4];

@@ -30,6 +30,9 @@
 #ifndef EDS_GATHER_STAGES
 #define EDS_GATHER_STAGES 2      // groups the strip kernels consume their points in, each behind a counted wait (1: one wait for all rows)
 #endif
+#ifndef EDS_TILE_REFETCH
+#define EDS_TILE_REFETCH 1       // the first-solve tile kernels (pairs, one CU per alignment): toroidal patch cache, only the NEW taps of a shifted patch are fetched (0: every tap of a patch whose cell changed)
+#endif
 #include "eds_handle.hpp"
 #include "eds_launch_rule.hpp"
 #include "eds_math.hpp"
@@ -400,6 +403,93 @@ __global__ __launch_bounds__(MAXT, (TEAM > 1 && PPT == 1) ? EDS_TEAM_P1_WAVES_PE
                 const float iz_j = (j & 1) ? pg[g].iz.y : pg[g].iz.x, un_j = (j & 1) ? pg[g].un.y : pg[g].un.x, vn_j = (j & 1) ? pg[g].vn.y : pg[g].vn.x;
                 const float w_j = (j & 1) ? k2w[g].y : k2w[g].x, mh_j = (j & 1) ? k2mh[g].y : k2mh[g].x;
                 rcand[j] = row6_accumulate<(QUAD == 4)>(ps_fx, ps_fy, iz_j, un_j, vn_j, EEc.x, dE.x, EEc.y, w_j, mh_j, tau, A6);
+            }
+            A6.unpack(acc);
+        } else if constexpr (EDS_TILE_REFETCH != 0 && QUAD == 1 && TEAM == 1 && PPT > 0 && PPT % 2 == 0) {
+            // ---- the same gather on pairs with a TOROIDAL cache and incremental refetch (eds_device.hpp, torus_*) ----
+            // phase A: every point compares its clamped origin with the cached one and sends origin and refetch word round the quad; lane
+            // jr, which owns the patch row of frame row = jr (mod 4), puts in flight only the tile pieces that hold a tap it lacks
+            const int jr = lane & 3;
+            float* __restrict__ cache = &s_patch[0][0] + 16 * (tid & ~3) + 4 * jr;
+            const int swz = (tid >> 2) & 3;
+            const int cq0 = 16 * (0 ^ swz), cq1 = 16 * (1 ^ swz), cq2 = 16 * (2 ^ swz), cq3 = 16 * (3 ^ swz);
+            const int cq[4] = {cq0, cq1, cq2, cq3};
+            const float* __restrict__ rtf = spec_mode ? sp.spec[kcur].rt.f : s_posef;
+            EDS_LOAD_POSE_SCALARS(rtf, s_posef + 12);
+            PairGeom pg[NPAIR];
+            int ref[NREG];
+            float4 ra[NREG][4];
+            float3v rb[NREG][4];
+            // one lane constant for two uses: its bits 0-4 are this lane's bit of a refetch word's new rows (all v_bfe_i32 reads of a bit
+            // position), its bits 16-17 the rows from the patch's first row up to this lane's tile row (torus_row_offset: what the low
+            // bits add to the origin's column field stays in that field and is shifted out)
+            const int rowbit = ((3 - jr) << 16) | (12 + jr);
+            const unsigned rowc = (unsigned)rowbit, tile_row_bytes = (unsigned)frame.TW * 64u;
+            // (a per-lane 64-bit base: as a uniform base the pointer is kept in VGPRs for want of SGPRs and read out, two v_readfirstlane and
+            // a wait, in front of every load)
+            const char* __restrict__ tbase = reinterpret_cast<const char*>(tiles) + 16 * jr;
+#pragma unroll
+            for (int g = 0; g < NPAIR; ++g) {
+                int r0[2], c0[2];
+                project_pair(EDS_POSE_SCALARS, k2x[g], k2y[g], k2rhop[g], k2f0x[g], k2f0y[g], kcell[2 * g], kcell[2 * g + 1], pg[g], r0, c0);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int j = 2 * g + e, i = tid + j * nthr;
+                    const int org = torus_origin(frame, r0[e], c0[e]);
+                    ref[j] = torus_refetch(org, s_cell[i]);
+                    s_cell[i] = org;
+                    const int o0 = quad_bcast_i<0>(org), o1 = quad_bcast_i<1>(org), o2 = quad_bcast_i<2>(org), o3 = quad_bcast_i<3>(org);
+                    const int w0 = quad_bcast_i<0>(ref[j]), w1 = quad_bcast_i<1>(ref[j]), w2 = quad_bcast_i<2>(ref[j]), w3 = quad_bcast_i<3>(ref[j]);
+                    const int oq[4] = {o0, o1, o2, o3}, wq[4] = {w0, w1, w2, w3};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        asm("" : "=v"(ra[j][q].x), "=v"(ra[j][q].y), "=v"(ra[j][q].z), "=v"(ra[j][q].w));      // content does not matter where nothing is fetched: no instruction
+                        asm("" : "=v"(rb[j][q].x), "=v"(rb[j][q].y), "=v"(rb[j][q].z));
+                        const int m = torus_lane_mask(wq[q], rowbit);
+                        const char* __restrict__ src = tbase + torus_row_offset(oq[q], rowc, tile_row_bytes);
+                        if (m & 0x000f0000) ra[j][q] = *reinterpret_cast<const float4*>(src);
+                        if (m & 0x00700000) rb[j][q] = *reinterpret_cast<const float3v*>(src + 64);      // (asked for only where a tap lies in it: inside the allocation)
+                    }
+                }
+            }
+            // phase B (branch-free): the new taps into the cached unit, the unit back to the cache, its taps into patch order, the row
+            // splines of two patches per packed instruction, the transposes, the row results into patch order at the lane that owns the
+            // point; from there on as below
+            Acc6 A6;
+            A6.clear();
+#pragma unroll
+            for (int j = 0; j < NREG; ++j) {
+                const int g = j >> 1;
+                const float ax_j = (j & 1) ? pg[g].ax.y : pg[g].ax.x, ay_j = (j & 1) ? pg[g].ay.y : pg[g].ay.x;
+                // (the lane masks are formed again, not kept from phase A: sixteen registers less while every load is in flight)
+                asm volatile("" : "+v"(ref[j]));
+                const int w0 = quad_bcast_i<0>(ref[j]), w1 = quad_bcast_i<1>(ref[j]), w2 = quad_bcast_i<2>(ref[j]), w3 = quad_bcast_i<3>(ref[j]);
+                const int wq[4] = {w0, w1, w2, w3};
+                const f2 x01 = {quad_bcast_f<0>(ax_j), quad_bcast_f<1>(ax_j)}, x23 = {quad_bcast_f<2>(ax_j), quad_bcast_f<3>(ax_j)};
+                float t[4][4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float4 c = *reinterpret_cast<const float4*>(cache + cq[q] + 16 * j * nthr);
+                    const int m = torus_lane_mask(wq[q], rowbit);
+                    torus_merge(ra[j][q], rb[j][q], c, m);
+                    *reinterpret_cast<float4*>(cache + cq[q] + 16 * j * nthr) = c;
+                    torus_rotate<24>(c.x, c.y, c.z, c.w, m, t[q]);
+                }
+                f2 f01, d01, f23, d23;
+                hermite_pair((f2){t[0][0], t[1][0]}, (f2){t[0][1], t[1][1]}, (f2){t[0][2], t[1][2]}, (f2){t[0][3], t[1][3]}, x01, 0.5f * x01, 3.0f * x01, f01, d01);
+                hermite_pair((f2){t[2][0], t[3][0]}, (f2){t[2][1], t[3][1]}, (f2){t[2][2], t[3][2]}, (f2){t[2][3], t[3][3]}, x23, 0.5f * x23, 3.0f * x23, f23, d23);
+                float fr[4] = {f01.x, f01.y, f23.x, f23.y}, dr[4] = {d01.x, d01.y, d23.x, d23.y};
+                quad_transpose(fr, lane);
+                quad_transpose(dr, lane);
+                float f[4], d[4];             // lane k sent the row of residue k: patch row p is residue (row of patch row 0 + p) & 3
+                torus_rotate<10>(fr[0], fr[1], fr[2], fr[3], ref[j], f);
+                torus_rotate<10>(dr[0], dr[1], dr[2], dr[3], ref[j], d);
+                f2 EEc, dE;
+                const f2 y2 = (f2)(ay_j);
+                hermite_pair((f2){f[0], d[0]}, (f2){f[1], d[1]}, (f2){f[2], d[2]}, (f2){f[3], d[3]}, y2, 0.5f * y2, 3.0f * y2, EEc, dE);
+                const float iz_j = (j & 1) ? pg[g].iz.y : pg[g].iz.x, un_j = (j & 1) ? pg[g].un.y : pg[g].un.x, vn_j = (j & 1) ? pg[g].vn.y : pg[g].vn.x;
+                const float w_j = (j & 1) ? k2w[g].y : k2w[g].x, mh_j = (j & 1) ? k2mh[g].y : k2mh[g].x;
+                rcand[j] = row6_accumulate<false>(ps_fx, ps_fy, iz_j, un_j, vn_j, EEc.x, dE.x, EEc.y, w_j, mh_j, tau, A6);
             }
             A6.unpack(acc);
         } else if constexpr (QUAD != 0 && PPT > 0 && PPT % 2 == 0) {

@@ -38,9 +38,12 @@ stats = {short(r["Name"]): r for r in csv.DictReader(open(stats_csv))}
 
 pmc = collections.defaultdict(lambda: collections.defaultdict(list))
 for which in ("fetch", "write"):
-    for f in [newest(os.path.join(src, f"pmc_{which}", "*", "*_counter_collection.csv"))]:
-        for r in csv.DictReader(open(f)):
-            pmc[short(r["Kernel_Name"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
+    try:
+        f = newest(os.path.join(src, f"pmc_{which}", "*", "*_counter_collection.csv"))
+    except ValueError:                          # a digest of request counts only (kernel trace + the L2 pass): no byte columns
+        continue
+    for r in csv.DictReader(open(f)):
+        pmc[short(r["Kernel_Name"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
 
 l2 = collections.defaultdict(lambda: collections.defaultdict(list))
 try:
