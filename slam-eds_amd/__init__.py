@@ -9,5 +9,6 @@ alias module at the repo root).  Sub-modules:
 * ``tracker`` — Python mirror of ``eds::tracking::Tracker`` (reference Tracker.hpp:36-114)
 * ``batch``   — batched / multi-GPU alignment driver (one process per GPU, RCCL gather)
 * ``depth``   — Python mirror of ``eds::mapping::DepthPoints`` whose seeds live on the device (include/eds_hip_depth.h)
+* ``immature`` — DSO's immature points traced along epipolar lines on the device (include/eds_hip_immature.h)
 """
 __version__ = "0.1.0"

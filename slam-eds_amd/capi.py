@@ -74,6 +74,11 @@ KFS_EXPORTS = ("eds_kfs_abi_version", "eds_kfs_tree_capacity", "eds_kfs_chunk_si
                "eds_kfs_build_keyframes_dev")
 KFS_DEPTH_NONE, KFS_DEPTH_HOST, KFS_DEPTH_DEVICE, KFS_DEPTH_SLOTS = 0, 1, 2, 3      # enum eds_kfs_depth_source
 
+# every symbol include/eds_hip_immature.h declares: DSO's immature points traced along epipolar lines (bound in immature.py)
+IMM_EXPORTS = ("eds_imm_abi_version", "eds_imm_params_default", "eds_imm_create", "eds_imm_destroy", "eds_imm_set_params", "eds_imm_get_params",
+               "eds_imm_set_host_images", "eds_imm_set_target_images", "eds_imm_create_points", "eds_imm_num_points", "eds_imm_trace",
+               "eds_imm_get", "eds_imm_get_points", "eds_imm_get_image")
+
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
     "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
@@ -185,6 +190,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_device.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfpoints.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfswitch.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_immature.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
