@@ -11,5 +11,6 @@ alias module at the repo root).  Sub-modules:
 * ``depth``   — Python mirror of ``eds::mapping::DepthPoints`` whose seeds live on the device (include/eds_hip_depth.h)
 * ``immature`` — DSO's immature points traced along epipolar lines on the device (include/eds_hip_immature.h)
 * ``coarse``  — DSO's coarse image tracker for the pose of every new image frame, on the device (include/eds_hip_coarse.h)
+* ``window``  — the window optimiser's linearize, applyRes and per-point Hessian sums on the device (include/eds_hip_window.h)
 """
 __version__ = "0.1.0"

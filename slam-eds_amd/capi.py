@@ -83,6 +83,11 @@ IMM_EXPORTS = ("eds_imm_abi_version", "eds_imm_params_default", "eds_imm_create"
 CT_EXPORTS = ("eds_ct_abi_version", "eds_ct_params_default", "eds_ct_create", "eds_ct_destroy", "eds_ct_set_params", "eds_ct_get_params",
               "eds_ct_set_calib", "eds_ct_get_k", "eds_ct_set_ref", "eds_ct_set_new", "eds_ct_track", "eds_ct_calc_res", "eds_ct_get_level")
 
+# every symbol include/eds_hip_window.h declares: the window optimiser's linearize, applyRes and per-point sums (bound in window.py)
+WIN_EXPORTS = ("eds_win_abi_version", "eds_win_params_default", "eds_win_create", "eds_win_destroy", "eds_win_set_params", "eds_win_get_params",
+               "eds_win_set_calib", "eds_win_set_frames", "eds_win_get_frame", "eds_win_set_points", "eds_win_set_idepths", "eds_win_set_residuals",
+               "eds_win_linearize", "eds_win_apply", "eds_win_point_hessians", "eds_win_accumulate", "eds_win_acc_size", "eds_win_get_residuals", "eds_win_get_points")
+
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
     "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
@@ -196,6 +201,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfswitch.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_immature.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_coarse.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_window.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
