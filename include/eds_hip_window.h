@@ -8,8 +8,9 @@
  *
  * eds_win_accumulate adds every accumulator of the two addPoint()s (acc[h + F t], accHcc, accbc, accD, accE, accEB) on the device and
  * both stitches (in fp64, one thread per output entry, the addends in the header's order) and returns H_A, b_A, H_sc, b_sc.
- * NOT here (they stay with the caller): modes 1 and 2 of the top accumulator, marginalisation, the priors of usePrior (a diagonal add),
- * the dense solve, resubstituteF.  Residuals with isLinearized must not be put into the table: their sums come in through lf.
+ * NOT here: modes 1 and 2 of the top accumulator, point marginalisation, the priors of usePrior (a diagonal add), the dense solve and
+ * resubstituteF are eds_hip_winsolve.h's, over this object.  Without that header no residual carries isLinearized: such residuals must
+ * then stay out of the table, and their sums come in through lf (lf = NULL: the sums eds_hip_winsolve.h left on the device, if any).
  *
  * Conventions are those of eds_hip_coarse.h: plain pointers and sizes, caller-owned host buffers, EDS_OK or a negative eds_status,
  * eds_last_error() for the text.  Every call returns when its results are on the device or the host.

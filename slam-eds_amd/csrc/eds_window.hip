@@ -18,6 +18,7 @@
 #include "../../include/eds_hip_window.h"
 #include "eds_capi_internal.hpp"
 #include "eds_window.hpp"
+#include "eds_window_internal.hpp"
 
 using edscapi::fail;
 using edswin::Calib;
@@ -27,40 +28,12 @@ using edswin::PointOut;
 using edswin::Precalc;
 using edswin::Px;
 using edswin::J_WORDS;
+using edswin::Sum;
 
 static_assert(sizeof(Params) == sizeof(eds_win_params), "edswin::Params is eds_win_params member for member");
 static_assert(sizeof(Precalc) == EDS_WIN_PRECALC_FLOATS * sizeof(float), "one precalc record is 27 floats");
 static_assert(edswin::MAX_FRAMES == EDS_WIN_MAX_FRAMES && J_WORDS == EDS_WIN_J_WORDS, "header constants");
 static_assert(sizeof(PointOut) == 10 * sizeof(float), "ten words per point");
-
-namespace {
-struct Sum { double energy; int32_t counts[4]; };
-}
-
-struct eds_win {
-    int dev = 0, H = 0, W = 0, max_frames = 0, max_points = 0, max_residuals = 0;
-    Params prm;
-    Calib cal;
-    bool calib_set = false, linearized = false;
-    uint32_t frames_set = 0;                              // bit f: frame f holds an image
-    int n = 0, m = 0, max_host = -1, max_target = -1;
-    std::vector<int32_t> host_of, h_point, h_target;     // host copies for the checks and the (point, target) -> residual map
-    int32_t *res_of = nullptr, *first = nullptr;          // [max_points * 8], [9]
-    double* acc = nullptr;                                // [acc_size(8)]
-    double *ad = nullptr, *stitched = nullptr;            // adHost then adTarget [2][64][64]; H_A, b_A, H_sc, b_sc [stitch_words(8)]
-    hipStream_t st = nullptr;
-    Px* frames = nullptr;
-    float* in_img = nullptr;
-    Point* pts = nullptr;
-    float *ids = nullptr, *idz = nullptr;                 // idepth_scaled, idepth_zero_scaled per point
-    int32_t *res_first = nullptr, *res_point = nullptr, *res_target = nullptr, *state = nullptr, *new_state = nullptr, *active = nullptr;
-    float *energy = nullptr, *new_energy = nullptr, *new_energy_wo = nullptr, *ret = nullptr, *cp = nullptr, *proj = nullptr, *J = nullptr,
-          *efJ = nullptr, *JpJdF = nullptr, *th = nullptr, *prior = nullptr, *delta = nullptr, *lf = nullptr;
-    Precalc* pcs = nullptr;
-    Sum* sum = nullptr;
-    PointOut* pout = nullptr;
-    int32_t* nres = nullptr;
-};
 
 namespace {
 
@@ -227,22 +200,25 @@ __global__ void __launch_bounds__(TB) k_win_apply(Dev t, int m, int copy_jacobia
     if (j == 0) { t.state[i] = ns; t.energy[i] = t.new_energy[i]; }
 }
 
-// addPoint<0>'s per-point sums and the Schur complement's per-point prologue, one thread per point; nres is an integer atomic
+// addPoint<0>'s per-point sums (mode 2: zero, for the points of sel) and the Schur complement's per-point prologue, one thread per point;
+// nres, the residuals added, is an integer atomic
 __global__ void __launch_bounds__(TB) k_win_points(int n, const int32_t* __restrict__ res_first, const int32_t* __restrict__ active,
+                                                   const int32_t* __restrict__ lin, int mode, const int32_t* __restrict__ sel,
                                                    const float* __restrict__ efJ, const float* __restrict__ prior, const float* __restrict__ delta,
                                                    const float* __restrict__ lf, int has_prior, int has_delta, int has_lf, int shift,
                                                    PointOut* __restrict__ out, int32_t* nres) {
     const int p = blockIdx.x * TB + threadIdx.x;
-    if (p >= n) return;
+    if (p >= n || (sel && !sel[p])) return;
     float l[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if (has_lf) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) l[k] = lf[6 * p + k];
     }
-    const PointOut o = edswin::point_sums(active, efJ, res_first[p], res_first[p + 1], has_prior ? prior[p] : 0.0f, has_delta ? delta[p] : 0.0f, l,
-                                          shift != 0);
+    int added = 0;
+    const PointOut o = edswin::point_sums_mode(active, lin, efJ, res_first[p], res_first[p + 1], has_prior ? prior[p] : 0.0f,
+                                               has_delta ? delta[p] : 0.0f, l, shift != 0, mode, &added);
     out[p] = o;
-    if (o.nres) atomicAdd(nres, o.nres);
+    if (added) atomicAdd(nres, added);
 }
 
 // one accumulator word per workgroup: the 512 lanes stride the host frame's points, fold as the header says
@@ -260,9 +236,9 @@ __global__ void __launch_bounds__(edswin::LANES) k_win_acc(edswin::AccIn in, dou
 
 // both stitches, one thread per output entry (edswin::stitch_entry: the addends and their order are stitch_serial's)
 __global__ void __launch_bounds__(TB) k_win_stitch(int F, const double* __restrict__ acc, const double* __restrict__ adH, const double* __restrict__ adT,
-                                                   double* __restrict__ out) {
+                                                   int entries, double* __restrict__ out) {
     const int e = blockIdx.x * TB + threadIdx.x;
-    if (e < edswin::stitch_words(F)) edswin::stitch_entry(F, acc, adH, adT, e, out);
+    if (e < entries) edswin::stitch_entry(F, acc, adH, adT, e, out);
 }
 
 int check_handle(const eds_win* h) { return h ? EDS_OK : fail(EDS_ERR_INVALID, "null eds_win handle"); }
@@ -276,6 +252,24 @@ bool all_finite_f(const float* x, size_t n) {
     for (size_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false;
     return true;
 }
+// the (point, target) -> residual map and the hosts' runs [first[h], first[h + 1])
+int build_maps(const eds_win* h, int F, std::vector<int32_t>& res_of, std::vector<int32_t>& first) {
+    res_of.assign((size_t)h->n * F, -1);
+    first.assign((size_t)9, h->n);
+    for (int i = 0; i < h->m; ++i) {
+        int32_t& slot = res_of[(size_t)h->h_point[i] * F + h->h_target[i]];
+        if (slot >= 0) return fail(EDS_ERR_INVALID, "a point has two residuals towards one target");
+        slot = i;
+    }
+    // the fold walks [first[h], first[h + 1]): the hosts' runs must tile 0 .. n in host order
+    for (int p = 1; p < h->n; ++p)
+        if (h->host_of[p] < h->host_of[p - 1]) return fail(EDS_ERR_INVALID, "eds_win_accumulate needs the points in nondecreasing host order");
+    for (int f = 0, p = 0; f < 9; ++f) {
+        first[f] = p;
+        while (p < h->n && h->host_of[p] == f) ++p;
+    }
+    return EDS_OK;
+}
 template <class T> int download(eds_win* h, T* dst, const T* src, size_t n) {
     if (!dst || !n) return EDS_OK;
     EDS_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, h->st));
@@ -283,6 +277,36 @@ template <class T> int download(eds_win* h, T* dst, const T* src, size_t n) {
 }
 
 }  // namespace
+
+namespace edswin_internal {
+
+int upload_maps(eds_win* h, int F) {
+    std::vector<int32_t> res_of, first;
+    if (int rc = build_maps(h, F, res_of, first)) return rc;
+    if (h->n) EDS_HIP_TRY(hipMemcpyAsync(h->res_of, res_of.data(), res_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->first, first.data(), 9 * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->st));                  // the two vectors end here
+    return EDS_OK;
+}
+
+void queue_points(eds_win* h, int mode, const int32_t* sel, int shift) {
+    if (!h->n) return;
+    (void)hipMemsetAsync(h->nres, 0, sizeof(int32_t), h->st);
+    hipLaunchKernelGGL(k_win_points, dim3(blocks((size_t)h->n)), dim3(TB), 0, h->st, h->n, h->res_first, h->active, lin_flags(h), mode, sel, h->efJ,
+                       h->prior, h->delta, h->lf, 1, 1, lf_on_device(h) ? 1 : 0, shift, h->pout, h->nres);
+}
+
+void queue_acc(eds_win* h, int F, int mode, const int32_t* sel, int has_lf, int words, double* acc) {
+    const edswin::AccIn in = {F, has_lf, h->first, h->res_of, h->active, h->efJ, h->JpJdF, h->pout, h->lf,
+                              mode, lin_flags(h), h->wsv ? h->wsv->res_approx : nullptr, sel};
+    hipLaunchKernelGGL(k_win_acc, dim3((unsigned)words), dim3(edswin::LANES), 0, h->st, in, acc);
+}
+
+void queue_stitch(eds_win* h, int F, const double* acc, const double* ad, int entries, double* out) {
+    hipLaunchKernelGGL(k_win_stitch, dim3(blocks((size_t)entries)), dim3(TB), 0, h->st, F, acc, ad, ad + (size_t)F * F * 64, entries, out);
+}
+
+}  // namespace edswin_internal
 
 extern "C" {
 
@@ -360,7 +384,9 @@ int eds_win_create(int device, int H, int W, int max_frames, int max_points, int
 void eds_win_destroy(eds_win* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
-    if (h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
+    if (h->st) (void)hipStreamSynchronize(h->st);
+    edswin_internal::wsv_release(h);
+    if (h->st) (void)hipStreamDestroy(h->st);
     void* all[] = {h->frames, h->in_img, h->pts, h->ids, h->idz, h->res_first, h->res_point, h->res_target, h->state, h->new_state, h->active, h->energy,
                    h->new_energy, h->new_energy_wo, h->ret, h->cp, h->proj, h->J, h->efJ, h->JpJdF, h->th, h->prior, h->delta, h->lf, h->pcs,
                    h->sum, h->pout, h->nres, h->res_of, h->first, h->acc, h->ad, h->stitched};
@@ -472,6 +498,7 @@ int eds_win_set_points(eds_win* h, int n, const int32_t* host, const float* uv, 
     EDS_HIP_TRY(hipMemsetAsync(h->pout, 0, (size_t)h->max_points * sizeof(PointOut), h->st));
     EDS_HIP_TRY(hipStreamSynchronize(h->st));
     h->n = n; h->m = 0; h->max_host = max_host; h->max_target = -1; h->linearized = false;
+    edswin_internal::wsv_invalidate(h);
     h->host_of.assign(host, host + n);
     h->h_point.clear(); h->h_target.clear();
     return EDS_OK;
@@ -529,6 +556,7 @@ int eds_win_set_residuals(eds_win* h, int m, const int32_t* point, const int32_t
     }
     EDS_HIP_TRY(hipStreamSynchronize(h->st));
     h->m = m; h->max_target = max_target; h->linearized = false;
+    edswin_internal::wsv_invalidate(h);
     h->h_point.assign(point, point + m); h->h_target.assign(target, target + m);
     return EDS_OK;
 }
@@ -585,10 +613,15 @@ int eds_win_point_hessians(eds_win* h, const float* priorF, const float* deltaF,
         EDS_HIP_TRY(hipSetDevice(h->dev));
         if (priorF) EDS_HIP_TRY(hipMemcpyAsync(h->prior, priorF, n * sizeof(float), hipMemcpyHostToDevice, h->st));
         if (deltaF) EDS_HIP_TRY(hipMemcpyAsync(h->delta, deltaF, n * sizeof(float), hipMemcpyHostToDevice, h->st));
-        if (lf) EDS_HIP_TRY(hipMemcpyAsync(h->lf, lf, 6 * n * sizeof(float), hipMemcpyHostToDevice, h->st));
+        if (lf) {
+            EDS_HIP_TRY(hipMemcpyAsync(h->lf, lf, 6 * n * sizeof(float), hipMemcpyHostToDevice, h->st));
+            if (h->wsv) h->wsv->lf_on_device = false;           // the caller's sums replace what modes 1 / 2 left there
+        }
         EDS_HIP_TRY(hipMemsetAsync(h->nres, 0, sizeof(int32_t), h->st));
-        hipLaunchKernelGGL(k_win_points, dim3(blocks(n)), dim3(TB), 0, h->st, h->n, h->res_first, h->active, h->efJ, h->prior, h->delta, h->lf,
-                           priorF ? 1 : 0, deltaF ? 1 : 0, lf ? 1 : 0, shift_prior_to_zero, h->pout, h->nres);
+        // lf == NULL: the sums modes 1 / 2 of include/eds_hip_winsolve.h left on the device, when there are any
+        hipLaunchKernelGGL(k_win_points, dim3(blocks(n)), dim3(TB), 0, h->st, h->n, h->res_first, h->active, edswin_internal::lin_flags(h), 0,
+                           (const int32_t*)nullptr, h->efJ, h->prior, h->delta, h->lf, priorF ? 1 : 0, deltaF ? 1 : 0,
+                           lf || edswin_internal::lf_on_device(h) ? 1 : 0, shift_prior_to_zero, h->pout, h->nres);
         EDS_HIP_TRY(hipGetLastError());
         EDS_HIP_TRY(hipMemcpyAsync(&back, h->nres, sizeof(back), hipMemcpyDeviceToHost, h->st));
         EDS_HIP_TRY(hipStreamSynchronize(h->st));
@@ -605,33 +638,21 @@ int eds_win_accumulate(eds_win* h, int F, const double* adHost, const double* ad
     if (h->max_host >= F || h->max_target >= F) return fail(EDS_ERR_INVALID, "a point's host or a residual's target is not below F");
     for (size_t i = 0; i < (size_t)F * F * 64; ++i)
         if (!std::isfinite(adHost[i]) || !std::isfinite(adTarget[i])) return fail(EDS_ERR_INVALID, "the adjoints are not finite");
-    std::vector<int32_t> res_of((size_t)h->n * F, -1), first((size_t)9, h->n);
-    for (int i = 0; i < h->m; ++i) {
-        int32_t& slot = res_of[(size_t)h->h_point[i] * F + h->h_target[i]];
-        if (slot >= 0) return fail(EDS_ERR_INVALID, "a point has two residuals towards one target");
-        slot = i;
-    }
-    // the fold walks [first[h], first[h + 1]): the hosts' runs must tile 0 .. n in host order
-    for (int p = 1; p < h->n; ++p)
-        if (h->host_of[p] < h->host_of[p - 1]) return fail(EDS_ERR_INVALID, "eds_win_accumulate needs the points in nondecreasing host order");
-    for (int f = 0, p = 0; f < 9; ++f) {
-        first[f] = p;
-        while (p < h->n && h->host_of[p] == f) ++p;
-    }
+    std::vector<int32_t> res_of, first;
+    if (int rc = build_maps(h, F, res_of, first)) return rc;
     if (int rc = eds_win_point_hessians(h, priorF, deltaF, lf, shift_prior_to_zero, nres)) return rc;
     const int words = edswin::acc_size(F);
     std::vector<double> acc((size_t)words, 0.0);
     EDS_HIP_TRY(hipSetDevice(h->dev));
     if (h->n) EDS_HIP_TRY(hipMemcpyAsync(h->res_of, res_of.data(), res_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
     EDS_HIP_TRY(hipMemcpyAsync(h->first, first.data(), 9 * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    const edswin::AccIn in = {F, lf ? 1 : 0, h->first, h->res_of, h->active, h->efJ, h->JpJdF, h->pout, h->lf};
-    hipLaunchKernelGGL(k_win_acc, dim3((unsigned)words), dim3(edswin::LANES), 0, h->st, in, h->acc);
+    edswin_internal::queue_acc(h, F, 0, nullptr, lf || edswin_internal::lf_on_device(h) ? 1 : 0, words, h->acc);
     EDS_HIP_TRY(hipGetLastError());
     const size_t N = 4 + 8 * (size_t)F, ad_words = (size_t)F * F * 64;
     const int sw = edswin::stitch_words(F);
     EDS_HIP_TRY(hipMemcpyAsync(h->ad, adHost, ad_words * sizeof(double), hipMemcpyHostToDevice, h->st));
     EDS_HIP_TRY(hipMemcpyAsync(h->ad + ad_words, adTarget, ad_words * sizeof(double), hipMemcpyHostToDevice, h->st));
-    hipLaunchKernelGGL(k_win_stitch, dim3(blocks((size_t)sw)), dim3(TB), 0, h->st, F, h->acc, h->ad, h->ad + ad_words, h->stitched);
+    edswin_internal::queue_stitch(h, F, h->acc, h->ad, sw, h->stitched);
     EDS_HIP_TRY(hipGetLastError());
     std::vector<double> st((size_t)sw);
     EDS_HIP_TRY(hipMemcpyAsync(st.data(), h->stitched, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));

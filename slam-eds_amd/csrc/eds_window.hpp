@@ -218,29 +218,40 @@ EDS_WIN_HD void apply_one(const ResState& r, int i, bool copy_jacobians) {
 // addPoint (AccumulatedSCHessian.cpp:36-55), residuals in residualsAll order = the order of the residual table -----------------------------
 struct PointOut { float Hdd_accAF, bd_accAF, Hcd_accAF[4], HdiF, bdSumF, idepth_hessian; int32_t nres; };
 
-// Mode 0 of the top accumulator skips residuals with isLinearized while the Schur complement's ngoodres counts every active one; the
-// residual table carries no such flag, so the caller must NOT put linearized residuals into it (their sums come in through lf).
-// the point's residuals are [r0, r1) of the table; prior, delta and the linearized sums Hdd_accLF, bd_accLF, Hcd_accLF[4] are inputs
-EDS_WIN_HD PointOut point_sums(const int32_t* active, const float* efJ, int r0, int r1, float priorF, float deltaF, const float* lf,
-                               bool shift_prior_to_zero) {
+// Mode 0 of the top accumulator skips residuals with isLinearized while the Schur complement's ngoodres counts every active one.  The
+// flags live beside the table (lin[r], NULL: none is set; include/eds_hip_winsolve.h sets them); PointOut::nres is ngoodres.
+// One residual's addends to bd_acc, Hdd_acc and Hcd_acc (AccumulatedTopHessian.cpp:102-137); res: the eight words of resApprox
+EDS_WIN_HD void top_point_term(const float* J, const float* res, float& bd, float& Hdd, float* Hcd) {
+    float jr0 = 0, jr1 = 0;
+    for (int i = 0; i < PATTERN; ++i) {
+        jr0 += res[i] * J[J_JIDX + i];
+        jr1 += res[i] * J[J_JIDX + 8 + i];
+    }
+    const float d0 = J[J_JPDD], d1 = J[J_JPDD + 1];
+    const float q0 = J[J_JIDX2] * d0 + J[J_JIDX2 + 1] * d1, q1 = J[J_JIDX2 + 2] * d0 + J[J_JIDX2 + 3] * d1;
+    bd += jr0 * d0 + jr1 * d1;
+    Hdd += q0 * d0 + q1 * d1;
+    for (int k = 0; k < 4; ++k) Hcd[k] += J[J_JPDC + k] * q0 + J[J_JPDC + 4 + k] * q1;
+}
+// the residual filter of addPoint<mode>: 0 active and not linearized, 1 active and linearized, 2 active
+EDS_WIN_HD bool top_filter(int mode, int is_active, int is_lin) { return is_active && (mode == 2 || (mode == 1) == (is_lin != 0)); }
+
+// the point's residuals are [r0, r1) of the table; prior, delta and the linearized sums Hdd_accLF, bd_accLF, Hcd_accLF[4] are inputs.
+// mode 0: the A sums over the residuals that are active and not linearized; mode 2: the A sums are zero (addPoint<2> zeroes them)
+EDS_WIN_HD PointOut point_sums_mode(const int32_t* active, const int32_t* lin, const float* efJ, int r0, int r1, float priorF, float deltaF,
+                                    const float* lf, bool shift_prior_to_zero, int mode, int* added) {
     PointOut o;
     float bd = 0, Hdd = 0, Hcd[4] = {0, 0, 0, 0};
-    int n = 0;
+    int n = 0, na = 0;
     for (int r = r0; r < r1; ++r) {
         if (!active[r]) continue;
-        const float* J = efJ + (size_t)r * J_WORDS;
-        float jr0 = 0, jr1 = 0;
-        for (int i = 0; i < PATTERN; ++i) {
-            jr0 += J[J_RESF + i] * J[J_JIDX + i];
-            jr1 += J[J_RESF + i] * J[J_JIDX + 8 + i];
-        }
-        const float d0 = J[J_JPDD], d1 = J[J_JPDD + 1];
-        const float q0 = J[J_JIDX2] * d0 + J[J_JIDX2 + 1] * d1, q1 = J[J_JIDX2 + 2] * d0 + J[J_JIDX2 + 3] * d1;
-        bd += jr0 * d0 + jr1 * d1;
-        Hdd += q0 * d0 + q1 * d1;
-        for (int k = 0; k < 4; ++k) Hcd[k] += J[J_JPDC + k] * q0 + J[J_JPDC + 4 + k] * q1;
         ++n;
+        if (mode != 0 || (lin && lin[r])) continue;
+        const float* J = efJ + (size_t)r * J_WORDS;
+        top_point_term(J, J + J_RESF, bd, Hdd, Hcd);
+        ++na;
     }
+    *added = na;
     o.Hdd_accAF = Hdd; o.bd_accAF = bd; o.nres = n;
     for (int k = 0; k < 4; ++k) o.Hcd_accAF[k] = Hcd[k];
     if (n == 0) { o.HdiF = 0.0f; o.bdSumF = 0.0f; o.idepth_hessian = 0.0f; return o; }
@@ -251,6 +262,11 @@ EDS_WIN_HD PointOut point_sums(const int32_t* active, const float* efJ, int r0, 
     o.bdSumF = bd + lf[1];
     if (shift_prior_to_zero) o.bdSumF += priorF * deltaF;
     return o;
+}
+EDS_WIN_HD PointOut point_sums(const int32_t* active, const float* efJ, int r0, int r1, float priorF, float deltaF, const float* lf,
+                               bool shift_prior_to_zero) {
+    int added;
+    return point_sums_mode(active, nullptr, efJ, r0, r1, priorF, deltaF, lf, shift_prior_to_zero, 0, &added);
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -364,8 +380,9 @@ EDS_WIN_HD float jy(const float* J, int k) { return k < 4 ? J[J_JPDC + 4 + k] : 
 // sum_i a[i] b[i] from 0 in index order (JI_r, Jab_r, rr of AccumulatedTopHessian.cpp:102-112)
 EDS_WIN_HD float dot8(const float* a, const float* b) { float r = 0; for (int i = 0; i < PATTERN; ++i) r += a[i] * b[i]; return r; }
 
-// entry e of what one active residual adds to acc[h + F t] (AccumulatedTopHessian.cpp:115-129)
-EDS_WIN_HD float top_term(const float* J, int e) {
+// entry e of what one active residual adds to acc[h + F t] (AccumulatedTopHessian.cpp:115-129); res: the eight words of resApprox (mode 0:
+// the J's own resF)
+EDS_WIN_HD float top_term(const float* J, const float* res, int e) {
     if (e < 55) {                                               // Data: column c, rows r = c ... 9
         int c = 0, base = 0;
         while (e >= base + (10 - c)) { base += 10 - c; ++c; }
@@ -376,27 +393,36 @@ EDS_WIN_HD float top_term(const float* J, int e) {
     }
     if (e < 85) {                                               // TopRight: x TR0q + y TR1q
         const int k = (e - 55) / 3, q = (e - 55) % 3;
-        const float t0 = q == 0 ? J[J_JABJIDX] : q == 1 ? J[J_JABJIDX + 2] : dot8(J + J_RESF, J + J_JIDX);
-        const float t1 = q == 0 ? J[J_JABJIDX + 1] : q == 1 ? J[J_JABJIDX + 3] : dot8(J + J_RESF, J + J_JIDX + 8);
+        const float t0 = q == 0 ? J[J_JABJIDX] : q == 1 ? J[J_JABJIDX + 2] : dot8(res, J + J_JIDX);
+        const float t1 = q == 0 ? J[J_JABJIDX + 1] : q == 1 ? J[J_JABJIDX + 3] : dot8(res, J + J_JIDX + 8);
         return jx(J, k) * t0 + jy(J, k) * t1;
     }
     switch (e) {
         case 85: return J[J_JAB2];
         case 86: return J[J_JAB2 + 1];
-        case 87: return dot8(J + J_RESF, J + J_JABF);
+        case 87: return dot8(res, J + J_JABF);
         case 88: return J[J_JAB2 + 3];
-        case 89: return dot8(J + J_RESF, J + J_JABF + 8);
-        case 90: return dot8(J + J_RESF, J + J_RESF);
+        case 89: return dot8(res, J + J_JABF + 8);
+        case 90: return dot8(res, res);
         default: return 1.0f;
     }
 }
+EDS_WIN_HD float top_term(const float* J, int e) { return top_term(J, J + J_RESF, e); }
 
 // what a term reads; res_of[p F + t]: the residual of point p towards target t, or -1
-struct AccIn { int32_t F, has_lf; const int32_t* first; const int32_t* res_of; const int32_t* active; const float* efJ; const float* JpJdF; const PointOut* pout; const float* lf; };
+// The trailing members are zero in every brace list that ends at lf: mode 0, no linearized flag, every point.  lin[r]: isLinearized;
+// res_approx[r][8]: resApprox of modes 1 and 2; sel[p]: only the points with sel[p] != 0 contribute (marginalisation)
+struct AccIn { int32_t F, has_lf; const int32_t* first; const int32_t* res_of; const int32_t* active; const float* efJ; const float* JpJdF; const PointOut* pout; const float* lf;
+               int32_t mode; const int32_t* lin; const float* res_approx; const int32_t* sel; };
 
 EDS_WIN_HD int active_res(const AccIn& in, int p, int t) {
     const int r = in.res_of[p * in.F + t];
     return r >= 0 && in.active[r] ? r : -1;
+}
+// the residual of point p towards target t that addPoint<mode> of the top accumulator takes, or -1
+EDS_WIN_HD int top_res(const AccIn& in, int p, int t) {
+    const int r = in.res_of[p * in.F + t];
+    return r >= 0 && top_filter(in.mode, in.active[r], in.lin ? in.lin[r] : 0) ? r : -1;
 }
 // Hcd = Hcd_accAF + Hcd_accLF (AccumulatedSCHessian.cpp:55)
 EDS_WIN_HD float hcd(const AccIn& in, int p, int k) { return in.pout[p].Hcd_accAF[k] + (in.has_lf ? in.lf[6 * p + 2 + k] : 0.0f); }
@@ -411,9 +437,12 @@ EDS_WIN_HD int acc_host(int F, int j) {
 }
 EDS_WIN_HD double acc_value(const AccIn& in, int j, int p) {
     const int F = in.F;
+    if (in.sel && !in.sel[p]) return 0.0;
     if (j < acc_off_e(F)) {
-        const int r = active_res(in, p, (j / TOP_WORDS) / F);
-        return r < 0 ? 0.0 : (double)top_term(in.efJ + (size_t)r * J_WORDS, j % TOP_WORDS);
+        const int r = top_res(in, p, (j / TOP_WORDS) / F);
+        if (r < 0) return 0.0;
+        const float* J = in.efJ + (size_t)r * J_WORDS;
+        return (double)top_term(J, in.mode == 0 ? J + J_RESF : in.res_approx + (size_t)r * PATTERN, j % TOP_WORDS);
     }
     if (j < acc_off_d(F)) {
         const int q = j - acc_off_e(F), e = q % E_WORDS, r = active_res(in, p, (q / E_WORDS) / F);

@@ -1,0 +1,76 @@
+// What eds_window.hip and eds_winsolve.hip share: the definition of the opaque eds_win of include/eds_hip_window.h, the state
+// include/eds_hip_winsolve.h keeps beside it, and the launches of eds_window.hip that the solve queues into the window's stream.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "eds_window.hpp"
+
+namespace edswin {
+struct Sum { double energy; int32_t counts[4]; };
+}
+
+// include/eds_hip_winsolve.h's part of a window: eds_wsv_set_state allocates it, eds_win_destroy releases it (wsv_release)
+struct eds_wsv_state {
+    bool valid = false;                                    // eds_win_set_points and eds_win_set_residuals clear it
+    bool lf_on_device = false;                             // eds_win::lf holds the sums modes 1 / 2 wrote
+    bool have_backup = false, have_step = false, have_system = false;
+    std::vector<double> last_x;                            // x of the last solve
+    int F = 0;
+    int32_t* lin = nullptr;                                // [max_residuals] isLinearized
+    int32_t* sel = nullptr;                                // [max(max_residuals, max_points)] a call's selection
+    float *rtz = nullptr, *res_approx = nullptr;           // [max_residuals][8] res_toZeroF, resApprox
+    float *adF = nullptr, *adHTdeltaF = nullptr;           // adHostF then adTargetF [2][64][64]; [64][8]
+    float *cF = nullptr;                                   // cDeltaF[4], cPriorF[4]
+    float *xAd = nullptr, *step = nullptr, *backup = nullptr;   // [64][8] then cstep[4]; [max_points]; [max_points]
+    double *ad = nullptr;                                  // adHost then adTarget as doubles [2][64][64]
+    double *vec = nullptr;                                 // delta[68], prior[68], prior * delta_prior[68], delta_prior[68]
+    double *accL = nullptr, *work = nullptr;               // the accumulators of mode 1; the solve's matrices (edswsv::work_words)
+    double *stL = nullptr;                                 // mode 1's stitch H_L, b_L
+    int32_t* flag = nullptr;                               // [4] x not finite, residuals modes 1 / 2 added, residuals that refuse a marginalisation
+    double* e_out = nullptr;                               // [2] an energy
+};
+
+struct eds_win {
+    int dev = 0, H = 0, W = 0, max_frames = 0, max_points = 0, max_residuals = 0;
+    edswin::Params prm;
+    edswin::Calib cal;
+    bool calib_set = false, linearized = false;
+    uint32_t frames_set = 0;                              // bit f: frame f holds an image
+    int n = 0, m = 0, max_host = -1, max_target = -1;
+    std::vector<int32_t> host_of, h_point, h_target;     // host copies for the checks and the (point, target) -> residual map
+    int32_t *res_of = nullptr, *first = nullptr;          // [max_points * 8], [9]
+    double* acc = nullptr;                                // [acc_size(8)]
+    double *ad = nullptr, *stitched = nullptr;            // adHost then adTarget [2][64][64]; H_A, b_A, H_sc, b_sc [stitch_words(8)]
+    hipStream_t st = nullptr;
+    edswin::Px* frames = nullptr;
+    float* in_img = nullptr;
+    edswin::Point* pts = nullptr;
+    float *ids = nullptr, *idz = nullptr;                 // idepth_scaled, idepth_zero_scaled per point
+    int32_t *res_first = nullptr, *res_point = nullptr, *res_target = nullptr, *state = nullptr, *new_state = nullptr, *active = nullptr;
+    float *energy = nullptr, *new_energy = nullptr, *new_energy_wo = nullptr, *ret = nullptr, *cp = nullptr, *proj = nullptr, *J = nullptr,
+          *efJ = nullptr, *JpJdF = nullptr, *th = nullptr, *prior = nullptr, *delta = nullptr, *lf = nullptr;
+    edswin::Precalc* pcs = nullptr;
+    edswin::Sum* sum = nullptr;
+    edswin::PointOut* pout = nullptr;
+    int32_t* nres = nullptr;
+    eds_wsv_state* wsv = nullptr;
+};
+
+namespace edswin_internal {
+// isLinearized of every residual, or NULL while no eds_wsv state holds
+inline const int32_t* lin_flags(const eds_win* h) { return h->wsv && h->wsv->valid ? h->wsv->lin : nullptr; }
+inline bool lf_on_device(const eds_win* h) { return h->wsv && h->wsv->valid && h->wsv->lf_on_device; }
+// eds_window.hip: the (point, target) -> residual map and the hosts' runs, uploaded; EDS_ERR_INVALID as eds_win_accumulate refuses
+int upload_maps(eds_win* h, int F);
+// eds_window.hip, queued into h->st without a wait: the per-point prologue from the device's priorF / deltaF / lf (mode 0 or 2, sel may be
+// NULL), every accumulator word into `acc`, and entries [e0, e1) of both stitches from `acc` and the device adjoints into `out`
+void queue_points(eds_win* h, int mode, const int32_t* sel, int shift);
+void queue_acc(eds_win* h, int F, int mode, const int32_t* sel, int has_lf, int words, double* acc);
+void queue_stitch(eds_win* h, int F, const double* acc, const double* ad, int entries, double* out);
+// eds_winsolve.hip
+void wsv_release(eds_win* h);
+void wsv_invalidate(eds_win* h);
+}  // namespace edswin_internal
