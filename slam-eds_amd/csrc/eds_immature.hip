@@ -20,6 +20,7 @@
 #include "../../include/eds_hip_immature.h"
 #include "eds_capi_internal.hpp"
 #include "eds_immature.hpp"
+#include "eds_immature_internal.hpp"
 
 using edscapi::fail;
 using edsimm::Frame;
@@ -32,23 +33,6 @@ using edsimm::Pre;
 static_assert(sizeof(Point) == 128, "one point is 32 words");
 static_assert(sizeof(Params) == sizeof(eds_imm_params), "edsimm::Params is eds_imm_params member for member");
 static_assert(sizeof(Pre) == 64, "one host's precalc is 16 words");
-
-struct eds_imm {
-    int dev = 0, H = 0, W = 0, max_hosts = 0, max_points = 0, max_targets = 0;
-    Params prm;
-    hipStream_t st = nullptr;
-    float *host_c = nullptr, *target_c = nullptr;      // [frames][H][W]
-    Grad *host_g = nullptr, *target_g = nullptr;
-    Point* points = nullptr;                           // [max_hosts][max_points]
-    Pre* pre = nullptr;                                // [max_hosts]
-    int32_t* summary = nullptr;                        // [max_hosts][NUM_STATUS]
-    double* in_distance = nullptr;                     // eds_imm_create_points' inputs, [max_points] each
-    int32_t* in_uv = nullptr;
-    float *in_type = nullptr, *in_idepth = nullptr;
-    uint8_t* in_alive = nullptr;
-    std::vector<int> n;
-    std::vector<uint8_t> host_set, target_set;
-};
 
 namespace {
 
@@ -196,6 +180,7 @@ int set_images(eds_imm* h, bool target, int first, int count, const float* image
     EDS_HIP_TRY(hipStreamSynchronize(h->st));
     std::vector<uint8_t>& set = target ? h->target_set : h->host_set;
     for (int b = 0; b < count; ++b) set[first + b] = 1;
+    if (!target) edsimm_internal::act_invalidate(h);
     return EDS_OK;
 }
 
@@ -272,6 +257,7 @@ void eds_imm_destroy(eds_imm* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
+    edsimm_internal::act_release(h);
     void* all[] = {h->host_c, h->host_g, h->target_c, h->target_g, h->points, h->pre, h->summary, h->in_distance, h->in_uv, h->in_type,
                    h->in_idepth, h->in_alive};
     for (void* p : all) if (p) (void)hipFree(p);
@@ -313,6 +299,7 @@ int eds_imm_create_points(eds_imm* h, int host, int n, const int32_t* uv, const 
     if (n > 0 && (!uv || !type)) return fail(EDS_ERR_INVALID, "uv and type are required");
     if ((idepth == nullptr) != (distance == nullptr)) return fail(EDS_ERR_INVALID, "idepth and distance come together");
     if (!h->host_set[host]) return fail(EDS_ERR_STATE, "host " + std::to_string(host) + " has no image");
+    edsimm_internal::act_invalidate(h);
     if (n == 0) { h->n[host] = 0; return EDS_OK; }
     EDS_HIP_TRY(hipSetDevice(h->dev));
     EDS_HIP_TRY(hipMemcpyAsync(h->in_uv, uv, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
