@@ -24,7 +24,7 @@
  *  2. makeImages, all levels (HessianBlocks.cpp:139-202).  Colour of level l is 0.25f * (((a + b) + c) + d) over (2x, 2y), (2x + 1, 2y),
  *     (2x, 2y + 1), (2x + 1, 2y + 1); dx, dy at every level follow the FLAT-index rule eds_hip_immature.h documents for level 0 (at
  *     column 0 and w - 1 the horizontal neighbour is the pixel of the adjacent row); a non-finite difference is 0; rows 0 and h - 1
- *     have gradient 0.  absSquaredGrad is not formed.  Level 0 equals eds_imm_get_image of the same frame bit for bit.
+ *     have gradient 0.  absSquaredGrad is not formed here (eds_hip_select.h forms it).  Level 0 equals eds_imm_get_image of the same frame bit for bit.
  *  3. setCoarseTrackingRef / makeCoarseDepthL0 (:126-283).  The caller passes, per active residual, centerProjectedTo (n x 3 floats)
  *     and HdiF (n floats).  u = (int)(x + 0.5f), truncating towards zero; weight = sqrtf((float)(1e-3 / (HdiF + 1e-12))) with the sum and
  *     the quotient in fp64.  A contribution whose x + 0.5f or y + 0.5f is not finite, <= -1 or >= W (H) is DROPPED and counted (the

@@ -20,7 +20,8 @@
  * central differences, a non-finite difference replaced by 0.  The reference's loop runs over the FLAT index W .. W (H - 1) - 1:
  *   dx[i] = 0.5f * (c[i + 1] - c[i - 1]);   dy[i] = 0.5f * (c[i + W] - c[i - W]);
  * so at column 0 and W - 1 the horizontal neighbour is the pixel of the adjacent row, and that is restated here.  Rows 0 and H - 1 are
- * left uninitialised by the reference: here their gradient is 0.  Pyramid levels above 0 and absSquaredGrad are not formed.
+ * left uninitialised by the reference: here their gradient is 0.  Pyramid levels above 0 and absSquaredGrad are not formed
+ * here: only the pixel selector reads absSquaredGrad, and include/eds_hip_select.h forms it.
  *
  * Defined behaviour where the reference reads out of bounds or is undefined.  A sample at (x, y) takes the cell ix = (int)x, iy = (int)y
  * (truncation towards zero, so -1 < x < 0 is cell 0 with a negative fraction, as in the reference) and the 2 x 2 footprint
@@ -116,6 +117,18 @@ int eds_imm_set_target_images(eds_imm* imm, int first, int count, const float* i
 int eds_imm_create_points(eds_imm* imm, int host, int n, const int32_t* uv, const float* type, const float* idepth, const double* distance,
                           uint8_t* alive_out);
 int eds_imm_num_points(const eds_imm* imm, int host, int* n);
+
+/* The first constructor for the pixels an eds_sel (include/eds_hip_select.h) selected, read from the device: the non-zero pixels of its
+ * map inside the inclusive rectangle x_min .. x_max, y_min .. y_max, in row-major order, my_type the map value (1, 2 or 4), replacing the
+ * points `host` held.  The result equals, bit for bit, eds_imm_create_points called with eds_sel_get_selection's list filtered to the
+ * same rectangle.  The rectangle is an argument because the loop that walks the map, FullSystem::makeNewTraces, is not in the reference
+ * tree; DSO's own loop runs over patternPadding + 1 <= x < W - patternPadding - 2 with patternPadding = 2, which is x_min = y_min = 3,
+ * x_max = W - 5, y_max = H - 5.  n_out (may be NULL): the number of points created; alive_out (may be NULL) takes that many bytes, at
+ * the most the n of eds_sel_get_selection.  EDS_ERR_INVALID: imm and sel differ in H, W or device, a rectangle that is not inside the
+ * image, more points than max_points_per_host.  EDS_ERR_STATE: no selection yet (eds_sel_make_maps), no host image. */
+struct eds_sel;
+int eds_imm_create_points_selected(eds_imm* imm, int host, const struct eds_sel* sel, int x_min, int y_min, int x_max, int y_max,
+                                   uint8_t* alive_out, int* n_out);
 
 /* traceOn for every live point of hosts first_host .. first_host + count - 1, host first_host + b against target target_index[b] with
  * hostToFrame_KRKi = KRKi[b] (row-major 3 x 3), hostToFrame_Kt = Kt[b], hostToFrame_affine = aff[b].  The same index count times is

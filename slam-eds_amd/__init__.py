@@ -11,6 +11,7 @@ alias module at the repo root).  Sub-modules:
 * ``depth``   — Python mirror of ``eds::mapping::DepthPoints`` whose seeds live on the device (include/eds_hip_depth.h)
 * ``immature`` — DSO's immature points traced along epipolar lines on the device (include/eds_hip_immature.h)
 * ``coarse``  — DSO's coarse image tracker for the pose of every new image frame, on the device (include/eds_hip_coarse.h)
+* ``select``  — DSO's pixel selector: which pixels of a keyframe become immature points, on the device (include/eds_hip_select.h)
 * ``window``  — the window optimiser's linearize, applyRes and per-point Hessian sums on the device (include/eds_hip_window.h)
 """
 __version__ = "0.1.0"

@@ -77,7 +77,7 @@ KFS_DEPTH_NONE, KFS_DEPTH_HOST, KFS_DEPTH_DEVICE, KFS_DEPTH_SLOTS = 0, 1, 2, 3  
 # every symbol include/eds_hip_immature.h declares: DSO's immature points traced along epipolar lines (bound in immature.py)
 IMM_EXPORTS = ("eds_imm_abi_version", "eds_imm_params_default", "eds_imm_create", "eds_imm_destroy", "eds_imm_set_params", "eds_imm_get_params",
                "eds_imm_set_host_images", "eds_imm_set_target_images", "eds_imm_create_points", "eds_imm_num_points", "eds_imm_trace",
-               "eds_imm_get", "eds_imm_get_points", "eds_imm_get_image")
+               "eds_imm_get", "eds_imm_get_points", "eds_imm_get_image", "eds_imm_create_points_selected")
 
 # every symbol include/eds_hip_coarse.h declares: DSO's coarse image tracker (bound in coarse.py)
 CT_EXPORTS = ("eds_ct_abi_version", "eds_ct_params_default", "eds_ct_create", "eds_ct_destroy", "eds_ct_set_params", "eds_ct_get_params",
@@ -95,6 +95,11 @@ WSV_EXPORTS = ("eds_wsv_abi_version", "eds_wsv_set_state", "eds_wsv_fix_lineariz
 # every symbol include/eds_hip_activate.h declares: the distance map, the candidate rule and the idepth fit over an eds_imm (bound in activate.py)
 ACT_EXPORTS = ("eds_act_abi_version", "eds_act_params_default", "eds_act_set_params", "eds_act_get_params", "eds_act_set_calib",
                "eds_act_make_distance_map", "eds_act_get_distance_map", "eds_act_select", "eds_act_optimize", "eds_act_get", "eds_act_get_activated")
+
+# every symbol include/eds_hip_select.h declares: DSO's pixel selector over its own eds_sel (bound in select.py)
+SEL_EXPORTS = ("eds_sel_abi_version", "eds_sel_params_default", "eds_sel_create", "eds_sel_destroy", "eds_sel_set_params", "eds_sel_get_params",
+               "eds_sel_set_random_pattern", "eds_sel_fill_reference_pattern", "eds_sel_set_potential", "eds_sel_get_potential", "eds_sel_set_image",
+               "eds_sel_make_maps", "eds_sel_get_map", "eds_sel_get_selection", "eds_sel_get_level", "eds_sel_get_thresholds", "eds_sel_get_scan_info")
 
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
@@ -212,6 +217,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_window.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winsolve.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_activate.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_select.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]

@@ -21,6 +21,7 @@
 #include "eds_capi_internal.hpp"
 #include "eds_immature.hpp"
 #include "eds_immature_internal.hpp"
+#include "eds_pixsel_internal.hpp"
 
 using edscapi::fail;
 using edsimm::Frame;
@@ -59,6 +60,36 @@ __global__ void __launch_bounds__(256) k_imm_construct(Point* __restrict__ pts, 
                       has_depth ? distance[i] : 0.0);
     pts[i] = p;
     alive[i] = (uint8_t)p.alive;
+}
+
+// eds_imm_create_points_selected: the entries of a selection list (row-major order) inside the inclusive rectangle, in their order, as
+// eds_imm_create_points' staged inputs.  One workgroup walks the list 256 at a time, so the order is the list's; an entry past `cap`
+// is counted and not stored.
+__global__ void __launch_bounds__(256) k_imm_filter_rect(const int32_t* __restrict__ uv, const float* __restrict__ type, int n, int x_min, int y_min,
+                                                         int x_max, int y_max, int cap, int32_t* __restrict__ out_uv, float* __restrict__ out_type,
+                                                         int32_t* __restrict__ n_out) {
+    __shared__ int wcnt[256 / WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 256) {
+        const int i = i0 + (int)threadIdx.x;
+        int u = 0, v = 0;
+        bool in = false;
+        if (i < n) {
+            u = uv[2 * i]; v = uv[2 * i + 1];
+            in = u >= x_min && u <= x_max && v >= y_min && v <= y_max;
+        }
+        const unsigned long long m = __ballot(in);
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int k = 0; k < 256 / WAVE; ++k) { if (k < wave) before += wcnt[k]; total += wcnt[k]; }
+        const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
+        if (in && pos < cap) { out_uv[2 * pos] = u; out_uv[2 * pos + 1] = v; out_type[pos] = type[i]; }
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *n_out = base;
 }
 
 __global__ void __launch_bounds__(TRACE_THREADS) k_imm_trace(Point* __restrict__ points, int max_points, int first_host,
@@ -194,6 +225,21 @@ int read_points(eds_imm* h, int host, std::vector<Point>& out) {
     return EDS_OK;
 }
 
+// the constructor kernel over the n staged inputs (in_uv, in_type, and in_idepth, in_distance for the second constructor)
+int construct_staged(eds_imm* h, int host, int n, bool has_depth, uint8_t* alive_out) {
+    h->n[host] = 0;                                     // what the host held is gone once the kernel is queued
+    hipLaunchKernelGGL(k_imm_construct, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->points + (size_t)host * h->max_points,
+                       h->host_c + (size_t)h->W * h->H * host, h->W, h->H, h->prm, n, h->in_uv, h->in_type, h->in_idepth, h->in_distance,
+                       has_depth ? 1 : 0, h->in_alive);
+    EDS_HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> alive((size_t)n);
+    EDS_HIP_TRY(hipMemcpyAsync(alive.data(), h->in_alive, (size_t)n, hipMemcpyDeviceToHost, h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (alive_out) std::memcpy(alive_out, alive.data(), (size_t)n);
+    h->n[host] = n;
+    return EDS_OK;
+}
+
 bool all_finite(const float* x, int n) {
     for (int i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false;
     return true;
@@ -308,17 +354,34 @@ int eds_imm_create_points(eds_imm* h, int host, int n, const int32_t* uv, const 
         EDS_HIP_TRY(hipMemcpyAsync(h->in_idepth, idepth, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->st));
         EDS_HIP_TRY(hipMemcpyAsync(h->in_distance, distance, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->st));
     }
-    h->n[host] = 0;                                     // what the host held is gone once the kernel is queued
-    hipLaunchKernelGGL(k_imm_construct, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->points + (size_t)host * h->max_points,
-                       h->host_c + (size_t)h->W * h->H * host, h->W, h->H, h->prm, n, h->in_uv, h->in_type, h->in_idepth, h->in_distance,
-                       idepth ? 1 : 0, h->in_alive);
-    EDS_HIP_TRY(hipGetLastError());
-    std::vector<uint8_t> alive((size_t)n);
-    EDS_HIP_TRY(hipMemcpyAsync(alive.data(), h->in_alive, (size_t)n, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    if (alive_out) std::memcpy(alive_out, alive.data(), (size_t)n);
-    h->n[host] = n;
-    return EDS_OK;
+    return construct_staged(h, host, n, idepth != nullptr, alive_out);
+}
+
+int eds_imm_create_points_selected(eds_imm* h, int host, const eds_sel* sel, int x_min, int y_min, int x_max, int y_max, uint8_t* alive_out,
+                                   int* n_out) {
+    if (int rc = check_host(h, host)) return rc;
+    if (!sel) return fail(EDS_ERR_INVALID, "null eds_sel handle");
+    if (sel->H != h->H || sel->W != h->W || sel->dev != h->dev) return fail(EDS_ERR_INVALID, "the selector and the points differ in H, W or device");
+    if (x_min < 0 || y_min < 0 || x_max >= h->W || y_max >= h->H || x_min > x_max || y_min > y_max)
+        return fail(EDS_ERR_INVALID, "the rectangle lies inside the image, min <= max");
+    if (!sel->sel_valid) return fail(EDS_ERR_STATE, "no selection: eds_sel_make_maps first");
+    if (!h->host_set[host]) return fail(EDS_ERR_STATE, "host " + std::to_string(host) + " has no image");
+    EDS_HIP_TRY(hipSetDevice(h->dev));
+    int32_t n = 0;
+    if (sel->n_sel > 0) {
+        // the staging buffers hold nothing a caller can see; the selector's calls have returned, so its list is complete
+        hipLaunchKernelGGL(k_imm_filter_rect, dim3(1), dim3(256), 0, h->st, sel->uv, sel->type, sel->n_sel, x_min, y_min, x_max, y_max, h->max_points,
+                           h->in_uv, h->in_type, h->summary);
+        EDS_HIP_TRY(hipGetLastError());
+        EDS_HIP_TRY(hipMemcpyAsync(&n, h->summary, sizeof(n), hipMemcpyDeviceToHost, h->st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    }
+    if (n > h->max_points)
+        return fail(EDS_ERR_INVALID, std::to_string(n) + " selected points, the handle holds 0 .. " + std::to_string(h->max_points) + " per host");
+    edsimm_internal::act_invalidate(h);
+    if (n_out) *n_out = n;
+    if (n == 0) { h->n[host] = 0; return EDS_OK; }
+    return construct_staged(h, host, n, false, alive_out);
 }
 
 int eds_imm_num_points(const eds_imm* h, int host, int* n) {

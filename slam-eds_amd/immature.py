@@ -50,6 +50,7 @@ def _lib():
         L.eds_imm_set_host_images.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int]
         L.eds_imm_set_target_images.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int]
         L.eds_imm_create_points.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        L.eds_imm_create_points_selected.argtypes = [vp, C.c_int, vp] + [C.c_int] * 4 + [vp, C.POINTER(C.c_int)]
         L.eds_imm_num_points.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
         L.eds_imm_trace.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
         L.eds_imm_get.argtypes = [vp, C.c_int] + [vp] * 6
@@ -164,6 +165,16 @@ class ImmaturePoints:
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         capi._check(_lib().eds_imm_create_points(self._h, int(host), n, vp(uv), vp(typ), vp(idp), vp(dist), vp(alive)))
         return alive.astype(bool)
+
+    def create_points_selected(self, host, selector, rect=None):
+        """The first constructor for the pixels ``selector`` (a ``select.Selector`` after ``make_maps``) chose inside the inclusive
+        rectangle ``(x_min, y_min, x_max, y_max)``, read from the device; ``None`` is DSO's own bounds, 3 .. W - 5 and 3 .. H - 5.
+        Returns the alive mask, one entry per point created."""
+        x0, y0, x1, y1 = (3, 3, self.W - 5, self.H - 5) if rect is None else (int(v) for v in rect)
+        alive = np.zeros(max(1, min(selector.num_selected, self.max_points)), dtype=np.uint8)
+        n = C.c_int()
+        capi._check(_lib().eds_imm_create_points_selected(self._h, int(host), selector._h, x0, y0, x1, y1, alive.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return alive[:n.value].astype(bool)
 
     def num_points(self, host):
         n = C.c_int()

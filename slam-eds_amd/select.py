@@ -1,0 +1,204 @@
+"""ctypes binding of include/eds_hip_select.h: DSO's pixel selector — ``PixelSelector::makeMaps`` with ``makeHists`` and ``select`` over
+levels 0 .. 2 of ``makeImages`` including ``absSquaredGrad`` — on the device.
+
+Plumbing only: every number comes from the HIP kernels behind the C ABI (csrc/eds_pixsel.hip); there is no CPU fallback.  ``Selector``
+owns one ``eds_sel``.  The random table is an input: ``reference_pattern`` is what the reference's constructor draws.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+THS, THS_SMOOTHED = 0, 1
+MAX_POTENTIAL = 1 << 30
+
+
+class Params(C.Structure):
+    """``eds_sel_params`` — the setting_* values the selector reads (reference src/utils/settings.cpp:145-148)."""
+    _fields_ = [("min_grad_hist_cut", C.c_float), ("min_grad_hist_add", C.c_float), ("grad_downweight_per_level", C.c_float),
+                ("select_direction_distribution", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Pass(C.Structure):
+    """``eds_sel_pass`` — one select pass of ``make_maps``."""
+    _fields_ = [("potential", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32), ("n4", C.c_int32)]
+
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    L = capi.lib()
+    if not _bound:
+        missing = [s for s in capi.SEL_EXPORTS if not hasattr(L, s)]
+        if missing:
+            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
+        vp, ip = C.c_void_p, C.POINTER(C.c_int)
+        L.eds_sel_params_default.argtypes = [C.POINTER(Params)]
+        L.eds_sel_params_default.restype = None
+        L.eds_sel_create.argtypes = [C.c_int] * 3 + [C.POINTER(vp)]
+        L.eds_sel_destroy.argtypes = [vp]
+        L.eds_sel_destroy.restype = None
+        L.eds_sel_set_params.argtypes = [vp, C.POINTER(Params)]
+        L.eds_sel_get_params.argtypes = [vp, C.POINTER(Params)]
+        L.eds_sel_set_random_pattern.argtypes = [vp, vp, C.c_size_t]
+        L.eds_sel_fill_reference_pattern.argtypes = [vp, C.c_size_t]
+        L.eds_sel_set_potential.argtypes = [vp, C.c_int]
+        L.eds_sel_get_potential.argtypes = [vp, ip]
+        L.eds_sel_set_image.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
+        L.eds_sel_make_maps.argtypes = [vp, C.c_float, C.c_int, C.c_float, ip, C.POINTER(Pass), C.c_int, ip, vp]
+        L.eds_sel_get_map.argtypes = [vp, vp]
+        L.eds_sel_get_selection.argtypes = [vp, ip, vp, vp]
+        L.eds_sel_get_level.argtypes = [vp, C.c_int, vp]
+        L.eds_sel_get_thresholds.argtypes = [vp, C.c_int, vp]
+        L.eds_sel_get_scan_info.argtypes = [vp, ip, ip]
+        _bound = True
+    return L
+
+
+def default_params(**over) -> Params:
+    p = Params()
+    _lib().eds_sel_params_default(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def reference_pattern(n):
+    """The ``randomPattern`` of the reference's constructor: srand(3141592), then n times rand() & 0xFF.  Reseeds the C library's generator."""
+    out = np.zeros(int(n), np.uint8)
+    capi._check(_lib().eds_sel_fill_reference_pattern(out.ctypes.data_as(C.c_void_p), out.size))
+    return out
+
+
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class Selector:
+    """The pixel selector of one image size, in device memory.  ``potential`` is the reference's currentPotential."""
+
+    def __init__(self, H, W, device=0, table=None, **params):
+        self._h = C.c_void_p()
+        self.H, self.W, self.device = int(H), int(W), int(device)
+        capi._check(_lib().eds_sel_create(self.device, self.H, self.W, C.byref(self._h)))
+        self.passes = []
+        self.pass_maps = None
+        if params:
+            self.set_params(**params)
+        if table is not None:
+            self.set_random_pattern(table)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib().eds_sel_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, **over):
+        p = self.params()
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        capi._check(_lib().eds_sel_set_params(self._h, C.byref(p)))
+
+    def params(self) -> Params:
+        p = Params()
+        capi._check(_lib().eds_sel_get_params(self._h, C.byref(p)))
+        return p
+
+    def set_random_pattern(self, table):
+        t = np.ascontiguousarray(table, dtype=np.uint8).reshape(-1)
+        capi._check(_lib().eds_sel_set_random_pattern(self._h, _vp(t), t.size))
+
+    @property
+    def potential(self):
+        v = C.c_int()
+        capi._check(_lib().eds_sel_get_potential(self._h, C.byref(v)))
+        return v.value
+
+    @potential.setter
+    def potential(self, v):
+        capi._check(_lib().eds_sel_set_potential(self._h, int(v)))
+
+    def set_image(self, image, B=None):
+        """fp32 intensities 0 .. 255: a numpy array H x W (its row stride is kept) or device memory (``capi.DeviceArray`` and the like);
+        B: None, or the 256 floats of ``CalibHessian::B``"""
+        b = None if B is None else np.ascontiguousarray(B, dtype=np.float32).reshape(256)
+        raw = isinstance(image, tuple) and len(image) == 4 and isinstance(image[0], int)
+        if not raw and not hasattr(image, "__cuda_array_interface__"):
+            a = np.asarray(image, dtype=np.float32)
+            if a.shape != (self.H, self.W):
+                raise ValueError(f"the image must be {self.H} x {self.W}, not {a.shape}")
+            if a.strides[1] != 4 or a.strides[0] % 4 or a.strides[0] < 4 * self.W:
+                a = np.ascontiguousarray(a)
+            capi._check(_lib().eds_sel_set_image(self._h, _vp(a), a.strides[0] // 4, 0, _vp(b)))
+            return
+        ptr, shape, est, dt = capi.device_array_info(image)
+        if dt != np.float32 or tuple(shape) != (self.H, self.W) or est[1] != 1:
+            raise ValueError(f"a device image must be float32 {self.H} x {self.W} with contiguous rows")
+        capi._check(_lib().eds_sel_set_image(self._h, C.c_void_p(ptr), int(est[0]), 1, _vp(b)))
+
+    def make_maps(self, density, recursions_left=1, th_factor=1.0, keep_pass_maps=False):
+        """``makeMaps``; returns numHaveSub.  ``passes`` then holds (potential, n2, n3, n4) of every select pass, ``pass_maps`` the map
+        after each of them when asked for."""
+        cap = int(recursions_left) + 1
+        ps = (Pass * max(1, cap))()
+        n, npass = C.c_int(), C.c_int()
+        maps = np.zeros((max(1, cap), self.H, self.W), np.uint8) if keep_pass_maps else None
+        capi._check(_lib().eds_sel_make_maps(self._h, float(density), int(recursions_left), float(th_factor), C.byref(n), ps, max(1, cap),
+                                             C.byref(npass), _vp(maps)))
+        self.passes = [(p.potential, p.n2, p.n3, p.n4) for p in ps[:npass.value]]
+        self.pass_maps = None if maps is None else maps[:npass.value]
+        return n.value
+
+    def map(self):
+        out = np.zeros((self.H, self.W), np.uint8)
+        capi._check(_lib().eds_sel_get_map(self._h, _vp(out)))
+        return out
+
+    @property
+    def num_selected(self):
+        n = C.c_int()
+        capi._check(_lib().eds_sel_get_selection(self._h, C.byref(n), None, None))
+        return n.value
+
+    def selection(self):
+        """uv (n x 2 int32) and type (n floats) of the map's non-zero pixels in row-major order"""
+        n = self.num_selected
+        uv, typ = np.zeros((n, 2), np.int32), np.zeros(n, np.float32)
+        m = C.c_int()
+        capi._check(_lib().eds_sel_get_selection(self._h, C.byref(m), _vp(uv), _vp(typ)))
+        return uv, typ
+
+    def level(self, lvl):
+        """(H >> lvl) x (W >> lvl) x (colour, dx, dy, absSquaredGrad)"""
+        out = np.zeros((self.H >> lvl, self.W >> lvl, 4), np.float32)
+        capi._check(_lib().eds_sel_get_level(self._h, int(lvl), _vp(out)))
+        return out
+
+    def thresholds(self, which=THS_SMOOTHED):
+        out = np.zeros((self.H // 32, self.W // 32), np.float32)
+        capi._check(_lib().eds_sel_get_thresholds(self._h, int(which), _vp(out)))
+        return out
+
+    def scan_info(self):
+        """(ambiguous cells, n2 of the certain cells alone) of the last select pass"""
+        a, c = C.c_int(), C.c_int()
+        capi._check(_lib().eds_sel_get_scan_info(self._h, C.byref(a), C.byref(c)))
+        return a.value, c.value
