@@ -92,6 +92,10 @@ WIN_EXPORTS = ("eds_win_abi_version", "eds_win_params_default", "eds_win_create"
 WSV_EXPORTS = ("eds_wsv_abi_version", "eds_wsv_set_state", "eds_wsv_fix_linearization", "eds_wsv_solve", "eds_wsv_backup_idepths",
                "eds_wsv_step_idepths", "eds_wsv_get_steps", "eds_wsv_l_energy", "eds_wsv_m_energy", "eds_wsv_marginalize_points", "eds_wsv_get")
 
+# every symbol include/eds_hip_winedit.h declares: the window's tables edited on the device (bound in winedit.py)
+WED_EXPORTS = ("eds_wed_abi_version", "eds_wed_remove_residuals", "eds_wed_remove_points", "eds_wed_marginalize_frame", "eds_wed_insert_activated", "eds_wed_set_state",
+               "eds_wed_counts", "eds_wed_get")
+
 # every symbol include/eds_hip_activate.h declares: the distance map, the candidate rule and the idepth fit over an eds_imm (bound in activate.py)
 ACT_EXPORTS = ("eds_act_abi_version", "eds_act_params_default", "eds_act_set_params", "eds_act_get_params", "eds_act_set_calib",
                "eds_act_make_distance_map", "eds_act_get_distance_map", "eds_act_select", "eds_act_optimize", "eds_act_get", "eds_act_get_activated")
@@ -216,6 +220,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_coarse.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_window.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winsolve.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winedit.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_activate.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_select.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

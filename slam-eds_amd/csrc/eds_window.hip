@@ -386,6 +386,7 @@ void eds_win_destroy(eds_win* h) {
     (void)hipSetDevice(h->dev);
     if (h->st) (void)hipStreamSynchronize(h->st);
     edswin_internal::wsv_release(h);
+    edswin_internal::wed_release(h);
     if (h->st) (void)hipStreamDestroy(h->st);
     void* all[] = {h->frames, h->in_img, h->pts, h->ids, h->idz, h->res_first, h->res_point, h->res_target, h->state, h->new_state, h->active, h->energy,
                    h->new_energy, h->new_energy_wo, h->ret, h->cp, h->proj, h->J, h->efJ, h->JpJdF, h->th, h->prior, h->delta, h->lf, h->pcs,

@@ -1,5 +1,6 @@
-// What eds_window.hip and eds_winsolve.hip share: the definition of the opaque eds_win of include/eds_hip_window.h, the state
-// include/eds_hip_winsolve.h keeps beside it, and the launches of eds_window.hip that the solve queues into the window's stream.
+// What eds_window.hip, eds_winsolve.hip and eds_winedit.hip share: the definition of the opaque eds_win of include/eds_hip_window.h, the
+// state include/eds_hip_winsolve.h keeps beside it, the second set of buffers include/eds_hip_winedit.h moves the rows into, and the
+// launches of eds_window.hip that the solve queues into the window's stream.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,8 @@ struct Sum { double energy; int32_t counts[4]; };
 // include/eds_hip_winsolve.h's part of a window: eds_wsv_set_state allocates it, eds_win_destroy releases it (wsv_release)
 struct eds_wsv_state {
     bool valid = false;                                    // eds_win_set_points and eds_win_set_residuals clear it
+    bool rows_live = false;                                // the per-point and per-residual rows belong to the tables as they stand: set with the
+                                                           // state, cleared with `valid` by those two calls, KEPT when a frame leaves (eds_hip_winedit.h)
     bool lf_on_device = false;                             // eds_win::lf holds the sums modes 1 / 2 wrote
     bool have_backup = false, have_step = false, have_system = false;
     std::vector<double> last_x;                            // x of the last solve
@@ -31,6 +34,29 @@ struct eds_wsv_state {
     double *stL = nullptr;                                 // mode 1's stitch H_L, b_L
     int32_t* flag = nullptr;                               // [4] x not finite, residuals modes 1 / 2 added, residuals that refuse a marginalisation
     double* e_out = nullptr;                               // [2] an energy
+};
+
+// include/eds_hip_winedit.h's part of a window: the first eds_wed_* call allocates it, eds_win_destroy releases it (wed_release).  An edit
+// gathers every row into the second set and then exchanges the pointers with the window's (and the eds_wsv state's) own.
+struct eds_wed_state {
+    edswin::Point* pts = nullptr;
+    float *ids = nullptr, *idz = nullptr, *prior = nullptr, *delta = nullptr, *lf = nullptr;
+    edswin::PointOut* pout = nullptr;
+    int32_t *res_first = nullptr, *res_point = nullptr, *res_target = nullptr, *state = nullptr, *new_state = nullptr, *active = nullptr;
+    float *energy = nullptr, *new_energy = nullptr, *new_energy_wo = nullptr, *ret = nullptr, *cp = nullptr, *proj = nullptr, *J = nullptr,
+          *efJ = nullptr, *JpJdF = nullptr;
+    bool have_wsv = false;                                 // the second set of the eds_wsv state's rows, allocated once such a state exists
+    int32_t* lin = nullptr;
+    float *rtz = nullptr, *res_approx = nullptr, *step = nullptr, *backup = nullptr;
+    int32_t* flag = nullptr;                               // [max(max_points, max_residuals)] the caller's flags
+    int32_t *keep_r = nullptr, *excl_r = nullptr, *map_r = nullptr;   // [max_residuals], [max_residuals + 1], [max_residuals]
+    int32_t *keep_p = nullptr, *excl_p = nullptr, *map_p = nullptr;   // the same per point
+    int32_t *block = nullptr, *total = nullptr;            // the scan's per-workgroup sums; [4] the surviving residuals and points, the frame marginalisation's flag
+    // eds_wed_insert_activated, sized for the eds_imm at its first call: C candidates, G = 8 C grid cells
+    size_t ins_cap = 0;
+    int32_t *ins_keep = nullptr, *ins_excl_c = nullptr, *ins_excl_g = nullptr, *ins_map_c = nullptr, *ins_map_g = nullptr;   // [C + G], [C + 1], [G + 1], [C], [G]
+    int32_t *ins_tile = nullptr, *ins_first = nullptr;     // the scans' tile sums; [9] the hosts' runs before the insert
+    double* marg = nullptr;                                // eds_wed_marginalize_frame: HM, bM, prior, delta_prior in; then HM', bM' out
 };
 
 struct eds_win {
@@ -57,6 +83,7 @@ struct eds_win {
     edswin::PointOut* pout = nullptr;
     int32_t* nres = nullptr;
     eds_wsv_state* wsv = nullptr;
+    eds_wed_state* wed = nullptr;
 };
 
 namespace edswin_internal {
@@ -73,4 +100,8 @@ void queue_stitch(eds_win* h, int F, const double* acc, const double* ad, int en
 // eds_winsolve.hip
 void wsv_release(eds_win* h);
 void wsv_invalidate(eds_win* h);
+int wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarget, const double* delta, const double* prior, const double* delta_prior,
+                  const double* cPrior, const double* cDelta, const float* priorF, const float* deltaF, bool from_device);
+// eds_winedit.hip
+void wed_release(eds_win* h);
 }  // namespace edswin_internal

@@ -89,6 +89,12 @@ __global__ void __launch_bounds__(TB) k_wsv_step_idepths(int n, float scale, flo
     if (p < n) ids[p] = edswsv::stepped_idepth_scaled(backup[p], fac, step[p], scale);
 }
 
+// setDeltaF's per-point part from the device's inverse depths (EnergyFunctional.cpp:190)
+__global__ void __launch_bounds__(TB) k_wsv_delta_of_idepths(int n, float scale, const float* __restrict__ ids, const float* __restrict__ idz, float* __restrict__ delta) {
+    const int p = blockIdx.x * TB + threadIdx.x;
+    if (p < n) delta[p] = edswsv::delta_of_idepths(ids[p], idz[p], scale);
+}
+
 __device__ inline double wave_fold(double v) {
     for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
     return v;
@@ -199,17 +205,14 @@ void wsv_release(eds_win* h) {
 
 void wsv_invalidate(eds_win* h) {
     if (!h->wsv) return;
+    h->wsv->rows_live = false;
     h->wsv->valid = false; h->wsv->lf_on_device = false; h->wsv->have_backup = false; h->wsv->have_step = false; h->wsv->have_system = false;
 }
 
-}  // namespace edswin_internal
-
-extern "C" {
-
-int eds_wsv_abi_version(void) { return EDS_HIP_WINSOLVE_ABI_VERSION; }
-
-int eds_wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarget, const double* delta, const double* prior,
-                      const double* delta_prior, const double* cPrior, const double* cDelta, const float* priorF, const float* deltaF) {
+// eds_wsv_set_state, and with from_device eds_wed_set_state (include/eds_hip_winedit.h): deltaF from the device's inverse depths, and,
+// where a state was set since the last eds_win_set_points / eds_win_set_residuals, priorF, isLinearized and res_toZeroF kept
+int wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarget, const double* delta, const double* prior, const double* delta_prior,
+                  const double* cPrior, const double* cDelta, const float* priorF, const float* deltaF, bool from_device) {
     if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
     if (F < 2 || F > h->max_frames) return fail(EDS_ERR_INVALID, "F is 2 .. max_frames");
     if (!adHost || !adTarget || !delta || !prior || !delta_prior || !cPrior || !cDelta)
@@ -223,6 +226,7 @@ int eds_wsv_set_state(eds_win* h, int F, const double* adHost, const double* adT
     EDS_HIP_TRY(hipSetDevice(h->dev));
     if (int rc = alloc_state(h)) return rc;
     eds_wsv_state* s = h->wsv;
+    const bool keep = from_device && s->rows_live;              // include/eds_hip_winedit.h: priorF, isLinearized and res_toZeroF stay
     // the float casts and setDeltaF on the host, by the code the oracle runs (a few thousand operations)
     std::vector<float> adF(2 * adw), adht((size_t)F * F * 8), cF(8);
     for (size_t i = 0; i < adw; ++i) { adF[i] = (float)adHost[i]; adF[adw + i] = (float)adTarget[i]; }
@@ -249,20 +253,39 @@ int eds_wsv_set_state(eds_win* h, int F, const double* adHost, const double* adT
     EDS_HIP_TRY(hipMemcpyAsync(s->vec, vec.data(), vec.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (n) {
         if (priorF) EDS_HIP_TRY(hipMemcpyAsync(h->prior, priorF, n * sizeof(float), hipMemcpyHostToDevice, st));
-        else EDS_HIP_TRY(hipMemsetAsync(h->prior, 0, n * sizeof(float), st));
-        if (deltaF) EDS_HIP_TRY(hipMemcpyAsync(h->delta, deltaF, n * sizeof(float), hipMemcpyHostToDevice, st));
-        else EDS_HIP_TRY(hipMemsetAsync(h->delta, 0, n * sizeof(float), st));
+        else if (!keep) EDS_HIP_TRY(hipMemsetAsync(h->prior, 0, n * sizeof(float), st));
+        if (from_device) {
+            hipLaunchKernelGGL(k_wsv_delta_of_idepths, dim3(blocks(n)), dim3(TB), 0, st, h->n, h->prm.scale_idepth, h->ids, h->idz, h->delta);
+            EDS_HIP_TRY(hipGetLastError());
+        } else if (deltaF) {
+            EDS_HIP_TRY(hipMemcpyAsync(h->delta, deltaF, n * sizeof(float), hipMemcpyHostToDevice, st));
+        } else {
+            EDS_HIP_TRY(hipMemsetAsync(h->delta, 0, n * sizeof(float), st));
+        }
         EDS_HIP_TRY(hipMemsetAsync(h->lf, 0, 6 * n * sizeof(float), st));
         EDS_HIP_TRY(hipMemsetAsync(s->step, 0, n * sizeof(float), st));
     }
     if (h->m) {
-        EDS_HIP_TRY(hipMemsetAsync(s->lin, 0, (size_t)h->m * sizeof(int32_t), st));
-        EDS_HIP_TRY(hipMemsetAsync(s->rtz, 0, (size_t)h->m * 8 * sizeof(float), st));
+        if (!keep) {
+            EDS_HIP_TRY(hipMemsetAsync(s->lin, 0, (size_t)h->m * sizeof(int32_t), st));
+            EDS_HIP_TRY(hipMemsetAsync(s->rtz, 0, (size_t)h->m * 8 * sizeof(float), st));
+        }
         EDS_HIP_TRY(hipMemsetAsync(s->res_approx, 0, (size_t)h->m * 8 * sizeof(float), st));
     }
     EDS_HIP_TRY(hipStreamSynchronize(st));
-    s->F = F; s->valid = true; s->lf_on_device = false; s->have_backup = false; s->have_step = false; s->have_system = false;
+    s->F = F; s->valid = true; s->rows_live = true; s->lf_on_device = false; s->have_backup = false; s->have_step = false; s->have_system = false;
     return EDS_OK;
+}
+
+}  // namespace edswin_internal
+
+extern "C" {
+
+int eds_wsv_abi_version(void) { return EDS_HIP_WINSOLVE_ABI_VERSION; }
+
+int eds_wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarget, const double* delta, const double* prior,
+                      const double* delta_prior, const double* cPrior, const double* cDelta, const float* priorF, const float* deltaF) {
+    return edswin_internal::wsv_set_state(h, F, adHost, adTarget, delta, prior, delta_prior, cPrior, cDelta, priorF, deltaF, false);
 }
 
 int eds_wsv_fix_linearization(eds_win* h, const int32_t* select) {

@@ -365,6 +365,11 @@ EDS_WSV_HD float point_step(const Lin& t, const PointOut& o, const float* lf, co
 }
 // idepth = SCALE_IDEPTH_INVERSE idepth_scaled (setIdepthScaled), and back after the step
 EDS_WSV_HD float idepth_of(float idepth_scaled, float scale_idepth) { return (1.0f / scale_idepth) * idepth_scaled; }
+// setDeltaF's per-point line (EnergyFunctional.cpp:190): deltaF = idepth - idepth_zero, each the scaled value times 1 / SCALE_IDEPTH
+EDS_WSV_HD float delta_of_idepths(float idepth_scaled, float idepth_zero_scaled, float scale_idepth) {
+    const float inv = 1.0f / scale_idepth;
+    return inv * idepth_scaled - inv * idepth_zero_scaled;
+}
 EDS_WSV_HD float stepped_idepth_scaled(float backup, float fac, float step, float scale_idepth) { return scale_idepth * (backup + fac * step); }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
