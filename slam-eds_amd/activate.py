@@ -8,6 +8,7 @@ way DSO does; ``next_min_act_dist`` is the three comparisons of the currentMinAc
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -23,49 +24,33 @@ PRECALC_FLOATS = 14
 ST_IN, ST_OOB, ST_OUTLIER = 0, 1, 2
 
 
-class Params(C.Structure):
+class Params(capi.ParamStruct):
     """``eds_act_params`` — the setting_* values the activation reads."""
     _fields_ = [("min_idepth_h_act", C.c_float), ("gn_its_on_point_activation", C.c_int32), ("min_trace_quality", C.c_float),
                 ("max_trace_pixel_interval", C.c_float), ("min_obs", C.c_int32), ("scale_idepth", C.c_float)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-_bound = False
-
-
+@functools.lru_cache(maxsize=None)
 def _lib():
-    global _bound
-    L = capi.lib()
-    if not _bound:
-        missing = [s for s in capi.ACT_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
-        vp, f = C.c_void_p, C.c_float
-        L.eds_act_params_default.argtypes = [C.POINTER(Params)]
-        L.eds_act_params_default.restype = None
-        L.eds_act_set_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_act_get_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_act_set_calib.argtypes = [vp, f, f, f, f]
-        L.eds_act_make_distance_map.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int]
-        L.eds_act_get_distance_map.argtypes = [vp, vp]
-        L.eds_act_select.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, f, vp]
-        L.eds_act_optimize.argtypes = [vp, C.c_int, vp, vp]
-        L.eds_act_get.argtypes = [vp, C.c_int] + [vp] * 7
-        L.eds_act_get_activated.argtypes = [vp, C.c_int, C.POINTER(C.c_int)] + [vp] * 8
-        _bound = True
-    return L
+    vp, f = C.c_void_p, C.c_float
+    return capi.bind(capi.ACT_EXPORTS, {
+        "eds_act_params_default": ([C.POINTER(Params)], None),
+        "eds_act_set_params": [vp, C.POINTER(Params)],
+        "eds_act_get_params": [vp, C.POINTER(Params)],
+        "eds_act_set_calib": [vp, f, f, f, f],
+        "eds_act_make_distance_map": [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int],
+        "eds_act_get_distance_map": [vp, vp],
+        "eds_act_select": [vp, C.c_int, C.c_int, vp, vp, vp, f, vp],
+        "eds_act_optimize": [vp, C.c_int, vp, vp],
+        "eds_act_get": [vp, C.c_int] + [vp] * 7,
+        "eds_act_get_activated": [vp, C.c_int, C.POINTER(C.c_int)] + [vp] * 8,
+    })
 
 
 def default_params(**over) -> Params:
     p = Params()
     _lib().eds_act_params_default(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return p.update(**over)
 
 
 def _k3(K):
@@ -119,8 +104,7 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp = capi.vp
 
 
 class Activation:
@@ -140,11 +124,7 @@ class Activation:
         return self.points._h
 
     def set_params(self, **over):
-        p = self.params()
-        for k, v in over.items():
-            if not hasattr(p, k):
-                raise KeyError(k)
-            setattr(p, k, v)
+        p = self.params().update(**over)
         capi._check(_lib().eds_act_set_params(self._h, C.byref(p)))
 
     def params(self) -> Params:
@@ -164,10 +144,10 @@ class Activation:
         k, t = _f32(KRKi1).reshape(-1, 9), _f32(Kt1).reshape(-1, 3)
         if len(k) != len(t):
             raise ValueError("one KRKi1 and Kt1 per host")
-        if active_host is None or (not hasattr(active_host, "__cuda_array_interface__") and not isinstance(active_host, tuple) and len(active_host) == 0):
+        if active_host is None or (not capi.is_device_source(active_host) and len(active_host) == 0):
             capi._check(_lib().eds_act_make_distance_map(self._h, int(newest), len(k), _vp(k), _vp(t), 0, None, None, 0))
             return
-        if hasattr(active_host, "__cuda_array_interface__") or isinstance(active_host, tuple):
+        if capi.is_device_source(active_host):
             hp, hs, _, hd = capi.device_array_info(active_host)
             ap, ash, _, ad = capi.device_array_info(active_uv_idepth)
             if hd != np.int32 or ad != np.float32 or int(np.prod(ash)) != 3 * int(np.prod(hs)):

@@ -394,6 +394,69 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(_dp)
 
 
+def vp(a):
+    """a numpy array's memory as a ``void*``; None stays None"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def bind(exports, signatures):
+    """The loaded library, after one check that it exports every name of `exports`, with the prototypes of `signatures` set:
+    ``name -> argtypes``, or ``name -> (argtypes, restype)`` where the function does not return an int."""
+    L = lib()
+    missing = [s for s in exports if not hasattr(L, s)]
+    if missing:
+        raise EdsError(ERR_INVALID, f"{LIB_PATH} does not export {missing}")
+    for name, sig in signatures.items():
+        if isinstance(sig, tuple):
+            getattr(L, name).argtypes, getattr(L, name).restype = sig
+        else:
+            getattr(L, name).argtypes = sig
+    return L
+
+
+class ParamStruct(C.Structure):
+    """A ``*_params`` record of the C ABI."""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+    def update(self, **over):
+        """sets the named members (KeyError for a name the record does not have); returns the record"""
+        for k, v in over.items():
+            if not hasattr(self, k):
+                raise KeyError(k)
+            setattr(self, k, v)
+        return self
+
+
+class OwnedHandle:
+    """An object that owns one handle of the C ABI in ``_h``: ``close`` destroys it once, so do garbage collection and the end of a
+    ``with`` block.  ``_destroy`` names the C function (its prototype is set by the module's ``bind``)."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def is_device_source(obj) -> bool:
+    """device memory as the bindings take it: ``__cuda_array_interface__``, or a raw ``(ptr, shape, strides, dtype)`` tuple"""
+    return hasattr(obj, "__cuda_array_interface__") or (isinstance(obj, tuple) and len(obj) == 4 and isinstance(obj[0], int))
+
+
 def _rows(a, count, width):
     """per-slot rows -> (contiguous count x stride [x width] float64 array, stride): an array is taken as it is, a list of
     per-slot arrays of different lengths is padded to the longest"""

@@ -7,6 +7,7 @@ Plumbing only: every number comes from the HIP kernels behind the C ABI (csrc/ed
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -16,12 +17,9 @@ MAX_LEVELS, MAX_DECISIONS, MAX_POINTS = 5, 512, 65536           # EDS_CT_MAX_LEV
 REF_IMAGE, NEW_IMAGE, IDEPTH, WEIGHT_SUMS, PC = range(5)
 
 
-class Params(C.Structure):
+class Params(capi.ParamStruct):
     """``eds_ct_params`` — the setting_* values trackNewestCoarse reads (reference src/utils/settings.cpp:119-138)."""
     _fields_ = [("huber_th", C.c_float), ("coarse_cutoff_th", C.c_float), ("affine_opt_mode_a", C.c_float), ("affine_opt_mode_b", C.c_float)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Result(C.Structure):
@@ -40,43 +38,30 @@ ROW = np.dtype([("in_e", "i4"), ("warped", "i4"), ("flow", "i4"), ("energy", "f4
                 ("shift_rt_pos", "f4"), ("shift_rt_neg", "f4")])
 assert RESULT.itemsize == C.sizeof(Result) and ROW.itemsize == 64
 
-_bound = False
 
-
+@functools.lru_cache(maxsize=None)
 def _lib():
-    global _bound
-    L = capi.lib()
-    if not _bound:
-        missing = [s for s in capi.CT_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
-        vp, i64, f, d = C.c_void_p, C.c_int64, C.c_float, C.c_double
-        L.eds_ct_params_default.argtypes = [C.POINTER(Params)]
-        L.eds_ct_params_default.restype = None
-        L.eds_ct_create.argtypes = [C.c_int] * 6 + [C.POINTER(vp)]
-        L.eds_ct_destroy.argtypes = [vp]
-        L.eds_ct_destroy.restype = None
-        L.eds_ct_set_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_ct_get_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_ct_set_calib.argtypes = [vp, f, f, f, f]
-        L.eds_ct_get_k.argtypes = [vp, C.c_int, vp]
-        L.eds_ct_set_ref.argtypes = [vp, vp, i64, C.c_int, f, d, d, C.c_int, vp, vp, vp, vp]
-        L.eds_ct_set_new.argtypes = [vp, vp, i64, C.c_int, f]
-        L.eds_ct_track.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
-        L.eds_ct_calc_res.argtypes = [vp, C.c_int, vp, vp, f, vp, vp, vp, vp]
-        L.eds_ct_get_level.argtypes = [vp, C.c_int, C.c_int, vp, vp]
-        _bound = True
-    return L
+    vp, i64, f, d = C.c_void_p, C.c_int64, C.c_float, C.c_double
+    return capi.bind(capi.CT_EXPORTS, {
+        "eds_ct_params_default": ([C.POINTER(Params)], None),
+        "eds_ct_create": [C.c_int] * 6 + [C.POINTER(vp)],
+        "eds_ct_destroy": ([vp], None),
+        "eds_ct_set_params": [vp, C.POINTER(Params)],
+        "eds_ct_get_params": [vp, C.POINTER(Params)],
+        "eds_ct_set_calib": [vp, f, f, f, f],
+        "eds_ct_get_k": [vp, C.c_int, vp],
+        "eds_ct_set_ref": [vp, vp, i64, C.c_int, f, d, d, C.c_int, vp, vp, vp, vp],
+        "eds_ct_set_new": [vp, vp, i64, C.c_int, f],
+        "eds_ct_track": [vp, C.c_int, vp, vp, C.c_int, vp, vp],
+        "eds_ct_calc_res": [vp, C.c_int, vp, vp, f, vp, vp, vp, vp],
+        "eds_ct_get_level": [vp, C.c_int, C.c_int, vp, vp],
+    })
 
 
 def default_params(**over) -> Params:
     p = Params()
     _lib().eds_ct_params_default(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return p.update(**over)
 
 
 def trace_precalc(K, T, aff_host, aff_target, exposures=(1.0, 1.0)):
@@ -87,12 +72,12 @@ def trace_precalc(K, T, aff_host, aff_target, exposures=(1.0, 1.0)):
     return immature.precalc(K, T[:, :3], T[:, 3], aff_host, aff_target, exposures)
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp = capi.vp
 
 
-class CoarseTracker:
+class CoarseTracker(capi.OwnedHandle):
     """One reference keyframe with its coarse depth, one new frame, and the alignment of the two, in device memory."""
+    _destroy = "eds_ct_destroy"
 
     def __init__(self, H, W, levels=5, max_points=20000, max_tries=8, device=0, **params):
         self._h = C.c_void_p()
@@ -102,23 +87,8 @@ class CoarseTracker:
         if params:
             self.set_params(**params)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib().eds_ct_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_params(self, **over):
-        p = self.params()
-        for k, v in over.items():
-            if not hasattr(p, k):
-                raise KeyError(k)
-            setattr(p, k, v)
+        p = self.params().update(**over)
         capi._check(_lib().eds_ct_set_params(self._h, C.byref(p)))
 
     def params(self) -> Params:
@@ -136,8 +106,7 @@ class CoarseTracker:
 
     def _image(self, image):
         """(pointer, row stride in elements, on_device, keep-alive)"""
-        raw = isinstance(image, tuple) and len(image) == 4 and isinstance(image[0], int)
-        if not raw and not hasattr(image, "__cuda_array_interface__"):
+        if not capi.is_device_source(image):
             a = np.ascontiguousarray(image, dtype=np.float32)
             if a.shape != (self.H, self.W):
                 raise ValueError(f"image must be {self.H} x {self.W}, not {a.shape}")

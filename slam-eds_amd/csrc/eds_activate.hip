@@ -24,6 +24,7 @@
 using edsact::Calib;
 using edsact::Params;
 using edscapi::fail;
+using edscapi::read_back;
 using edsimm::Grad;
 using edsimm::Point;
 
@@ -183,48 +184,40 @@ __global__ void __launch_bounds__(256) k_act_count(const int32_t* __restrict__ f
     if (threadIdx.x < edsact::NUM_FATES) out[threadIdx.x] = cnt[threadIdx.x];
 }
 
-int check_handle(const eds_imm* h) { return h ? EDS_OK : fail(EDS_ERR_INVALID, "null eds_imm handle"); }
-
 bool all_finite(const float* x, size_t n) {
     for (size_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false;
     return true;
 }
 
-void free_state(eds_act_state* a) {
-    void* all[] = {a->map, a->mark, a->fate, a->fit, a->res_state, a->res_energy, a->krki, a->kt, a->pre, a->n, a->counts, a->flagged, a->active,
-                   a->active_host};
-    for (void* p : all) if (p) (void)hipFree(p);
-    delete a;
-}
-
 // the state, allocated by the first call that needs it
 int state_of(eds_imm* h, eds_act_state** out) {
     if (h->act) { *out = h->act; return EDS_OK; }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     eds_act_state* a = new eds_act_state;
     a->prm = edsact::params_default();
     a->stride = h->max_hosts < edsact::MAX_FRAMES ? h->max_hosts : edsact::MAX_FRAMES;
     const size_t cells = (size_t)(h->W >> 1) * (h->H >> 1), pts = (size_t)h->max_hosts * h->max_points, st = (size_t)a->stride;
-    const bool ok = edscapi::device_alloc({{(void**)&a->map, cells},
-                                           {(void**)&a->mark, cells * sizeof(uint32_t)},
-                                           {(void**)&a->fate, pts * sizeof(int32_t)},
-                                           {(void**)&a->fit, pts * 4 * sizeof(float)},
-                                           {(void**)&a->res_state, pts * st * sizeof(int32_t)},
-                                           {(void**)&a->res_energy, pts * st * sizeof(float)},
-                                           {(void**)&a->krki, (size_t)h->max_hosts * 9 * sizeof(float)},
-                                           {(void**)&a->kt, (size_t)h->max_hosts * 3 * sizeof(float)},
-                                           {(void**)&a->pre, st * st * edsact::PRE_WORDS * sizeof(float)},
-                                           {(void**)&a->n, (size_t)h->max_hosts * sizeof(int32_t)},
-                                           {(void**)&a->counts, edsact::NUM_FATES * sizeof(int32_t)},
-                                           {(void**)&a->flagged, (size_t)h->max_hosts}});
+    const size_t mark = h->own.live();
+    const bool ok = h->own.alloc({{(void**)&a->map, cells},
+                                  {(void**)&a->mark, cells * sizeof(uint32_t)},
+                                  {(void**)&a->fate, pts * sizeof(int32_t)},
+                                  {(void**)&a->fit, pts * 4 * sizeof(float)},
+                                  {(void**)&a->res_state, pts * st * sizeof(int32_t)},
+                                  {(void**)&a->res_energy, pts * st * sizeof(float)},
+                                  {(void**)&a->krki, (size_t)h->max_hosts * 9 * sizeof(float)},
+                                  {(void**)&a->kt, (size_t)h->max_hosts * 3 * sizeof(float)},
+                                  {(void**)&a->pre, st * st * edsact::PRE_WORDS * sizeof(float)},
+                                  {(void**)&a->n, (size_t)h->max_hosts * sizeof(int32_t)},
+                                  {(void**)&a->counts, edsact::NUM_FATES * sizeof(int32_t)},
+                                  {(void**)&a->flagged, (size_t)h->max_hosts}});
     if (!ok) {
-        (void)hipGetLastError();
-        free_state(a);
+        delete a;
         return fail(EDS_ERR_HIP, "eds_act: the device refused an allocation");
     }
-    if (hipMemsetAsync(a->fate, 0, pts * sizeof(int32_t), h->st) != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess) {
+    if (hipMemsetAsync(a->fate, 0, pts * sizeof(int32_t), h->own.st) != hipSuccess || hipStreamSynchronize(h->own.st) != hipSuccess) {
         (void)hipGetLastError();
-        free_state(a);
+        h->own.release_from(mark);
+        delete a;
         return fail(EDS_ERR_HIP, "eds_act: the device refused a memset");
     }
     h->act = a;
@@ -241,17 +234,16 @@ int check_window(const eds_imm* h, int newest, int n_hosts) {
 
 int upload_counts(eds_imm* h, eds_act_state* a, int n_hosts) {
     std::vector<int32_t> n(h->n.begin(), h->n.begin() + n_hosts);
-    EDS_HIP_TRY(hipMemcpyAsync(a->n, n.data(), n.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));       // n is a local
+    EDS_HIP_TRY(hipMemcpyAsync(a->n, n.data(), n.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));       // n is a local
     return EDS_OK;
 }
 
 int read_counts(eds_imm* h, eds_act_state* a, int n_hosts, int32_t* counts_out) {
-    hipLaunchKernelGGL(k_act_count, dim3(1), dim3(256), 0, h->st, a->fate, h->max_points, a->n, n_hosts, a->counts);
+    hipLaunchKernelGGL(k_act_count, dim3(1), dim3(256), 0, h->own.st, a->fate, h->max_points, a->n, n_hosts, a->counts);
     EDS_HIP_TRY(hipGetLastError());
     int32_t c[edsact::NUM_FATES];
-    EDS_HIP_TRY(hipMemcpyAsync(c, a->counts, sizeof(c), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, c, a->counts, sizeof(c))) return rc;
     if (counts_out) std::memcpy(counts_out, c, sizeof(c));
     return EDS_OK;
 }
@@ -260,7 +252,7 @@ int read_counts(eds_imm* h, eds_act_state* a, int n_hosts, int32_t* counts_out) 
 
 namespace edsimm_internal {
 void act_release(eds_imm* h) {
-    if (h->act) free_state(h->act);
+    delete h->act;
     h->act = nullptr;
 }
 void act_invalidate(eds_imm* h) {
@@ -279,7 +271,7 @@ void eds_act_params_default(eds_act_params* p) {
 }
 
 int eds_act_set_params(eds_imm* h, const eds_act_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null parameters");
     Params s;
     std::memcpy(&s, p, sizeof(s));
@@ -292,7 +284,7 @@ int eds_act_set_params(eds_imm* h, const eds_act_params* p) {
 }
 
 int eds_act_get_params(eds_imm* h, eds_act_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null output");
     const Params s = h->act ? h->act->prm : edsact::params_default();
     std::memcpy(p, &s, sizeof(s));
@@ -300,9 +292,8 @@ int eds_act_get_params(eds_imm* h, eds_act_params* p) {
 }
 
 int eds_act_set_calib(eds_imm* h, float fx, float fy, float cx, float cy) {
-    if (int rc = check_handle(h)) return rc;
-    if (!(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy) && fx > 0 && fy > 0))
-        return fail(EDS_ERR_INVALID, "calibration: fx, fy finite and positive, cx, cy finite");
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
+    if (!edscapi::check_calib(fx, fy, cx, cy)) return fail(EDS_ERR_INVALID, "calibration: fx, fy finite and positive, cx, cy finite");
     if ((h->W >> 1) < 3 || (h->H >> 1) < 3) return fail(EDS_ERR_INVALID, "the level-1 map is at least 3 x 3");
     eds_act_state* a;
     if (int rc = state_of(h, &a)) return rc;
@@ -314,7 +305,7 @@ int eds_act_set_calib(eds_imm* h, float fx, float fy, float cx, float cy) {
 
 int eds_act_make_distance_map(eds_imm* h, int newest, int n_hosts, const float* KRKi1, const float* Kt1, int n_active, const int32_t* active_host,
                               const float* active, int on_device) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (int rc = check_window(h, newest, n_hosts)) return rc;
     if (!KRKi1 || !Kt1) return fail(EDS_ERR_INVALID, "KRKi1 and Kt1 are required");
     if (n_active < 0 || n_active > (1 << 26)) return fail(EDS_ERR_INVALID, "n_active is 0 .. 2^26");
@@ -323,15 +314,14 @@ int eds_act_make_distance_map(eds_imm* h, int newest, int n_hosts, const float* 
     if (!all_finite(KRKi1, 9 * (size_t)n_hosts) || !all_finite(Kt1, 3 * (size_t)n_hosts)) return fail(EDS_ERR_INVALID, "KRKi1 or Kt1 is not finite");
     if (!h->act || !h->act->calib_set) return fail(EDS_ERR_STATE, "eds_act_set_calib first");
     eds_act_state* a = h->act;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     std::vector<int32_t> hosts((size_t)n_active);
     if (n_active > 0) {
         if (on_device) {
             if (reinterpret_cast<uintptr_t>(active_host) % 4 || reinterpret_cast<uintptr_t>(active) % 4) return fail(EDS_ERR_INVALID, "active points: not aligned to 4 bytes");
-            if (int rc = eds_dev_check_range(h->dev, active_host, (size_t)n_active * sizeof(int32_t))) return rc;
-            if (int rc = eds_dev_check_range(h->dev, active, (size_t)n_active * 3 * sizeof(float))) return rc;
-            EDS_HIP_TRY(hipMemcpyAsync(hosts.data(), active_host, hosts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-            EDS_HIP_TRY(hipStreamSynchronize(h->st));
+            if (int rc = eds_dev_check_range(h->own.dev, active_host, (size_t)n_active * sizeof(int32_t))) return rc;
+            if (int rc = eds_dev_check_range(h->own.dev, active, (size_t)n_active * 3 * sizeof(float))) return rc;
+            if (int rc = read_back(h->own, hosts.data(), active_host, hosts.size() * sizeof(int32_t))) return rc;
         } else {
             std::memcpy(hosts.data(), active_host, hosts.size() * sizeof(int32_t));
         }
@@ -344,56 +334,50 @@ int eds_act_make_distance_map(eds_imm* h, int newest, int n_hosts, const float* 
         }
         if (!on_device) {
             if (n_active > a->active_cap) {
-                float* na = nullptr;
-                int32_t* nh = nullptr;
-                if (!edscapi::device_alloc({{(void**)&na, (size_t)n_active * 3 * sizeof(float)}, {(void**)&nh, (size_t)n_active * sizeof(int32_t)}})) {
-                    (void)hipGetLastError();
-                    if (na) (void)hipFree(na);
+                h->own.release(a->active);
+                h->own.release(a->active_host);
+                a->active_cap = 0;
+                if (!h->own.alloc({{(void**)&a->active, (size_t)n_active * 3 * sizeof(float)}, {(void**)&a->active_host, (size_t)n_active * sizeof(int32_t)}}))
                     return fail(EDS_ERR_HIP, "eds_act_make_distance_map: the device refused an allocation");
-                }
-                if (a->active) (void)hipFree(a->active);
-                if (a->active_host) (void)hipFree(a->active_host);
-                a->active = na; a->active_host = nh; a->active_cap = n_active;
+                a->active_cap = n_active;
             }
-            EDS_HIP_TRY(hipMemcpyAsync(a->active, active, (size_t)n_active * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
-            EDS_HIP_TRY(hipMemcpyAsync(a->active_host, hosts.data(), hosts.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+            EDS_HIP_TRY(hipMemcpyAsync(a->active, active, (size_t)n_active * 3 * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+            EDS_HIP_TRY(hipMemcpyAsync(a->active_host, hosts.data(), hosts.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
             active = a->active;
             active_host = a->active_host;
         }
     }
     const int w1 = a->cal.w1, h1 = a->cal.h1, cells = w1 * h1;
     a->map_valid = a->sel_valid = false;
-    EDS_HIP_TRY(hipMemcpyAsync(a->krki, KRKi1, 9 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(a->kt, Kt1, 3 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemsetAsync(a->map, edsact::FAR, (size_t)cells, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(a->krki, KRKi1, 9 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(a->kt, Kt1, 3 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(a->map, edsact::FAR, (size_t)cells, h->own.st));
     if (n_active > 0) {
-        hipLaunchKernelGGL(k_act_seed, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, h->st, a->map, w1, h1, newest, a->krki, a->kt, n_active,
+        hipLaunchKernelGGL(k_act_seed, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, h->own.st, a->map, w1, h1, newest, a->krki, a->kt, n_active,
                            active_host, active);
         EDS_HIP_TRY(hipGetLastError());
-        for (int k = 1; k <= edsact::ROUNDS; ++k) hipLaunchKernelGGL(k_act_round, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->st, a->map, w1, h1, k);
+        for (int k = 1; k <= edsact::ROUNDS; ++k) hipLaunchKernelGGL(k_act_round, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->own.st, a->map, w1, h1, k);
         EDS_HIP_TRY(hipGetLastError());
     }
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     a->map_valid = true;
     return EDS_OK;
 }
 
 int eds_act_get_distance_map(eds_imm* h, float* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     if (!h->act || !h->act->map_valid) return fail(EDS_ERR_STATE, "no distance map: eds_act_make_distance_map first");
     const size_t cells = (size_t)h->act->cal.w1 * h->act->cal.h1;
     std::vector<uint8_t> m(cells);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(m.data(), h->act->map, cells, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, m.data(), h->act->map, cells)) return rc;
     for (size_t i = 0; i < cells; ++i) out[i] = edsact::map_value(m[i]);
     return EDS_OK;
 }
 
 int eds_act_select(eds_imm* h, int newest, int n_hosts, const float* KRKi1, const float* Kt1, const uint8_t* flagged, float current_min_act_dist,
                    int32_t* counts_out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (int rc = check_window(h, newest, n_hosts)) return rc;
     if (!KRKi1 || !Kt1) return fail(EDS_ERR_INVALID, "KRKi1 and Kt1 are required");
     if (!all_finite(KRKi1, 9 * (size_t)n_hosts) || !all_finite(Kt1, 3 * (size_t)n_hosts) || !std::isfinite(current_min_act_dist))
@@ -401,21 +385,20 @@ int eds_act_select(eds_imm* h, int newest, int n_hosts, const float* KRKi1, cons
     if (!h->act || !h->act->calib_set) return fail(EDS_ERR_STATE, "eds_act_set_calib first");
     eds_act_state* a = h->act;
     if (!a->map_valid) return fail(EDS_ERR_STATE, "no distance map: eds_act_make_distance_map first");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     std::vector<uint8_t> fl((size_t)n_hosts, 0);
     if (flagged) for (int i = 0; i < n_hosts; ++i) fl[i] = flagged[i] ? 1 : 0;
     a->sel_valid = a->fit_valid = false;
-    EDS_HIP_TRY(hipMemcpyAsync(a->krki, KRKi1, 9 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(a->kt, Kt1, 3 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(a->flagged, fl.data(), fl.size(), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(a->krki, KRKi1, 9 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(a->kt, Kt1, 3 * (size_t)n_hosts * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(a->flagged, fl.data(), fl.size(), hipMemcpyHostToDevice, h->own.st));
     if (int rc = upload_counts(h, a, n_hosts)) return rc;
     edsact::SelectIn in = {h->points, h->max_points, a->n, newest, n_hosts, a->krki, a->kt, a->flagged, current_min_act_dist, a->prm, a->cal.w1, a->cal.h1,
                            a->map, a->mark, a->fate, a->counts};
-    hipLaunchKernelGGL(k_act_select, dim3(1), dim3(SELECT_THREADS), 0, h->st, in);
+    hipLaunchKernelGGL(k_act_select, dim3(1), dim3(SELECT_THREADS), 0, h->own.st, in);
     EDS_HIP_TRY(hipGetLastError());
     int32_t c[edsact::NUM_FATES];
-    EDS_HIP_TRY(hipMemcpyAsync(c, a->counts, sizeof(c), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, c, a->counts, sizeof(c))) return rc;
     if (counts_out) std::memcpy(counts_out, c, sizeof(c));
     a->sel_valid = true;
     a->sel_hosts = n_hosts;
@@ -423,7 +406,7 @@ int eds_act_select(eds_imm* h, int newest, int n_hosts, const float* KRKi1, cons
 }
 
 int eds_act_optimize(eds_imm* h, int n_hosts, const float* precalc, int32_t* counts_out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (!precalc) return fail(EDS_ERR_INVALID, "precalc is required");
     if (!h->act || !h->act->sel_valid) return fail(EDS_ERR_STATE, "no selection: eds_act_select first");
     eds_act_state* a = h->act;
@@ -433,13 +416,13 @@ int eds_act_optimize(eds_imm* h, int n_hosts, const float* precalc, int32_t* cou
             if (i != j && !all_finite(precalc + (size_t)(i * n_hosts + j) * edsact::PRE_WORDS, edsact::PRE_WORDS)) return fail(EDS_ERR_INVALID, "precalc is not finite");
     for (int i = 0; i < n_hosts; ++i)
         if (!h->host_set[i]) return fail(EDS_ERR_STATE, "frame " + std::to_string(i) + " has no image");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     a->sel_valid = false;
-    EDS_HIP_TRY(hipMemcpyAsync(a->pre, precalc, (size_t)n_hosts * n_hosts * edsact::PRE_WORDS * sizeof(float), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(a->pre, precalc, (size_t)n_hosts * n_hosts * edsact::PRE_WORDS * sizeof(float), hipMemcpyHostToDevice, h->own.st));
     int max_n = 0;
     for (int i = 0; i < n_hosts; ++i) if (h->n[i] > max_n) max_n = h->n[i];
     if (max_n > 0) {
-        hipLaunchKernelGGL(k_act_optimize, dim3((unsigned)max_n, (unsigned)n_hosts), dim3(64), 0, h->st, h->points, h->max_points, a->n, n_hosts, a->pre,
+        hipLaunchKernelGGL(k_act_optimize, dim3((unsigned)max_n, (unsigned)n_hosts), dim3(64), 0, h->own.st, h->points, h->max_points, a->n, n_hosts, a->pre,
                            h->host_c, h->host_g, a->cal, a->prm, h->prm.huber_th, a->fate, a->fit, a->res_state, a->res_energy, a->stride);
         EDS_HIP_TRY(hipGetLastError());
     }
@@ -449,7 +432,7 @@ int eds_act_optimize(eds_imm* h, int n_hosts, const float* precalc, int32_t* cou
 }
 
 int eds_act_get(eds_imm* h, int host, int32_t* fate, float* idepth, float* energy, float* hdd, float* bd, int32_t* res_state, float* res_energy) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (host < 0 || host >= h->max_hosts) return fail(EDS_ERR_INVALID, "host " + std::to_string(host) + " outside 0 .. " + std::to_string(h->max_hosts - 1));
     if (!h->act || !(h->act->sel_valid || h->act->fit_valid)) return fail(EDS_ERR_STATE, "no selection: eds_act_select first");
     eds_act_state* a = h->act;
@@ -459,12 +442,10 @@ int eds_act_get(eds_imm* h, int host, int32_t* fate, float* idepth, float* energ
     if (n == 0) return EDS_OK;
     std::vector<int32_t> f(n), rs(n * st);
     std::vector<float> ft(n * 4), re(n * st);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(f.data(), a->fate + o, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(ft.data(), a->fit + o * 4, n * 4 * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(rs.data(), a->res_state + o * st, n * st * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(re.data(), a->res_energy + o * st, n * st * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, f.data(), a->fate + o, n * sizeof(int32_t))) return rc;
+    if (int rc = read_back(h->own, ft.data(), a->fit + o * 4, n * 4 * sizeof(float))) return rc;
+    if (int rc = read_back(h->own, rs.data(), a->res_state + o * st, n * st * sizeof(int32_t))) return rc;
+    if (int rc = read_back(h->own, re.data(), a->res_energy + o * st, n * st * sizeof(float))) return rc;
     for (size_t i = 0; i < n; ++i) {
         const bool fitted = f[i] == edsact::KEPT_WEAK || f[i] == edsact::DROPPED || f[i] == edsact::ACTIVATED;
         if (fate) fate[i] = f[i];
@@ -482,13 +463,12 @@ int eds_act_get(eds_imm* h, int host, int32_t* fate, float* idepth, float* energ
 
 int eds_act_get_activated(eds_imm* h, int cap, int* n_out, int32_t* host, int32_t* index, float* uv, float* type, float* idepth, float* color,
                           float* weights, uint64_t* target_mask) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (!n_out || cap < 0) return fail(EDS_ERR_INVALID, "n is required and cap is not negative");
     if (!h->act || !h->act->fit_valid) return fail(EDS_ERR_STATE, "no fit: eds_act_optimize first");
     eds_act_state* a = h->act;
     const int F = a->sel_hosts;
     const size_t st = (size_t)a->stride;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
     int m = 0;
     for (int hh = 0; hh < F; ++hh) {
         const size_t n = (size_t)h->n[hh], o = (size_t)hh * h->max_points;
@@ -496,11 +476,10 @@ int eds_act_get_activated(eds_imm* h, int cap, int* n_out, int32_t* host, int32_
         std::vector<int32_t> f(n), rs(n * st);
         std::vector<float> ft(n * 4);
         std::vector<Point> pts(n);
-        EDS_HIP_TRY(hipMemcpyAsync(f.data(), a->fate + o, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(ft.data(), a->fit + o * 4, n * 4 * sizeof(float), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(rs.data(), a->res_state + o * st, n * st * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(pts.data(), h->points + o, n * sizeof(Point), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        if (int rc = read_back(h->own, f.data(), a->fate + o, n * sizeof(int32_t))) return rc;
+        if (int rc = read_back(h->own, ft.data(), a->fit + o * 4, n * 4 * sizeof(float))) return rc;
+        if (int rc = read_back(h->own, rs.data(), a->res_state + o * st, n * st * sizeof(int32_t))) return rc;
+        if (int rc = read_back(h->own, pts.data(), h->points + o, n * sizeof(Point))) return rc;
         for (size_t i = 0; i < n; ++i) {
             if (f[i] != edsact::ACTIVATED) continue;
             if (m < cap) {

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/eds_hip.h"
+#include "eds_device_owner.hpp"                       // fail, EDS_HIP_TRY, DevAlloc
 #include "eds_fused.hpp"
 #include "eds_handle.hpp"
 #include "eds_kernels.hpp"
@@ -17,15 +18,6 @@
 #include "eds_solver.hpp"
 
 namespace edscapi {
-
-int fail(int code, const std::string& msg);          // records the message for eds_last_error() (thread-local), returns `code`
-
-#define EDS_HIP_TRY(expr)                                                                             \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return edscapi::fail(EDS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    } while (0)
 
 // eds_capi.hip
 int effective_blocks(const eds_trk* h);
@@ -45,7 +37,6 @@ int check_idle_slots(const eds_trk* h, int first, int count, int need);
 int read_xy_planes(eds_trk* h, const double* plane, int first, int count, int stride, double* dst);
 int workgroup_lds_limit(const eds_trk* h, size_t* bytes);     // selects the handle's device; the LDS one workgroup may ask for
 bool row_bins_fit(const eds_trk* h, size_t limit);            // k_klt_bin's two [H + 2] int arrays fit `limit`, H and W fit a key's 16 bits
-struct DevAlloc { void** p; size_t bytes; };
 bool device_alloc(std::initializer_list<DevAlloc> table);     // hipMalloc of every entry in turn; false at the first that fails
 // eds_trk_update_points_batch after its argument checks; dev: see eds_points_update_batch
 int update_points_range(eds_trk* h, int first, int count, int delete_out_points, int stride, double* coord_xy, double* tracks_xy,

@@ -16,10 +16,10 @@
 #include <vector>
 
 #include "../../include/eds_hip_coarse.h"
-#include "../../include/eds_hip_device.h"
 #include "eds_capi_internal.hpp"
 #include "eds_coarse.hpp"
 
+using edscapi::blocks;
 using edscapi::fail;
 using edsct::Geo;
 using edsct::Level;
@@ -37,14 +37,14 @@ static_assert(sizeof(Term) == 16 * sizeof(float) && sizeof(Term) == sizeof(eds_c
 static_assert(edsct::MAX_DECISIONS == EDS_CT_MAX_DECISIONS && edsct::MAX_LEVELS == EDS_CT_MAX_LEVELS, "header constants");
 
 struct eds_ct {
-    int dev = 0, max_points = 0, max_tries = 0;
+    edscapi::DeviceOwner own;
+    int max_points = 0, max_tries = 0;
     Geo geo;
     Params prm;
     Photo ph;
     bool calib_set = false, ref_set = false, new_set = false;
     int32_t pc_n[edsct::MAX_LEVELS] = {0, 0, 0, 0, 0};
     int max_blocks = 0;
-    hipStream_t st = nullptr;
     Geo* d_geo = nullptr;
     Px *ref_px = nullptr, *new_px = nullptr;             // [geo.total]
     float *idA = nullptr, *wsA = nullptr, *idB = nullptr, *wsB = nullptr;
@@ -341,40 +341,20 @@ __global__ void __launch_bounds__(TB) k_ct_rows(const Geo* __restrict__ g, Param
     rows[i] = edsct::point_term(w, new_px + L.off, pc[L.off + i], i);
 }
 
-int check_handle(const eds_ct* h) { return h ? EDS_OK : fail(EDS_ERR_INVALID, "null eds_ct handle"); }
-
 int check_level(const eds_ct* h, int lvl) {
     if (lvl < 0 || lvl >= h->geo.levels) return fail(EDS_ERR_INVALID, "level " + std::to_string(lvl) + " outside 0 .. " + std::to_string(h->geo.levels - 1));
-    return EDS_OK;
-}
-
-unsigned blocks(int n) { return (unsigned)((n + TB - 1) / TB); }
-
-// what a set_* call checks of its image before anything changes; *rs becomes the effective row stride
-int check_frame(const eds_ct* h, const float* image, int64_t* rs, int on_device) {
-    const int H = h->geo.H, W = h->geo.W;
-    if (!image) return fail(EDS_ERR_INVALID, "image: NULL pointer");
-    if (on_device != 0 && on_device != 1) return fail(EDS_ERR_INVALID, "on_device is 0 or 1");
-    if (*rs == 0) *rs = W;
-    if (*rs < W || *rs > (int64_t)1 << 30) return fail(EDS_ERR_INVALID, "bad row stride");
-    if (reinterpret_cast<uintptr_t>(image) % sizeof(float)) return fail(EDS_ERR_INVALID, "image: not aligned to 4 bytes");
-    if (on_device) {
-        const size_t bytes = (size_t)((int64_t)(H - 1) * *rs + W) * sizeof(float);
-        if (int rc = eds_dev_check_range(h->dev, image, bytes)) return rc;
-    }
     return EDS_OK;
 }
 
 // the checked image into in_img (dense), then every level of `px`; queued, not waited for
 int load_frame(eds_ct* h, Px* px, const float* image, int64_t rs, int on_device) {
     const int H = h->geo.H, W = h->geo.W;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpy2DAsync(h->in_img, (size_t)W * sizeof(float), image, (size_t)rs * sizeof(float), (size_t)W * sizeof(float), (size_t)H,
-                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    if (int rc = edscapi::upload_image(h->own, h->in_img, H, W, image, rs, on_device)) return rc;
     for (int l = 0; l < h->geo.levels; ++l) {
         const unsigned nb = blocks(h->geo.l[l].w * h->geo.l[l].h);
-        hipLaunchKernelGGL(k_ct_pyramid, dim3(nb), dim3(TB), 0, h->st, h->in_img, px, h->d_geo, l);
-        hipLaunchKernelGGL(k_ct_gradient, dim3(nb), dim3(TB), 0, h->st, px, h->d_geo, l);
+        hipLaunchKernelGGL(k_ct_pyramid, dim3(nb), dim3(TB), 0, h->own.st, h->in_img, px, h->d_geo, l);
+        hipLaunchKernelGGL(k_ct_gradient, dim3(nb), dim3(TB), 0, h->own.st, px, h->d_geo, l);
     }
     EDS_HIP_TRY(hipGetLastError());
     return EDS_OK;
@@ -411,46 +391,39 @@ int eds_ct_create(int device, int H, int W, int levels, int max_points, int max_
         return fail(EDS_ERR_INVALID, "levels are 1 .. 5, H and W 8 .. 8192 and divisible by 2^(levels - 1), the coarsest level at least 8 x 8");
     if (max_points < 1 || max_points > EDS_CT_MAX_POINTS || max_tries < 1 || max_tries > 4096)
         return fail(EDS_ERR_INVALID, "max_points is 1 .. 65536, max_tries 1 .. 4096");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return fail(EDS_ERR_NO_DEVICE, "no HIP device");
-    }
-    if (device < 0 || device >= ndev) return fail(EDS_ERR_INVALID, "device " + std::to_string(device) + " of " + std::to_string(ndev));
-    EDS_HIP_TRY(hipSetDevice(device));
     eds_ct* h = new eds_ct;
-    h->dev = device; h->max_points = max_points; h->max_tries = max_tries;
+    if (int rc = h->own.open(device)) { delete h; return rc; }
+    h->max_points = max_points; h->max_tries = max_tries;
     edsct::make_shape(h->geo, H, W, levels);
     h->prm = edsct::params_default();
     h->ph.exposure_ref = h->ph.exposure_new = 1.0f; h->ph.ref_a = h->ph.ref_b = 0.0;
     h->max_blocks = (int)blocks(H * W);
     const size_t tot = (size_t)h->geo.total, px0 = (size_t)H * W, mp = (size_t)max_points;
-    const bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess &&
-                    edscapi::device_alloc({{(void**)&h->d_geo, sizeof(Geo)},
-                                           {(void**)&h->ref_px, tot * sizeof(Px)},
-                                           {(void**)&h->new_px, tot * sizeof(Px)},
-                                           {(void**)&h->idA, tot * sizeof(float)},
-                                           {(void**)&h->wsA, tot * sizeof(float)},
-                                           {(void**)&h->idB, tot * sizeof(float)},
-                                           {(void**)&h->wsB, tot * sizeof(float)},
-                                           {(void**)&h->pc, tot * sizeof(Pc)},
-                                           {(void**)&h->d_pc_n, 8 * sizeof(int32_t)},
-                                           {(void**)&h->block_cnt, (size_t)h->max_blocks * sizeof(int32_t)},
-                                           {(void**)&h->first, px0 * sizeof(int32_t)},
-                                           {(void**)&h->last, px0 * sizeof(int32_t)},
-                                           {(void**)&h->pix, mp * sizeof(int32_t)},
-                                           {(void**)&h->dropped, sizeof(int32_t)},
-                                           {(void**)&h->in_img, px0 * sizeof(float)},
-                                           {(void**)&h->in_cp, mp * 3 * sizeof(float)},
-                                           {(void**)&h->in_hdif, mp * sizeof(float)},
-                                           {(void**)&h->wgt, mp * sizeof(float)},
-                                           {(void**)&h->d_out, (size_t)max_tries * sizeof(TrackOut)},
-                                           {(void**)&h->d_T, (size_t)max_tries * 12 * sizeof(double)},
-                                           {(void**)&h->d_aff, (size_t)max_tries * 2 * sizeof(double)},
-                                           {(void**)&h->d_min_res, 5 * sizeof(double)},
-                                           {(void**)&h->d_calc, 78 * sizeof(double)},
-                                           {(void**)&h->d_rows, px0 * sizeof(Term)}});
-    if (!ok || hipMemsetAsync(h->d_pc_n, 0, 8 * sizeof(int32_t), h->st) != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess) {
+    const bool ok = h->own.alloc({{(void**)&h->d_geo, sizeof(Geo)},
+                                  {(void**)&h->ref_px, tot * sizeof(Px)},
+                                  {(void**)&h->new_px, tot * sizeof(Px)},
+                                  {(void**)&h->idA, tot * sizeof(float)},
+                                  {(void**)&h->wsA, tot * sizeof(float)},
+                                  {(void**)&h->idB, tot * sizeof(float)},
+                                  {(void**)&h->wsB, tot * sizeof(float)},
+                                  {(void**)&h->pc, tot * sizeof(Pc)},
+                                  {(void**)&h->d_pc_n, 8 * sizeof(int32_t)},
+                                  {(void**)&h->block_cnt, (size_t)h->max_blocks * sizeof(int32_t)},
+                                  {(void**)&h->first, px0 * sizeof(int32_t)},
+                                  {(void**)&h->last, px0 * sizeof(int32_t)},
+                                  {(void**)&h->pix, mp * sizeof(int32_t)},
+                                  {(void**)&h->dropped, sizeof(int32_t)},
+                                  {(void**)&h->in_img, px0 * sizeof(float)},
+                                  {(void**)&h->in_cp, mp * 3 * sizeof(float)},
+                                  {(void**)&h->in_hdif, mp * sizeof(float)},
+                                  {(void**)&h->wgt, mp * sizeof(float)},
+                                  {(void**)&h->d_out, (size_t)max_tries * sizeof(TrackOut)},
+                                  {(void**)&h->d_T, (size_t)max_tries * 12 * sizeof(double)},
+                                  {(void**)&h->d_aff, (size_t)max_tries * 2 * sizeof(double)},
+                                  {(void**)&h->d_min_res, 5 * sizeof(double)},
+                                  {(void**)&h->d_calc, 78 * sizeof(double)},
+                                  {(void**)&h->d_rows, px0 * sizeof(Term)}});
+    if (!ok || hipMemsetAsync(h->d_pc_n, 0, 8 * sizeof(int32_t), h->own.st) != hipSuccess || hipStreamSynchronize(h->own.st) != hipSuccess) {
         (void)hipGetLastError();
         eds_ct_destroy(h);
         return fail(EDS_ERR_HIP, "eds_ct_create: the device refused a stream or an allocation");
@@ -461,16 +434,12 @@ int eds_ct_create(int device, int H, int W, int levels, int max_points, int max_
 
 void eds_ct_destroy(eds_ct* h) {
     if (!h) return;
-    (void)hipSetDevice(h->dev);
-    if (h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
-    void* all[] = {h->d_geo, h->ref_px, h->new_px, h->idA, h->wsA, h->idB, h->wsB, h->pc, h->d_pc_n, h->block_cnt, h->first, h->last, h->pix,
-                   h->dropped, h->in_img, h->in_cp, h->in_hdif, h->wgt, h->d_out, h->d_T, h->d_aff, h->d_min_res, h->d_calc, h->d_rows};
-    for (void* p : all) if (p) (void)hipFree(p);
+    h->own.close();
     delete h;
 }
 
 int eds_ct_set_params(eds_ct* h, const eds_ct_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null parameters");
     Params s;
     std::memcpy(&s, p, sizeof(s));
@@ -480,28 +449,27 @@ int eds_ct_set_params(eds_ct* h, const eds_ct_params* p) {
 }
 
 int eds_ct_get_params(const eds_ct* h, eds_ct_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null output");
     std::memcpy(p, &h->prm, sizeof(*p));
     return EDS_OK;
 }
 
 int eds_ct_set_calib(eds_ct* h, float fx, float fy, float cx, float cy) {
-    if (int rc = check_handle(h)) return rc;
-    if (!(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy)) || !(fx > 0.0f) || !(fy > 0.0f))
-        return fail(EDS_ERR_INVALID, "calibration: fx, fy, cx, cy finite, fx and fy > 0");
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
+    if (!edscapi::check_calib(fx, fy, cx, cy)) return fail(EDS_ERR_INVALID, "calibration: fx, fy, cx, cy finite, fx and fy > 0");
     Geo g = h->geo;
     edsct::make_k(g, fx, fy, cx, cy);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(h->d_geo, &g, sizeof(g), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipMemcpyAsync(h->d_geo, &g, sizeof(g), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     h->geo = g;
     h->calib_set = true;
     return EDS_OK;
 }
 
 int eds_ct_get_k(const eds_ct* h, int lvl, float* K) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (int rc = check_level(h, lvl)) return rc;
     if (!K) return fail(EDS_ERR_INVALID, "null output");
     if (!h->calib_set) return fail(EDS_ERR_STATE, "eds_ct: no calibration set");
@@ -512,40 +480,40 @@ int eds_ct_get_k(const eds_ct* h, int lvl, float* K) {
 
 int eds_ct_set_ref(eds_ct* h, const float* image, int64_t row_stride, int on_device, float exposure, double aff_a, double aff_b, int n,
                    const float* center_projected, const float* hdif, int32_t* pc_n_out, int32_t* dropped_out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (!h->calib_set) return fail(EDS_ERR_STATE, "eds_ct: no calibration set");
     if (n < 0 || n > h->max_points) return fail(EDS_ERR_INVALID, std::to_string(n) + " contributions, the handle holds 0 .. " + std::to_string(h->max_points));
     if (n > 0 && (!center_projected || !hdif)) return fail(EDS_ERR_INVALID, "center_projected and hdif are required");
     if (!std::isfinite(exposure) || !std::isfinite(aff_a) || !std::isfinite(aff_b)) return fail(EDS_ERR_INVALID, "exposure and the affine pair must be finite");
-    if (int rc = check_frame(h, image, &row_stride, on_device)) return rc;
+    if (int rc = edscapi::check_images(h->own.dev, h->geo.H, h->geo.W, 1, image, &row_stride, nullptr, on_device, "image")) return rc;
     h->ref_set = false;
     if (int rc = load_frame(h, h->ref_px, image, row_stride, on_device)) return rc;
     const Geo& g = h->geo;
     const size_t px0 = (size_t)g.W * g.H;
-    EDS_HIP_TRY(hipMemsetAsync(h->idA, 0, px0 * sizeof(float), h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->wsA, 0, px0 * sizeof(float), h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->first, 0x7f, px0 * sizeof(int32_t), h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->last, 0xff, px0 * sizeof(int32_t), h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->dropped, 0, sizeof(int32_t), h->st));
+    EDS_HIP_TRY(hipMemsetAsync(h->idA, 0, px0 * sizeof(float), h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->wsA, 0, px0 * sizeof(float), h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->first, 0x7f, px0 * sizeof(int32_t), h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->last, 0xff, px0 * sizeof(int32_t), h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->dropped, 0, sizeof(int32_t), h->own.st));
     if (n > 0) {
-        EDS_HIP_TRY(hipMemcpyAsync(h->in_cp, center_projected, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->in_hdif, hdif, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->in_cp, center_projected, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->in_hdif, hdif, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
         for (int pass = 0; pass < 2; ++pass)
-            hipLaunchKernelGGL(k_ct_splat, dim3(blocks(n)), dim3(TB), 0, h->st, pass, n, h->in_cp, h->in_hdif, g.W, g.H, h->pix, h->wgt, h->first,
+            hipLaunchKernelGGL(k_ct_splat, dim3(blocks(n)), dim3(TB), 0, h->own.st, pass, n, h->in_cp, h->in_hdif, g.W, g.H, h->pix, h->wgt, h->first,
                                h->last, h->dropped, h->idA, h->wsA);
     }
     for (int l = 1; l < g.levels; ++l)
-        hipLaunchKernelGGL(k_ct_levels, dim3(blocks(g.l[l].w * g.l[l].h)), dim3(TB), 0, h->st, h->idA, h->wsA, h->d_geo, l);
+        hipLaunchKernelGGL(k_ct_levels, dim3(blocks(g.l[l].w * g.l[l].h)), dim3(TB), 0, h->own.st, h->idA, h->wsA, h->d_geo, l);
     for (int l = 0; l < g.levels; ++l) {
         const unsigned nb = blocks(g.l[l].w * g.l[l].h);
-        hipLaunchKernelGGL(k_ct_dilate, dim3(nb), dim3(TB), 0, h->st, h->idA, h->wsA, h->idB, h->wsB, h->ref_px, h->d_geo, l, h->block_cnt);
-        hipLaunchKernelGGL(k_ct_select, dim3(nb), dim3(TB), 0, h->st, h->idB, h->ref_px, h->pc, h->d_pc_n, h->block_cnt, h->d_geo, l);
+        hipLaunchKernelGGL(k_ct_dilate, dim3(nb), dim3(TB), 0, h->own.st, h->idA, h->wsA, h->idB, h->wsB, h->ref_px, h->d_geo, l, h->block_cnt);
+        hipLaunchKernelGGL(k_ct_select, dim3(nb), dim3(TB), 0, h->own.st, h->idB, h->ref_px, h->pc, h->d_pc_n, h->block_cnt, h->d_geo, l);
     }
     EDS_HIP_TRY(hipGetLastError());
     int32_t back[6] = {0, 0, 0, 0, 0, 0};
-    EDS_HIP_TRY(hipMemcpyAsync(back, h->d_pc_n, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(back + 5, h->dropped, sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(back, h->d_pc_n, 5 * sizeof(int32_t), hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(back + 5, h->dropped, sizeof(int32_t), hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     for (int l = 0; l < edsct::MAX_LEVELS; ++l) h->pc_n[l] = l < g.levels ? back[l] : 0;
     if (pc_n_out) for (int l = 0; l < g.levels; ++l) pc_n_out[l] = back[l];
     if (dropped_out) *dropped_out = back[5];
@@ -555,12 +523,12 @@ int eds_ct_set_ref(eds_ct* h, const float* image, int64_t row_stride, int on_dev
 }
 
 int eds_ct_set_new(eds_ct* h, const float* image, int64_t row_stride, int on_device, float exposure) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (!std::isfinite(exposure)) return fail(EDS_ERR_INVALID, "exposure must be finite");
-    if (int rc = check_frame(h, image, &row_stride, on_device)) return rc;
+    if (int rc = edscapi::check_images(h->own.dev, h->geo.H, h->geo.W, 1, image, &row_stride, nullptr, on_device, "image")) return rc;
     h->new_set = false;
     if (int rc = load_frame(h, h->new_px, image, row_stride, on_device)) return rc;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     h->ph.exposure_new = exposure;
     h->new_set = true;
     return EDS_OK;
@@ -568,49 +536,49 @@ int eds_ct_set_new(eds_ct* h, const float* image, int64_t row_stride, int on_dev
 
 int eds_ct_track(eds_ct* h, int count, const double* T_init, const double* aff_init, int coarsest_lvl, const double* min_res_for_abort,
                  eds_ct_result* results) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (count < 1 || count > h->max_tries) return fail(EDS_ERR_INVALID, std::to_string(count) + " tries, the handle holds 1 .. " + std::to_string(h->max_tries));
     if (!T_init || !aff_init || !min_res_for_abort || !results) return fail(EDS_ERR_INVALID, "T_init, aff_init, min_res_for_abort and results are required");
     if (int rc = check_level(h, coarsest_lvl)) return rc;
     if (!all_finite_d(T_init, 12 * count) || !all_finite_d(aff_init, 2 * count)) return fail(EDS_ERR_INVALID, "T_init or aff_init is not finite");
     if (int rc = check_ready(h)) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(h->d_T, T_init, (size_t)count * 12 * sizeof(double), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(h->d_aff, aff_init, (size_t)count * 2 * sizeof(double), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(h->d_min_res, min_res_for_abort, 5 * sizeof(double), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->d_out, 0, (size_t)count * sizeof(TrackOut), h->st));
-    hipLaunchKernelGGL(k_ct_track, dim3((unsigned)count), dim3(edsct::LANES), 0, h->st, h->d_geo, h->prm, h->ph, h->new_px, h->pc, h->d_pc_n, h->d_T,
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipMemcpyAsync(h->d_T, T_init, (size_t)count * 12 * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->d_aff, aff_init, (size_t)count * 2 * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->d_min_res, min_res_for_abort, 5 * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->d_out, 0, (size_t)count * sizeof(TrackOut), h->own.st));
+    hipLaunchKernelGGL(k_ct_track, dim3((unsigned)count), dim3(edsct::LANES), 0, h->own.st, h->d_geo, h->prm, h->ph, h->new_px, h->pc, h->d_pc_n, h->d_T,
                        h->d_aff, coarsest_lvl, h->d_min_res, h->d_out);
     EDS_HIP_TRY(hipGetLastError());
     std::vector<TrackOut> back((size_t)count);
-    EDS_HIP_TRY(hipMemcpyAsync(back.data(), h->d_out, back.size() * sizeof(TrackOut), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(back.data(), h->d_out, back.size() * sizeof(TrackOut), hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     std::memcpy(results, back.data(), back.size() * sizeof(TrackOut));
     return EDS_OK;
 }
 
 int eds_ct_calc_res(eds_ct* h, int lvl, const double* T, const double* aff, float cutoff, double* rs_out, double* H_out, double* b_out,
                     eds_ct_row* rows_out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (int rc = check_level(h, lvl)) return rc;
     if (!T || !aff) return fail(EDS_ERR_INVALID, "T and aff are required");
     if (!all_finite_d(T, 12) || !all_finite_d(aff, 2) || !std::isfinite(cutoff)) return fail(EDS_ERR_INVALID, "T, aff or the cutoff is not finite");
     if (int rc = check_ready(h)) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(h->d_T, T, 12 * sizeof(double), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(h->d_aff, aff, 2 * sizeof(double), hipMemcpyHostToDevice, h->st));
-    hipLaunchKernelGGL(k_ct_calc, dim3(1), dim3(edsct::LANES), 0, h->st, h->d_geo, h->prm, h->ph, h->new_px, h->pc, h->d_pc_n, lvl, h->d_T, h->d_aff,
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipMemcpyAsync(h->d_T, T, 12 * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->d_aff, aff, 2 * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    hipLaunchKernelGGL(k_ct_calc, dim3(1), dim3(edsct::LANES), 0, h->own.st, h->d_geo, h->prm, h->ph, h->new_px, h->pc, h->d_pc_n, lvl, h->d_T, h->d_aff,
                        cutoff, h->d_calc);
     const int n = h->pc_n[lvl];
     if (rows_out && n > 0)
-        hipLaunchKernelGGL(k_ct_rows, dim3(blocks(n)), dim3(TB), 0, h->st, h->d_geo, h->prm, h->ph, h->new_px, h->pc, h->d_pc_n, lvl, h->d_T,
+        hipLaunchKernelGGL(k_ct_rows, dim3(blocks(n)), dim3(TB), 0, h->own.st, h->d_geo, h->prm, h->ph, h->new_px, h->pc, h->d_pc_n, lvl, h->d_T,
                            h->d_aff, cutoff, h->d_rows);
     EDS_HIP_TRY(hipGetLastError());
     double back[78];
     std::vector<Term> rows(rows_out ? (size_t)n : 0);
-    EDS_HIP_TRY(hipMemcpyAsync(back, h->d_calc, sizeof(back), hipMemcpyDeviceToHost, h->st));
-    if (!rows.empty()) EDS_HIP_TRY(hipMemcpyAsync(rows.data(), h->d_rows, rows.size() * sizeof(Term), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(back, h->d_calc, sizeof(back), hipMemcpyDeviceToHost, h->own.st));
+    if (!rows.empty()) EDS_HIP_TRY(hipMemcpyAsync(rows.data(), h->d_rows, rows.size() * sizeof(Term), hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     if (rs_out) std::memcpy(rs_out, back, 6 * sizeof(double));
     if (H_out) std::memcpy(H_out, back + 6, 64 * sizeof(double));
     if (b_out) std::memcpy(b_out, back + 70, 8 * sizeof(double));
@@ -619,34 +587,28 @@ int eds_ct_calc_res(eds_ct* h, int lvl, const double* T, const double* aff, floa
 }
 
 int eds_ct_get_level(eds_ct* h, int which, int lvl, float* out, int32_t* n_out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_ct")) return rc;
     if (int rc = check_level(h, lvl)) return rc;
     if (which < EDS_CT_REF_IMAGE || which > EDS_CT_PC) return fail(EDS_ERR_INVALID, "which is EDS_CT_REF_IMAGE .. EDS_CT_PC");
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     if (which == EDS_CT_NEW_IMAGE ? !h->new_set : !h->ref_set) return fail(EDS_ERR_STATE, "eds_ct: that frame was never set");
     const Level& L = h->geo.l[lvl];
     const size_t px = (size_t)L.w * L.h;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
     if (which == EDS_CT_REF_IMAGE || which == EDS_CT_NEW_IMAGE) {
         std::vector<Px> p(px);
-        EDS_HIP_TRY(hipMemcpyAsync(p.data(), (which == EDS_CT_REF_IMAGE ? h->ref_px : h->new_px) + L.off, px * sizeof(Px), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        if (int rc = edscapi::read_back(h->own, p.data(), (which == EDS_CT_REF_IMAGE ? h->ref_px : h->new_px) + L.off, px * sizeof(Px))) return rc;
         for (size_t i = 0; i < px; ++i) { out[3 * i] = p[i].c; out[3 * i + 1] = p[i].dx; out[3 * i + 2] = p[i].dy; }
         if (n_out) *n_out = (int32_t)px;
     } else if (which == EDS_CT_IDEPTH || which == EDS_CT_WEIGHT_SUMS) {
         std::vector<float> p(px);
-        EDS_HIP_TRY(hipMemcpyAsync(p.data(), (which == EDS_CT_IDEPTH ? h->idB : h->wsB) + L.off, px * sizeof(float), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        if (int rc = edscapi::read_back(h->own, p.data(), (which == EDS_CT_IDEPTH ? h->idB : h->wsB) + L.off, px * sizeof(float))) return rc;
         std::memcpy(out, p.data(), px * sizeof(float));
         if (n_out) *n_out = (int32_t)px;
     } else {
         const size_t n = (size_t)h->pc_n[lvl];
         std::vector<Pc> p(n);
-        if (n) {
-            EDS_HIP_TRY(hipMemcpyAsync(p.data(), h->pc + L.off, n * sizeof(Pc), hipMemcpyDeviceToHost, h->st));
-            EDS_HIP_TRY(hipStreamSynchronize(h->st));
-            std::memcpy(out, p.data(), n * sizeof(Pc));
-        }
+        if (int rc = edscapi::read_back(h->own, p.data(), h->pc + L.off, n * sizeof(Pc))) return rc;
+        if (n) std::memcpy(out, p.data(), n * sizeof(Pc));
         if (n_out) *n_out = (int32_t)n;
     }
     return EDS_OK;

@@ -16,7 +16,6 @@
 #include <string>
 #include <vector>
 
-#include "../../include/eds_hip_device.h"
 #include "../../include/eds_hip_immature.h"
 #include "eds_capi_internal.hpp"
 #include "eds_immature.hpp"
@@ -24,6 +23,7 @@
 #include "eds_pixsel_internal.hpp"
 
 using edscapi::fail;
+using edscapi::read_back;
 using edsimm::Frame;
 using edsimm::Grad;
 using edsimm::Line;
@@ -174,41 +174,29 @@ __global__ void __launch_bounds__(256) k_imm_summary(const Point* __restrict__ p
     if (threadIdx.x < edsimm::NUM_STATUS) out[blockIdx.x * edsimm::NUM_STATUS + threadIdx.x] = cnt[threadIdx.x];
 }
 
-int check_handle(const eds_imm* h) { return h ? EDS_OK : fail(EDS_ERR_INVALID, "null eds_imm handle"); }
-
 int check_host(const eds_imm* h, int host) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (host < 0 || host >= h->max_hosts) return fail(EDS_ERR_INVALID, "host " + std::to_string(host) + " outside 0 .. " + std::to_string(h->max_hosts - 1));
     return EDS_OK;
 }
 
 int set_images(eds_imm* h, bool target, int first, int count, const float* images, int64_t fs, int64_t rs, int on_device) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     const int cap = target ? h->max_targets : h->max_hosts;
     if (first < 0 || count < 1 || first > cap - count)
         return fail(EDS_ERR_INVALID, "frames " + std::to_string(first) + " .. +" + std::to_string(count) + " outside 0 .. " + std::to_string(cap - 1));
-    if (!images) return fail(EDS_ERR_INVALID, "images: NULL pointer");
-    if (on_device != 0 && on_device != 1) return fail(EDS_ERR_INVALID, "on_device is 0 or 1");
     const int H = h->H, W = h->W;
-    if (rs == 0) rs = W;
-    if (fs == 0) fs = (int64_t)H * rs;
-    if (rs < W || fs < (int64_t)(H - 1) * rs + W || rs > (int64_t)1 << 30 || fs > (int64_t)1 << 40) return fail(EDS_ERR_INVALID, "bad image strides");
-    if (reinterpret_cast<uintptr_t>(images) % sizeof(float)) return fail(EDS_ERR_INVALID, "images: not aligned to 4 bytes");
-    if (on_device) {
-        const size_t bytes = (size_t)((int64_t)(count - 1) * fs + (int64_t)(H - 1) * rs + W) * sizeof(float);
-        if (int rc = eds_dev_check_range(h->dev, images, bytes)) return rc;
-    }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    if (int rc = edscapi::check_images(h->own.dev, H, W, count, images, &rs, &fs, on_device, "images", "bad image strides")) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t px = (size_t)W * H;
     float* c = (target ? h->target_c : h->host_c) + px * first;
     Grad* g = (target ? h->target_g : h->host_g) + px * first;
     for (int b = 0; b < count; ++b)
-        EDS_HIP_TRY(hipMemcpy2DAsync(c + px * b, (size_t)W * sizeof(float), images + (int64_t)b * fs, (size_t)rs * sizeof(float),
-                                     (size_t)W * sizeof(float), (size_t)H, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->st));
+        if (int rc = edscapi::upload_image(h->own, c + px * b, H, W, images + (int64_t)b * fs, rs, on_device)) return rc;
     const int64_t total = (int64_t)px * count;
-    hipLaunchKernelGGL(k_imm_gradient, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->st, c, g, W, H, count);
+    hipLaunchKernelGGL(k_imm_gradient, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->own.st, c, g, W, H, count);
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     std::vector<uint8_t>& set = target ? h->target_set : h->host_set;
     for (int b = 0; b < count; ++b) set[first + b] = 1;
     if (!target) edsimm_internal::act_invalidate(h);
@@ -218,23 +206,18 @@ int set_images(eds_imm* h, bool target, int first, int count, const float* image
 // the points of `host` on the host; waits
 int read_points(eds_imm* h, int host, std::vector<Point>& out) {
     out.resize((size_t)h->n[host]);
-    if (out.empty()) return EDS_OK;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(out.data(), h->points + (size_t)host * h->max_points, out.size() * sizeof(Point), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return read_back(h->own, out.data(), h->points + (size_t)host * h->max_points, out.size() * sizeof(Point));
 }
 
 // the constructor kernel over the n staged inputs (in_uv, in_type, and in_idepth, in_distance for the second constructor)
 int construct_staged(eds_imm* h, int host, int n, bool has_depth, uint8_t* alive_out) {
     h->n[host] = 0;                                     // what the host held is gone once the kernel is queued
-    hipLaunchKernelGGL(k_imm_construct, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->st, h->points + (size_t)host * h->max_points,
+    hipLaunchKernelGGL(k_imm_construct, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->own.st, h->points + (size_t)host * h->max_points,
                        h->host_c + (size_t)h->W * h->H * host, h->W, h->H, h->prm, n, h->in_uv, h->in_type, h->in_idepth, h->in_distance,
                        has_depth ? 1 : 0, h->in_alive);
     EDS_HIP_TRY(hipGetLastError());
     std::vector<uint8_t> alive((size_t)n);
-    EDS_HIP_TRY(hipMemcpyAsync(alive.data(), h->in_alive, (size_t)n, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, alive.data(), h->in_alive, (size_t)n)) return rc;
     if (alive_out) std::memcpy(alive_out, alive.data(), (size_t)n);
     h->n[host] = n;
     return EDS_OK;
@@ -263,35 +246,27 @@ int eds_imm_create(int device, int H, int W, int max_hosts, int max_points_per_h
     if (H < 8 || W < 8 || H > 16384 || W > 16384) return fail(EDS_ERR_INVALID, "H and W are 8 .. 16384");
     if (max_hosts < 1 || max_points_per_host < 1 || max_targets < 1 || max_hosts > 4096 || max_targets > 4096 || max_points_per_host > (1 << 22))
         return fail(EDS_ERR_INVALID, "max_hosts and max_targets are 1 .. 4096, max_points_per_host 1 .. 4194304");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return fail(EDS_ERR_NO_DEVICE, "no HIP device");
-    }
-    if (device < 0 || device >= ndev) return fail(EDS_ERR_INVALID, "device " + std::to_string(device) + " of " + std::to_string(ndev));
-    EDS_HIP_TRY(hipSetDevice(device));
     eds_imm* h = new eds_imm;
-    h->dev = device; h->H = H; h->W = W; h->max_hosts = max_hosts; h->max_points = max_points_per_host; h->max_targets = max_targets;
+    if (int rc = h->own.open(device)) { delete h; return rc; }
+    h->H = H; h->W = W; h->max_hosts = max_hosts; h->max_points = max_points_per_host; h->max_targets = max_targets;
     h->prm = edsimm::params_default();
     h->n.assign(max_hosts, 0);
     h->host_set.assign(max_hosts, 0);
     h->target_set.assign(max_targets, 0);
     const size_t px = (size_t)H * W, mp = (size_t)max_points_per_host;
-    const bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess &&
-                    edscapi::device_alloc({{(void**)&h->host_c, px * max_hosts * sizeof(float)},
-                                           {(void**)&h->host_g, px * max_hosts * sizeof(Grad)},
-                                           {(void**)&h->target_c, px * max_targets * sizeof(float)},
-                                           {(void**)&h->target_g, px * max_targets * sizeof(Grad)},
-                                           {(void**)&h->points, mp * max_hosts * sizeof(Point)},
-                                           {(void**)&h->pre, (size_t)max_hosts * sizeof(Pre)},
-                                           {(void**)&h->summary, (size_t)max_hosts * edsimm::NUM_STATUS * sizeof(int32_t)},
-                                           {(void**)&h->in_distance, mp * sizeof(double)},
-                                           {(void**)&h->in_uv, mp * 2 * sizeof(int32_t)},
-                                           {(void**)&h->in_type, mp * sizeof(float)},
-                                           {(void**)&h->in_idepth, mp * sizeof(float)},
-                                           {(void**)&h->in_alive, mp}});
+    const bool ok = h->own.alloc({{(void**)&h->host_c, px * max_hosts * sizeof(float)},
+                                  {(void**)&h->host_g, px * max_hosts * sizeof(Grad)},
+                                  {(void**)&h->target_c, px * max_targets * sizeof(float)},
+                                  {(void**)&h->target_g, px * max_targets * sizeof(Grad)},
+                                  {(void**)&h->points, mp * max_hosts * sizeof(Point)},
+                                  {(void**)&h->pre, (size_t)max_hosts * sizeof(Pre)},
+                                  {(void**)&h->summary, (size_t)max_hosts * edsimm::NUM_STATUS * sizeof(int32_t)},
+                                  {(void**)&h->in_distance, mp * sizeof(double)},
+                                  {(void**)&h->in_uv, mp * 2 * sizeof(int32_t)},
+                                  {(void**)&h->in_type, mp * sizeof(float)},
+                                  {(void**)&h->in_idepth, mp * sizeof(float)},
+                                  {(void**)&h->in_alive, mp}});
     if (!ok) {
-        (void)hipGetLastError();
         eds_imm_destroy(h);
         return fail(EDS_ERR_HIP, "eds_imm_create: the device refused a stream or an allocation");
     }
@@ -301,17 +276,13 @@ int eds_imm_create(int device, int H, int W, int max_hosts, int max_points_per_h
 
 void eds_imm_destroy(eds_imm* h) {
     if (!h) return;
-    (void)hipSetDevice(h->dev);
-    if (h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
+    h->own.close();
     edsimm_internal::act_release(h);
-    void* all[] = {h->host_c, h->host_g, h->target_c, h->target_g, h->points, h->pre, h->summary, h->in_distance, h->in_uv, h->in_type,
-                   h->in_idepth, h->in_alive};
-    for (void* p : all) if (p) (void)hipFree(p);
     delete h;
 }
 
 int eds_imm_set_params(eds_imm* h, const eds_imm_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null parameters");
     Params s;
     std::memcpy(&s, p, sizeof(s));
@@ -323,7 +294,7 @@ int eds_imm_set_params(eds_imm* h, const eds_imm_params* p) {
 }
 
 int eds_imm_get_params(const eds_imm* h, eds_imm_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null output");
     std::memcpy(p, &h->prm, sizeof(*p));
     return EDS_OK;
@@ -347,12 +318,12 @@ int eds_imm_create_points(eds_imm* h, int host, int n, const int32_t* uv, const 
     if (!h->host_set[host]) return fail(EDS_ERR_STATE, "host " + std::to_string(host) + " has no image");
     edsimm_internal::act_invalidate(h);
     if (n == 0) { h->n[host] = 0; return EDS_OK; }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(h->in_uv, uv, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(h->in_type, type, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipMemcpyAsync(h->in_uv, uv, (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->in_type, type, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
     if (idepth) {
-        EDS_HIP_TRY(hipMemcpyAsync(h->in_idepth, idepth, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->in_distance, distance, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->in_idepth, idepth, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->in_distance, distance, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->own.st));
     }
     return construct_staged(h, host, n, idepth != nullptr, alive_out);
 }
@@ -361,20 +332,19 @@ int eds_imm_create_points_selected(eds_imm* h, int host, const eds_sel* sel, int
                                    int* n_out) {
     if (int rc = check_host(h, host)) return rc;
     if (!sel) return fail(EDS_ERR_INVALID, "null eds_sel handle");
-    if (sel->H != h->H || sel->W != h->W || sel->dev != h->dev) return fail(EDS_ERR_INVALID, "the selector and the points differ in H, W or device");
+    if (sel->H != h->H || sel->W != h->W || sel->own.dev != h->own.dev) return fail(EDS_ERR_INVALID, "the selector and the points differ in H, W or device");
     if (x_min < 0 || y_min < 0 || x_max >= h->W || y_max >= h->H || x_min > x_max || y_min > y_max)
         return fail(EDS_ERR_INVALID, "the rectangle lies inside the image, min <= max");
     if (!sel->sel_valid) return fail(EDS_ERR_STATE, "no selection: eds_sel_make_maps first");
     if (!h->host_set[host]) return fail(EDS_ERR_STATE, "host " + std::to_string(host) + " has no image");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     int32_t n = 0;
     if (sel->n_sel > 0) {
         // the staging buffers hold nothing a caller can see; the selector's calls have returned, so its list is complete
-        hipLaunchKernelGGL(k_imm_filter_rect, dim3(1), dim3(256), 0, h->st, sel->uv, sel->type, sel->n_sel, x_min, y_min, x_max, y_max, h->max_points,
+        hipLaunchKernelGGL(k_imm_filter_rect, dim3(1), dim3(256), 0, h->own.st, sel->uv, sel->type, sel->n_sel, x_min, y_min, x_max, y_max, h->max_points,
                            h->in_uv, h->in_type, h->summary);
         EDS_HIP_TRY(hipGetLastError());
-        EDS_HIP_TRY(hipMemcpyAsync(&n, h->summary, sizeof(n), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        if (int rc = read_back(h->own, &n, h->summary, sizeof(n))) return rc;
     }
     if (n > h->max_points)
         return fail(EDS_ERR_INVALID, std::to_string(n) + " selected points, the handle holds 0 .. " + std::to_string(h->max_points) + " per host");
@@ -393,7 +363,7 @@ int eds_imm_num_points(const eds_imm* h, int host, int* n) {
 
 int eds_imm_trace(eds_imm* h, int first_host, int count, const int32_t* target_index, const float* KRKi, const float* Kt, const float* aff,
                   int32_t* summary_out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (first_host < 0 || count < 1 || first_host > h->max_hosts - count)
         return fail(EDS_ERR_INVALID, "hosts " + std::to_string(first_host) + " .. +" + std::to_string(count) + " outside 0 .. " + std::to_string(h->max_hosts - 1));
     if (!target_index || !KRKi || !Kt || !aff) return fail(EDS_ERR_INVALID, "target_index, KRKi, Kt and aff are required");
@@ -414,22 +384,22 @@ int eds_imm_trace(eds_imm* h, int first_host, int count, const int32_t* target_i
         pre[b].n = h->n[first_host + b];
         if (pre[b].n > max_n) max_n = pre[b].n;
     }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(h->pre, pre.data(), pre.size() * sizeof(Pre), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipMemcpyAsync(h->pre, pre.data(), pre.size() * sizeof(Pre), hipMemcpyHostToDevice, h->own.st));
     constexpr int per_wg = TRACE_THREADS / WAVE;
     if (max_n > 0) {
-        hipLaunchKernelGGL(k_imm_trace, dim3((unsigned)((max_n + per_wg - 1) / per_wg), (unsigned)count), dim3(TRACE_THREADS), 0, h->st, h->points,
+        hipLaunchKernelGGL(k_imm_trace, dim3((unsigned)((max_n + per_wg - 1) / per_wg), (unsigned)count), dim3(TRACE_THREADS), 0, h->own.st, h->points,
                            h->max_points, first_host, h->pre, h->target_c, h->target_g, h->W, h->H, h->prm);
         EDS_HIP_TRY(hipGetLastError());
     }
     std::vector<int32_t> summary;
     if (summary_out) {
-        hipLaunchKernelGGL(k_imm_summary, dim3((unsigned)count), dim3(256), 0, h->st, h->points, h->max_points, first_host, h->pre, h->summary);
+        hipLaunchKernelGGL(k_imm_summary, dim3((unsigned)count), dim3(256), 0, h->own.st, h->points, h->max_points, first_host, h->pre, h->summary);
         EDS_HIP_TRY(hipGetLastError());
         summary.resize((size_t)count * edsimm::NUM_STATUS);
-        EDS_HIP_TRY(hipMemcpyAsync(summary.data(), h->summary, summary.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(summary.data(), h->summary, summary.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->own.st));
     }
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     if (summary_out) std::memcpy(summary_out, summary.data(), summary.size() * sizeof(int32_t));
     return EDS_OK;
 }
@@ -467,7 +437,7 @@ int eds_imm_get_points(eds_imm* h, int host, float* color, float* weights, float
 }
 
 int eds_imm_get_image(eds_imm* h, int which, int index, float* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_imm")) return rc;
     if (which != EDS_IMM_HOST_IMAGE && which != EDS_IMM_TARGET_IMAGE) return fail(EDS_ERR_INVALID, "which is EDS_IMM_HOST_IMAGE or EDS_IMM_TARGET_IMAGE");
     const bool target = which == EDS_IMM_TARGET_IMAGE;
     const int cap = target ? h->max_targets : h->max_hosts;
@@ -477,10 +447,8 @@ int eds_imm_get_image(eds_imm* h, int which, int index, float* out) {
     const size_t px = (size_t)h->W * h->H;
     std::vector<float> c(px);
     std::vector<Grad> g(px);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(c.data(), (target ? h->target_c : h->host_c) + px * index, px * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(g.data(), (target ? h->target_g : h->host_g) + px * index, px * sizeof(Grad), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, c.data(), (target ? h->target_c : h->host_c) + px * index, px * sizeof(float))) return rc;
+    if (int rc = read_back(h->own, g.data(), (target ? h->target_g : h->host_g) + px * index, px * sizeof(Grad))) return rc;
     for (size_t i = 0; i < px; ++i) { out[3 * i] = c[i]; out[3 * i + 1] = g[i].x; out[3 * i + 2] = g[i].y; }
     return EDS_OK;
 }

@@ -7,10 +7,11 @@
 #include <vector>
 
 #include "eds_activate.hpp"
+#include "eds_device_owner.hpp"
 #include "eds_immature.hpp"
 
-// include/eds_hip_activate.h's part of an eds_imm: the first eds_act_* call that needs it allocates it, eds_imm_destroy releases it
-// (act_release)
+// include/eds_hip_activate.h's part of an eds_imm: the first eds_act_* call that needs it allocates it through the eds_imm's owner, which
+// frees the device memory with the handle; act_release deletes the struct
 struct eds_act_state {
     edsact::Params prm;
     edsact::Calib cal;
@@ -32,9 +33,9 @@ struct eds_act_state {
 };
 
 struct eds_imm {
-    int dev = 0, H = 0, W = 0, max_hosts = 0, max_points = 0, max_targets = 0;
+    edscapi::DeviceOwner own;
+    int H = 0, W = 0, max_hosts = 0, max_points = 0, max_targets = 0;
     edsimm::Params prm;
-    hipStream_t st = nullptr;
     float *host_c = nullptr, *target_c = nullptr;      // [frames][H][W]
     edsimm::Grad *host_g = nullptr, *target_g = nullptr;
     edsimm::Point* points = nullptr;                   // [max_hosts][max_points]

@@ -19,13 +19,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/eds_hip_device.h"
 #include "../../include/eds_hip_select.h"
 #include "eds_capi_internal.hpp"
 #include "eds_pixsel.hpp"
 #include "eds_pixsel_internal.hpp"
 
+using edscapi::blocks;
 using edscapi::fail;
+using edscapi::read_back;
 using edspix::Block;
 using edspix::Geo;
 using edspix::Key;
@@ -209,23 +210,19 @@ __global__ void __launch_bounds__(TB) k_sel_rank(uint8_t* __restrict__ map, cons
     }
 }
 
-int check_handle(const eds_sel* h) { return h ? EDS_OK : fail(EDS_ERR_INVALID, "null eds_sel handle"); }
-unsigned blocks(int64_t n) { return (unsigned)((n + TB - 1) / TB); }
-
 // one select pass at `potential`; n[3] = n2, n3, n4 on the host
 int select_pass(eds_sel* h, int potential, float thf, int32_t* n) {
     const Sel S = edspix::make_sel(h->lv[0], h->lv[1], h->lv[2], h->ths_s, h->g, h->prm, thf, potential);
     const int nb = S.nbx * S.nby, ns = nb * SLOTS, wh = h->W * h->H;
     if (ns > h->max_slots) return fail(EDS_ERR_INVALID, "select: more cells than the handle holds");
-    EDS_HIP_TRY(hipMemsetAsync(h->map, 0, (size_t)wh, h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->counts, 0, C_COUNTS * sizeof(int32_t), h->st));
-    hipLaunchKernelGGL(k_sel_hits, dim3(blocks(ns)), dim3(TB), 0, h->st, S, h->mask, ns);
-    hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(SCAN), 0, h->st, h->mask, h->table, h->n2_start, h->cell_sel, h->counts, ns, wh);
-    hipLaunchKernelGGL(k_sel_pick, dim3((unsigned)nb), dim3(PICK), 0, h->st, S, h->n2_start, h->cell_sel, h->table, h->map, h->counts);
+    EDS_HIP_TRY(hipMemsetAsync(h->map, 0, (size_t)wh, h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->counts, 0, C_COUNTS * sizeof(int32_t), h->own.st));
+    hipLaunchKernelGGL(k_sel_hits, dim3(blocks(ns)), dim3(TB), 0, h->own.st, S, h->mask, ns);
+    hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(SCAN), 0, h->own.st, h->mask, h->table, h->n2_start, h->cell_sel, h->counts, ns, wh);
+    hipLaunchKernelGGL(k_sel_pick, dim3((unsigned)nb), dim3(PICK), 0, h->own.st, S, h->n2_start, h->cell_sel, h->table, h->map, h->counts);
     EDS_HIP_TRY(hipGetLastError());
     int32_t c[C_COUNTS];
-    EDS_HIP_TRY(hipMemcpyAsync(c, h->counts, sizeof(c), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, c, h->counts, sizeof(c))) return rc;
     n[0] = c[C_N2]; n[1] = c[C_N3]; n[2] = c[C_N4];
     h->ambiguous = c[C_AMBIGUOUS];
     h->n2_certain = c[C_N2_CERTAIN];
@@ -248,38 +245,31 @@ int eds_sel_create(int device, int H, int W, eds_sel** sel) {
     if (!sel) return fail(EDS_ERR_INVALID, "null output");
     *sel = nullptr;
     if (H < 32 || W < 32 || H > edspix::MAX_SIDE || W > edspix::MAX_SIDE) return fail(EDS_ERR_INVALID, "H and W are 32 .. 8192");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return fail(EDS_ERR_NO_DEVICE, "no HIP device");
-    }
-    if (device < 0 || device >= ndev) return fail(EDS_ERR_INVALID, "device " + std::to_string(device) + " of " + std::to_string(ndev));
-    EDS_HIP_TRY(hipSetDevice(device));
     eds_sel* h = new eds_sel;
-    h->dev = device; h->H = H; h->W = W;
+    if (int rc = h->own.open(device)) { delete h; return rc; }
+    h->H = H; h->W = W;
     h->g = edspix::make_geo(H, W);
     h->prm = edspix::params_default();
     h->max_slots = SLOTS * ((W + 3) / 4) * ((H + 3) / 4);          // potential 1
     const size_t px = (size_t)H * W, nt = (size_t)h->g.w32 * h->g.h32;
     h->n_blocks256 = (int)((px + TB - 1) / TB);
-    const bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess &&
-                    edscapi::device_alloc({{(void**)&h->lv[0], px * sizeof(Px)},
-                                           {(void**)&h->lv[1], (size_t)h->g.w1 * h->g.h1 * sizeof(Px)},
-                                           {(void**)&h->lv[2], (size_t)h->g.w2 * h->g.h2 * sizeof(Px)},
-                                           {(void**)&h->in_img, px * sizeof(float)},
-                                           {(void**)&h->B, 256 * sizeof(float)},
-                                           {(void**)&h->ths, nt * sizeof(float)},
-                                           {(void**)&h->ths_s, nt * sizeof(float)},
-                                           {(void**)&h->map, px},
-                                           {(void**)&h->table, px},
-                                           {(void**)&h->mask, (size_t)h->max_slots * sizeof(uint32_t)},
-                                           {(void**)&h->n2_start, (size_t)h->max_slots * sizeof(int32_t)},
-                                           {(void**)&h->cell_sel, (size_t)h->max_slots},
-                                           {(void**)&h->counts, C_COUNTS * sizeof(int32_t)},
-                                           {(void**)&h->block_cnt, (size_t)2 * h->n_blocks256 * sizeof(int32_t)},
-                                           {(void**)&h->uv, px * 2 * sizeof(int32_t)},
-                                           {(void**)&h->type, px * sizeof(float)}}) &&
-                    hipMemsetAsync(h->map, 0, px, h->st) == hipSuccess && hipStreamSynchronize(h->st) == hipSuccess;
+    const bool ok = h->own.alloc({{(void**)&h->lv[0], px * sizeof(Px)},
+                                  {(void**)&h->lv[1], (size_t)h->g.w1 * h->g.h1 * sizeof(Px)},
+                                  {(void**)&h->lv[2], (size_t)h->g.w2 * h->g.h2 * sizeof(Px)},
+                                  {(void**)&h->in_img, px * sizeof(float)},
+                                  {(void**)&h->B, 256 * sizeof(float)},
+                                  {(void**)&h->ths, nt * sizeof(float)},
+                                  {(void**)&h->ths_s, nt * sizeof(float)},
+                                  {(void**)&h->map, px},
+                                  {(void**)&h->table, px},
+                                  {(void**)&h->mask, (size_t)h->max_slots * sizeof(uint32_t)},
+                                  {(void**)&h->n2_start, (size_t)h->max_slots * sizeof(int32_t)},
+                                  {(void**)&h->cell_sel, (size_t)h->max_slots},
+                                  {(void**)&h->counts, C_COUNTS * sizeof(int32_t)},
+                                  {(void**)&h->block_cnt, (size_t)2 * h->n_blocks256 * sizeof(int32_t)},
+                                  {(void**)&h->uv, px * 2 * sizeof(int32_t)},
+                                  {(void**)&h->type, px * sizeof(float)}}) &&
+                    hipMemsetAsync(h->map, 0, px, h->own.st) == hipSuccess && hipStreamSynchronize(h->own.st) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         eds_sel_destroy(h);
@@ -291,16 +281,12 @@ int eds_sel_create(int device, int H, int W, eds_sel** sel) {
 
 void eds_sel_destroy(eds_sel* h) {
     if (!h) return;
-    (void)hipSetDevice(h->dev);
-    if (h->st) { (void)hipStreamSynchronize(h->st); (void)hipStreamDestroy(h->st); }
-    void* all[] = {h->lv[0], h->lv[1], h->lv[2], h->in_img, h->B, h->ths, h->ths_s, h->map, h->table, h->mask, h->n2_start, h->cell_sel,
-                   h->counts, h->block_cnt, h->uv, h->type};
-    for (void* p : all) if (p) (void)hipFree(p);
+    h->own.close();
     delete h;
 }
 
 int eds_sel_set_params(eds_sel* h, const eds_sel_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null parameters");
     Params s;
     std::memcpy(&s, p, sizeof(s));
@@ -311,19 +297,19 @@ int eds_sel_set_params(eds_sel* h, const eds_sel_params* p) {
 }
 
 int eds_sel_get_params(const eds_sel* h, eds_sel_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null output");
     std::memcpy(p, &h->prm, sizeof(*p));
     return EDS_OK;
 }
 
 int eds_sel_set_random_pattern(eds_sel* h, const uint8_t* table, size_t n) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!table) return fail(EDS_ERR_INVALID, "table: NULL pointer");
     if (n != (size_t)h->W * h->H) return fail(EDS_ERR_INVALID, "the table holds W * H = " + std::to_string((size_t)h->W * h->H) + " bytes");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(h->table, table, n, hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipMemcpyAsync(h->table, table, n, hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     h->table_set = true;
     return EDS_OK;
 }
@@ -335,55 +321,48 @@ int eds_sel_fill_reference_pattern(uint8_t* out, size_t n) {
 }
 
 int eds_sel_set_potential(eds_sel* h, int potential) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (potential < 1 || potential > edspix::MAX_POTENTIAL) return fail(EDS_ERR_INVALID, "the potential is 1 .. 2^30");
     h->potential = potential;
     return EDS_OK;
 }
 
 int eds_sel_get_potential(const eds_sel* h, int* potential) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!potential) return fail(EDS_ERR_INVALID, "null output");
     *potential = h->potential;
     return EDS_OK;
 }
 
 int eds_sel_set_image(eds_sel* h, const float* image, int64_t rs, int on_device, const float* B) {
-    if (int rc = check_handle(h)) return rc;
-    if (!image) return fail(EDS_ERR_INVALID, "image: NULL pointer");
-    if (on_device != 0 && on_device != 1) return fail(EDS_ERR_INVALID, "on_device is 0 or 1");
-    const int H = h->H, W = h->W;
-    if (rs == 0) rs = W;
-    if (rs < W || rs > (int64_t)1 << 30) return fail(EDS_ERR_INVALID, "bad row stride");
-    if (reinterpret_cast<uintptr_t>(image) % sizeof(float)) return fail(EDS_ERR_INVALID, "image: not aligned to 4 bytes");
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
+    size_t bytes = 0;
+    if (int rc = edscapi::check_image_layout(h->H, h->W, 1, image, &rs, nullptr, on_device, "image", nullptr, &bytes)) return rc;
     if (B)
         for (int i = 0; i < 256; ++i)
             if (!std::isfinite(B[i])) return fail(EDS_ERR_INVALID, "B is not finite");
-    if (on_device) {
-        const size_t bytes = (size_t)((int64_t)(H - 1) * rs + W) * sizeof(float);
-        if (int rc = eds_dev_check_range(h->dev, image, bytes)) return rc;
-    }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpy2DAsync(h->in_img, (size_t)W * sizeof(float), image, (size_t)rs * sizeof(float), (size_t)W * sizeof(float), (size_t)H,
-                                 on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->st));
-    if (B) EDS_HIP_TRY(hipMemcpyAsync(h->B, B, 256 * sizeof(float), hipMemcpyHostToDevice, h->st));
+    if (on_device)                                       // after B, as the checks have always run
+        if (int rc = eds_dev_check_range(h->own.dev, image, bytes)) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    if (int rc = edscapi::upload_image(h->own, h->in_img, h->H, h->W, image, rs, on_device)) return rc;
+    if (B) EDS_HIP_TRY(hipMemcpyAsync(h->B, B, 256 * sizeof(float), hipMemcpyHostToDevice, h->own.st));
     h->image_set = false;                               // what was stored is gone once the kernels are queued
     h->hist_valid = false;
     for (int l = 0; l < edspix::LEVELS; ++l) {
         const int w = edspix::level_w(h->g, l), hh = edspix::level_h(h->g, l);
-        hipLaunchKernelGGL(k_sel_level, dim3(blocks((int64_t)w * hh)), dim3(TB), 0, h->st, h->in_img, l ? h->lv[l - 1] : (const Px*)nullptr, h->lv[l], w,
+        hipLaunchKernelGGL(k_sel_level, dim3(blocks((int64_t)w * hh)), dim3(TB), 0, h->own.st, h->in_img, l ? h->lv[l - 1] : (const Px*)nullptr, h->lv[l], w,
                            hh, l ? edspix::level_w(h->g, l - 1) : 0);
-        hipLaunchKernelGGL(k_sel_gradient, dim3(blocks((int64_t)w * hh)), dim3(TB), 0, h->st, h->lv[l], w, hh, B ? h->B : (const float*)nullptr);
+        hipLaunchKernelGGL(k_sel_gradient, dim3(blocks((int64_t)w * hh)), dim3(TB), 0, h->own.st, h->lv[l], w, hh, B ? h->B : (const float*)nullptr);
     }
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     h->image_set = true;
     return EDS_OK;
 }
 
 int eds_sel_make_maps(eds_sel* h, float density, int recursions_left, float th_factor, int* num_have_sub, eds_sel_pass* passes, int max_passes,
                       int* n_passes, uint8_t* pass_maps) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!num_have_sub) return fail(EDS_ERR_INVALID, "null output");
     if (!(density > 0.0f) || !std::isfinite(density)) return fail(EDS_ERR_INVALID, "density is positive and finite");
     if (!(th_factor > 0.0f) || !std::isfinite(th_factor)) return fail(EDS_ERR_INVALID, "th_factor is positive and finite");
@@ -392,12 +371,12 @@ int eds_sel_make_maps(eds_sel* h, float density, int recursions_left, float th_f
     if (pass_maps && max_passes < 1) return fail(EDS_ERR_INVALID, "pass_maps comes with passes");
     if (!h->table_set) return fail(EDS_ERR_STATE, "no random pattern: eds_sel_set_random_pattern first");
     if (!h->image_set) return fail(EDS_ERR_STATE, "no image: eds_sel_set_image first");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const int wh = h->W * h->H, nt = h->g.w32 * h->g.h32;
     h->sel_valid = false;
     if (!h->hist_valid) {
-        hipLaunchKernelGGL(k_sel_hist, dim3((unsigned)nt), dim3(TB), 0, h->st, h->lv[0], h->g, h->prm, h->ths);
-        hipLaunchKernelGGL(k_sel_smooth, dim3(blocks(nt)), dim3(TB), 0, h->st, h->ths, h->ths_s, h->g.w32, h->g.h32);
+        hipLaunchKernelGGL(k_sel_hist, dim3((unsigned)nt), dim3(TB), 0, h->own.st, h->lv[0], h->g, h->prm, h->ths);
+        hipLaunchKernelGGL(k_sel_smooth, dim3(blocks(nt)), dim3(TB), 0, h->own.st, h->ths, h->ths_s, h->g.w32, h->g.h32);
         EDS_HIP_TRY(hipGetLastError());
         h->hist_valid = true;
     }
@@ -411,8 +390,7 @@ int eds_sel_make_maps(eds_sel* h, float density, int recursions_left, float th_f
             done.push_back(edspix::Pass{h->potential, n[0], n[1], n[2]});
             if (pass_maps) {
                 maps.resize((size_t)(np + 1) * wh);
-                EDS_HIP_TRY(hipMemcpyAsync(maps.data() + (size_t)np * wh, h->map, (size_t)wh, hipMemcpyDeviceToHost, h->st));
-                EDS_HIP_TRY(hipStreamSynchronize(h->st));
+                if (int rc = read_back(h->own, maps.data() + (size_t)np * wh, h->map, (size_t)wh)) return rc;
             }
         }
         ++np;
@@ -421,18 +399,17 @@ int eds_sel_make_maps(eds_sel* h, float density, int recursions_left, float th_f
         if (D.recurse) { --recursions_left; continue; }
         int32_t* cnt0 = h->block_cnt;
         int32_t* cnt1 = h->block_cnt + h->n_blocks256;
-        hipLaunchKernelGGL(k_sel_count, dim3(blocks(wh)), dim3(TB), 0, h->st, h->map, cnt0, wh);
+        hipLaunchKernelGGL(k_sel_count, dim3(blocks(wh)), dim3(TB), 0, h->own.st, h->map, cnt0, wh);
         if (D.subselect) {
-            hipLaunchKernelGGL(k_sel_rank, dim3(blocks(wh)), dim3(TB), 0, h->st, h->map, cnt0, h->table, 1, D.char_th, cnt1, h->uv, h->type, h->counts,
+            hipLaunchKernelGGL(k_sel_rank, dim3(blocks(wh)), dim3(TB), 0, h->own.st, h->map, cnt0, h->table, 1, D.char_th, cnt1, h->uv, h->type, h->counts,
                                wh, h->W);
             cnt0 = cnt1;
         }
-        hipLaunchKernelGGL(k_sel_rank, dim3(blocks(wh)), dim3(TB), 0, h->st, h->map, cnt0, h->table, 0, 0, (int32_t*)nullptr, h->uv, h->type, h->counts,
+        hipLaunchKernelGGL(k_sel_rank, dim3(blocks(wh)), dim3(TB), 0, h->own.st, h->map, cnt0, h->table, 0, 0, (int32_t*)nullptr, h->uv, h->type, h->counts,
                            wh, h->W);
         EDS_HIP_TRY(hipGetLastError());
         int32_t n_list = 0;
-        EDS_HIP_TRY(hipMemcpyAsync(&n_list, h->counts + C_LIST, sizeof(n_list), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        if (int rc = read_back(h->own, &n_list, h->counts + C_LIST, sizeof(n_list))) return rc;
         h->n_sel = n_list;
         h->sel_valid = true;
         *num_have_sub = n_list;
@@ -444,52 +421,42 @@ int eds_sel_make_maps(eds_sel* h, float density, int recursions_left, float th_f
 }
 
 int eds_sel_get_map(eds_sel* h, uint8_t* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     if (!h->sel_valid) return fail(EDS_ERR_STATE, "no selection: eds_sel_make_maps first");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(out, h->map, (size_t)h->W * h->H, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return read_back(h->own, out, h->map, (size_t)h->W * h->H);
 }
 
 int eds_sel_get_selection(eds_sel* h, int* n, int32_t* uv, float* type) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!n) return fail(EDS_ERR_INVALID, "null output");
     if (!h->sel_valid) return fail(EDS_ERR_STATE, "no selection: eds_sel_make_maps first");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    if (uv && h->n_sel > 0) EDS_HIP_TRY(hipMemcpyAsync(uv, h->uv, (size_t)h->n_sel * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    if (type && h->n_sel > 0) EDS_HIP_TRY(hipMemcpyAsync(type, h->type, (size_t)h->n_sel * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    const size_t k = h->n_sel > 0 ? (size_t)h->n_sel : 0;
+    if (int rc = read_back(h->own, uv, h->uv, k * 2 * sizeof(int32_t))) return rc;
+    if (int rc = read_back(h->own, type, h->type, k * sizeof(float))) return rc;
     *n = h->n_sel;
     return EDS_OK;
 }
 
 int eds_sel_get_level(eds_sel* h, int lvl, float* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (lvl < 0 || lvl >= edspix::LEVELS) return fail(EDS_ERR_INVALID, "level 0 .. 2");
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     if (!h->image_set) return fail(EDS_ERR_STATE, "no image: eds_sel_set_image first");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
     const size_t n = (size_t)edspix::level_w(h->g, lvl) * edspix::level_h(h->g, lvl);
-    EDS_HIP_TRY(hipMemcpyAsync(out, h->lv[lvl], n * sizeof(Px), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return read_back(h->own, out, h->lv[lvl], n * sizeof(Px));
 }
 
 int eds_sel_get_thresholds(eds_sel* h, int which, float* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (which != EDS_SEL_THS && which != EDS_SEL_THS_SMOOTHED) return fail(EDS_ERR_INVALID, "which is EDS_SEL_THS or EDS_SEL_THS_SMOOTHED");
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     if (!h->hist_valid) return fail(EDS_ERR_STATE, "no histograms: eds_sel_make_maps first");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(out, which == EDS_SEL_THS ? h->ths : h->ths_s, (size_t)h->g.w32 * h->g.h32 * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return read_back(h->own, out, which == EDS_SEL_THS ? h->ths : h->ths_s, (size_t)h->g.w32 * h->g.h32 * sizeof(float));
 }
 
 int eds_sel_get_scan_info(eds_sel* h, int* ambiguous_cells, int* n2_certain) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_sel")) return rc;
     if (!h->sel_valid) return fail(EDS_ERR_STATE, "no selection: eds_sel_make_maps first");
     if (ambiguous_cells) *ambiguous_cells = h->ambiguous;
     if (n2_certain) *n2_certain = h->n2_certain;

@@ -5,17 +5,18 @@
 
 #include <cstdint>
 
+#include "eds_device_owner.hpp"
 #include "eds_pixsel.hpp"
 
 struct eds_sel {
-    int dev = 0, H = 0, W = 0;
+    edscapi::DeviceOwner own;
+    int H = 0, W = 0;
     edspix::Geo g;
     edspix::Params prm;
     int potential = 3;
     bool table_set = false, image_set = false, hist_valid = false, sel_valid = false;
     int max_slots = 0, n_blocks256 = 0;
     int n_sel = 0, ambiguous = 0, n2_certain = 0;      // of the selection that holds
-    hipStream_t st = nullptr;
     edspix::Px* lv[edspix::LEVELS] = {nullptr, nullptr, nullptr};
     float *in_img = nullptr, *B = nullptr;             // [H * W], [256]
     float *ths = nullptr, *ths_s = nullptr;            // [w32 * h32]

@@ -14,13 +14,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/eds_hip_device.h"
 #include "../../include/eds_hip_window.h"
 #include "eds_capi_internal.hpp"
 #include "eds_window.hpp"
 #include "eds_window_internal.hpp"
 
+using edscapi::blocks;
 using edscapi::fail;
+using edscapi::read_back;
 using edswin::Calib;
 using edswin::Params;
 using edswin::Point;
@@ -241,8 +242,6 @@ __global__ void __launch_bounds__(TB) k_win_stitch(int F, const double* __restri
     if (e < entries) edswin::stitch_entry(F, acc, adH, adT, e, out);
 }
 
-int check_handle(const eds_win* h) { return h ? EDS_OK : fail(EDS_ERR_INVALID, "null eds_win handle"); }
-unsigned blocks(size_t n) { return (unsigned)((n + TB - 1) / TB); }
 Dev tables(const eds_win* h) {
     Dev t = {h->res_point, h->res_target, h->state, h->new_state, h->active, h->energy, h->new_energy, h->new_energy_wo, h->ret, h->cp, h->proj,
              h->J, h->efJ, h->JpJdF};
@@ -270,11 +269,7 @@ int build_maps(const eds_win* h, int F, std::vector<int32_t>& res_of, std::vecto
     }
     return EDS_OK;
 }
-template <class T> int download(eds_win* h, T* dst, const T* src, size_t n) {
-    if (!dst || !n) return EDS_OK;
-    EDS_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, h->st));
-    return EDS_OK;
-}
+template <class T> int download(eds_win* h, T* dst, const T* src, size_t n) { return read_back(h->own, dst, src, n * sizeof(T)); }
 
 }  // namespace
 
@@ -283,27 +278,27 @@ namespace edswin_internal {
 int upload_maps(eds_win* h, int F) {
     std::vector<int32_t> res_of, first;
     if (int rc = build_maps(h, F, res_of, first)) return rc;
-    if (h->n) EDS_HIP_TRY(hipMemcpyAsync(h->res_of, res_of.data(), res_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(h->first, first.data(), 9 * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));                  // the two vectors end here
+    if (h->n) EDS_HIP_TRY(hipMemcpyAsync(h->res_of, res_of.data(), res_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->first, first.data(), 9 * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));                  // the two vectors end here
     return EDS_OK;
 }
 
 void queue_points(eds_win* h, int mode, const int32_t* sel, int shift) {
     if (!h->n) return;
-    (void)hipMemsetAsync(h->nres, 0, sizeof(int32_t), h->st);
-    hipLaunchKernelGGL(k_win_points, dim3(blocks((size_t)h->n)), dim3(TB), 0, h->st, h->n, h->res_first, h->active, lin_flags(h), mode, sel, h->efJ,
+    (void)hipMemsetAsync(h->nres, 0, sizeof(int32_t), h->own.st);
+    hipLaunchKernelGGL(k_win_points, dim3(blocks((size_t)h->n)), dim3(TB), 0, h->own.st, h->n, h->res_first, h->active, lin_flags(h), mode, sel, h->efJ,
                        h->prior, h->delta, h->lf, 1, 1, lf_on_device(h) ? 1 : 0, shift, h->pout, h->nres);
 }
 
 void queue_acc(eds_win* h, int F, int mode, const int32_t* sel, int has_lf, int words, double* acc) {
     const edswin::AccIn in = {F, has_lf, h->first, h->res_of, h->active, h->efJ, h->JpJdF, h->pout, h->lf,
                               mode, lin_flags(h), h->wsv ? h->wsv->res_approx : nullptr, sel};
-    hipLaunchKernelGGL(k_win_acc, dim3((unsigned)words), dim3(edswin::LANES), 0, h->st, in, acc);
+    hipLaunchKernelGGL(k_win_acc, dim3((unsigned)words), dim3(edswin::LANES), 0, h->own.st, in, acc);
 }
 
 void queue_stitch(eds_win* h, int F, const double* acc, const double* ad, int entries, double* out) {
-    hipLaunchKernelGGL(k_win_stitch, dim3(blocks((size_t)entries)), dim3(TB), 0, h->st, F, acc, ad, ad + (size_t)F * F * 64, entries, out);
+    hipLaunchKernelGGL(k_win_stitch, dim3(blocks((size_t)entries)), dim3(TB), 0, h->own.st, F, acc, ad, ad + (size_t)F * F * 64, entries, out);
 }
 
 }  // namespace edswin_internal
@@ -325,54 +320,47 @@ int eds_win_create(int device, int H, int W, int max_frames, int max_points, int
     if (max_frames < 2 || max_frames > EDS_WIN_MAX_FRAMES) return fail(EDS_ERR_INVALID, "max_frames is 2 .. 8");
     if (max_points < 1 || max_points > (1 << 22) || max_residuals < 1 || max_residuals > (1 << 24))
         return fail(EDS_ERR_INVALID, "max_points is 1 .. 2^22, max_residuals 1 .. 2^24");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return fail(EDS_ERR_NO_DEVICE, "no HIP device");
-    }
-    if (device < 0 || device >= ndev) return fail(EDS_ERR_INVALID, "device " + std::to_string(device) + " of " + std::to_string(ndev));
-    EDS_HIP_TRY(hipSetDevice(device));
     eds_win* h = new eds_win;
-    h->dev = device; h->H = H; h->W = W; h->max_frames = max_frames; h->max_points = max_points; h->max_residuals = max_residuals;
+    if (int rc = h->own.open(device)) { delete h; return rc; }
+    h->H = H; h->W = W; h->max_frames = max_frames; h->max_points = max_points; h->max_residuals = max_residuals;
     h->prm = edswin::params_default();
     const size_t px = (size_t)H * W, mp = (size_t)max_points, mr = (size_t)max_residuals;
-    const bool ok = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) == hipSuccess &&
-                    edscapi::device_alloc({{(void**)&h->frames, px * max_frames * sizeof(Px)},
-                                           {(void**)&h->in_img, px * sizeof(float)},
-                                           {(void**)&h->pts, mp * sizeof(Point)},
-                                           {(void**)&h->ids, mp * sizeof(float)},
-                                           {(void**)&h->idz, mp * sizeof(float)},
-                                           {(void**)&h->res_first, (mp + 1) * sizeof(int32_t)},
-                                           {(void**)&h->res_point, mr * sizeof(int32_t)},
-                                           {(void**)&h->res_target, mr * sizeof(int32_t)},
-                                           {(void**)&h->state, mr * sizeof(int32_t)},
-                                           {(void**)&h->new_state, mr * sizeof(int32_t)},
-                                           {(void**)&h->active, mr * sizeof(int32_t)},
-                                           {(void**)&h->energy, mr * sizeof(float)},
-                                           {(void**)&h->new_energy, mr * sizeof(float)},
-                                           {(void**)&h->new_energy_wo, mr * sizeof(float)},
-                                           {(void**)&h->ret, mr * sizeof(float)},
-                                           {(void**)&h->cp, mr * 3 * sizeof(float)},
-                                           {(void**)&h->proj, mr * 16 * sizeof(float)},
-                                           {(void**)&h->J, mr * J_WORDS * sizeof(float)},
-                                           {(void**)&h->efJ, mr * J_WORDS * sizeof(float)},
-                                           {(void**)&h->JpJdF, mr * 8 * sizeof(float)},
-                                           {(void**)&h->th, 8 * sizeof(float)},
-                                           {(void**)&h->prior, mp * sizeof(float)},
-                                           {(void**)&h->delta, mp * sizeof(float)},
-                                           {(void**)&h->lf, mp * 6 * sizeof(float)},
-                                           {(void**)&h->pcs, 64 * sizeof(Precalc)},
-                                           {(void**)&h->sum, sizeof(Sum)},
-                                           {(void**)&h->pout, mp * sizeof(PointOut)},
-                                           {(void**)&h->nres, sizeof(int32_t)},
-                                           {(void**)&h->res_of, mp * 8 * sizeof(int32_t)},
-                                           {(void**)&h->first, 9 * sizeof(int32_t)},
-                                           {(void**)&h->acc, (size_t)edswin::acc_size(8) * sizeof(double)},
-                                           {(void**)&h->ad, 2 * 64 * 64 * sizeof(double)},
-                                           {(void**)&h->stitched, (size_t)edswin::stitch_words(8) * sizeof(double)}});
-    if (!ok || hipMemsetAsync(h->pout, 0, mp * sizeof(PointOut), h->st) != hipSuccess ||
-        hipMemsetAsync(h->res_first, 0, (mp + 1) * sizeof(int32_t), h->st) != hipSuccess || hipMemsetAsync(h->active, 0, mr * sizeof(int32_t), h->st) != hipSuccess ||
-        hipStreamSynchronize(h->st) != hipSuccess) {
+    const bool ok = h->own.alloc({{(void**)&h->frames, px * max_frames * sizeof(Px)},
+                                  {(void**)&h->in_img, px * sizeof(float)},
+                                  {(void**)&h->pts, mp * sizeof(Point)},
+                                  {(void**)&h->ids, mp * sizeof(float)},
+                                  {(void**)&h->idz, mp * sizeof(float)},
+                                  {(void**)&h->res_first, (mp + 1) * sizeof(int32_t)},
+                                  {(void**)&h->res_point, mr * sizeof(int32_t)},
+                                  {(void**)&h->res_target, mr * sizeof(int32_t)},
+                                  {(void**)&h->state, mr * sizeof(int32_t)},
+                                  {(void**)&h->new_state, mr * sizeof(int32_t)},
+                                  {(void**)&h->active, mr * sizeof(int32_t)},
+                                  {(void**)&h->energy, mr * sizeof(float)},
+                                  {(void**)&h->new_energy, mr * sizeof(float)},
+                                  {(void**)&h->new_energy_wo, mr * sizeof(float)},
+                                  {(void**)&h->ret, mr * sizeof(float)},
+                                  {(void**)&h->cp, mr * 3 * sizeof(float)},
+                                  {(void**)&h->proj, mr * 16 * sizeof(float)},
+                                  {(void**)&h->J, mr * J_WORDS * sizeof(float)},
+                                  {(void**)&h->efJ, mr * J_WORDS * sizeof(float)},
+                                  {(void**)&h->JpJdF, mr * 8 * sizeof(float)},
+                                  {(void**)&h->th, 8 * sizeof(float)},
+                                  {(void**)&h->prior, mp * sizeof(float)},
+                                  {(void**)&h->delta, mp * sizeof(float)},
+                                  {(void**)&h->lf, mp * 6 * sizeof(float)},
+                                  {(void**)&h->pcs, 64 * sizeof(Precalc)},
+                                  {(void**)&h->sum, sizeof(Sum)},
+                                  {(void**)&h->pout, mp * sizeof(PointOut)},
+                                  {(void**)&h->nres, sizeof(int32_t)},
+                                  {(void**)&h->res_of, mp * 8 * sizeof(int32_t)},
+                                  {(void**)&h->first, 9 * sizeof(int32_t)},
+                                  {(void**)&h->acc, (size_t)edswin::acc_size(8) * sizeof(double)},
+                                  {(void**)&h->ad, 2 * 64 * 64 * sizeof(double)},
+                                  {(void**)&h->stitched, (size_t)edswin::stitch_words(8) * sizeof(double)}});
+    if (!ok || hipMemsetAsync(h->pout, 0, mp * sizeof(PointOut), h->own.st) != hipSuccess ||
+        hipMemsetAsync(h->res_first, 0, (mp + 1) * sizeof(int32_t), h->own.st) != hipSuccess || hipMemsetAsync(h->active, 0, mr * sizeof(int32_t), h->own.st) != hipSuccess ||
+        hipStreamSynchronize(h->own.st) != hipSuccess) {
         (void)hipGetLastError();
         eds_win_destroy(h);
         return fail(EDS_ERR_HIP, "eds_win_create: the device refused a stream or an allocation");
@@ -383,20 +371,14 @@ int eds_win_create(int device, int H, int W, int max_frames, int max_points, int
 
 void eds_win_destroy(eds_win* h) {
     if (!h) return;
-    (void)hipSetDevice(h->dev);
-    if (h->st) (void)hipStreamSynchronize(h->st);
+    h->own.close();                                            // the window's buffers and both states', whichever set holds them now
     edswin_internal::wsv_release(h);
     edswin_internal::wed_release(h);
-    if (h->st) (void)hipStreamDestroy(h->st);
-    void* all[] = {h->frames, h->in_img, h->pts, h->ids, h->idz, h->res_first, h->res_point, h->res_target, h->state, h->new_state, h->active, h->energy,
-                   h->new_energy, h->new_energy_wo, h->ret, h->cp, h->proj, h->J, h->efJ, h->JpJdF, h->th, h->prior, h->delta, h->lf, h->pcs,
-                   h->sum, h->pout, h->nres, h->res_of, h->first, h->acc, h->ad, h->stitched};
-    for (void* p : all) if (p) (void)hipFree(p);
     delete h;
 }
 
 int eds_win_set_params(eds_win* h, const eds_win_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null parameters");
     Params s;
     std::memcpy(&s, p, sizeof(s));
@@ -407,70 +389,55 @@ int eds_win_set_params(eds_win* h, const eds_win_params* p) {
 }
 
 int eds_win_get_params(const eds_win* h, eds_win_params* p) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!p) return fail(EDS_ERR_INVALID, "null output");
     std::memcpy(p, &h->prm, sizeof(*p));
     return EDS_OK;
 }
 
 int eds_win_set_calib(eds_win* h, float fx, float fy, float cx, float cy) {
-    if (int rc = check_handle(h)) return rc;
-    if (!(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy)) || !(fx > 0.0f) || !(fy > 0.0f))
-        return fail(EDS_ERR_INVALID, "calibration: fx, fy, cx, cy finite, fx and fy > 0");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
+    if (!edscapi::check_calib(fx, fy, cx, cy)) return fail(EDS_ERR_INVALID, "calibration: fx, fy, cx, cy finite, fx and fy > 0");
     h->cal = edswin::make_calib(h->H, h->W, fx, fy, cx, cy);
     h->calib_set = true;
     return EDS_OK;
 }
 
 int eds_win_set_frames(eds_win* h, int first, int count, const float* images, int64_t row_stride, int64_t frame_stride, int on_device) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     const int H = h->H, W = h->W;
     if (first < 0 || count < 1 || first > h->max_frames - count) return fail(EDS_ERR_INVALID, "frames first .. first + count - 1 outside the handle's");
-    if (!images) return fail(EDS_ERR_INVALID, "images: NULL pointer");
-    if (on_device != 0 && on_device != 1) return fail(EDS_ERR_INVALID, "on_device is 0 or 1");
-    if (row_stride == 0) row_stride = W;
-    if (row_stride < W || row_stride > (int64_t)1 << 30) return fail(EDS_ERR_INVALID, "bad row stride");
-    const int64_t frame_extent = (int64_t)(H - 1) * row_stride + W;
-    if (frame_stride == 0) frame_stride = (int64_t)H * row_stride;
-    if (frame_stride < frame_extent || frame_stride > (int64_t)1 << 40) return fail(EDS_ERR_INVALID, "bad frame stride");
-    if (reinterpret_cast<uintptr_t>(images) % sizeof(float)) return fail(EDS_ERR_INVALID, "images: not aligned to 4 bytes");
-    if (on_device) {
-        const size_t bytes = (size_t)((int64_t)(count - 1) * frame_stride + frame_extent) * sizeof(float);
-        if (int rc = eds_dev_check_range(h->dev, images, bytes)) return rc;
-    }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    if (int rc = edscapi::check_images(h->own.dev, H, W, count, images, &row_stride, &frame_stride, on_device, "images")) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t px = (size_t)H * W;
     for (int f = 0; f < count; ++f) {
         h->frames_set &= ~(1u << (first + f));
         Px* dst = h->frames + (size_t)(first + f) * px;
-        EDS_HIP_TRY(hipMemcpy2DAsync(h->in_img, (size_t)W * sizeof(float), images + (int64_t)f * frame_stride, (size_t)row_stride * sizeof(float),
-                                     (size_t)W * sizeof(float), (size_t)H, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->st));
-        hipLaunchKernelGGL(k_win_image, dim3(blocks(px)), dim3(TB), 0, h->st, h->in_img, dst, (int)px);
-        hipLaunchKernelGGL(k_win_gradient, dim3(blocks(px)), dim3(TB), 0, h->st, dst, W, H);
+        if (int rc = edscapi::upload_image(h->own, h->in_img, H, W, images + (int64_t)f * frame_stride, row_stride, on_device)) return rc;
+        hipLaunchKernelGGL(k_win_image, dim3(blocks(px)), dim3(TB), 0, h->own.st, h->in_img, dst, (int)px);
+        hipLaunchKernelGGL(k_win_gradient, dim3(blocks(px)), dim3(TB), 0, h->own.st, dst, W, H);
         EDS_HIP_TRY(hipGetLastError());
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));                // the host image may be pageable, and in_img is reused by the next frame
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));                // the host image may be pageable, and in_img is reused by the next frame
         h->frames_set |= 1u << (first + f);
     }
     return EDS_OK;
 }
 
 int eds_win_get_frame(eds_win* h, int frame, float* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (frame < 0 || frame >= h->max_frames) return fail(EDS_ERR_INVALID, "frame outside the handle's");
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     if (!(h->frames_set >> frame & 1u)) return fail(EDS_ERR_STATE, "eds_win: that frame was never set");
     const size_t px = (size_t)h->H * h->W;
     std::vector<Px> p(px);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(p.data(), h->frames + (size_t)frame * px, px * sizeof(Px), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, p.data(), h->frames + (size_t)frame * px, px * sizeof(Px))) return rc;
     for (size_t i = 0; i < px; ++i) { out[3 * i] = p[i].c; out[3 * i + 1] = p[i].dx; out[3 * i + 2] = p[i].dy; }
     return EDS_OK;
 }
 
 int eds_win_set_points(eds_win* h, int n, const int32_t* host, const float* uv, const float* color, const float* weights,
                        const float* idepth_scaled, const float* idepth_zero_scaled) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (n < 0 || n > h->max_points) return fail(EDS_ERR_INVALID, std::to_string(n) + " points, the handle holds 0 .. " + std::to_string(h->max_points));
     if (n > 0 && (!host || !uv || !color || !weights || !idepth_scaled || !idepth_zero_scaled))
         return fail(EDS_ERR_INVALID, "host, uv, color, weights, idepth_scaled and idepth_zero_scaled are required");
@@ -487,17 +454,17 @@ int eds_win_set_points(eds_win* h, int n, const int32_t* host, const float* uv, 
         p[i].host = host[i]; p[i].u = uv[2 * i]; p[i].v = uv[2 * i + 1];
         for (int k = 0; k < 8; ++k) { p[i].color[k] = color[8 * i + k]; p[i].weights[k] = weights[8 * i + k]; }
     }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (n) {
-        EDS_HIP_TRY(hipMemcpyAsync(h->pts, p.data(), p.size() * sizeof(Point), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->ids, idepth_scaled, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->idz, idepth_zero_scaled, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->pts, p.data(), p.size() * sizeof(Point), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->ids, idepth_scaled, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->idz, idepth_zero_scaled, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
     }
     // the residual table becomes empty ON THE DEVICE too: every point's run is [0, 0) and nothing is active
-    EDS_HIP_TRY(hipMemsetAsync(h->res_first, 0, ((size_t)h->max_points + 1) * sizeof(int32_t), h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->active, 0, (size_t)h->max_residuals * sizeof(int32_t), h->st));
-    EDS_HIP_TRY(hipMemsetAsync(h->pout, 0, (size_t)h->max_points * sizeof(PointOut), h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemsetAsync(h->res_first, 0, ((size_t)h->max_points + 1) * sizeof(int32_t), h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->active, 0, (size_t)h->max_residuals * sizeof(int32_t), h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(h->pout, 0, (size_t)h->max_points * sizeof(PointOut), h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     h->n = n; h->m = 0; h->max_host = max_host; h->max_target = -1; h->linearized = false;
     edswin_internal::wsv_invalidate(h);
     h->host_of.assign(host, host + n);
@@ -506,19 +473,19 @@ int eds_win_set_points(eds_win* h, int n, const int32_t* host, const float* uv, 
 }
 
 int eds_win_set_idepths(eds_win* h, const float* idepth_scaled, const float* idepth_zero_scaled) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!idepth_scaled && !idepth_zero_scaled) return fail(EDS_ERR_INVALID, "idepth_scaled or idepth_zero_scaled is required");
     if (!h->n) return EDS_OK;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t bytes = (size_t)h->n * sizeof(float);
-    if (idepth_scaled) EDS_HIP_TRY(hipMemcpyAsync(h->ids, idepth_scaled, bytes, hipMemcpyHostToDevice, h->st));
-    if (idepth_zero_scaled) EDS_HIP_TRY(hipMemcpyAsync(h->idz, idepth_zero_scaled, bytes, hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (idepth_scaled) EDS_HIP_TRY(hipMemcpyAsync(h->ids, idepth_scaled, bytes, hipMemcpyHostToDevice, h->own.st));
+    if (idepth_zero_scaled) EDS_HIP_TRY(hipMemcpyAsync(h->idz, idepth_zero_scaled, bytes, hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
 int eds_win_set_residuals(eds_win* h, int m, const int32_t* point, const int32_t* target, const int32_t* state, const float* energy) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (m < 0 || m > h->max_residuals) return fail(EDS_ERR_INVALID, std::to_string(m) + " residuals, the handle holds 0 .. " + std::to_string(h->max_residuals));
     if (m > 0 && (!point || !target)) return fail(EDS_ERR_INVALID, "point and target are required");
     int max_target = -1;
@@ -536,26 +503,26 @@ int eds_win_set_residuals(eds_win* h, int m, const int32_t* point, const int32_t
     if (state) st.assign(state, state + m);
     std::vector<float> en((size_t)m, 0.0f);
     if (energy) en.assign(energy, energy + m);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t mm = (size_t)m;
-    EDS_HIP_TRY(hipMemcpyAsync(h->res_first, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->res_first, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
     if (m) {
-        EDS_HIP_TRY(hipMemcpyAsync(h->res_point, point, mm * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->res_target, target, mm * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->state, st.data(), mm * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->new_state, ns.data(), mm * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->energy, en.data(), mm * sizeof(float), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->new_energy, en.data(), mm * sizeof(float), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->active, 0, mm * sizeof(int32_t), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->new_energy_wo, 0, mm * sizeof(float), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->ret, 0, mm * sizeof(float), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->cp, 0, mm * 3 * sizeof(float), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->proj, 0, mm * 16 * sizeof(float), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->J, 0, mm * J_WORDS * sizeof(float), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->efJ, 0, mm * J_WORDS * sizeof(float), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(h->JpJdF, 0, mm * 8 * sizeof(float), h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->res_point, point, mm * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->res_target, target, mm * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->state, st.data(), mm * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->new_state, ns.data(), mm * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->energy, en.data(), mm * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->new_energy, en.data(), mm * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->active, 0, mm * sizeof(int32_t), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->new_energy_wo, 0, mm * sizeof(float), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->ret, 0, mm * sizeof(float), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->cp, 0, mm * 3 * sizeof(float), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->proj, 0, mm * 16 * sizeof(float), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->J, 0, mm * J_WORDS * sizeof(float), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->efJ, 0, mm * J_WORDS * sizeof(float), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(h->JpJdF, 0, mm * 8 * sizeof(float), h->own.st));
     }
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     h->m = m; h->max_target = max_target; h->linearized = false;
     edswin_internal::wsv_invalidate(h);
     h->h_point.assign(point, point + m); h->h_target.assign(target, target + m);
@@ -563,7 +530,7 @@ int eds_win_set_residuals(eds_win* h, int m, const int32_t* point, const int32_t
 }
 
 int eds_win_linearize(eds_win* h, int F, const float* precalc, const float* frame_energy_th, double* energy, int32_t* counts) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (F < 2 || F > h->max_frames) return fail(EDS_ERR_INVALID, "F is 2 .. max_frames");
     if (!precalc || !frame_energy_th) return fail(EDS_ERR_INVALID, "precalc and frame_energy_th are required");
     if (!h->calib_set) return fail(EDS_ERR_STATE, "eds_win: no calibration set");
@@ -575,15 +542,14 @@ int eds_win_linearize(eds_win* h, int F, const float* precalc, const float* fram
     Sum back;
     back.energy = 0.0; back.counts[0] = back.counts[1] = back.counts[2] = back.counts[3] = 0;
     if (h->m) {
-        EDS_HIP_TRY(hipSetDevice(h->dev));
-        EDS_HIP_TRY(hipMemcpyAsync(h->pcs, precalc, (size_t)F * F * sizeof(Precalc), hipMemcpyHostToDevice, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(h->th, frame_energy_th, (size_t)F * sizeof(float), hipMemcpyHostToDevice, h->st));
-        hipLaunchKernelGGL(k_win_linearize, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->st, h->cal, h->prm, F, h->pcs, h->th, h->frames, h->pts,
+        EDS_HIP_TRY(hipSetDevice(h->own.dev));
+        EDS_HIP_TRY(hipMemcpyAsync(h->pcs, precalc, (size_t)F * F * sizeof(Precalc), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->th, frame_energy_th, (size_t)F * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+        hipLaunchKernelGGL(k_win_linearize, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, h->cal, h->prm, F, h->pcs, h->th, h->frames, h->pts,
                            h->ids, h->idz, tables(h), h->m);
-        hipLaunchKernelGGL(k_win_energy, dim3(1), dim3(edswin::LANES), 0, h->st, h->ret, h->new_state, h->m, h->sum);
+        hipLaunchKernelGGL(k_win_energy, dim3(1), dim3(edswin::LANES), 0, h->own.st, h->ret, h->new_state, h->m, h->sum);
         EDS_HIP_TRY(hipGetLastError());
-        EDS_HIP_TRY(hipMemcpyAsync(&back, h->sum, sizeof(back), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        if (int rc = read_back(h->own, &back, h->sum, sizeof(back))) return rc;
     }
     h->linearized = true;
     if (energy) *energy = back.energy;
@@ -592,40 +558,39 @@ int eds_win_linearize(eds_win* h, int F, const float* precalc, const float* fram
 }
 
 int eds_win_apply(eds_win* h, int copy_jacobians) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (copy_jacobians != 0 && copy_jacobians != 1) return fail(EDS_ERR_INVALID, "copy_jacobians is 0 or 1");
     if (!h->linearized) return fail(EDS_ERR_STATE, "eds_win_apply before eds_win_linearize");
     if (!h->m) return EDS_OK;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    hipLaunchKernelGGL(k_win_apply, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->st, tables(h), h->m, copy_jacobians);
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    hipLaunchKernelGGL(k_win_apply, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, tables(h), h->m, copy_jacobians);
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
 int eds_win_point_hessians(eds_win* h, const float* priorF, const float* deltaF, const float* lf, int shift_prior_to_zero, int32_t* nres) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (shift_prior_to_zero != 0 && shift_prior_to_zero != 1) return fail(EDS_ERR_INVALID, "shift_prior_to_zero is 0 or 1");
     const size_t n = (size_t)h->n;
     if ((priorF && !all_finite_f(priorF, n)) || (deltaF && !all_finite_f(deltaF, n)) || (lf && !all_finite_f(lf, 6 * n)))
         return fail(EDS_ERR_INVALID, "priorF, deltaF or the linearized sums are not finite");
     int32_t back = 0;
     if (n) {
-        EDS_HIP_TRY(hipSetDevice(h->dev));
-        if (priorF) EDS_HIP_TRY(hipMemcpyAsync(h->prior, priorF, n * sizeof(float), hipMemcpyHostToDevice, h->st));
-        if (deltaF) EDS_HIP_TRY(hipMemcpyAsync(h->delta, deltaF, n * sizeof(float), hipMemcpyHostToDevice, h->st));
+        EDS_HIP_TRY(hipSetDevice(h->own.dev));
+        if (priorF) EDS_HIP_TRY(hipMemcpyAsync(h->prior, priorF, n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
+        if (deltaF) EDS_HIP_TRY(hipMemcpyAsync(h->delta, deltaF, n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
         if (lf) {
-            EDS_HIP_TRY(hipMemcpyAsync(h->lf, lf, 6 * n * sizeof(float), hipMemcpyHostToDevice, h->st));
+            EDS_HIP_TRY(hipMemcpyAsync(h->lf, lf, 6 * n * sizeof(float), hipMemcpyHostToDevice, h->own.st));
             if (h->wsv) h->wsv->lf_on_device = false;           // the caller's sums replace what modes 1 / 2 left there
         }
-        EDS_HIP_TRY(hipMemsetAsync(h->nres, 0, sizeof(int32_t), h->st));
+        EDS_HIP_TRY(hipMemsetAsync(h->nres, 0, sizeof(int32_t), h->own.st));
         // lf == NULL: the sums modes 1 / 2 of include/eds_hip_winsolve.h left on the device, when there are any
-        hipLaunchKernelGGL(k_win_points, dim3(blocks(n)), dim3(TB), 0, h->st, h->n, h->res_first, h->active, edswin_internal::lin_flags(h), 0,
+        hipLaunchKernelGGL(k_win_points, dim3(blocks(n)), dim3(TB), 0, h->own.st, h->n, h->res_first, h->active, edswin_internal::lin_flags(h), 0,
                            (const int32_t*)nullptr, h->efJ, h->prior, h->delta, h->lf, priorF ? 1 : 0, deltaF ? 1 : 0,
                            lf || edswin_internal::lf_on_device(h) ? 1 : 0, shift_prior_to_zero, h->pout, h->nres);
         EDS_HIP_TRY(hipGetLastError());
-        EDS_HIP_TRY(hipMemcpyAsync(&back, h->nres, sizeof(back), hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        if (int rc = read_back(h->own, &back, h->nres, sizeof(back))) return rc;
     }
     if (nres) *nres = back;
     return EDS_OK;
@@ -633,7 +598,7 @@ int eds_win_point_hessians(eds_win* h, const float* priorF, const float* deltaF,
 
 int eds_win_accumulate(eds_win* h, int F, const double* adHost, const double* adTarget, const float* priorF, const float* deltaF, const float* lf,
                        int shift_prior_to_zero, double* H_A, double* b_A, double* H_sc, double* b_sc, double* acc_out, int32_t* nres) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (F < 2 || F > h->max_frames) return fail(EDS_ERR_INVALID, "F is 2 .. max_frames");
     if (!adHost || !adTarget) return fail(EDS_ERR_INVALID, "adHost and adTarget are required");
     if (h->max_host >= F || h->max_target >= F) return fail(EDS_ERR_INVALID, "a point's host or a residual's target is not below F");
@@ -644,21 +609,21 @@ int eds_win_accumulate(eds_win* h, int F, const double* adHost, const double* ad
     if (int rc = eds_win_point_hessians(h, priorF, deltaF, lf, shift_prior_to_zero, nres)) return rc;
     const int words = edswin::acc_size(F);
     std::vector<double> acc((size_t)words, 0.0);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    if (h->n) EDS_HIP_TRY(hipMemcpyAsync(h->res_of, res_of.data(), res_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(h->first, first.data(), 9 * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    if (h->n) EDS_HIP_TRY(hipMemcpyAsync(h->res_of, res_of.data(), res_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->first, first.data(), 9 * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
     edswin_internal::queue_acc(h, F, 0, nullptr, lf || edswin_internal::lf_on_device(h) ? 1 : 0, words, h->acc);
     EDS_HIP_TRY(hipGetLastError());
     const size_t N = 4 + 8 * (size_t)F, ad_words = (size_t)F * F * 64;
     const int sw = edswin::stitch_words(F);
-    EDS_HIP_TRY(hipMemcpyAsync(h->ad, adHost, ad_words * sizeof(double), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(h->ad + ad_words, adTarget, ad_words * sizeof(double), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->ad, adHost, ad_words * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->ad + ad_words, adTarget, ad_words * sizeof(double), hipMemcpyHostToDevice, h->own.st));
     edswin_internal::queue_stitch(h, F, h->acc, h->ad, sw, h->stitched);
     EDS_HIP_TRY(hipGetLastError());
     std::vector<double> st((size_t)sw);
-    EDS_HIP_TRY(hipMemcpyAsync(st.data(), h->stitched, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
-    if (acc_out) EDS_HIP_TRY(hipMemcpyAsync(acc.data(), h->acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));   // only when asked for
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(st.data(), h->stitched, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->own.st));
+    if (acc_out) EDS_HIP_TRY(hipMemcpyAsync(acc.data(), h->acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->own.st));   // only when asked for
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     if (H_A) std::memcpy(H_A, st.data(), N * N * sizeof(double));
     if (b_A) std::memcpy(b_A, st.data() + N * N, N * sizeof(double));
     if (H_sc) std::memcpy(H_sc, st.data() + N * N + N, N * N * sizeof(double));
@@ -668,11 +633,10 @@ int eds_win_accumulate(eds_win* h, int F, const double* adHost, const double* ad
 }
 
 int eds_win_get_residuals(eds_win* h, const eds_win_residual_out* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     const size_t m = (size_t)h->m;
     if (!m) return EDS_OK;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
     if (int rc = download(h, out->state, h->state, m)) return rc;
     if (int rc = download(h, out->energy, h->energy, m)) return rc;
     if (int rc = download(h, out->new_state, h->new_state, m)) return rc;
@@ -684,22 +648,18 @@ int eds_win_get_residuals(eds_win* h, const eds_win_residual_out* out) {
     if (int rc = download(h, out->projected_to, h->proj, 16 * m)) return rc;
     if (int rc = download(h, out->J, h->J, J_WORDS * m)) return rc;
     if (int rc = download(h, out->ef_J, h->efJ, J_WORDS * m)) return rc;
-    if (int rc = download(h, out->JpJdF, h->JpJdF, 8 * m)) return rc;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return download(h, out->JpJdF, h->JpJdF, 8 * m);
 }
 
 int eds_win_acc_size(int F) { return F >= 2 && F <= EDS_WIN_MAX_FRAMES ? edswin::acc_size(F) : 0; }
 
 int eds_win_get_points(eds_win* h, const eds_win_point_out* out) {
-    if (int rc = check_handle(h)) return rc;
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!out) return fail(EDS_ERR_INVALID, "null output");
     const size_t n = (size_t)h->n;
     if (!n) return EDS_OK;
     std::vector<PointOut> p(n);
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(p.data(), h->pout, n * sizeof(PointOut), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (int rc = read_back(h->own, p.data(), h->pout, n * sizeof(PointOut))) return rc;
     for (size_t i = 0; i < n; ++i) {
         if (out->Hdd_accAF) out->Hdd_accAF[i] = p[i].Hdd_accAF;
         if (out->bd_accAF) out->bd_accAF[i] = p[i].bd_accAF;

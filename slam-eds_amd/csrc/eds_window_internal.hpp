@@ -7,13 +7,15 @@
 #include <cstdint>
 #include <vector>
 
+#include "eds_device_owner.hpp"
 #include "eds_window.hpp"
 
 namespace edswin {
 struct Sum { double energy; int32_t counts[4]; };
 }
 
-// include/eds_hip_winsolve.h's part of a window: eds_wsv_set_state allocates it, eds_win_destroy releases it (wsv_release)
+// include/eds_hip_winsolve.h's part of a window: eds_wsv_set_state allocates it through the window's owner, eds_win_destroy deletes it
+// (wsv_release) once the owner has freed the device memory
 struct eds_wsv_state {
     bool valid = false;                                    // eds_win_set_points and eds_win_set_residuals clear it
     bool rows_live = false;                                // the per-point and per-residual rows belong to the tables as they stand: set with the
@@ -36,7 +38,7 @@ struct eds_wsv_state {
     double* e_out = nullptr;                               // [2] an energy
 };
 
-// include/eds_hip_winedit.h's part of a window: the first eds_wed_* call allocates it, eds_win_destroy releases it (wed_release).  An edit
+// include/eds_hip_winedit.h's part of a window: the first eds_wed_* call allocates it, likewise (wed_release).  An edit
 // gathers every row into the second set and then exchanges the pointers with the window's (and the eds_wsv state's) own.
 struct eds_wed_state {
     edswin::Point* pts = nullptr;
@@ -60,7 +62,8 @@ struct eds_wed_state {
 };
 
 struct eds_win {
-    int dev = 0, H = 0, W = 0, max_frames = 0, max_points = 0, max_residuals = 0;
+    edscapi::DeviceOwner own;                             // the window's buffers and both states' below
+    int H = 0, W = 0, max_frames = 0, max_points = 0, max_residuals = 0;
     edswin::Params prm;
     edswin::Calib cal;
     bool calib_set = false, linearized = false;
@@ -70,7 +73,6 @@ struct eds_win {
     int32_t *res_of = nullptr, *first = nullptr;          // [max_points * 8], [9]
     double* acc = nullptr;                                // [acc_size(8)]
     double *ad = nullptr, *stitched = nullptr;            // adHost then adTarget [2][64][64]; H_A, b_A, H_sc, b_sc [stitch_words(8)]
-    hipStream_t st = nullptr;
     edswin::Px* frames = nullptr;
     float* in_img = nullptr;
     edswin::Point* pts = nullptr;

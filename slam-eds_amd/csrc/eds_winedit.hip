@@ -21,6 +21,7 @@
 #include "eds_window_internal.hpp"
 #include "eds_winedit.hpp"
 
+using edscapi::blocks;
 using edscapi::fail;
 using edswed::Cols;
 using edswed::SCAN_ITEMS;
@@ -206,65 +207,56 @@ __global__ void __launch_bounds__(TB) k_wed_ins_new_residuals(edswed::Ins s, int
     new_state[r] = edswed::ST_OUTLIER;
 }
 
-unsigned blocks(int64_t n, int per = TB) { return (unsigned)((n + per - 1) / per); }
-
 int ensure_state(eds_win* h) {
     const size_t mp = (size_t)h->max_points, mr = (size_t)h->max_residuals, ms = mp > mr ? mp : mr, jw = edswin::J_WORDS;
     if (!h->wed) {
         eds_wed_state* s = new eds_wed_state;
-        h->wed = s;
-        const bool ok = edscapi::device_alloc({{(void**)&s->pts, mp * sizeof(edswin::Point)},
-                                               {(void**)&s->ids, mp * sizeof(float)},
-                                               {(void**)&s->idz, mp * sizeof(float)},
-                                               {(void**)&s->prior, mp * sizeof(float)},
-                                               {(void**)&s->delta, mp * sizeof(float)},
-                                               {(void**)&s->lf, mp * 6 * sizeof(float)},
-                                               {(void**)&s->pout, mp * sizeof(edswin::PointOut)},
-                                               {(void**)&s->res_first, (mp + 1) * sizeof(int32_t)},
-                                               {(void**)&s->res_point, mr * sizeof(int32_t)},
-                                               {(void**)&s->res_target, mr * sizeof(int32_t)},
-                                               {(void**)&s->state, mr * sizeof(int32_t)},
-                                               {(void**)&s->new_state, mr * sizeof(int32_t)},
-                                               {(void**)&s->active, mr * sizeof(int32_t)},
-                                               {(void**)&s->energy, mr * sizeof(float)},
-                                               {(void**)&s->new_energy, mr * sizeof(float)},
-                                               {(void**)&s->new_energy_wo, mr * sizeof(float)},
-                                               {(void**)&s->ret, mr * sizeof(float)},
-                                               {(void**)&s->cp, mr * 3 * sizeof(float)},
-                                               {(void**)&s->proj, mr * 16 * sizeof(float)},
-                                               {(void**)&s->J, mr * jw * sizeof(float)},
-                                               {(void**)&s->efJ, mr * jw * sizeof(float)},
-                                               {(void**)&s->JpJdF, mr * 8 * sizeof(float)},
-                                               {(void**)&s->flag, ms * sizeof(int32_t)},
-                                               {(void**)&s->keep_r, mr * sizeof(int32_t)},
-                                               {(void**)&s->excl_r, (mr + 1) * sizeof(int32_t)},
-                                               {(void**)&s->map_r, mr * sizeof(int32_t)},
-                                               {(void**)&s->keep_p, mp * sizeof(int32_t)},
-                                               {(void**)&s->excl_p, (mp + 1) * sizeof(int32_t)},
-                                               {(void**)&s->map_p, mp * sizeof(int32_t)},
-                                               {(void**)&s->block, (ms / SCAN_TILE + 1) * sizeof(int32_t)},
-                                               {(void**)&s->total, 4 * sizeof(int32_t)},
-                                               {(void**)&s->marg, (size_t)MARG_WORDS * sizeof(double)}});
+        const bool ok = h->own.alloc({{(void**)&s->pts, mp * sizeof(edswin::Point)},
+                                      {(void**)&s->ids, mp * sizeof(float)},
+                                      {(void**)&s->idz, mp * sizeof(float)},
+                                      {(void**)&s->prior, mp * sizeof(float)},
+                                      {(void**)&s->delta, mp * sizeof(float)},
+                                      {(void**)&s->lf, mp * 6 * sizeof(float)},
+                                      {(void**)&s->pout, mp * sizeof(edswin::PointOut)},
+                                      {(void**)&s->res_first, (mp + 1) * sizeof(int32_t)},
+                                      {(void**)&s->res_point, mr * sizeof(int32_t)},
+                                      {(void**)&s->res_target, mr * sizeof(int32_t)},
+                                      {(void**)&s->state, mr * sizeof(int32_t)},
+                                      {(void**)&s->new_state, mr * sizeof(int32_t)},
+                                      {(void**)&s->active, mr * sizeof(int32_t)},
+                                      {(void**)&s->energy, mr * sizeof(float)},
+                                      {(void**)&s->new_energy, mr * sizeof(float)},
+                                      {(void**)&s->new_energy_wo, mr * sizeof(float)},
+                                      {(void**)&s->ret, mr * sizeof(float)},
+                                      {(void**)&s->cp, mr * 3 * sizeof(float)},
+                                      {(void**)&s->proj, mr * 16 * sizeof(float)},
+                                      {(void**)&s->J, mr * jw * sizeof(float)},
+                                      {(void**)&s->efJ, mr * jw * sizeof(float)},
+                                      {(void**)&s->JpJdF, mr * 8 * sizeof(float)},
+                                      {(void**)&s->flag, ms * sizeof(int32_t)},
+                                      {(void**)&s->keep_r, mr * sizeof(int32_t)},
+                                      {(void**)&s->excl_r, (mr + 1) * sizeof(int32_t)},
+                                      {(void**)&s->map_r, mr * sizeof(int32_t)},
+                                      {(void**)&s->keep_p, mp * sizeof(int32_t)},
+                                      {(void**)&s->excl_p, (mp + 1) * sizeof(int32_t)},
+                                      {(void**)&s->map_p, mp * sizeof(int32_t)},
+                                      {(void**)&s->block, (ms / SCAN_TILE + 1) * sizeof(int32_t)},
+                                      {(void**)&s->total, 4 * sizeof(int32_t)},
+                                      {(void**)&s->marg, (size_t)MARG_WORDS * sizeof(double)}});
         if (!ok) {                                              // nothing half-allocated stays behind: the next call allocates again
-            (void)hipGetLastError();
-            edswin_internal::wed_release(h);
+            delete s;
             return fail(EDS_ERR_HIP, "eds_wed: the device refused an allocation for the second set of tables");
         }
+        h->wed = s;
     }
     eds_wed_state* s = h->wed;
     if (h->wsv && !s->have_wsv) {
-        const bool ok = edscapi::device_alloc({{(void**)&s->lin, mr * sizeof(int32_t)},
-                                               {(void**)&s->rtz, mr * 8 * sizeof(float)},
-                                               {(void**)&s->res_approx, mr * 8 * sizeof(float)},
-                                               {(void**)&s->step, mp * sizeof(float)},
-                                               {(void**)&s->backup, mp * sizeof(float)}});
-        if (!ok) {
-            (void)hipGetLastError();
-            void* all[] = {s->lin, s->rtz, s->res_approx, s->step, s->backup};
-            for (void* p : all) if (p) (void)hipFree(p);
-            s->lin = nullptr; s->rtz = s->res_approx = s->step = s->backup = nullptr;
-            return fail(EDS_ERR_HIP, "eds_wed: the device refused an allocation for the second set of the solver's rows");
-        }
+        const bool ok = h->own.alloc({{(void**)&s->lin, mr * sizeof(int32_t)},
+                                      {(void**)&s->rtz, mr * 8 * sizeof(float)},
+                                      {(void**)&s->res_approx, mr * 8 * sizeof(float)},
+                                      {(void**)&s->step, mp * sizeof(float)},
+                                      {(void**)&s->backup, mp * sizeof(float)}});
+        if (!ok) return fail(EDS_ERR_HIP, "eds_wed: the device refused an allocation for the second set of the solver's rows");
         s->have_wsv = true;
     }
     return EDS_OK;
@@ -273,7 +265,7 @@ int ensure_state(eds_win* h) {
 // the caller's flags into the scratch array (host memory, or device memory that eds_dev_check_range has passed)
 int stage_flags(eds_win* h, const int32_t* flags, int on_device, size_t count) {
     if (!count) return EDS_OK;
-    EDS_HIP_TRY(hipMemcpyAsync(h->wed->flag, flags, count * sizeof(int32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->wed->flag, flags, count * sizeof(int32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->own.st));
     return EDS_OK;
 }
 
@@ -281,14 +273,14 @@ int stage_flags(eds_win* h, const int32_t* flags, int on_device, size_t count) {
 int queue_scan(eds_win* h, const int32_t* keep, int n, int32_t* excl, int32_t* map, int32_t* total, int32_t* tile = nullptr) {
     if (!tile) tile = h->wed->block;
     if (!n) {
-        EDS_HIP_TRY(hipMemsetAsync(excl, 0, sizeof(int32_t), h->st));
-        EDS_HIP_TRY(hipMemsetAsync(total, 0, sizeof(int32_t), h->st));
+        EDS_HIP_TRY(hipMemsetAsync(excl, 0, sizeof(int32_t), h->own.st));
+        EDS_HIP_TRY(hipMemsetAsync(total, 0, sizeof(int32_t), h->own.st));
         return EDS_OK;
     }
     const int tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(k_wed_tile_sums, dim3((unsigned)tiles), dim3(SCAN_TB), 0, h->st, keep, n, tile);
-    hipLaunchKernelGGL(k_wed_tile_offsets, dim3(1), dim3(SCAN_TB), 0, h->st, tile, tiles, total);
-    hipLaunchKernelGGL(k_wed_number, dim3((unsigned)tiles), dim3(SCAN_TB), 0, h->st, keep, n, tile, excl, map);
+    hipLaunchKernelGGL(k_wed_tile_sums, dim3((unsigned)tiles), dim3(SCAN_TB), 0, h->own.st, keep, n, tile);
+    hipLaunchKernelGGL(k_wed_tile_offsets, dim3(1), dim3(SCAN_TB), 0, h->own.st, tile, tiles, total);
+    hipLaunchKernelGGL(k_wed_number, dim3((unsigned)tiles), dim3(SCAN_TB), 0, h->own.st, keep, n, tile, excl, map);
     EDS_HIP_TRY(hipGetLastError());
     return EDS_OK;
 }
@@ -309,9 +301,9 @@ void queue_residual_rows(eds_win* h, const int32_t* map, int rows) {
     edswed::cols_add(t, h->cp, s->cp, 3); edswed::cols_add(t, h->proj, s->proj, 16); edswed::cols_add(t, h->JpJdF, s->JpJdF, 8);
     if (v) { edswed::cols_add(t, v->lin, s->lin, 1); edswed::cols_add(t, v->rtz, s->rtz, 8); edswed::cols_add(t, v->res_approx, s->res_approx, 8); }
     const int64_t words = (int64_t)rows * t.words, pieces = (int64_t)rows * edswed::WIDE_PIECES;
-    hipLaunchKernelGGL(k_wed_words, dim3(blocks(words)), dim3(TB), 0, h->st, t, map, words);
-    hipLaunchKernelGGL(k_wed_wide, dim3(blocks(pieces)), dim3(TB), 0, h->st, (const char*)h->J, (char*)s->J, map, pieces);
-    hipLaunchKernelGGL(k_wed_wide, dim3(blocks(pieces)), dim3(TB), 0, h->st, (const char*)h->efJ, (char*)s->efJ, map, pieces);
+    hipLaunchKernelGGL(k_wed_words, dim3(blocks(words)), dim3(TB), 0, h->own.st, t, map, words);
+    hipLaunchKernelGGL(k_wed_wide, dim3(blocks(pieces)), dim3(TB), 0, h->own.st, (const char*)h->J, (char*)s->J, map, pieces);
+    hipLaunchKernelGGL(k_wed_wide, dim3(blocks(pieces)), dim3(TB), 0, h->own.st, (const char*)h->efJ, (char*)s->efJ, map, pieces);
 }
 void queue_point_rows(eds_win* h, const int32_t* map, int rows) {
     eds_wed_state* s = h->wed;
@@ -323,7 +315,7 @@ void queue_point_rows(eds_win* h, const int32_t* map, int rows) {
     edswed::cols_add(t, h->pout, s->pout, (int)(sizeof(edswin::PointOut) / 4));
     if (v) { edswed::cols_add(t, v->step, s->step, 1); edswed::cols_add(t, v->backup, s->backup, 1); }
     const int64_t words = (int64_t)rows * t.words;
-    hipLaunchKernelGGL(k_wed_words, dim3(blocks(words)), dim3(TB), 0, h->st, t, map, words);
+    hipLaunchKernelGGL(k_wed_words, dim3(blocks(words)), dim3(TB), 0, h->own.st, t, map, words);
 }
 // the second set becomes the window's
 void exchange_sets(eds_win* h, bool points_too) {
@@ -345,7 +337,7 @@ void exchange_sets(eds_win* h, bool points_too) {
 // row into the second set, exchanges the sets and brings the host copies up to date.
 int compact(eds_win* h, bool points_change, int32_t* removed_points, int32_t* removed_residuals) {
     eds_wed_state* s = h->wed;
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     const int n = h->n, m = h->m;
     if (int rc = queue_scan(h, s->keep_r, m, s->excl_r, s->map_r, s->total)) return rc;
     if (points_change)
@@ -387,11 +379,11 @@ int compact(eds_win* h, bool points_change, int32_t* removed_points, int32_t* re
 
 // what every edit checks before anything is queued
 int check_flags(const eds_win* h, const int32_t* flags, int on_device, size_t count, bool required) {
-    if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (on_device != 0 && on_device != 1) return fail(EDS_ERR_INVALID, "on_device is 0 or 1");
     if (!flags) return required && count ? fail(EDS_ERR_INVALID, "the flags are required") : (int)EDS_OK;
     if (on_device && count)
-        if (int rc = eds_dev_check_range(h->dev, flags, count * sizeof(int32_t))) return rc;
+        if (int rc = eds_dev_check_range(h->own.dev, flags, count * sizeof(int32_t))) return rc;
     return EDS_OK;
 }
 
@@ -400,14 +392,7 @@ int check_flags(const eds_win* h, const int32_t* flags, int on_device, size_t co
 namespace edswin_internal {
 
 void wed_release(eds_win* h) {
-    eds_wed_state* s = h->wed;
-    if (!s) return;
-    void* all[] = {s->pts, s->ids, s->idz, s->prior, s->delta, s->lf, s->pout, s->res_first, s->res_point, s->res_target, s->state, s->new_state, s->active,
-                   s->energy, s->new_energy, s->new_energy_wo, s->ret, s->cp, s->proj, s->J, s->efJ, s->JpJdF, s->lin, s->rtz, s->res_approx, s->step,
-                   s->backup, s->flag, s->keep_r, s->excl_r, s->map_r, s->keep_p, s->excl_p, s->map_p, s->block, s->total, s->marg, s->ins_keep,
-                   s->ins_excl_c, s->ins_excl_g, s->ins_map_c, s->ins_map_g, s->ins_tile, s->ins_first};
-    for (void* p : all) if (p) (void)hipFree(p);
-    delete s;
+    delete h->wed;
     h->wed = nullptr;
 }
 
@@ -419,29 +404,29 @@ int eds_wed_abi_version(void) { return EDS_HIP_WINEDIT_ABI_VERSION; }
 
 int eds_wed_remove_residuals(eds_win* h, const int32_t* select, int on_device, int32_t* removed_out) {
     if (int rc = check_flags(h, select, on_device, h ? (size_t)h->m : 0, false)) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = ensure_state(h)) return rc;
     if (select)
         if (int rc = stage_flags(h, select, on_device, (size_t)h->m)) return rc;
     if (h->m)
-        hipLaunchKernelGGL(k_wed_keep_residuals, dim3(blocks(h->m)), dim3(TB), 0, h->st, h->m, select ? h->wed->flag : (const int32_t*)nullptr, h->state,
+        hipLaunchKernelGGL(k_wed_keep_residuals, dim3(blocks(h->m)), dim3(TB), 0, h->own.st, h->m, select ? h->wed->flag : (const int32_t*)nullptr, h->state,
                            h->wed->keep_r);
     return compact(h, false, nullptr, removed_out);
 }
 
 int eds_wed_remove_points(eds_win* h, const int32_t* flag, int on_device, int32_t* removed_points_out, int32_t* removed_residuals_out) {
     if (int rc = check_flags(h, flag, on_device, h ? (size_t)h->n : 0, true)) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = ensure_state(h)) return rc;
     if (int rc = stage_flags(h, flag, on_device, (size_t)h->n)) return rc;
-    if (h->n) hipLaunchKernelGGL(k_wed_keep_points, dim3(blocks(h->n)), dim3(TB), 0, h->st, h->n, h->wed->flag, h->wed->keep_p);
-    if (h->m) hipLaunchKernelGGL(k_wed_keep_residuals_of, dim3(blocks(h->m)), dim3(TB), 0, h->st, h->m, h->wed->keep_p, h->res_point, h->wed->keep_r);
+    if (h->n) hipLaunchKernelGGL(k_wed_keep_points, dim3(blocks(h->n)), dim3(TB), 0, h->own.st, h->n, h->wed->flag, h->wed->keep_p);
+    if (h->m) hipLaunchKernelGGL(k_wed_keep_residuals_of, dim3(blocks(h->m)), dim3(TB), 0, h->own.st, h->m, h->wed->keep_p, h->res_point, h->wed->keep_r);
     return compact(h, true, removed_points_out, removed_residuals_out);
 }
 
 int eds_wed_marginalize_frame(eds_win* h, int frame, const double* prior, const double* delta_prior, const double* HM, const double* bM, double* HM_out,
                               double* bM_out) {
-    if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!prior || !delta_prior || !HM || !bM || !HM_out || !bM_out) return fail(EDS_ERR_INVALID, "prior, delta_prior, HM, bM, HM_out and bM_out are required");
     if (!h->wsv || !h->wsv->valid)
         return fail(EDS_ERR_STATE, "eds_wed_marginalize_frame: no eds_wsv state set (the reference asserts EFDeltaValid and EFAdjointsValid); F is that state's");
@@ -455,10 +440,10 @@ int eds_wed_marginalize_frame(eds_win* h, int frame, const double* prior, const 
         if (!std::isfinite(prior[k]) || !std::isfinite(delta_prior[k])) return fail(EDS_ERR_INVALID, "eds_wed_marginalize_frame: a prior is not finite");
     for (int32_t host : h->host_of)
         if (host == frame) return fail(EDS_ERR_STATE, "eds_wed_marginalize_frame: a point is still hosted by frame " + std::to_string(frame) + " (the reference asserts)");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = ensure_state(h)) return rc;
     eds_wed_state* s = h->wed;
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     // the arithmetic first: when it refuses, nothing has changed
     std::vector<double> in((size_t)MARG_IN), out((size_t)nd * (nd + 1));
     std::memcpy(in.data(), HM, NN * sizeof(double));
@@ -507,9 +492,9 @@ int eds_wed_set_state(eds_win* h, int F, const double* adHost, const double* adT
 }
 
 int eds_wed_insert_activated(eds_win* h, eds_imm* im, int32_t* inserted_points_out, int32_t* inserted_residuals_out) {
-    if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!im) return fail(EDS_ERR_INVALID, "null eds_imm handle");
-    if (im->dev != h->dev) return fail(EDS_ERR_INVALID, "eds_wed_insert_activated: the eds_imm lives on another device");
+    if (im->own.dev != h->own.dev) return fail(EDS_ERR_INVALID, "eds_wed_insert_activated: the eds_imm lives on another device");
     if (im->H != h->H || im->W != h->W) return fail(EDS_ERR_INVALID, "eds_wed_insert_activated: the eds_imm's H x W is not the window's");
     if (!im->act || !im->act->fit_valid) return fail(EDS_ERR_STATE, "eds_wed_insert_activated: no fit (eds_act_optimize first)");
     const eds_act_state* a = im->act;
@@ -521,23 +506,19 @@ int eds_wed_insert_activated(eds_win* h, eds_imm* im, int32_t* inserted_points_o
     if (h->max_host >= F || h->max_target >= F) return fail(EDS_ERR_INVALID, "a point's host or a residual's target is not below F");
     const size_t C = (size_t)F * mp, G = C * F;
     if (G > ((size_t)1 << 30)) return fail(EDS_ERR_INVALID, "eds_wed_insert_activated: the eds_imm is too large");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = ensure_state(h)) return rc;
     eds_wed_state* s = h->wed;
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     if (s->ins_cap < C) {                                       // scratch for this eds_imm: C candidates, up to 8 C cells
-        void* old[] = {s->ins_keep, s->ins_excl_c, s->ins_excl_g, s->ins_map_c, s->ins_map_g, s->ins_tile, s->ins_first};
-        for (void* p : old) if (p) (void)hipFree(p);
-        s->ins_keep = s->ins_excl_c = s->ins_excl_g = s->ins_map_c = s->ins_map_g = s->ins_tile = s->ins_first = nullptr;
+        for (int32_t** p : {&s->ins_keep, &s->ins_excl_c, &s->ins_excl_g, &s->ins_map_c, &s->ins_map_g, &s->ins_tile, &s->ins_first}) h->own.release(*p);
         s->ins_cap = 0;
         const size_t C8 = (size_t)EDS_WIN_MAX_FRAMES * mp, G8 = C8 * EDS_WIN_MAX_FRAMES;
-        if (!edscapi::device_alloc({{(void**)&s->ins_keep, (C8 + G8) * sizeof(int32_t)}, {(void**)&s->ins_excl_c, (C8 + 1) * sizeof(int32_t)},
-                                    {(void**)&s->ins_excl_g, (G8 + 1) * sizeof(int32_t)}, {(void**)&s->ins_map_c, C8 * sizeof(int32_t)},
-                                    {(void**)&s->ins_map_g, G8 * sizeof(int32_t)}, {(void**)&s->ins_tile, (G8 / SCAN_TILE + 1) * sizeof(int32_t)},
-                                    {(void**)&s->ins_first, 9 * sizeof(int32_t)}})) {
-            (void)hipGetLastError();
+        if (!h->own.alloc({{(void**)&s->ins_keep, (C8 + G8) * sizeof(int32_t)}, {(void**)&s->ins_excl_c, (C8 + 1) * sizeof(int32_t)},
+                           {(void**)&s->ins_excl_g, (G8 + 1) * sizeof(int32_t)}, {(void**)&s->ins_map_c, C8 * sizeof(int32_t)},
+                           {(void**)&s->ins_map_g, G8 * sizeof(int32_t)}, {(void**)&s->ins_tile, (G8 / SCAN_TILE + 1) * sizeof(int32_t)},
+                           {(void**)&s->ins_first, 9 * sizeof(int32_t)}}))
             return fail(EDS_ERR_HIP, "eds_wed_insert_activated: the device refused an allocation");
-        }
         s->ins_cap = C8;
     }
     int32_t *keep_c = s->ins_keep, *keep_g = s->ins_keep + C;
@@ -603,7 +584,7 @@ int eds_wed_insert_activated(eds_win* h, eds_imm* im, int32_t* inserted_points_o
 }
 
 int eds_wed_counts(eds_win* h, int32_t* n, int32_t* m, int32_t* per_host) {
-    if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (n) *n = h->n;
     if (m) *m = h->m;
     if (per_host) edswed::per_host_counts(h->host_of, per_host);
@@ -611,12 +592,12 @@ int eds_wed_counts(eds_win* h, int32_t* n, int32_t* m, int32_t* per_host) {
 }
 
 int eds_wed_get(eds_win* h, const eds_wed_out* o) {
-    if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!o) return fail(EDS_ERR_INVALID, "null output");
     if (o->idepth_backup && !h->wsv) return fail(EDS_ERR_STATE, "eds_wed_get: no eds_wsv state was ever set, so there is no idepth backup");
     const size_t n = (size_t)h->n, m = (size_t)h->m;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    hipStream_t st = h->st;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    hipStream_t st = h->own.st;
     std::vector<edswin::Point> p(o->host || o->uv || o->color || o->weights ? n : 0);
 #define WED_GET(dst, src, count) if (o->dst && (count)) EDS_HIP_TRY(hipMemcpyAsync(o->dst, src, (count) * sizeof(*o->dst), hipMemcpyDeviceToHost, st))
     WED_GET(point, h->res_point, m);

@@ -19,7 +19,9 @@
 #include "eds_window_internal.hpp"
 #include "eds_winsolve.hpp"
 
+using edscapi::blocks;
 using edscapi::fail;
+using edscapi::read_back;
 using edswin::PointOut;
 using edswsv::Lin;
 using edswsv::MAX_N;
@@ -145,12 +147,11 @@ __global__ void __launch_bounds__(TB) k_wsv_marg_add(int N, double w, const doub
     if (e < half) io[e] = io[e] + w * (st[e] - st[half + e]);
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + TB - 1) / TB); }
 bool finite_all(const double* x, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; }
 bool finite_all(const float* x, size_t n) { for (size_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; }
 
 int check(const eds_win* h) {
-    if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (!h->wsv || !h->wsv->valid) return fail(EDS_ERR_STATE, "eds_wsv: no state set (eds_wsv_set_state; eds_win_set_points and eds_win_set_residuals invalidate it)");
     return EDS_OK;
 }
@@ -163,29 +164,28 @@ int alloc_state(eds_win* h) {
     if (h->wsv) return EDS_OK;
     eds_wsv_state* s = new eds_wsv_state;
     const size_t mp = (size_t)h->max_points, mr = (size_t)h->max_residuals, ms = mp > mr ? mp : mr;
-    const bool ok = edscapi::device_alloc({{(void**)&s->lin, mr * sizeof(int32_t)},
-                                           {(void**)&s->sel, ms * sizeof(int32_t)},
-                                           {(void**)&s->rtz, mr * 8 * sizeof(float)},
-                                           {(void**)&s->res_approx, mr * 8 * sizeof(float)},
-                                           {(void**)&s->adF, 2 * 64 * 64 * sizeof(float)},
-                                           {(void**)&s->adHTdeltaF, 64 * 8 * sizeof(float)},
-                                           {(void**)&s->cF, 8 * sizeof(float)},
-                                           {(void**)&s->xAd, (64 * 8 + 4) * sizeof(float)},
-                                           {(void**)&s->step, mp * sizeof(float)},
-                                           {(void**)&s->backup, mp * sizeof(float)},
-                                           {(void**)&s->ad, 2 * 64 * 64 * sizeof(double)},
-                                           {(void**)&s->vec, 4 * MAX_N * sizeof(double)},
-                                           {(void**)&s->accL, (size_t)edswin::acc_size(8) * sizeof(double)},
-                                           {(void**)&s->stL, (size_t)MAX_N * (MAX_N + 1) * sizeof(double)},
-                                           {(void**)&s->work, (size_t)edswsv::work_words() * sizeof(double)},
-                                           {(void**)&s->flag, 4 * sizeof(int32_t)},
-                                           {(void**)&s->e_out, 2 * sizeof(double)}});
-    h->wsv = s;
+    const bool ok = h->own.alloc({{(void**)&s->lin, mr * sizeof(int32_t)},
+                                  {(void**)&s->sel, ms * sizeof(int32_t)},
+                                  {(void**)&s->rtz, mr * 8 * sizeof(float)},
+                                  {(void**)&s->res_approx, mr * 8 * sizeof(float)},
+                                  {(void**)&s->adF, 2 * 64 * 64 * sizeof(float)},
+                                  {(void**)&s->adHTdeltaF, 64 * 8 * sizeof(float)},
+                                  {(void**)&s->cF, 8 * sizeof(float)},
+                                  {(void**)&s->xAd, (64 * 8 + 4) * sizeof(float)},
+                                  {(void**)&s->step, mp * sizeof(float)},
+                                  {(void**)&s->backup, mp * sizeof(float)},
+                                  {(void**)&s->ad, 2 * 64 * 64 * sizeof(double)},
+                                  {(void**)&s->vec, 4 * MAX_N * sizeof(double)},
+                                  {(void**)&s->accL, (size_t)edswin::acc_size(8) * sizeof(double)},
+                                  {(void**)&s->stL, (size_t)MAX_N * (MAX_N + 1) * sizeof(double)},
+                                  {(void**)&s->work, (size_t)edswsv::work_words() * sizeof(double)},
+                                  {(void**)&s->flag, 4 * sizeof(int32_t)},
+                                  {(void**)&s->e_out, 2 * sizeof(double)}});
     if (!ok) {                                                  // nothing half-allocated stays behind: the next call allocates again
-        (void)hipGetLastError();
-        edswin_internal::wsv_release(h);
+        delete s;
         return fail(EDS_ERR_HIP, "eds_wsv_set_state: the device refused an allocation");
     }
+    h->wsv = s;
     return EDS_OK;
 }
 
@@ -194,12 +194,7 @@ int alloc_state(eds_win* h) {
 namespace edswin_internal {
 
 void wsv_release(eds_win* h) {
-    eds_wsv_state* s = h->wsv;
-    if (!s) return;
-    void* all[] = {s->lin, s->sel, s->rtz, s->res_approx, s->adF, s->adHTdeltaF, s->cF, s->xAd, s->step, s->backup, s->ad, s->vec, s->accL, s->stL,
-                   s->work, s->flag, s->e_out};
-    for (void* p : all) if (p) (void)hipFree(p);
-    delete s;
+    delete h->wsv;
     h->wsv = nullptr;
 }
 
@@ -213,7 +208,7 @@ void wsv_invalidate(eds_win* h) {
 // where a state was set since the last eds_win_set_points / eds_win_set_residuals, priorF, isLinearized and res_toZeroF kept
 int wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarget, const double* delta, const double* prior, const double* delta_prior,
                   const double* cPrior, const double* cDelta, const float* priorF, const float* deltaF, bool from_device) {
-    if (!h) return fail(EDS_ERR_INVALID, "null eds_win handle");
+    if (int rc = edscapi::check_handle(h, "eds_win")) return rc;
     if (F < 2 || F > h->max_frames) return fail(EDS_ERR_INVALID, "F is 2 .. max_frames");
     if (!adHost || !adTarget || !delta || !prior || !delta_prior || !cPrior || !cDelta)
         return fail(EDS_ERR_INVALID, "adHost, adTarget, delta, prior, delta_prior, cPrior and cDelta are required");
@@ -223,7 +218,7 @@ int wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarge
         !finite_all(delta_prior, 8 * (size_t)F) || !finite_all(cPrior, 4) || !finite_all(cDelta, 4) || (priorF && !finite_all(priorF, n)) ||
         (deltaF && !finite_all(deltaF, n)))
         return fail(EDS_ERR_INVALID, "eds_wsv_set_state: an input is not finite");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = alloc_state(h)) return rc;
     eds_wsv_state* s = h->wsv;
     const bool keep = from_device && s->rows_live;              // include/eds_hip_winedit.h: priorF, isLinearized and res_toZeroF stay
@@ -245,7 +240,7 @@ int wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarge
     for (int i = 0; i < 8 * F; ++i) {
         vec[4 + i] = delta[i]; vec[MAX_N + 4 + i] = prior[i]; vec[2 * MAX_N + 4 + i] = prior[i] * delta_prior[i]; vec[3 * MAX_N + 4 + i] = delta_prior[i];
     }
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     EDS_HIP_TRY(hipMemcpyAsync(s->adF, adF.data(), adF.size() * sizeof(float), hipMemcpyHostToDevice, st));
     EDS_HIP_TRY(hipMemcpyAsync(s->adHTdeltaF, adht.data(), adht.size() * sizeof(float), hipMemcpyHostToDevice, st));
     EDS_HIP_TRY(hipMemcpyAsync(s->cF, cF.data(), 8 * sizeof(float), hipMemcpyHostToDevice, st));
@@ -293,11 +288,11 @@ int eds_wsv_fix_linearization(eds_win* h, const int32_t* select) {
     if (!select && h->m) return fail(EDS_ERR_INVALID, "select is required");
     if (!h->m) return EDS_OK;
     eds_wsv_state* s = h->wsv;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(s->sel, select, (size_t)h->m * sizeof(int32_t), hipMemcpyHostToDevice, h->st));
-    hipLaunchKernelGGL(k_wsv_fix, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->st, lin_of(h), h->m, s->sel, s->rtz, s->lin);
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipMemcpyAsync(s->sel, select, (size_t)h->m * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+    hipLaunchKernelGGL(k_wsv_fix, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, lin_of(h), h->m, s->sel, s->rtz, s->lin);
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
@@ -313,13 +308,13 @@ int eds_wsv_solve(eds_win* h, int iteration, double lambda, int mode, int have_f
     if (!HM || !bM || !x) return fail(EDS_ERR_INVALID, "HM, bM and x are required");
     if (!finite_all(HM, NN) || !finite_all(bM, (size_t)N) || (projector && !finite_all(projector, NN)))
         return fail(EDS_ERR_INVALID, "eds_wsv_solve: HM, bM or the projector is not finite");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = edswin_internal::upload_maps(h, F)) return rc;
     lambda = edswsv::mode_lambda(mode, lambda);
     const int system = (mode & edswsv::SOLVER_ORTHOGONALIZE_SYSTEM) ? 1 : 0;
     const int orth_system = system && !have_first_frame && projector ? 1 : 0;
     const int orth_x = edswsv::mode_orth_x(mode, iteration) && projector ? 1 : 0;
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     edswsv::Sys sys = {N, system, orth_system, lambda, h->stitched, h->stitched + NN, h->stitched + NN + N, h->stitched + 2 * NN + N, s->stL, s->stL + NN,
                        s->vec, s->work};
     EDS_HIP_TRY(hipMemcpyAsync(sys.mat(edswsv::W_HM), HM, NN * sizeof(double), hipMemcpyHostToDevice, st));
@@ -372,11 +367,11 @@ int eds_wsv_solve(eds_win* h, int iteration, double lambda, int mode, int have_f
 
 int eds_wsv_backup_idepths(eds_win* h) {
     if (int rc = check(h)) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (h->n) {
-        hipLaunchKernelGGL(k_wsv_backup, dim3(blocks((size_t)h->n)), dim3(TB), 0, h->st, h->n, h->prm.scale_idepth, h->ids, h->wsv->backup);
+        hipLaunchKernelGGL(k_wsv_backup, dim3(blocks((size_t)h->n)), dim3(TB), 0, h->own.st, h->n, h->prm.scale_idepth, h->ids, h->wsv->backup);
         EDS_HIP_TRY(hipGetLastError());
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     }
     h->wsv->have_backup = true;
     return EDS_OK;
@@ -387,34 +382,28 @@ int eds_wsv_step_idepths(eds_win* h, float fac) {
     if (!std::isfinite(fac)) return fail(EDS_ERR_INVALID, "fac is not finite");
     if (!h->wsv->have_backup || !h->wsv->have_step) return fail(EDS_ERR_STATE, "eds_wsv_step_idepths needs eds_wsv_backup_idepths and a usable eds_wsv_solve first");
     if (!h->n) return EDS_OK;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    hipLaunchKernelGGL(k_wsv_step_idepths, dim3(blocks((size_t)h->n)), dim3(TB), 0, h->st, h->n, h->prm.scale_idepth, fac, h->wsv->backup, h->wsv->step, h->ids);
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    hipLaunchKernelGGL(k_wsv_step_idepths, dim3(blocks((size_t)h->n)), dim3(TB), 0, h->own.st, h->n, h->prm.scale_idepth, fac, h->wsv->backup, h->wsv->step, h->ids);
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
 int eds_wsv_get_steps(eds_win* h, float* step) {
     if (int rc = check(h)) return rc;
     if (!step) return fail(EDS_ERR_INVALID, "null output");
-    if (!h->n) return EDS_OK;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipMemcpyAsync(step, h->wsv->step, (size_t)h->n * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return read_back(h->own, step, h->wsv->step, (size_t)h->n * sizeof(float));
 }
 
 int eds_wsv_l_energy(eds_win* h, double* energy) {
     if (int rc = check(h)) return rc;
     if (!energy) return fail(EDS_ERR_INVALID, "null output");
     eds_wsv_state* s = h->wsv;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = edswin_internal::upload_maps(h, s->F)) return rc;
-    hipLaunchKernelGGL(k_wsv_l_energy, dim3(1), dim3(edswin::LANES), 0, h->st, lin_of(h), h->first, s->vec, s->cF, s->e_out);
+    hipLaunchKernelGGL(k_wsv_l_energy, dim3(1), dim3(edswin::LANES), 0, h->own.st, lin_of(h), h->first, s->vec, s->cF, s->e_out);
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipMemcpyAsync(energy, s->e_out, sizeof(double), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return read_back(h->own, energy, s->e_out, sizeof(double));
 }
 
 int eds_wsv_m_energy(eds_win* h, const double* HM, const double* bM, double* energy) {
@@ -424,16 +413,14 @@ int eds_wsv_m_energy(eds_win* h, const double* HM, const double* bM, double* ene
     const int N = 4 + 8 * s->F;
     const size_t NN = (size_t)N * N;
     if (!finite_all(HM, NN) || !finite_all(bM, (size_t)N)) return fail(EDS_ERR_INVALID, "eds_wsv_m_energy: HM or bM is not finite");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     double* dHM = s->work + (size_t)edswsv::W_HM * MAX_N * MAX_N;
     double* dbM = s->work + (size_t)edswsv::W_MATS * MAX_N * MAX_N + (size_t)edswsv::V_BM * MAX_N;
-    EDS_HIP_TRY(hipMemcpyAsync(dHM, HM, NN * sizeof(double), hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(dbM, bM, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->st));
-    hipLaunchKernelGGL(k_wsv_m_energy, dim3(1), dim3(SOLVE_TB), 0, h->st, N, dHM, dbM, s->vec, s->e_out + 1);
+    EDS_HIP_TRY(hipMemcpyAsync(dHM, HM, NN * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(dbM, bM, (size_t)N * sizeof(double), hipMemcpyHostToDevice, h->own.st));
+    hipLaunchKernelGGL(k_wsv_m_energy, dim3(1), dim3(SOLVE_TB), 0, h->own.st, N, dHM, dbM, s->vec, s->e_out + 1);
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipMemcpyAsync(energy, s->e_out + 1, sizeof(double), hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
-    return EDS_OK;
+    return read_back(h->own, energy, s->e_out + 1, sizeof(double));
 }
 
 int eds_wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac, double weight_fac, double* HM, double* bM, int32_t* res_in_m) {
@@ -444,9 +431,9 @@ int eds_wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac,
     const size_t NN = (size_t)N * N;
     if (!std::isfinite(prior_fac) || !std::isfinite(weight_fac) || !finite_all(HM, NN) || !finite_all(bM, (size_t)N))
         return fail(EDS_ERR_INVALID, "eds_wsv_marginalize_points: a factor, HM or bM is not finite");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = edswin_internal::upload_maps(h, F)) return rc;
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     int32_t flag[4] = {0, 0, 0, 0};
     EDS_HIP_TRY(hipMemsetAsync(s->flag, 0, 4 * sizeof(int32_t), st));
     if (h->n) EDS_HIP_TRY(hipMemcpyAsync(s->sel, marg, (size_t)h->n * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -454,8 +441,7 @@ int eds_wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac,
         hipLaunchKernelGGL(k_wsv_marg_check, dim3(blocks((size_t)h->m)), dim3(TB), 0, st, h->m, h->res_point, h->active, s->lin, s->sel, s->flag + 2);
         EDS_HIP_TRY(hipGetLastError());
     }
-    EDS_HIP_TRY(hipMemcpyAsync(flag, s->flag, sizeof(flag), hipMemcpyDeviceToHost, st));
-    EDS_HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = read_back(h->own, flag, s->flag, sizeof(flag))) return rc;
     if (flag[2]) return fail(EDS_ERR_STATE, "eds_wsv_marginalize_points: " + std::to_string(flag[2]) + " active residuals of the flagged points are not linearized");
     const Lin t = lin_of(h);
     double* io = s->work + (size_t)edswsv::W_T1 * MAX_N * MAX_N;                // HM then bM, N (N + 1) words over two matrix slots
@@ -491,8 +477,8 @@ int eds_wsv_get(eds_win* h, const eds_wsv_out* o) {
     const size_t NN = (size_t)N * N, n = (size_t)h->n, m = (size_t)h->m;
     if ((o->HFinal || o->bFinal || o->xAd || o->frame_step) && !s->have_system)
         return fail(EDS_ERR_STATE, "eds_wsv_get: no eds_wsv_solve has run");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    hipStream_t st = h->st;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    hipStream_t st = h->own.st;
     const double* work = s->work;
 #define WSV_GET(dst, src, count) if (o->dst && (count)) EDS_HIP_TRY(hipMemcpyAsync(o->dst, src, (count) * sizeof(*o->dst), hipMemcpyDeviceToHost, st))
     WSV_GET(adHTdeltaF, s->adHTdeltaF, (size_t)F * F * 8);

@@ -8,6 +8,7 @@ Plumbing only: every number comes from the HIP kernels behind the C ABI (csrc/ed
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -18,56 +19,39 @@ STATUS_NAMES = ("IPS_GOOD", "IPS_OOB", "IPS_OUTLIER", "IPS_SKIPPED", "IPS_BADCON
 HOST_IMAGE, TARGET_IMAGE = 0, 1
 
 
-class Params(C.Structure):
+class Params(capi.ParamStruct):
     """``eds_imm_params`` — the setting_* values the constructors and traceOn read (reference src/utils/settings.cpp:90-165)."""
     _fields_ = [("max_pix_search", C.c_float), ("trace_stepsize", C.c_float), ("trace_gn_iterations", C.c_int32),
                 ("trace_gn_threshold", C.c_float), ("trace_extra_slack_on_th", C.c_float), ("trace_slack_interval", C.c_float),
                 ("trace_min_improvement_factor", C.c_float), ("min_trace_test_radius", C.c_int32), ("huber_th", C.c_float),
                 ("outlier_th", C.c_float), ("outlier_th_sum_component", C.c_float), ("overall_energy_th_weight", C.c_float)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-_bound = False
-
-
+@functools.lru_cache(maxsize=None)
 def _lib():
-    global _bound
-    L = capi.lib()
-    if not _bound:
-        missing = [s for s in capi.IMM_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
-        vp, i64 = C.c_void_p, C.c_int64
-        L.eds_imm_params_default.argtypes = [C.POINTER(Params)]
-        L.eds_imm_params_default.restype = None
-        L.eds_imm_create.argtypes = [C.c_int] * 6 + [C.POINTER(vp)]
-        L.eds_imm_destroy.argtypes = [vp]
-        L.eds_imm_destroy.restype = None
-        L.eds_imm_set_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_imm_get_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_imm_set_host_images.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int]
-        L.eds_imm_set_target_images.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int]
-        L.eds_imm_create_points.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        L.eds_imm_create_points_selected.argtypes = [vp, C.c_int, vp] + [C.c_int] * 4 + [vp, C.POINTER(C.c_int)]
-        L.eds_imm_num_points.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
-        L.eds_imm_trace.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        L.eds_imm_get.argtypes = [vp, C.c_int] + [vp] * 6
-        L.eds_imm_get_points.argtypes = [vp, C.c_int] + [vp] * 5
-        L.eds_imm_get_image.argtypes = [vp, C.c_int, C.c_int, vp]
-        _bound = True
-    return L
+    vp, i64 = C.c_void_p, C.c_int64
+    return capi.bind(capi.IMM_EXPORTS, {
+        "eds_imm_params_default": ([C.POINTER(Params)], None),
+        "eds_imm_create": [C.c_int] * 6 + [C.POINTER(vp)],
+        "eds_imm_destroy": ([vp], None),
+        "eds_imm_set_params": [vp, C.POINTER(Params)],
+        "eds_imm_get_params": [vp, C.POINTER(Params)],
+        "eds_imm_set_host_images": [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int],
+        "eds_imm_set_target_images": [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int],
+        "eds_imm_create_points": [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp],
+        "eds_imm_create_points_selected": [vp, C.c_int, vp] + [C.c_int] * 4 + [vp, C.POINTER(C.c_int)],
+        "eds_imm_num_points": [vp, C.c_int, C.POINTER(C.c_int)],
+        "eds_imm_trace": [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp],
+        "eds_imm_get": [vp, C.c_int] + [vp] * 6,
+        "eds_imm_get_points": [vp, C.c_int] + [vp] * 5,
+        "eds_imm_get_image": [vp, C.c_int, C.c_int, vp],
+    })
 
 
 def default_params(**over) -> Params:
     p = Params()
     _lib().eds_imm_params_default(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return p.update(**over)
 
 
 def precalc(K, R, t, aff_host=(0.0, 0.0), aff_target=(0.0, 0.0), exposures=(1.0, 1.0)):
@@ -93,8 +77,9 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-class ImmaturePoints:
+class ImmaturePoints(capi.OwnedHandle):
     """The immature points of up to ``max_hosts`` host frames and the frames they are traced on, in device memory."""
+    _destroy = "eds_imm_destroy"
 
     def __init__(self, H, W, max_hosts=1, max_points_per_host=2000, max_targets=1, device=0, **params):
         self._h = C.c_void_p()
@@ -103,23 +88,8 @@ class ImmaturePoints:
         if params:
             self.set_params(**params)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib().eds_imm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_params(self, **over):
-        p = self.params()
-        for k, v in over.items():
-            if not hasattr(p, k):
-                raise KeyError(k)
-            setattr(p, k, v)
+        p = self.params().update(**over)
         capi._check(_lib().eds_imm_set_params(self._h, C.byref(p)))
 
     def params(self) -> Params:
@@ -128,8 +98,7 @@ class ImmaturePoints:
         return p
 
     def _set_images(self, fn, first, images):
-        raw = isinstance(images, tuple) and len(images) == 4 and isinstance(images[0], int)       # (ptr, shape, strides, dtype)
-        if not raw and not hasattr(images, "__cuda_array_interface__"):
+        if not capi.is_device_source(images):
             a = _f32(images)
             a = a[None] if a.ndim == 2 else a
             if a.shape[1:] != (self.H, self.W):

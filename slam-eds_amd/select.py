@@ -7,6 +7,7 @@ owns one ``eds_sel``.  The random table is an input: ``reference_pattern`` is wh
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -16,13 +17,10 @@ THS, THS_SMOOTHED = 0, 1
 MAX_POTENTIAL = 1 << 30
 
 
-class Params(C.Structure):
+class Params(capi.ParamStruct):
     """``eds_sel_params`` — the setting_* values the selector reads (reference src/utils/settings.cpp:145-148)."""
     _fields_ = [("min_grad_hist_cut", C.c_float), ("min_grad_hist_add", C.c_float), ("grad_downweight_per_level", C.c_float),
                 ("select_direction_distribution", C.c_int32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Pass(C.Structure):
@@ -30,47 +28,33 @@ class Pass(C.Structure):
     _fields_ = [("potential", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32), ("n4", C.c_int32)]
 
 
-_bound = False
-
-
+@functools.lru_cache(maxsize=None)
 def _lib():
-    global _bound
-    L = capi.lib()
-    if not _bound:
-        missing = [s for s in capi.SEL_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
-        vp, ip = C.c_void_p, C.POINTER(C.c_int)
-        L.eds_sel_params_default.argtypes = [C.POINTER(Params)]
-        L.eds_sel_params_default.restype = None
-        L.eds_sel_create.argtypes = [C.c_int] * 3 + [C.POINTER(vp)]
-        L.eds_sel_destroy.argtypes = [vp]
-        L.eds_sel_destroy.restype = None
-        L.eds_sel_set_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_sel_get_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_sel_set_random_pattern.argtypes = [vp, vp, C.c_size_t]
-        L.eds_sel_fill_reference_pattern.argtypes = [vp, C.c_size_t]
-        L.eds_sel_set_potential.argtypes = [vp, C.c_int]
-        L.eds_sel_get_potential.argtypes = [vp, ip]
-        L.eds_sel_set_image.argtypes = [vp, vp, C.c_int64, C.c_int, vp]
-        L.eds_sel_make_maps.argtypes = [vp, C.c_float, C.c_int, C.c_float, ip, C.POINTER(Pass), C.c_int, ip, vp]
-        L.eds_sel_get_map.argtypes = [vp, vp]
-        L.eds_sel_get_selection.argtypes = [vp, ip, vp, vp]
-        L.eds_sel_get_level.argtypes = [vp, C.c_int, vp]
-        L.eds_sel_get_thresholds.argtypes = [vp, C.c_int, vp]
-        L.eds_sel_get_scan_info.argtypes = [vp, ip, ip]
-        _bound = True
-    return L
+    vp, ip = C.c_void_p, C.POINTER(C.c_int)
+    return capi.bind(capi.SEL_EXPORTS, {
+        "eds_sel_params_default": ([C.POINTER(Params)], None),
+        "eds_sel_create": [C.c_int] * 3 + [C.POINTER(vp)],
+        "eds_sel_destroy": ([vp], None),
+        "eds_sel_set_params": [vp, C.POINTER(Params)],
+        "eds_sel_get_params": [vp, C.POINTER(Params)],
+        "eds_sel_set_random_pattern": [vp, vp, C.c_size_t],
+        "eds_sel_fill_reference_pattern": [vp, C.c_size_t],
+        "eds_sel_set_potential": [vp, C.c_int],
+        "eds_sel_get_potential": [vp, ip],
+        "eds_sel_set_image": [vp, vp, C.c_int64, C.c_int, vp],
+        "eds_sel_make_maps": [vp, C.c_float, C.c_int, C.c_float, ip, C.POINTER(Pass), C.c_int, ip, vp],
+        "eds_sel_get_map": [vp, vp],
+        "eds_sel_get_selection": [vp, ip, vp, vp],
+        "eds_sel_get_level": [vp, C.c_int, vp],
+        "eds_sel_get_thresholds": [vp, C.c_int, vp],
+        "eds_sel_get_scan_info": [vp, ip, ip],
+    })
 
 
 def default_params(**over) -> Params:
     p = Params()
     _lib().eds_sel_params_default(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return p.update(**over)
 
 
 def reference_pattern(n):
@@ -80,12 +64,12 @@ def reference_pattern(n):
     return out
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp = capi.vp
 
 
-class Selector:
+class Selector(capi.OwnedHandle):
     """The pixel selector of one image size, in device memory.  ``potential`` is the reference's currentPotential."""
+    _destroy = "eds_sel_destroy"
 
     def __init__(self, H, W, device=0, table=None, **params):
         self._h = C.c_void_p()
@@ -98,23 +82,8 @@ class Selector:
         if table is not None:
             self.set_random_pattern(table)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib().eds_sel_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_params(self, **over):
-        p = self.params()
-        for k, v in over.items():
-            if not hasattr(p, k):
-                raise KeyError(k)
-            setattr(p, k, v)
+        p = self.params().update(**over)
         capi._check(_lib().eds_sel_set_params(self._h, C.byref(p)))
 
     def params(self) -> Params:
@@ -140,8 +109,7 @@ class Selector:
         """fp32 intensities 0 .. 255: a numpy array H x W (its row stride is kept) or device memory (``capi.DeviceArray`` and the like);
         B: None, or the 256 floats of ``CalibHessian::B``"""
         b = None if B is None else np.ascontiguousarray(B, dtype=np.float32).reshape(256)
-        raw = isinstance(image, tuple) and len(image) == 4 and isinstance(image[0], int)
-        if not raw and not hasattr(image, "__cuda_array_interface__"):
+        if not capi.is_device_source(image):
             a = np.asarray(image, dtype=np.float32)
             if a.shape != (self.H, self.W):
                 raise ValueError(f"the image must be {self.H} x {self.W}, not {a.shape}")

@@ -8,6 +8,7 @@ one ``eds_win``.  ``precalc`` forms ``FrameFramePrecalc::set``'s fp32 values; ``
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -25,14 +26,11 @@ POINT_FIELDS = (("Hdd_accAF", "f4", ()), ("bd_accAF", "f4", ()), ("Hcd_accAF", "
                 ("idepth_hessian", "f4", ()), ("nres", "i4", ()))
 
 
-class Params(C.Structure):
+class Params(capi.ParamStruct):
     """``eds_win_params`` — the setting_* values and SCALE_* constants linearize reads (settings.cpp:91-127, HessianBlocks.h:58-62)."""
     _fields_ = [("outlier_th_sum_component", C.c_float), ("huber_th", C.c_float), ("affine_opt_mode_a", C.c_float),
                 ("affine_opt_mode_b", C.c_float), ("scale_idepth", C.c_float), ("scale_f", C.c_float), ("scale_c", C.c_float),
                 ("reserved", C.c_float)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class ResidualOut(C.Structure):
@@ -43,49 +41,35 @@ class PointOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in POINT_FIELDS]
 
 
-_bound = False
-
-
+@functools.lru_cache(maxsize=None)
 def _lib():
-    global _bound
-    L = capi.lib()
-    if not _bound:
-        missing = [s for s in capi.WIN_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
-        vp, i64, f = C.c_void_p, C.c_int64, C.c_float
-        L.eds_win_params_default.argtypes = [C.POINTER(Params)]
-        L.eds_win_params_default.restype = None
-        L.eds_win_create.argtypes = [C.c_int] * 6 + [C.POINTER(vp)]
-        L.eds_win_destroy.argtypes = [vp]
-        L.eds_win_destroy.restype = None
-        L.eds_win_set_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_win_get_params.argtypes = [vp, C.POINTER(Params)]
-        L.eds_win_set_calib.argtypes = [vp, f, f, f, f]
-        L.eds_win_set_frames.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int]
-        L.eds_win_get_frame.argtypes = [vp, C.c_int, vp]
-        L.eds_win_set_points.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
-        L.eds_win_set_idepths.argtypes = [vp, vp, vp]
-        L.eds_win_set_residuals.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-        L.eds_win_linearize.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-        L.eds_win_apply.argtypes = [vp, C.c_int]
-        L.eds_win_point_hessians.argtypes = [vp, vp, vp, vp, C.c_int, vp]
-        L.eds_win_get_residuals.argtypes = [vp, C.POINTER(ResidualOut)]
-        L.eds_win_accumulate.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
-        L.eds_win_acc_size.argtypes = [C.c_int]
-        L.eds_win_get_points.argtypes = [vp, C.POINTER(PointOut)]
-        _bound = True
-    return L
+    vp, i64, f = C.c_void_p, C.c_int64, C.c_float
+    return capi.bind(capi.WIN_EXPORTS, {
+        "eds_win_params_default": ([C.POINTER(Params)], None),
+        "eds_win_create": [C.c_int] * 6 + [C.POINTER(vp)],
+        "eds_win_destroy": ([vp], None),
+        "eds_win_set_params": [vp, C.POINTER(Params)],
+        "eds_win_get_params": [vp, C.POINTER(Params)],
+        "eds_win_set_calib": [vp, f, f, f, f],
+        "eds_win_set_frames": [vp, C.c_int, C.c_int, vp, i64, i64, C.c_int],
+        "eds_win_get_frame": [vp, C.c_int, vp],
+        "eds_win_set_points": [vp, C.c_int, vp, vp, vp, vp, vp, vp],
+        "eds_win_set_idepths": [vp, vp, vp],
+        "eds_win_set_residuals": [vp, C.c_int, vp, vp, vp, vp],
+        "eds_win_linearize": [vp, C.c_int, vp, vp, vp, vp],
+        "eds_win_apply": [vp, C.c_int],
+        "eds_win_point_hessians": [vp, vp, vp, vp, C.c_int, vp],
+        "eds_win_get_residuals": [vp, C.POINTER(ResidualOut)],
+        "eds_win_accumulate": [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp],
+        "eds_win_acc_size": [C.c_int],
+        "eds_win_get_points": [vp, C.POINTER(PointOut)],
+    })
 
 
 def default_params(**over) -> Params:
     p = Params()
     _lib().eds_win_params_default(C.byref(p))
-    for k, v in over.items():
-        if not hasattr(p, k):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return p.update(**over)
 
 
 def _se3(T):
@@ -152,8 +136,7 @@ def adjoints(T_world_to_cam, aff=None, exposures=None):
     return adH, adT
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp = capi.vp
 
 
 def _f32(a, shape=None):
@@ -161,8 +144,9 @@ def _f32(a, shape=None):
     return a if shape is None else a.reshape(shape)
 
 
-class Window:
+class Window(capi.OwnedHandle):
     """The frames, points and residuals of one optimisation window in device memory."""
+    _destroy = "eds_win_destroy"
 
     def __init__(self, H, W, max_frames=MAX_FRAMES, max_points=20000, max_residuals=140000, device=0, **params):
         self._h = C.c_void_p()
@@ -172,23 +156,8 @@ class Window:
         if params:
             self.set_params(**params)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib().eds_win_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_params(self, **over):
-        p = self.params()
-        for k, v in over.items():
-            if not hasattr(p, k):
-                raise KeyError(k)
-            setattr(p, k, v)
+        p = self.params().update(**over)
         capi._check(_lib().eds_win_set_params(self._h, C.byref(p)))
 
     def params(self) -> Params:
@@ -201,7 +170,7 @@ class Window:
 
     def set_frames(self, first, images):
         """images: count x H x W (or one H x W) on the host, or a device array of that shape with contiguous rows"""
-        if hasattr(images, "__cuda_array_interface__") or (isinstance(images, tuple) and len(images) == 4 and isinstance(images[0], int)):
+        if capi.is_device_source(images):
             ptr, shape, est, dt = capi.device_array_info(images)
             shape, est = tuple(shape), tuple(est)
             if len(shape) == 2:

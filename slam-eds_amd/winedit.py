@@ -8,6 +8,7 @@ Plumbing only: every row is moved by the HIP kernels behind the C ABI (csrc/eds_
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -27,32 +28,25 @@ class Out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in OUT_FIELDS]
 
 
-_bound = False
-
-
+@functools.lru_cache(maxsize=None)
 def _lib():
-    global _bound
-    L = _wsv_lib()
-    if not _bound:
-        missing = [s for s in capi.WED_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
-        vp, i = C.c_void_p, C.c_int
-        L.eds_wed_remove_residuals.argtypes = [vp, vp, i, vp]
-        L.eds_wed_remove_points.argtypes = [vp, vp, i, vp, vp]
-        L.eds_wed_marginalize_frame.argtypes = [vp, i, vp, vp, vp, vp, vp, vp]
-        L.eds_wed_insert_activated.argtypes = [vp, vp, vp, vp]
-        L.eds_wed_set_state.argtypes = [vp, i] + [vp] * 7
-        L.eds_wed_counts.argtypes = [vp, vp, vp, vp]
-        L.eds_wed_get.argtypes = [vp, C.POINTER(Out)]
-        _bound = True
-    return L
+    _wsv_lib()
+    vp, i = C.c_void_p, C.c_int
+    return capi.bind(capi.WED_EXPORTS, {
+        "eds_wed_remove_residuals": [vp, vp, i, vp],
+        "eds_wed_remove_points": [vp, vp, i, vp, vp],
+        "eds_wed_marginalize_frame": [vp, i, vp, vp, vp, vp, vp, vp],
+        "eds_wed_insert_activated": [vp, vp, vp, vp],
+        "eds_wed_set_state": [vp, i] + [vp] * 7,
+        "eds_wed_counts": [vp, vp, vp, vp],
+        "eds_wed_get": [vp, C.POINTER(Out)],
+    })
 
 
 def _flags(flags, count):
     """(pointer, on_device, keep-alive) of `count` int32 flags: a numpy array (anything array-like), or a device array
     (``__cuda_array_interface__`` or a raw (ptr, shape, strides, dtype) tuple) that is contiguous int32"""
-    if hasattr(flags, "__cuda_array_interface__") or (isinstance(flags, tuple) and len(flags) == 4 and isinstance(flags[0], int)):
+    if capi.is_device_source(flags):
         ptr, shape, est, dt = capi.device_array_info(flags)
         if dt != np.int32 or tuple(shape) != (count,) or (count > 1 and tuple(est) != (1,)):
             raise ValueError(f"device flags must be {count} contiguous int32 values")

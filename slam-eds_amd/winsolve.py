@@ -7,6 +7,7 @@ Plumbing only: every number comes from the HIP kernels behind the C ABI (csrc/ed
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -37,29 +38,22 @@ class Out(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _, _ in OUT_FIELDS]
 
 
-_bound = False
-
-
+@functools.lru_cache(maxsize=None)
 def _lib():
-    global _bound
-    L = _win_lib()
-    if not _bound:
-        missing = [s for s in capi.WSV_EXPORTS if not hasattr(L, s)]
-        if missing:
-            raise capi.EdsError(capi.ERR_INVALID, f"{capi.LIB_PATH} does not export {missing}")
-        vp, d, f, i = C.c_void_p, C.c_double, C.c_float, C.c_int
-        L.eds_wsv_set_state.argtypes = [vp, i] + [vp] * 9
-        L.eds_wsv_fix_linearization.argtypes = [vp, vp]
-        L.eds_wsv_solve.argtypes = [vp, i, d, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
-        L.eds_wsv_backup_idepths.argtypes = [vp]
-        L.eds_wsv_step_idepths.argtypes = [vp, f]
-        L.eds_wsv_get_steps.argtypes = [vp, vp]
-        L.eds_wsv_l_energy.argtypes = [vp, vp]
-        L.eds_wsv_m_energy.argtypes = [vp, vp, vp, vp]
-        L.eds_wsv_marginalize_points.argtypes = [vp, vp, f, d, vp, vp, vp]
-        L.eds_wsv_get.argtypes = [vp, C.POINTER(Out)]
-        _bound = True
-    return L
+    _win_lib()
+    vp, d, f, i = C.c_void_p, C.c_double, C.c_float, C.c_int
+    return capi.bind(capi.WSV_EXPORTS, {
+        "eds_wsv_set_state": [vp, i] + [vp] * 9,
+        "eds_wsv_fix_linearization": [vp, vp],
+        "eds_wsv_solve": [vp, i, d, i, i, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)],
+        "eds_wsv_backup_idepths": [vp],
+        "eds_wsv_step_idepths": [vp, f],
+        "eds_wsv_get_steps": [vp, vp],
+        "eds_wsv_l_energy": [vp, vp],
+        "eds_wsv_m_energy": [vp, vp, vp, vp],
+        "eds_wsv_marginalize_points": [vp, vp, f, d, vp, vp, vp],
+        "eds_wsv_get": [vp, C.POINTER(Out)],
+    })
 
 
 def _f64(a, shape):

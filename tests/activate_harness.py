@@ -1,20 +1,17 @@
 """ctypes side of tests/host_logic/activate_harness.cpp: csrc/eds_activate.hpp (namespace edsact, what the device kernels run) compiled
 with g++ into a temporary directory where the tests run, and the stand-alone program of the same source with the cases dumped for it."""
-import atexit
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 
+import harness_build as hb
 from immature_harness import POINT
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host_logic", "activate_harness.cpp")
-CXXFLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"]
 PARAM_ORDER = ("min_idepth_h_act", "gn_its_on_point_activation", "min_trace_quality", "max_trace_pixel_interval", "min_obs", "scale_idepth")
 _INT = ("gn_its_on_point_activation", "min_obs")
 _vp = C.c_void_p
@@ -43,24 +40,13 @@ def pack_points(Ps):
     return np.stack([to_struct(P, mp) for P in Ps]), n, mp
 
 
-_dir = None
 _lib = None
-
-
-def _tmp():
-    global _dir
-    if _dir is None:
-        _dir = tempfile.mkdtemp(prefix="activate_harness_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
 
 
 def load_harness():
     global _lib
     if _lib is None:
-        so = os.path.join(_tmp(), "libactivate.so")
-        subprocess.check_call(["g++"] + CXXFLAGS + ["-fPIC", "-shared", "-o", so, SRC])
-        _lib = C.CDLL(so)
+        _lib = hb.load_library("activate", SRC)
         assert _lib.act_point_size() == POINT.itemsize == 128 and _lib.act_params_size() == len(pack_params({k: 0 for k in PARAM_ORDER}))
     return _lib
 
@@ -121,8 +107,7 @@ def dump_cases(path, cases, prm_of, huber):
 def run_standalone(cases, prm_of, huber, extra_flags=()):
     """builds the stand-alone program (extra_flags: e.g. -fsanitize=address,undefined -fno-sanitize-recover=all), runs it once over
     `cases` plus its own hostile inputs, returns its output; raises when it fails"""
-    exe, data = os.path.join(_tmp(), "activate_standalone"), os.path.join(_tmp(), "cases.bin")
-    subprocess.check_call(["g++"] + CXXFLAGS + list(extra_flags) + ["-DACT_STANDALONE", "-o", exe, SRC])
+    exe, data = hb.build_program("activate", SRC, "ACT_STANDALONE", extra_flags)
     dump_cases(data, cases, prm_of, huber)
     return subprocess.check_output([exe, data], text=True, stderr=subprocess.STDOUT)
 

@@ -1,20 +1,18 @@
 """ctypes side of tests/host_logic/coarse_harness.cpp: csrc/eds_coarse.hpp (namespace edsct, what the device kernels run) compiled with
 g++ into a temporary directory where the tests run — ``HostTracker`` has the methods of ``slam-eds_amd.coarse.CoarseTracker`` — and the
 stand-alone program of the same source with the cases dumped for it."""
-import atexit
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
+
+import harness_build as hb
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host_logic", "coarse_harness.cpp")
-CXXFLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"]
 PARAM_ORDER = ("huber_th", "coarse_cutoff_th", "affine_opt_mode_a", "affine_opt_mode_b")
 REF_IMAGE, NEW_IMAGE, IDEPTH, WEIGHT_SUMS, PC = range(5)
 
@@ -31,26 +29,13 @@ def pack_params(prm):
     return b"".join(struct.pack("<f", prm[k]) for k in PARAM_ORDER)
 
 
-_dir = None
-
-
-def _tmp():
-    global _dir
-    if _dir is None:
-        _dir = tempfile.mkdtemp(prefix="coarse_harness_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
-
-
 _lib = None
 
 
 def load_harness():
     global _lib
     if _lib is None:
-        so = os.path.join(_tmp(), "libcoarse.so")
-        subprocess.check_call(["g++"] + CXXFLAGS + ["-fPIC", "-shared", "-o", so, SRC])
-        L = C.CDLL(so)
+        L = hb.load_library("coarse", SRC)
         a, b = C.c_int(), C.c_int()
         assert L.ct_sizes(C.byref(a), C.byref(b)) == 512 and a.value == ROW.itemsize == 64 and b.value == RESULT.itemsize
         vp, f, d = C.c_void_p, C.c_float, C.c_double
@@ -71,8 +56,7 @@ def load_harness():
     return _lib
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp = hb.p
 
 
 def sincos(x):
@@ -187,8 +171,7 @@ def dump_cases(path, cases):
 def run_standalone(cases, extra_flags=()):
     """builds the stand-alone program (extra_flags: e.g. -fsanitize=address,undefined -fno-sanitize-recover=all), runs it once over
     `cases` plus its own hostile inputs, returns its output; raises when it fails"""
-    exe, data = os.path.join(_tmp(), "coarse_standalone"), os.path.join(_tmp(), "cases.bin")
-    subprocess.check_call(["g++"] + CXXFLAGS + list(extra_flags) + ["-DCT_STANDALONE", "-o", exe, SRC])
+    exe, data = hb.build_program("coarse", SRC, "CT_STANDALONE", extra_flags)
     dump_cases(data, cases)
     return subprocess.check_output([exe, data], text=True, stderr=subprocess.STDOUT)
 

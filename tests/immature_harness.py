@@ -1,19 +1,17 @@
 """ctypes side of tests/host_logic/immature_harness.cpp: csrc/eds_immature.hpp (namespace edsimm, what the device kernels run) compiled
 with g++ into a temporary directory where the tests run, and the stand-alone program of the same source with the cases dumped for it."""
-import atexit
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
+
+import harness_build as hb
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host_logic", "immature_harness.cpp")
-CXXFLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"]
 _fp = C.POINTER(C.c_float)
 
 # edsimm::Point, 32 words
@@ -31,26 +29,13 @@ def pack_params(prm):
     return b"".join(struct.pack("<i" if k in _INT else "<f", prm[k]) for k in PARAM_ORDER)
 
 
-_dir = None
-
-
-def _tmp():
-    global _dir
-    if _dir is None:
-        _dir = tempfile.mkdtemp(prefix="immature_harness_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
-
-
 _lib = None
 
 
 def load_harness():
     global _lib
     if _lib is None:
-        so = os.path.join(_tmp(), "libimmature.so")
-        subprocess.check_call(["g++"] + CXXFLAGS + ["-fPIC", "-shared", "-o", so, SRC])
-        _lib = C.CDLL(so)
+        _lib = hb.load_library("immature", SRC)
         assert _lib.imm_point_size() == POINT.itemsize == 128
     return _lib
 
@@ -136,8 +121,7 @@ def dump_cases(path, cases, params_of):
 def run_standalone(cases, params_of, extra_flags=()):
     """builds the stand-alone program (extra_flags: e.g. -fsanitize=address,undefined -fno-sanitize-recover=all), runs it once over
     `cases` plus its own degenerate inputs, returns its output; raises when it fails"""
-    exe, data = os.path.join(_tmp(), "immature_standalone"), os.path.join(_tmp(), "cases.bin")
-    subprocess.check_call(["g++"] + CXXFLAGS + list(extra_flags) + ["-DIMM_STANDALONE", "-o", exe, SRC])
+    exe, data = hb.build_program("immature", SRC, "IMM_STANDALONE", extra_flags)
     dump_cases(data, cases, params_of)
     return subprocess.check_output([exe, data], text=True, stderr=subprocess.STDOUT)
 

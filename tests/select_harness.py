@@ -1,19 +1,17 @@
 """ctypes side of tests/host_logic/select_harness.cpp: csrc/eds_pixsel.hpp (namespace edspix, what the device kernels run) compiled with
 g++ into a temporary directory where the tests run, and the stand-alone program of the same source with the cases dumped for it.
 ``HostSelector`` has the interface of ``select.Selector``, so one comparison serves the host restatement and the device."""
-import atexit
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 
+import harness_build as hb
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "host_logic", "select_harness.cpp")
-CXXFLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"]
 PARAM_ORDER = ("min_grad_hist_cut", "min_grad_hist_add", "grad_downweight_per_level", "select_direction_distribution")
 _vp = C.c_void_p
 
@@ -23,24 +21,13 @@ def pack_params(prm):
     return struct.pack("<fffi", *(prm[k] for k in PARAM_ORDER))
 
 
-_dir = None
 _lib = None
-
-
-def _tmp():
-    global _dir
-    if _dir is None:
-        _dir = tempfile.mkdtemp(prefix="select_harness_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
 
 
 def load_harness():
     global _lib
     if _lib is None:
-        so = os.path.join(_tmp(), "libselect.so")
-        subprocess.check_call(["g++"] + CXXFLAGS + ["-fPIC", "-shared", "-o", so, SRC])
-        _lib = C.CDLL(so)
+        _lib = hb.load_library("select", SRC)
         _lib.sel_new.restype = _vp
         _lib.sel_new.argtypes = [C.c_int, C.c_int]
         _lib.sel_free.argtypes = [_vp]
@@ -62,8 +49,7 @@ def load_harness():
     return _lib
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(_vp)
+_p = hb.p
 
 
 def reference_pattern(n):
@@ -165,8 +151,7 @@ def dump_cases(path, cases, prm_of):
 def run_standalone(cases, prm_of, extra_flags=()):
     """builds the stand-alone program (extra_flags: e.g. -fsanitize=address,undefined -fno-sanitize-recover=all), runs it once over
     `cases` plus its own hostile inputs, returns its output; raises when it fails"""
-    exe, data = os.path.join(_tmp(), "select_standalone"), os.path.join(_tmp(), "cases.bin")
-    subprocess.check_call(["g++"] + CXXFLAGS + list(extra_flags) + ["-DSEL_STANDALONE", "-o", exe, SRC])
+    exe, data = hb.build_program("select", SRC, "SEL_STANDALONE", extra_flags)
     dump_cases(data, cases, prm_of)
     return subprocess.check_output([exe, data], text=True, stderr=subprocess.STDOUT)
 

@@ -1,20 +1,18 @@
 """ctypes side of tests/host_logic/window_harness.cpp: csrc/eds_window.hpp (namespace edswin, what the device kernels run) compiled with
 g++ into a temporary directory where the tests run — ``HostWindow`` has the methods of ``slam-eds_amd.window.Window`` — and the
 stand-alone program of the same source with the cases dumped for it."""
-import atexit
 import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
+
+import harness_build as hb
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host_logic", "window_harness.cpp")
-CXXFLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"]
 PARAM_ORDER = ("outlier_th_sum_component", "huber_th", "affine_opt_mode_a", "affine_opt_mode_b", "scale_idepth", "scale_f", "scale_c")
 DEFAULTS = dict(outlier_th_sum_component=2500.0, huber_th=9.0, affine_opt_mode_a=1e12, affine_opt_mode_b=1e8, scale_idepth=1.0, scale_f=1.0,
                 scale_c=1.0)
@@ -31,26 +29,13 @@ def pack_params(prm):
     return b"".join(struct.pack("<f", prm[k]) for k in PARAM_ORDER) + struct.pack("<f", 0.0)
 
 
-_dir = None
-
-
-def _tmp():
-    global _dir
-    if _dir is None:
-        _dir = tempfile.mkdtemp(prefix="window_harness_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
-
-
 _lib = None
 
 
 def load_harness():
     global _lib
     if _lib is None:
-        so = os.path.join(_tmp(), "libwindow.so")
-        subprocess.check_call(["g++"] + CXXFLAGS + ["-fPIC", "-shared", "-o", so, SRC])
-        L = C.CDLL(so)
+        L = hb.load_library("window", SRC)
         a, b = C.c_int(), C.c_int()
         assert L.win_sizes(C.byref(a), C.byref(b)) == 76 and a.value == J_WORDS and b.value == 512
         vp, f = C.c_void_p, C.c_float
@@ -80,8 +65,7 @@ def load_harness():
     return _lib
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp = hb.p
 
 
 def _f32(a, shape):
@@ -257,8 +241,7 @@ def dump_cases(path, cases):
 def run_standalone(cases, extra_flags=()):
     """builds the stand-alone program (extra_flags: e.g. -g -fsanitize=address,undefined -fno-sanitize-recover=all), runs it once over
     `cases` plus its own hostile inputs, returns its output; raises when it fails"""
-    exe, data = os.path.join(_tmp(), "window_standalone"), os.path.join(_tmp(), "cases.bin")
-    subprocess.check_call(["g++"] + CXXFLAGS + list(extra_flags) + ["-DWIN_STANDALONE", "-o", exe, SRC])
+    exe, data = hb.build_program("window", SRC, "WIN_STANDALONE", extra_flags)
     dump_cases(data, cases)
     return subprocess.check_output([exe, data], text=True, stderr=subprocess.STDOUT)
 

@@ -9,6 +9,7 @@ import subprocess
 
 import numpy as np
 
+import harness_build as hb
 import window_harness as wh
 import winsolve_harness as wsh
 
@@ -23,7 +24,7 @@ STATE_FIELDS = ("idepth_backup",)
 WSV_ROWS = ("is_linearized", "res_toZeroF", "resApprox", "lf", "step", "idepth_scaled", "priorF")
 
 _lib = None
-_vp = wh._vp
+_vp = hb.p
 
 
 def load_harness():
@@ -31,9 +32,7 @@ def load_harness():
     global _lib
     if _lib is None:
         wsh.load_harness()
-        so = os.path.join(wh._tmp(), "libwinedit.so")
-        subprocess.check_call(["g++"] + wh.CXXFLAGS + ["-fPIC", "-shared", "-o", so, SRC])
-        L = C.CDLL(so)
+        L = hb.load_library("winedit", SRC)
         vp = C.c_void_p
         L.wed_remove_residuals.argtypes = [vp, vp, vp, vp]
         L.wed_remove_points.argtypes = [vp, vp, vp, vp, vp]
@@ -232,8 +231,7 @@ def after_edit(w, sv, s, HM, bM, full=True, accumulate=True):
 def run_standalone(cases, extra_flags=()):
     """builds the stand-alone program (extra_flags: e.g. -g -fsanitize=address,undefined -fno-sanitize-recover=all), runs it once over
     `cases` (winsolve cases) plus its own hostile flags, returns its output; raises when it fails"""
-    exe, data = os.path.join(wh._tmp(), "winedit_standalone"), os.path.join(wh._tmp(), "winedit_cases.bin")
-    subprocess.check_call(["g++"] + wh.CXXFLAGS + list(extra_flags) + ["-DWED_STANDALONE", "-o", exe, SRC])
+    exe, data = hb.build_program("winedit", SRC, "WED_STANDALONE", extra_flags)
     wsh.dump_cases(data, cases)
     return subprocess.check_output([exe, data], text=True, stderr=subprocess.STDOUT)
 

@@ -9,6 +9,7 @@ import subprocess
 
 import numpy as np
 
+import harness_build as hb
 import window_harness as wh
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,9 +44,7 @@ def load_harness():
     """the library of winsolve_harness.cpp: window_harness.cpp's functions (bound as window_harness binds them) and the wsv_* ones"""
     global _lib
     if _lib is None:
-        so = os.path.join(wh._tmp(), "libwinsolve.so")
-        subprocess.check_call(["g++"] + wh.CXXFLAGS + ["-fPIC", "-shared", "-o", so, SRC])
-        L = C.CDLL(so)
+        L = hb.load_library("winsolve", SRC)
         base = wh.load_harness()
         for name in _WIN_FUNCS:
             f, g = getattr(L, name), getattr(base, name)
@@ -96,7 +95,7 @@ class HostWindow(wh.HostWindow):
             self.solver.invalidate()
 
 
-_vp = wh._vp
+_vp = hb.p
 
 
 def _f64(a, shape):
@@ -300,8 +299,7 @@ def dump_cases(path, cases):
 def run_standalone(cases, extra_flags=()):
     """builds the stand-alone program (extra_flags: e.g. -g -fsanitize=address,undefined -fno-sanitize-recover=all), runs it once over
     `cases` plus its own hostile inputs, returns its output; raises when it fails"""
-    exe, data = os.path.join(wh._tmp(), "winsolve_standalone"), os.path.join(wh._tmp(), "winsolve_cases.bin")
-    subprocess.check_call(["g++"] + wh.CXXFLAGS + list(extra_flags) + ["-DWSV_STANDALONE", "-o", exe, SRC])
+    exe, data = hb.build_program("winsolve", SRC, "WSV_STANDALONE", extra_flags)
     dump_cases(data, cases)
     return subprocess.check_output([exe, data], text=True, stderr=subprocess.STDOUT)
 
