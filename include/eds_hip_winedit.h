@@ -9,8 +9,8 @@
  * counts cross the bus.  The symbols are exported by libeds_hip.so; no entry point of
  * the other headers changes, and a process that never calls eds_wed_* allocates and launches nothing new.
  *
- * NOT here: the flagging decisions themselves (flagPointsForRemoval, isOOB, isInlierNew: the flags are inputs);
- * SOLVER_ORTHOGONALIZE_POINTMARG / _FULL; the connectivity map.
+ * NOT here: SOLVER_ORTHOGONALIZE_POINTMARG / _FULL; the connectivity map.  The flags are inputs here; eds_hip_winflag.h decides them on
+ * the device (flagPointsForRemoval, isOOB, isInlierNew) from a per-point history that travels with every edit of this header.
  *
  * THE ONE ORDER.  eds_hip_window.h wants the points grouped by host in nondecreasing host index and the residuals grouped by point.
  * Every edit here is STABLE: the survivors keep their relative order.  The reference's swap-with-back (removePoint and dropResidual move

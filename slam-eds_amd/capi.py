@@ -96,6 +96,10 @@ WSV_EXPORTS = ("eds_wsv_abi_version", "eds_wsv_set_state", "eds_wsv_fix_lineariz
 WED_EXPORTS = ("eds_wed_abi_version", "eds_wed_remove_residuals", "eds_wed_remove_points", "eds_wed_marginalize_frame", "eds_wed_insert_activated", "eds_wed_set_state",
                "eds_wed_counts", "eds_wed_get")
 
+# every symbol include/eds_hip_winflag.h declares: each point's residual history on the device (bound in winflag.py)
+WFL_EXPORTS = ("eds_wfl_abi_version", "eds_wfl_set_history", "eds_wfl_get_history", "eds_wfl_insert_frame_residuals", "eds_wfl_apply_fixed",
+               "eds_wfl_params_default", "eds_wfl_flag_points", "eds_wfl_get_fates", "eds_wfl_marginalize_flagged", "eds_wfl_remove_flagged")
+
 # every symbol include/eds_hip_activate.h declares: the distance map, the candidate rule and the idepth fit over an eds_imm (bound in activate.py)
 ACT_EXPORTS = ("eds_act_abi_version", "eds_act_params_default", "eds_act_set_params", "eds_act_get_params", "eds_act_set_calib",
                "eds_act_make_distance_map", "eds_act_get_distance_map", "eds_act_select", "eds_act_optimize", "eds_act_get", "eds_act_get_activated")
@@ -221,6 +225,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_window.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winsolve.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winedit.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winflag.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_activate.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_select.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

@@ -69,7 +69,7 @@ __device__ inline float pick8(int j, float a0, float a1, float a2, float a3, flo
 
 __global__ void __launch_bounds__(TB) k_win_linearize(Calib K, Params s, int F, const Precalc* __restrict__ pcs, const float* __restrict__ th,
                                                       const Px* __restrict__ frames, const Point* __restrict__ pts, const float* __restrict__ ids,
-                                                      const float* __restrict__ idz, Dev t, int m) {
+                                                      const float* __restrict__ idz, Dev t, int m, const int32_t* __restrict__ mask) {
     __shared__ float sh_pc[edswin::MAX_FRAMES * edswin::MAX_FRAMES * 27];
     for (int k = threadIdx.x; k < F * F * 27; k += TB) sh_pc[k] = reinterpret_cast<const float*>(pcs)[k];
     __syncthreads();
@@ -78,6 +78,7 @@ __global__ void __launch_bounds__(TB) k_win_linearize(Calib K, Params s, int F, 
     const int i = valid ? gid >> 3 : m - 1;                     // the spare octets of the last wavefront redo the last residual and store nothing
     const bool entry_oob = t.state[i] == edswin::ST_OOB;
     const int ip = t.res_point[i], tg = t.res_target[i];
+    if (mask && !mask[ip]) return;                              // include/eds_hip_winflag.h: only the residuals of the points marked; a whole octet leaves
     const Point* pt = pts + ip;
     const int host = pt->host;
     Precalc pc;
@@ -181,9 +182,9 @@ __global__ void __launch_bounds__(edswin::LANES) k_win_energy(const float* __res
 
 // applyRes for one residual per octet of lanes: lane j copies every eighth word of J (edswin::apply_one's copy, coalesced), lane 0 forms
 // JpJdF from the words it copied from and moves the state
-__global__ void __launch_bounds__(TB) k_win_apply(Dev t, int m, int copy_jacobians) {
+__global__ void __launch_bounds__(TB) k_win_apply(Dev t, int m, int copy_jacobians, const int32_t* __restrict__ mask) {
     const int gid = blockIdx.x * TB + threadIdx.x, i = gid >> 3, j = gid & 7;
-    if (i >= m) return;
+    if (i >= m || (mask && !mask[t.res_point[i]])) return;
     // All eight lanes read the state before lane 0 stores it below.  That is ordered: an octet lies inside ONE wavefront (8 divides 64
     // and TB), a wavefront runs its instructions in program order for all its lanes, and these loads come before the store.
     const int st = t.state[i], ns = t.new_state[i];
@@ -297,6 +298,16 @@ void queue_acc(eds_win* h, int F, int mode, const int32_t* sel, int has_lf, int 
     hipLaunchKernelGGL(k_win_acc, dim3((unsigned)words), dim3(edswin::LANES), 0, h->own.st, in, acc);
 }
 
+void queue_apply(eds_win* h, int copy_jacobians, const int32_t* mask) {
+    if (!h->m) return;
+    hipLaunchKernelGGL(k_win_apply, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, tables(h), h->m, copy_jacobians, mask);
+}
+void queue_linearize(eds_win* h, int F, const int32_t* mask) {
+    if (!h->m) return;
+    hipLaunchKernelGGL(k_win_linearize, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, h->cal, h->prm, F, h->pcs, h->th, h->frames, h->pts, h->ids, h->idz,
+                       tables(h), h->m, mask);
+}
+
 void queue_stitch(eds_win* h, int F, const double* acc, const double* ad, int entries, double* out) {
     hipLaunchKernelGGL(k_win_stitch, dim3(blocks((size_t)entries)), dim3(TB), 0, h->own.st, F, acc, ad, ad + (size_t)F * F * 64, entries, out);
 }
@@ -374,6 +385,7 @@ void eds_win_destroy(eds_win* h) {
     h->own.close();                                            // the window's buffers and both states', whichever set holds them now
     edswin_internal::wsv_release(h);
     edswin_internal::wed_release(h);
+    edswin_internal::wfl_release(h);
     delete h;
 }
 
@@ -469,7 +481,7 @@ int eds_win_set_points(eds_win* h, int n, const int32_t* host, const float* uv, 
     edswin_internal::wsv_invalidate(h);
     h->host_of.assign(host, host + n);
     h->h_point.clear(); h->h_target.clear();
-    return EDS_OK;
+    return h->wfl ? edswin_internal::wfl_reset(h) : (int)EDS_OK;
 }
 
 int eds_win_set_idepths(eds_win* h, const float* idepth_scaled, const float* idepth_zero_scaled) {
@@ -526,7 +538,7 @@ int eds_win_set_residuals(eds_win* h, int m, const int32_t* point, const int32_t
     h->m = m; h->max_target = max_target; h->linearized = false;
     edswin_internal::wsv_invalidate(h);
     h->h_point.assign(point, point + m); h->h_target.assign(target, target + m);
-    return EDS_OK;
+    return h->wfl ? edswin_internal::wfl_reset(h) : (int)EDS_OK;
 }
 
 int eds_win_linearize(eds_win* h, int F, const float* precalc, const float* frame_energy_th, double* energy, int32_t* counts) {
@@ -545,8 +557,7 @@ int eds_win_linearize(eds_win* h, int F, const float* precalc, const float* fram
         EDS_HIP_TRY(hipSetDevice(h->own.dev));
         EDS_HIP_TRY(hipMemcpyAsync(h->pcs, precalc, (size_t)F * F * sizeof(Precalc), hipMemcpyHostToDevice, h->own.st));
         EDS_HIP_TRY(hipMemcpyAsync(h->th, frame_energy_th, (size_t)F * sizeof(float), hipMemcpyHostToDevice, h->own.st));
-        hipLaunchKernelGGL(k_win_linearize, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, h->cal, h->prm, F, h->pcs, h->th, h->frames, h->pts,
-                           h->ids, h->idz, tables(h), h->m);
+        edswin_internal::queue_linearize(h, F, nullptr);
         hipLaunchKernelGGL(k_win_energy, dim3(1), dim3(edswin::LANES), 0, h->own.st, h->ret, h->new_state, h->m, h->sum);
         EDS_HIP_TRY(hipGetLastError());
         if (int rc = read_back(h->own, &back, h->sum, sizeof(back))) return rc;
@@ -563,7 +574,7 @@ int eds_win_apply(eds_win* h, int copy_jacobians) {
     if (!h->linearized) return fail(EDS_ERR_STATE, "eds_win_apply before eds_win_linearize");
     if (!h->m) return EDS_OK;
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
-    hipLaunchKernelGGL(k_win_apply, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, tables(h), h->m, copy_jacobians);
+    edswin_internal::queue_apply(h, copy_jacobians, nullptr);
     EDS_HIP_TRY(hipGetLastError());
     EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;

@@ -1,6 +1,7 @@
-// What eds_window.hip, eds_winsolve.hip and eds_winedit.hip share: the definition of the opaque eds_win of include/eds_hip_window.h, the
-// state include/eds_hip_winsolve.h keeps beside it, the second set of buffers include/eds_hip_winedit.h moves the rows into, and the
-// launches of eds_window.hip that the solve queues into the window's stream.
+// What eds_window.hip, eds_winsolve.hip, eds_winedit.hip and eds_winflag.hip share: the definition of the opaque eds_win of
+// include/eds_hip_window.h, the state include/eds_hip_winsolve.h keeps beside it, the second set of buffers include/eds_hip_winedit.h
+// moves the rows into, the history columns of include/eds_hip_winflag.h, and the launches of eds_window.hip and eds_winedit.hip that
+// the other files queue into the window's stream.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,18 @@ struct eds_wed_state {
     double* marg = nullptr;                                // eds_wed_marginalize_frame: HM, bM, prior, delta_prior in; then HM', bM' out
 };
 
+// include/eds_hip_winflag.h's part of a window: the first eds_wfl_* call allocates it, likewise (wfl_release).  Both sets of every
+// column: the edits of eds_winedit.hip gather them with the window's rows and exchange them with the rest.
+struct eds_wfl_state {
+    int32_t *num_good = nullptr, *last_target = nullptr, *last_state = nullptr, *is_new = nullptr;   // [max_points], [max_points][2] twice, [max_residuals]
+    float* max_rel_baseline = nullptr;                     // [max_points]
+    int32_t *num_good2 = nullptr, *last_target2 = nullptr, *last_state2 = nullptr, *is_new2 = nullptr;   // the second set
+    float* max_rel_baseline2 = nullptr;
+    int32_t* counts = nullptr;                             // [32] a call's counts: the residuals IN / OOB / OUTLIER; or the fates' totals, then per host
+    int32_t *fate = nullptr, *mask = nullptr;              // [max_points] KEEP / MARGINALIZE / DROP; a call's selection of points
+    bool fates_current = false;                            // eds_wfl_flag_points sets it, every edit of the tables and eds_win_set_* clear it
+};
+
 struct eds_win {
     edscapi::DeviceOwner own;                             // the window's buffers and both states' below
     int H = 0, W = 0, max_frames = 0, max_points = 0, max_residuals = 0;
@@ -86,6 +99,7 @@ struct eds_win {
     int32_t* nres = nullptr;
     eds_wsv_state* wsv = nullptr;
     eds_wed_state* wed = nullptr;
+    eds_wfl_state* wfl = nullptr;
 };
 
 namespace edswin_internal {
@@ -99,11 +113,29 @@ int upload_maps(eds_win* h, int F);
 void queue_points(eds_win* h, int mode, const int32_t* sel, int shift);
 void queue_acc(eds_win* h, int F, int mode, const int32_t* sel, int has_lf, int words, double* acc);
 void queue_stitch(eds_win* h, int F, const double* acc, const double* ad, int entries, double* out);
+// k_win_linearize (the precalc records and thresholds are in h->pcs / h->th already) and k_win_apply over every residual, or with
+// `mask` (per point, device memory) over the residuals of the points it marks
+void queue_linearize(eds_win* h, int F, const int32_t* mask);
+void queue_apply(eds_win* h, int copy_jacobians, const int32_t* mask);
 // eds_winsolve.hip
 void wsv_release(eds_win* h);
 void wsv_invalidate(eds_win* h);
 int wsv_set_state(eds_win* h, int F, const double* adHost, const double* adTarget, const double* delta, const double* prior, const double* delta_prior,
                   const double* cPrior, const double* cDelta, const float* priorF, const float* deltaF, bool from_device);
+// k_wsv_fix for the residuals `select` (per residual, device memory) marks; eds_wsv_marginalize_points with the flags from host memory,
+// or (marg == NULL) already in the state's `sel`
+void wsv_queue_fix(eds_win* h, const int32_t* select);
+int wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac, double weight_fac, double* HM, double* bM, int32_t* res_in_m);
 // eds_winedit.hip
 void wed_release(eds_win* h);
+// ... and what an insert of eds_winflag.hip needs of it: the second set allocated, the exclusive sums of keep[0 .. n) (excl has n + 1
+// entries; the scan's tiles are the state's own), every per-residual column of the new rows 0 .. rows - 1 gathered into the second set
+// (row i is row map[i], zeros where map[i] < 0), and the two sets of the per-residual columns exchanged
+int wed_ensure_state(eds_win* h);
+int wed_queue_scan(eds_win* h, const int32_t* keep, int n, int32_t* excl, int32_t* map, int32_t* total);
+void wed_queue_residual_rows(eds_win* h, const int32_t* map, int rows);
+void wed_exchange_residual_sets(eds_win* h);
+// eds_winflag.hip
+void wfl_release(eds_win* h);
+int wfl_reset(eds_win* h);                                 // the defaults over the whole capacity: the tables were set anew
 }  // namespace edswin_internal

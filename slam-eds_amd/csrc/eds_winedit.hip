@@ -20,6 +20,7 @@
 #include "eds_immature_internal.hpp"
 #include "eds_window_internal.hpp"
 #include "eds_winedit.hpp"
+#include "eds_winflag.hpp"
 
 using edscapi::blocks;
 using edscapi::fail;
@@ -141,10 +142,23 @@ __global__ void __launch_bounds__(TB) k_wed_keep_not_towards(int m, const int32_
     if (r < m) keep[r] = edswed::keep_residual_not_towards(res_target, frame, r);
 }
 // hosts and targets above the frame that left go down by one, each entry by its own lane
-__global__ void __launch_bounds__(TB) k_wed_frames_down(int n, int m, int frame, edswin::Point* __restrict__ pts, int32_t* __restrict__ res_target) {
+// ... and, where the history columns exist, the targets lastResiduals names (last_target NULL: they do not)
+__global__ void __launch_bounds__(TB) k_wed_frames_down(int n, int m, int frame, edswin::Point* __restrict__ pts, int32_t* __restrict__ res_target,
+                                                        int32_t* __restrict__ last_target) {
     const int i = blockIdx.x * TB + threadIdx.x;
     if (i < n) pts[i].host = edswed::frame_after(pts[i].host, frame);
     if (i < m) res_target[i] = edswed::frame_after(res_target[i], frame);
+    if (last_target && i < n) {
+        last_target[2 * i] = edswfl::target_after(last_target[2 * i], frame);
+        last_target[2 * i + 1] = edswfl::target_after(last_target[2 * i + 1], frame);
+    }
+}
+// The history columns of include/eds_hip_winflag.h (only launched once they exist).  A residual that leaves while its point stays:
+// lastResiduals of the point no longer names it.  A point's residuals have distinct targets, so no two lanes store to one word.
+__global__ void __launch_bounds__(TB) k_wed_forget(int m, const int32_t* __restrict__ keep, const int32_t* __restrict__ res_point,
+                                                   const int32_t* __restrict__ res_target, int32_t* __restrict__ last_target) {
+    const int r = blockIdx.x * TB + threadIdx.x;
+    if (r < m && !keep[r]) edswfl::forget_residual(last_target, res_point[r], res_target[r]);
 }
 
 struct DevSync { __device__ void operator()() const { __syncthreads(); } };
@@ -205,6 +219,16 @@ __global__ void __launch_bounds__(TB) k_wed_ins_new_residuals(edswed::Ins s, int
     res_point_new[r] = edswed::ins_new_point(s, (int)(g / s.F));
     res_target[r] = (int)(g % s.F);
     new_state[r] = edswed::ST_OUTLIER;
+}
+// ... and their history: lastResiduals from the cells towards the two latest frames, is_new on every new residual
+__global__ void __launch_bounds__(TB) k_wed_ins_history(edswed::Ins s, int K, int R, const int32_t* __restrict__ map_c, const int32_t* __restrict__ map_g,
+                                                        const int32_t* __restrict__ keep_g, edswfl::Hist hist) {
+    const int k = blockIdx.x * TB + threadIdx.x;
+    if (k < K) {
+        const int c = map_c[k];
+        edswfl::activated_point(hist, edswed::ins_new_point(s, c), s.F, keep_g[(int64_t)c * s.F + s.F - 1], keep_g[(int64_t)c * s.F + s.F - 2]);
+    }
+    if (k < R) hist.is_new[edswed::ins_new_res(s, map_g[k])] = 1;
 }
 
 int ensure_state(eds_win* h) {
@@ -300,6 +324,7 @@ void queue_residual_rows(eds_win* h, const int32_t* map, int rows) {
     edswed::cols_add(t, h->new_energy_wo, s->new_energy_wo, 1); edswed::cols_add(t, h->ret, s->ret, 1);
     edswed::cols_add(t, h->cp, s->cp, 3); edswed::cols_add(t, h->proj, s->proj, 16); edswed::cols_add(t, h->JpJdF, s->JpJdF, 8);
     if (v) { edswed::cols_add(t, v->lin, s->lin, 1); edswed::cols_add(t, v->rtz, s->rtz, 8); edswed::cols_add(t, v->res_approx, s->res_approx, 8); }
+    if (const eds_wfl_state* f = h->wfl) edswed::cols_add(t, f->is_new, f->is_new2, 1);
     const int64_t words = (int64_t)rows * t.words, pieces = (int64_t)rows * edswed::WIDE_PIECES;
     hipLaunchKernelGGL(k_wed_words, dim3(blocks(words)), dim3(TB), 0, h->own.st, t, map, words);
     hipLaunchKernelGGL(k_wed_wide, dim3(blocks(pieces)), dim3(TB), 0, h->own.st, (const char*)h->J, (char*)s->J, map, pieces);
@@ -314,6 +339,10 @@ void queue_point_rows(eds_win* h, const int32_t* map, int rows) {
     edswed::cols_add(t, h->prior, s->prior, 1); edswed::cols_add(t, h->delta, s->delta, 1); edswed::cols_add(t, h->lf, s->lf, 6);
     edswed::cols_add(t, h->pout, s->pout, (int)(sizeof(edswin::PointOut) / 4));
     if (v) { edswed::cols_add(t, v->step, s->step, 1); edswed::cols_add(t, v->backup, s->backup, 1); }
+    if (const eds_wfl_state* f = h->wfl) {
+        edswed::cols_add(t, f->num_good, f->num_good2, 1); edswed::cols_add(t, f->max_rel_baseline, f->max_rel_baseline2, 1);
+        edswed::cols_add(t, f->last_target, f->last_target2, 2); edswed::cols_add(t, f->last_state, f->last_state2, 2);
+    }
     const int64_t words = (int64_t)rows * t.words;
     hipLaunchKernelGGL(k_wed_words, dim3(blocks(words)), dim3(TB), 0, h->own.st, t, map, words);
 }
@@ -321,6 +350,12 @@ void queue_point_rows(eds_win* h, const int32_t* map, int rows) {
 void exchange_sets(eds_win* h, bool points_too) {
     eds_wed_state* s = h->wed;
     eds_wsv_state* v = h->wsv;
+    eds_wfl_state* f = h->wfl;
+    if (f) swap_ptr(f->is_new, f->is_new2);
+    if (f && points_too) {
+        swap_ptr(f->num_good, f->num_good2); swap_ptr(f->max_rel_baseline, f->max_rel_baseline2);
+        swap_ptr(f->last_target, f->last_target2); swap_ptr(f->last_state, f->last_state2);
+    }
     swap_ptr(h->res_target, s->res_target); swap_ptr(h->state, s->state); swap_ptr(h->new_state, s->new_state); swap_ptr(h->active, s->active);
     swap_ptr(h->energy, s->energy); swap_ptr(h->new_energy, s->new_energy); swap_ptr(h->new_energy_wo, s->new_energy_wo); swap_ptr(h->ret, s->ret);
     swap_ptr(h->cp, s->cp); swap_ptr(h->proj, s->proj); swap_ptr(h->JpJdF, s->JpJdF); swap_ptr(h->J, s->J); swap_ptr(h->efJ, s->efJ);
@@ -358,6 +393,8 @@ int compact(eds_win* h, bool points_change, int32_t* removed_points, int32_t* re
         return fail(EDS_ERR_HIP, "eds_wed: the device numbered " + std::to_string(total[0]) + " residuals and " + std::to_string(total[1]) + " points, the flags hold " +
                                      std::to_string(m2) + " and " + std::to_string(n2));
     // per residual
+    if (h->wfl && !points_change && m)                          // a point that stays forgets the residuals that leave (one that leaves takes its history along)
+        hipLaunchKernelGGL(k_wed_forget, dim3(blocks(m)), dim3(TB), 0, st, m, s->keep_r, h->res_point, h->res_target, h->wfl->last_target);
     if (m2) {
         queue_residual_rows(h, s->map_r, m2);
         hipLaunchKernelGGL(k_wed_res_point, dim3(blocks(m2)), dim3(TB), 0, st, m2, h->res_point, s->map_r, points_change ? s->excl_p : (const int32_t*)nullptr,
@@ -372,6 +409,7 @@ int compact(eds_win* h, bool points_change, int32_t* removed_points, int32_t* re
     exchange_sets(h, points_change);
     h->host_of.swap(w.host_of); h->h_point.swap(w.point); h->h_target.swap(w.target);
     h->n = n2; h->m = m2; h->max_host = w.max_host; h->max_target = w.max_target;
+    if (h->wfl) h->wfl->fates_current = false;                  // the fates of include/eds_hip_winflag.h were decided for other tables
     if (removed_points) *removed_points = n - n2;
     if (removed_residuals) *removed_residuals = m - m2;
     return EDS_OK;
@@ -395,6 +433,10 @@ void wed_release(eds_win* h) {
     delete h->wed;
     h->wed = nullptr;
 }
+int wed_ensure_state(eds_win* h) { return ensure_state(h); }
+int wed_queue_scan(eds_win* h, const int32_t* keep, int n, int32_t* excl, int32_t* map, int32_t* total) { return queue_scan(h, keep, n, excl, map, total); }
+void wed_queue_residual_rows(eds_win* h, const int32_t* map, int rows) { queue_residual_rows(h, map, rows); }
+void wed_exchange_residual_sets(eds_win* h) { exchange_sets(h, false); }
 
 }  // namespace edswin_internal
 
@@ -465,7 +507,8 @@ int eds_wed_marginalize_frame(eds_win* h, int frame, const double* prior, const 
     if (h->m) hipLaunchKernelGGL(k_wed_keep_not_towards, dim3(blocks(h->m)), dim3(TB), 0, st, h->m, h->res_target, frame, s->keep_r);
     if (int rc = compact(h, false, nullptr, nullptr)) return rc;
     const int most = h->n > h->m ? h->n : h->m;
-    if (most) hipLaunchKernelGGL(k_wed_frames_down, dim3(blocks(most)), dim3(TB), 0, st, h->n, h->m, frame, h->pts, h->res_target);
+    if (most) hipLaunchKernelGGL(k_wed_frames_down, dim3(blocks(most)), dim3(TB), 0, st, h->n, h->m, frame, h->pts, h->res_target,
+                                 h->wfl ? h->wfl->last_target : (int32_t*)nullptr);
     EDS_HIP_TRY(hipGetLastError());
     const size_t px = (size_t)h->H * h->W;
     for (int f = frame + 1; f < F; ++f)
@@ -568,6 +611,11 @@ int eds_wed_insert_activated(eds_win* h, eds_imm* im, int32_t* inserted_points_o
     if (K) hipLaunchKernelGGL(k_wed_ins_new_points, dim3(blocks(K)), dim3(TB), 0, st, ds, K, s->ins_map_c, im->points, a->fit, a->prm.scale_idepth, s->pts, s->ids, s->idz,
                               s->res_first);
     if (R) hipLaunchKernelGGL(k_wed_ins_new_residuals, dim3(blocks(R)), dim3(TB), 0, st, ds, R, s->ins_map_g, s->res_point, s->res_target, s->new_state);
+    if (const eds_wfl_state* f = h->wfl) {                     // the second set's columns: exchange_sets makes them the window's
+        const edswfl::Hist hist = {f->num_good2, f->max_rel_baseline2, f->last_target2, f->last_state2, f->is_new2};
+        const int most_new = K > R ? K : R;
+        if (most_new) hipLaunchKernelGGL(k_wed_ins_history, dim3(blocks(most_new)), dim3(TB), 0, st, ds, K, R, s->ins_map_c, s->ins_map_g, keep_g, hist);
+    }
     EDS_HIP_TRY(hipGetLastError());
     const int32_t end = m2;
     EDS_HIP_TRY(hipMemcpyAsync(s->res_first + n2, &end, sizeof(end), hipMemcpyHostToDevice, st));
@@ -575,6 +623,7 @@ int eds_wed_insert_activated(eds_win* h, eds_imm* im, int32_t* inserted_points_o
     exchange_sets(h, true);
     h->host_of.swap(host_of); h->h_point.swap(h_point); h->h_target.swap(h_target);
     h->n = n2; h->m = m2; h->linearized = false;                // eds_win_apply is EDS_ERR_STATE until the next eds_win_linearize
+    if (h->wfl) h->wfl->fates_current = false;
     h->max_host = h->max_target = -1;
     for (int32_t v : h->host_of) if (v > h->max_host) h->max_host = v;
     for (int32_t v : h->h_target) if (v > h->max_target) h->max_target = v;

@@ -290,7 +290,7 @@ int eds_wsv_fix_linearization(eds_win* h, const int32_t* select) {
     eds_wsv_state* s = h->wsv;
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
     EDS_HIP_TRY(hipMemcpyAsync(s->sel, select, (size_t)h->m * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
-    hipLaunchKernelGGL(k_wsv_fix, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, lin_of(h), h->m, s->sel, s->rtz, s->lin);
+    edswin_internal::wsv_queue_fix(h, s->sel);
     EDS_HIP_TRY(hipGetLastError());
     EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
@@ -426,6 +426,21 @@ int eds_wsv_m_energy(eds_win* h, const double* HM, const double* bM, double* ene
 int eds_wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac, double weight_fac, double* HM, double* bM, int32_t* res_in_m) {
     if (int rc = check(h)) return rc;
     if (!HM || !bM || (!marg && h->n)) return fail(EDS_ERR_INVALID, "marg, HM and bM are required");
+    return edswin_internal::wsv_marginalize_points(h, marg, prior_fac, weight_fac, HM, bM, res_in_m);
+}
+
+}  // extern "C"
+
+namespace edswin_internal {
+
+void wsv_queue_fix(eds_win* h, const int32_t* select) {
+    if (!h->m) return;
+    hipLaunchKernelGGL(k_wsv_fix, dim3(blocks((size_t)h->m * 8)), dim3(TB), 0, h->own.st, lin_of(h), h->m, select, h->wsv->rtz, h->wsv->lin);
+}
+
+int wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac, double weight_fac, double* HM, double* bM, int32_t* res_in_m) {
+    if (int rc = check(h)) return rc;
+    if (!HM || !bM) return fail(EDS_ERR_INVALID, "HM and bM are required");
     eds_wsv_state* s = h->wsv;
     const int F = s->F, N = 4 + 8 * F;
     const size_t NN = (size_t)N * N;
@@ -436,7 +451,7 @@ int eds_wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac,
     hipStream_t st = h->own.st;
     int32_t flag[4] = {0, 0, 0, 0};
     EDS_HIP_TRY(hipMemsetAsync(s->flag, 0, 4 * sizeof(int32_t), st));
-    if (h->n) EDS_HIP_TRY(hipMemcpyAsync(s->sel, marg, (size_t)h->n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (h->n && marg) EDS_HIP_TRY(hipMemcpyAsync(s->sel, marg, (size_t)h->n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (h->m) {
         hipLaunchKernelGGL(k_wsv_marg_check, dim3(blocks((size_t)h->m)), dim3(TB), 0, st, h->m, h->res_point, h->active, s->lin, s->sel, s->flag + 2);
         EDS_HIP_TRY(hipGetLastError());
@@ -468,6 +483,10 @@ int eds_wsv_marginalize_points(eds_win* h, const int32_t* marg, float prior_fac,
     if (res_in_m) *res_in_m = flag[1];
     return EDS_OK;
 }
+
+}  // namespace edswin_internal
+
+extern "C" {
 
 int eds_wsv_get(eds_win* h, const eds_wsv_out* o) {
     if (int rc = check(h)) return rc;
