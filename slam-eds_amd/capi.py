@@ -109,6 +109,11 @@ SEL_EXPORTS = ("eds_sel_abi_version", "eds_sel_params_default", "eds_sel_create"
                "eds_sel_set_random_pattern", "eds_sel_fill_reference_pattern", "eds_sel_set_potential", "eds_sel_get_potential", "eds_sel_set_image",
                "eds_sel_make_maps", "eds_sel_get_map", "eds_sel_get_selection", "eds_sel_get_level", "eds_sel_get_thresholds", "eds_sel_get_scan_info")
 
+# every symbol include/eds_hip_init.h declares: DSO's two-frame initialiser over its own eds_ini (bound in init.py)
+INI_EXPORTS = ("eds_ini_abi_version", "eds_ini_params_default", "eds_ini_create", "eds_ini_destroy", "eds_ini_set_params", "eds_ini_get_params",
+               "eds_ini_set_calib", "eds_ini_set_first", "eds_ini_set_pose", "eds_ini_set_points", "eds_ini_set_points_selected", "eds_ini_set_neighbours",
+               "eds_ini_make_nn", "eds_ini_get_schedule_depth", "eds_ini_track_frame", "eds_ini_get_kernel_ms", "eds_ini_get_points", "eds_ini_get_jb", "eds_ini_get_level")
+
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
     "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
@@ -228,6 +233,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winflag.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_activate.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_select.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_init.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]

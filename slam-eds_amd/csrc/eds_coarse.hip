@@ -174,14 +174,8 @@ __global__ void __launch_bounds__(TB) k_ct_select(const float* __restrict__ idB,
 }
 
 // ---- the evaluator of edsct::track on the device --------------------------------------------------------------------------------------
-__device__ inline double wave_fold(double v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
-__device__ inline int wave_fold_i(int v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
+using edsct::wave_fold;
+using edsct::wave_fold_i;
 
 // a Warp is the same in every lane: say so, and its 31 words live in scalar registers through the strided loops
 __device__ inline Warp uniform_warp(Warp w) {

@@ -15,7 +15,10 @@
 // does not bound their arguments (an increment's angle and a difference of affine a's are whatever the solve gives), so the bounds
 // are stated over everything the functions accept: against libm, sin and cos are within SINCOS_MAX_ULP = 2 ulps over |x| <= 2^20
 // (NaN beyond), exp within EXP_MAX_ULP = 1 ulp over |x| <= 708 (inf and 0 beyond).  Measured: sin 2, cos 2, exp 1;
-// tests/test_coarse_header.py asserts these constants.
+// tests/test_coarse_header.py asserts these constants.  atan_d (the initialiser's SE3::log, eds_init.hpp) is of the same kind: |x| > 1
+// goes through 1 / |x|, the argument is reduced by the nearest c = k / 8 to r = (|x| - c) / (1 + |x| c), |r| <= 1/16, Taylor to r^19
+// and atan(k / 8) from a table; within ATAN_MAX_ULP = 2 ulps of libm over every argument (NaN stays NaN, +-inf gives +-pi/2).
+// Measured: 2 (near x = 1.06); tests/test_init_header.py asserts the constant.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -40,6 +43,7 @@ constexpr int MAX_DECISIONS = 512;             // 10 + 20 + 3 * 100 iterations a
 constexpr int NUM_SUMS = 45;
 constexpr int SINCOS_MAX_ULP = 2;
 constexpr int EXP_MAX_ULP = 1;
+constexpr int ATAN_MAX_ULP = 2;
 
 // eds_ct_params, member for member
 struct Params { float huber_th, coarse_cutoff_th, affine_opt_mode_a, affine_opt_mode_b; };
@@ -133,6 +137,34 @@ EDS_CT_HD double exp_d(double x) {
     double scale;
     memcpy(&scale, &bits, sizeof(scale));
     return e * scale;
+}
+
+// ---- fp64 atan in plain arithmetic ---------------------------------------------------------------------------------------------------
+EDS_CT_HD double atan_d(double x) {
+    if (!(x == x)) return x;
+    const double ATAN_K[9] = {0.0, 0.12435499454676144, 0.24497866312686414, 0.35877067027057225, 0.46364760900080609,
+                              0.55859931534356244, 0.64350110879328437, 0.71882999962162453, 0.78539816339744828};
+    double ax = fabs(x);
+    const bool inv = ax > 1.0;
+    if (inv) ax = 1.0 / ax;
+    const double kf = floor(ax * 8.0 + 0.5), c = kf * 0.125;
+    const double r = (ax - c) / (1.0 + ax * c), z = r * r;
+    double p = 1.0 / 19.0;
+    p = 1.0 / 17.0 - z * p;
+    p = 1.0 / 15.0 - z * p;
+    p = 1.0 / 13.0 - z * p;
+    p = 1.0 / 11.0 - z * p;
+    p = 1.0 / 9.0 - z * p;
+    p = 1.0 / 7.0 - z * p;
+    p = 1.0 / 5.0 - z * p;
+    p = 1.0 / 3.0 - z * p;
+    const int k = (int)kf;
+    double base = 0.0;
+EDS_CT_UNROLL
+    for (int q = 0; q < 9; ++q) if (q == k) base = ATAN_K[q];
+    double a = base + (r - (r * z) * p);
+    if (inv) a = (1.5707963267948966 - a) + 6.123233995736766e-17;
+    return x < 0.0 ? -a : a;
 }
 
 // ---- makeK (CoarseTracker.cpp:93-122) -----------------------------------------------------------------------------------------------
@@ -579,6 +611,18 @@ EDS_CT_UNROLL
         out->ok = 1;
     }
 }
+
+#if defined(__HIPCC__)
+// the fold inside 64 lanes on the device (eds_coarse.hip, eds_init.hip): lane 0 of the wavefront holds the total
+__device__ inline double wave_fold(double v) {
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
+    return v;
+}
+__device__ inline int wave_fold_i(int v) {
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
+    return v;
+}
+#endif
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 // ---- the serial side: the same pieces walked in the device's order -------------------------------------------------------------------
