@@ -13,5 +13,6 @@ alias module at the repo root).  Sub-modules:
 * ``coarse``  — DSO's coarse image tracker for the pose of every new image frame, on the device (include/eds_hip_coarse.h)
 * ``select``  — DSO's pixel selector: which pixels of a keyframe become immature points, on the device (include/eds_hip_select.h)
 * ``window``  — the window optimiser's linearize, applyRes and per-point Hessian sums on the device (include/eds_hip_window.h)
+* ``map``     — the map as a point cloud and as the next tracker keyframe's depth maps, on the device (include/eds_hip_map.h)
 """
 __version__ = "0.1.0"

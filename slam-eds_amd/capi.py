@@ -119,6 +119,10 @@ UND_EXPORTS = ("eds_und_abi_version", "eds_und_settings_default", "eds_und_creat
                "eds_und_is_passthrough", "eds_und_set_map", "eds_und_set_photometric", "eds_und_set_settings", "eds_und_get_settings",
                "eds_und_set_form", "eds_und_get_form", "eds_und_process", "eds_und_image", "eds_und_get_image")
 
+# every symbol include/eds_hip_map.h declares: the window's, the immature points' and a slot's point cloud, and the next keyframe's depth maps (bound in map.py)
+MAP_EXPORTS = ("eds_map_abi_version", "eds_map_window_cloud", "eds_map_window_depth_maps", "eds_map_immature_cloud", "eds_map_set_immature_trace",
+               "eds_map_slot_cloud")
+
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
     "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
@@ -240,6 +244,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_select.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_init.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_undistort.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_map.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]

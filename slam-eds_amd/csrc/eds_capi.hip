@@ -147,6 +147,7 @@ void free_all(eds_trk* h) {
     eds_klt_free(&h->klt);
     eds_epi_free(&h->epi);
     eds_kfp_free(&h->kfp);
+    edsmap_internal::release(h->map);
     eds_kfs_free(&h->kfs);
     eds_keyframe_free(&h->kf_build);
     void* hptrs[] = {h->h_pose, h->h_part, h->h_G, h->h_f32, h->h_r, h->h_fstage, h->h_rmap, h->h_idp, h->h_fprog, h->h_bstage};

@@ -10,6 +10,7 @@
 #include "eds_klt.hpp"
 #include "eds_kfpoints.hpp"
 #include "eds_kfswitch.hpp"
+#include "eds_map_internal.hpp"
 #include "eds_fused.hpp"
 #include "eds_kernels.hpp"
 #include "eds_launch_rule.hpp"
@@ -74,6 +75,7 @@ struct eds_trk {
     EdsDepthBuffers depth;
     EdsKltBuffers klt;                  // KLT tracks / flow planes (include/eds_hip_klt.h), allocated by the first KLT call
     EdsEpiBuffers epi;                  // epiline ef plane and work buffers (include/eds_hip_epiline.h), allocated by the first eds_epi_* call
+    eds_map_state* map = nullptr;       // include/eds_hip_map.h's scratch, allocated by the first eds_map_slot_cloud into host memory
     EdsKfpBuffers kfp;                  // refine / clean / erase / project (include/eds_hip_kfpoints.h), allocated by the first eds_kfp_* call that needs them
     EdsKeyframeBuffers kf_build;
     EdsKfsBuffers kfs;                  // the batched keyframe switch (include/eds_hip_kfswitch.h), allocated by the first eds_kfs_* call that needs them

@@ -278,6 +278,7 @@ void eds_imm_destroy(eds_imm* h) {
     if (!h) return;
     h->own.close();
     edsimm_internal::act_release(h);
+    edsmap_internal::release(h->map);
     delete h;
 }
 

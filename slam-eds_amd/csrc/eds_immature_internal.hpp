@@ -9,6 +9,7 @@
 #include "eds_activate.hpp"
 #include "eds_device_owner.hpp"
 #include "eds_immature.hpp"
+#include "eds_map_internal.hpp"
 
 // include/eds_hip_activate.h's part of an eds_imm: the first eds_act_* call that needs it allocates it through the eds_imm's owner, which
 // frees the device memory with the handle; act_release deletes the struct
@@ -48,6 +49,7 @@ struct eds_imm {
     std::vector<int> n;
     std::vector<uint8_t> host_set, target_set;
     eds_act_state* act = nullptr;
+    eds_map_state* map = nullptr;                      // include/eds_hip_map.h's scratch, allocated by the first eds_map_immature_cloud
 };
 
 namespace edsimm_internal {

@@ -386,6 +386,7 @@ void eds_win_destroy(eds_win* h) {
     edswin_internal::wsv_release(h);
     edswin_internal::wed_release(h);
     edswin_internal::wfl_release(h);
+    edsmap_internal::release(h->map);
     delete h;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "eds_device_owner.hpp"
+#include "eds_map_internal.hpp"
 #include "eds_window.hpp"
 
 namespace edswin {
@@ -100,6 +101,7 @@ struct eds_win {
     eds_wsv_state* wsv = nullptr;
     eds_wed_state* wed = nullptr;
     eds_wfl_state* wfl = nullptr;
+    eds_map_state* map = nullptr;                         // include/eds_hip_map.h's scratch, allocated by the first eds_map_window_* call
 };
 
 namespace edswin_internal {

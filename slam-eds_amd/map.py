@@ -1,0 +1,159 @@
+"""ctypes binding of include/eds_hip_map.h: the map as EDS publishes it and as the tracker takes it — ``dso::io::getMap`` over a
+``window.Window``, ``getImmatureMap`` over an ``immature.ImmaturePoints``, ``KeyFrame::getMap``'s points over a tracker ``capi.Handle``,
+and the depth maps the next event keyframes are created from (the window's points moved into each new keyframe and pushed through
+``IDepthMap::fromPoints``), which ``build_keyframes_from_window`` hands to ``eds_kfs_build_keyframes_dev`` without leaving the device.
+
+Plumbing only: every point is computed by the HIP kernels behind the C ABI (csrc/eds_map.hip); there is no CPU fallback.
+
+Results are numpy arrays, or with ``device=True`` torch tensors on the handle's device (torch must have been imported before the
+library was loaded, see ``capi.torch_loaded_first``), or with ``device="array"`` ``capi.DeviceArray`` objects; both have
+``__cuda_array_interface__``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+
+import numpy as np
+
+from . import capi
+
+FAN = 8
+MAX_IMM_HOSTS = 32
+# getImmatureMap's colour by lastTraceStatus (reference src/io/OutputMaps.cpp:112-123)
+STATUS_COLORS = ((0.0, 1.0, 0.0, 1.0), (1.0, 0.0, 0.0, 1.0), (0.0, 0.0, 1.0, 1.0), (0.0, 1.0, 1.0, 1.0), (1.0, 1.0, 1.0, 1.0), (0.0, 0.0, 0.0, 1.0))
+
+
+@functools.lru_cache(maxsize=None)
+def _lib():
+    vp, i, i64, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32
+    return capi.bind(capi.MAP_EXPORTS, {
+        "eds_map_window_cloud": [vp, i, u32, vp, i, vp, i, vp, vp],
+        "eds_map_window_depth_maps": [vp, i, u32, vp, i, vp, vp, i, i, i64, vp, vp, vp, i, vp],
+        "eds_map_immature_cloud": [vp, i, u32, vp, vp, i, i64, vp, vp, vp, i, vp],
+        "eds_map_set_immature_trace": [vp, i, vp, vp, vp],
+        "eds_map_slot_cloud": [vp, i, i, vp, i, vp, i, vp],
+    })
+
+
+def _poses(T, count):
+    """count poses as count x 12 doubles: rows of [R | t]; 3 x 4 and 4 x 4 matrices are taken too"""
+    a = np.asarray(T, dtype=np.float64)
+    if a.ndim == 3 and a.shape[1:] == (4, 4):
+        a = a[:, :3, :]
+    return np.ascontiguousarray(a).reshape(count, 12)
+
+
+def _mask(mask, n):
+    return (1 << n) - 1 if mask is None else int(mask) & 0xFFFFFFFF
+
+
+class _Out:
+    """one result array of `shape`: numpy (device False), a torch tensor (True) or a capi.DeviceArray ("array")"""
+
+    def __init__(self, shape, dtype, device, index):
+        self.shape, self.kind = tuple(int(n) for n in shape), device
+        if not device:
+            self.obj = np.zeros(self.shape, dtype)
+            self.ptr = self.obj.ctypes.data
+        elif device == "array":
+            self.obj = capi.DeviceArray(self.shape, dtype, index)
+            self.ptr = self.obj.ptr
+        else:
+            if capi.torch_loaded_first is False:
+                raise RuntimeError("device=True returns torch tensors, and PyTorch-ROCm only works on its own HIP runtime: import torch "
+                                   'before the first call into slam-eds_amd.capi (or ask for device="array")')
+            import torch
+            self.obj = torch.zeros(self.shape, dtype=getattr(torch, np.dtype(dtype).name), device=f"cuda:{index}")
+            torch.cuda.synchronize(index)                  # the zero-fill ran on torch's stream, the kernels run on the handle's
+            self.ptr = self.obj.data_ptr()
+
+    def head(self, n):
+        """the first n entries along axis 0: a view for numpy and torch, the whole array for a DeviceArray (n is returned beside it)"""
+        return self.obj if self.kind == "array" else self.obj[:n]
+
+
+def _ptr(o):
+    return C.c_void_p(o.ptr or None)
+
+
+def window_cloud(win, T_w_c, frame_mask=None, single_point=True, device=False):
+    """``dso::io::getMap`` for every frame of `win` whose bit is set (None: all F = len(T_w_c) frames): (points n x 3, per_host[8]).
+    With ``device="array"`` the points are a DeviceArray of n rows (n = per_host.sum() x (1 or 8))."""
+    F = len(T_w_c)
+    T = _poses(T_w_c, F)
+    mask, fan = _mask(frame_mask, F), 1 if single_point else FAN
+    per, n = np.zeros(8, np.int32), C.c_int32()
+    out = _Out((max(win.n, 1) * fan, 3), np.float64, device, getattr(win, "device", 0))
+    capi._check(_lib().eds_map_window_cloud(win._h, F, mask, capi.vp(T), 1 if single_point else 0, _ptr(out), 1 if device else 0,
+                                            C.cast(C.byref(n), C.c_void_p), capi.vp(per)))
+    return out.head(n.value), per
+
+
+def window_depth_maps(win, T_w_c, T_dst_w, K_dst, dst_H, dst_W, frame_mask=None, stride=None, src_index=True, device=False):
+    """The depth maps of len(T_dst_w) new keyframes from the window's points: dict(n, depth_xy count x stride x 2, depth_idp count x stride,
+    src_index count x stride or None, stride); map b holds n[b] points.  stride None: the window's point count."""
+    F, count = len(T_w_c), len(T_dst_w)
+    T, Td, K = _poses(T_w_c, F), _poses(T_dst_w, count), np.ascontiguousarray(K_dst, dtype=np.float64).reshape(count, 4)
+    stride = max(win.n, 1) if stride is None else int(stride)
+    dev = getattr(win, "device", 0)
+    xy, idp = _Out((count, stride, 2), np.float64, device, dev), _Out((count, stride), np.float64, device, dev)
+    src = _Out((count, stride), np.int32, device, dev) if src_index else None
+    n = np.zeros(count, np.int32)
+    capi._check(_lib().eds_map_window_depth_maps(win._h, F, _mask(frame_mask, F), capi.vp(T), count, capi.vp(Td), capi.vp(K), int(dst_H), int(dst_W),
+                                                 stride, _ptr(xy), _ptr(idp), _ptr(src) if src else None, 1 if device else 0, capi.vp(n)))
+    return dict(n=n, depth_xy=xy.obj, depth_idp=idp.obj, src_index=src.obj if src else None, stride=stride)
+
+
+def immature_cloud(imm, T_w_c, calib, host_mask=None, single_point=True, cap=None, colors=True, status=True, device=False):
+    """``getImmatureMap`` for every host of `imm` whose bit is set: dict(n, points, colors, status), each of n entries (a DeviceArray
+    keeps its cap entries).  cap None: room for every point.  A cap that is too small raises EdsError(ERR_INVALID) whose ``needed``
+    attribute is the count."""
+    H = len(T_w_c)
+    T, mask, fan = _poses(T_w_c, H), _mask(host_mask, H), 1 if single_point else FAN
+    cal = np.ascontiguousarray(calib, dtype=np.float32).reshape(4)
+    if cap is None:
+        cap = max(1, sum(imm.num_points(h) for h in range(H) if (mask >> h) & 1) * fan)
+    cap, dev = int(cap), getattr(imm, "device", 0)
+    pts = _Out((max(cap, 1), 3), np.float64, device, dev)
+    col = _Out((max(cap, 1), 4), np.float64, device, dev) if colors else None
+    st = _Out((max(cap, 1),), np.uint8, device, dev) if status else None
+    n = C.c_int32()
+    rc = _lib().eds_map_immature_cloud(imm._h, H, mask, capi.vp(T), capi.vp(cal), 1 if single_point else 0, cap, _ptr(pts), _ptr(col) if col else None,
+                                       _ptr(st) if st else None, 1 if device else 0, C.cast(C.byref(n), C.c_void_p))
+    if rc != capi.EDS_OK:
+        e = capi.EdsError(rc, capi.last_error())
+        e.needed = n.value
+        raise e
+    return dict(n=n.value, points=pts.head(n.value), colors=col.head(n.value) if col else None, status=st.head(n.value) if st else None)
+
+
+def set_immature_trace(imm, host, idepth_min=None, idepth_max=None, status=None):
+    """replaces a host's idepth_min / idepth_max / lastTraceStatus (None: that column stays)"""
+    n = imm.num_points(host)
+    a = None if idepth_min is None else np.ascontiguousarray(idepth_min, dtype=np.float32).reshape(n)
+    b = None if idepth_max is None else np.ascontiguousarray(idepth_max, dtype=np.float32).reshape(n)
+    s = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(n)
+    capi._check(_lib().eds_map_set_immature_trace(imm._h, int(host), capi.vp(a), capi.vp(b), capi.vp(s)))
+
+
+def slot_cloud(trk, T_w_kf, first=0, stride=None, device=False):
+    """``KeyFrame::getMap``'s points of slots first .. first + len(T_w_kf) - 1 of the tracker handle `trk`: (points count x stride x 3, n);
+    slot b holds n[b] points.  The IMG and EVENTS colour modes are not here: a slot holds neither the image nor the model."""
+    count = len(T_w_kf)
+    T = _poses(T_w_kf, count)
+    stride = trk.max_points if stride is None else int(stride)
+    out = _Out((count, stride, 3), np.float64, device, getattr(trk, "device", 0))
+    n = np.zeros(count, np.int32)
+    capi._check(_lib().eds_map_slot_cloud(trk._h, int(first), count, capi.vp(T), stride, _ptr(out), 1 if device else 0, capi.vp(n)))
+    return out.obj, n
+
+
+def build_keyframes_from_window(trk, images, K, win, T_w_c, T_dst_w, first=0, frame_mask=None, **kw):
+    """The keyframe switch end to end on the device: ``window_depth_maps(device=...)`` of `win` into ``eds_kfs_build_keyframes[_dev]`` of
+    the tracker handle `trk` as EDS_KFS_DEPTH_DEVICE.  K: count x 4, the new keyframes' intrinsics, also the maps' K_dst; the maps have
+    the handle's H x W.  Further keywords go to ``capi.Handle.build_keyframes``.  Returns (its result, the maps)."""
+    device = True if capi.torch_loaded_first else "array"
+    maps = window_depth_maps(win, T_w_c, T_dst_w, K, trk.H, trk.W, frame_mask=frame_mask, src_index=False, device=device)
+    out = trk.build_keyframes(images, K, first=first, depth=maps["depth_xy"], depth_idp=maps["depth_idp"], depth_n=maps["n"], **kw)
+    return out, maps

@@ -152,6 +152,7 @@ class Window(capi.OwnedHandle):
         self._h = C.c_void_p()
         self.H, self.W, self.max_frames, self.max_points, self.max_residuals = int(H), int(W), int(max_frames), int(max_points), int(max_residuals)
         self.n = self.m = 0
+        self.device = int(device)
         capi._check(_lib().eds_win_create(int(device), self.H, self.W, self.max_frames, self.max_points, self.max_residuals, C.byref(self._h)))
         if params:
             self.set_params(**params)
