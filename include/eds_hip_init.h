@@ -22,9 +22,11 @@
  *  3. setFirst's point set-up (:718-749) per level from a STATUS MAP the caller passes (a float per pixel of the level; non-zero:
  *     selected, and the value is my_type): the rectangle 3 <= x < w - 4, 3 <= y < h - 4 in row-major order by a stable compaction, u =
  *     (float)(x + 0.1), idepth = iR = 1, outlierTH = 8 outlier_th.  Level 0 may come straight from an eds_sel's map in device memory.
- *     makePixelStatus / gridMaxSelection for the upper levels are not restated: their maps are inputs.
- *  4. makeNN's tables (:884-958) are inputs too (eds_ini_set_neighbours); neighboursDist and parentDist, which the reference writes and
- *     never reads, have no counterpart.  eds_ini_make_nn fills the tables by an exhaustive search: smaller fp32 squared distance first,
+ *     makePixelStatus / gridMaxSelection for the upper levels are eds_hip_inisetup.h's (eds_ini_make_pixel_status,
+ *     eds_ini_set_points_status); a caller's own maps remain inputs here.
+ *  4. makeNN's tables (:884-958) are inputs here (eds_ini_set_neighbours); eds_hip_inisetup.h makes them on the device from the
+ *     level's points (eds_ini_make_neighbours).  neighboursDist and parentDist, which the reference writes and
+ *     never reads, have no counterpart.  eds_ini_make_nn fills the tables on the host by an exhaustive search: smaller fp32 squared distance first,
  *     then the lower index — which is not nanoflann's order: with every point at an integer pixel + 0.1 ties are common, and nanoflann
  *     resolves them by the order its tree is visited in.
  *  5. trackFrame (:75-262), whole, in ONE kernel launch and one wait: the new frame's pyramid, the un-snapped reset, the exposure guess

@@ -114,6 +114,11 @@ INI_EXPORTS = ("eds_ini_abi_version", "eds_ini_params_default", "eds_ini_create"
                "eds_ini_set_calib", "eds_ini_set_first", "eds_ini_set_pose", "eds_ini_set_points", "eds_ini_set_points_selected", "eds_ini_set_neighbours",
                "eds_ini_make_nn", "eds_ini_get_schedule_depth", "eds_ini_track_frame", "eds_ini_get_kernel_ms", "eds_ini_get_points", "eds_ini_get_jb", "eds_ini_get_level")
 
+# every symbol include/eds_hip_inisetup.h declares: the rest of setFirst over the same eds_ini (bound in init.py)
+INISETUP_EXPORTS = ("eds_ini_setup_abi_version", "eds_ini_get_sparsity", "eds_ini_set_sparsity", "eds_ini_make_pixel_status",
+                    "eds_ini_get_pixel_status", "eds_ini_set_points_status", "eds_ini_make_neighbours", "eds_ini_get_neighbours",
+                    "eds_ini_get_neighbours_kernel_ms", "eds_ini_setup_levels")
+
 # every symbol include/eds_hip_undistort.h declares: dso::Undistort with its PhotometricUndistorter over its own eds_und (bound in undistort.py)
 UND_EXPORTS = ("eds_und_abi_version", "eds_und_settings_default", "eds_und_create", "eds_und_destroy", "eds_und_get_K", "eds_und_get_map",
                "eds_und_is_passthrough", "eds_und_set_map", "eds_und_set_photometric", "eds_und_set_settings", "eds_und_get_settings",
@@ -243,6 +248,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_activate.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_select.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_init.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_inisetup.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_undistort.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_map.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)

@@ -16,6 +16,7 @@
 #include "../../include/eds_hip_init.h"
 #include "eds_capi_internal.hpp"
 #include "eds_init.hpp"
+#include "eds_init_internal.hpp"
 #include "eds_pixsel_internal.hpp"
 
 using edscapi::fail;
@@ -36,28 +37,8 @@ static_assert(edsini::MAX_DECISIONS == EDS_INI_MAX_DECISIONS && edsini::MAX_LEVE
                   edsini::MAX_ITERATIONS == EDS_INI_MAX_ITERATIONS,
               "header constants");
 
-struct eds_ini {
-    edscapi::DeviceOwner own;
-    int cap = 0;
-    Geo geo;
-    Params prm;
-    bool calib_set = false, first_set = false, new_set = false;
-    bool points_set[edsini::MAX_LEVELS] = {false, false, false, false, false}, tables_set[edsini::MAX_LEVELS] = {false, false, false, false, false};
-    int32_t n[edsini::MAX_LEVELS] = {0, 0, 0, 0, 0}, nd[edsini::MAX_LEVELS] = {0, 0, 0, 0, 0};
-    float exposure_first = 1.0f;
-    Carry carry;                                           // the host's copy of what the device hands from frame to frame
-    Px *first_px = nullptr, *new_px = nullptr;             // [geo.total]
-    float *in_img = nullptr, *in_status = nullptr;         // [H * W]
-    Pnt* pts = nullptr;                                    // [levels][cap]
-    int32_t *sched = nullptr, *parent = nullptr, *doff = nullptr, *coff = nullptr, *child = nullptr;
-    float *jb = nullptr, *iR_old = nullptr;
-    int32_t *good_old = nullptr, *d_count = nullptr;
-    Carry* d_carry = nullptr;
-    Result* d_out = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;               // around k_ini_track, for eds_ini_get_kernel_ms
-    float kernel_ms = -1.0f;
-    long n_launches = 0, n_waits = 0;                      // counted where this file launches and waits: INI_LAUNCH, ini_wait, ini_read_back
-};
+// struct eds_ini is eds_init_internal.hpp's, shared with eds_inisetup.hip.  Its device memory has one owner, the member
+// `edscapi::DeviceOwner own;`: this file allocates and frees through it alone.
 
 namespace {
 
@@ -194,7 +175,8 @@ int finish_points(eds_ini* h, int lvl, int32_t* n_out) {
     if (int rc = ini_read_back(h, &n, h->d_count, sizeof(n))) return rc;
     h->points_set[lvl] = false;
     h->tables_set[lvl] = false;
-    if (lvl > 0) h->tables_set[lvl - 1] = false;
+    h->nn_made[lvl] = false;
+    if (lvl > 0) h->tables_set[lvl - 1] = h->nn_made[lvl - 1] = false;
     if (n > h->cap) return fail(EDS_ERR_INVALID, std::to_string(n) + " selected pixels, the handle holds " + std::to_string(h->cap) + " per level");
     h->n[lvl] = n;
     h->points_set[lvl] = true;
@@ -203,6 +185,13 @@ int finish_points(eds_ini* h, int lvl, int32_t* n_out) {
 }
 
 }  // namespace
+
+int edsini_internal::points_from_bytes(eds_ini* h, int lvl, const uint8_t* map, int32_t* n_out) {
+    const Level& L = h->geo.l[lvl];
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    INI_LAUNCH(h, k_ini_points<uint8_t>, map, L.w, L.h, h->prm, h->pts + (size_t)lvl * h->cap, h->cap, h->d_count);
+    return finish_points(h, lvl, n_out);
+}
 
 extern "C" {
 
@@ -292,6 +281,7 @@ int eds_ini_set_first(eds_ini* h, const float* image, int64_t row_stride, int on
     if (!std::isfinite(exposure)) return fail(EDS_ERR_INVALID, "exposure must be finite");
     if (int rc = edscapi::check_images(h->own.dev, h->geo.H, h->geo.W, 1, image, &row_stride, nullptr, on_device, "image")) return rc;
     h->first_set = false;
+    for (int l = 0; l < edsini::MAX_LEVELS; ++l) h->status_set[l] = false;      // include/eds_hip_inisetup.h: the maps were of the frame before
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = edscapi::upload_image(h->own, h->in_img, h->geo.H, h->geo.W, image, row_stride, on_device)) return rc;
     INI_LAUNCH(h, k_ini_pyramid, h->geo, h->in_img, h->first_px);
@@ -364,6 +354,7 @@ int eds_ini_set_neighbours(eds_ini* h, int lvl, const int32_t* neighbours, const
     if (!edsini::derive_tables(n, neighbours, top ? nullptr : parent, np, sched.data(), doff.data(), &nd, coff.data(), child.data()))
         return fail(EDS_ERR_INVALID, "a neighbour is outside -1 .. n - 1 or a parent outside 0 .. n_up - 1");
     h->tables_set[lvl] = false;
+    h->nn_made[lvl] = false;                                // eds_ini_make_neighbours sets it again after this call
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t o = (size_t)lvl * h->cap, o1 = (size_t)lvl * (h->cap + 1);
     if (n > 0) {

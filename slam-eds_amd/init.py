@@ -49,7 +49,7 @@ assert POINT.itemsize == 64 and RESULT.itemsize == 712
 @functools.lru_cache(maxsize=None)
 def _lib():
     vp, i64, f, i = C.c_void_p, C.c_int64, C.c_float, C.c_int
-    return capi.bind(capi.INI_EXPORTS, {
+    return capi.bind(capi.INI_EXPORTS + capi.INISETUP_EXPORTS, {
         "eds_ini_params_default": ([C.POINTER(Params)], None),
         "eds_ini_create": [i] * 5 + [C.POINTER(vp)],
         "eds_ini_destroy": ([vp], None),
@@ -68,6 +68,17 @@ def _lib():
         "eds_ini_get_points": [vp, i, vp, vp],
         "eds_ini_get_jb": [vp, i, i, vp],
         "eds_ini_get_level": [vp, i, i, vp],
+        # include/eds_hip_inisetup.h
+        "eds_ini_setup_abi_version": [],
+        "eds_ini_get_sparsity": [vp, vp],
+        "eds_ini_set_sparsity": [vp, C.c_int32],
+        "eds_ini_make_pixel_status": [vp, i, f, i, f, vp, vp],
+        "eds_ini_get_pixel_status": [vp, i, vp],
+        "eds_ini_set_points_status": [vp, i, vp],
+        "eds_ini_make_neighbours": [vp, i],
+        "eds_ini_get_neighbours": [vp, i, vp, vp],
+        "eds_ini_get_neighbours_kernel_ms": [vp, vp],
+        "eds_ini_setup_levels": [vp, vp, vp, vp],
     })
 
 
@@ -205,3 +216,66 @@ class CoarseInitializer(capi.OwnedHandle):
         out = np.zeros((self.H >> lvl, self.W >> lvl, 3), np.float32)
         capi._check(_lib().eds_ini_get_level(self._h, int(which), int(lvl), _vp(out)))
         return out
+
+    # ---- include/eds_hip_inisetup.h: the rest of setFirst ----------------------------------------------------------------------------
+    @property
+    def sparsity(self):
+        """the reference's global ``sparsityFactor``: 5 on a new handle, left by every ``make_pixel_status`` as the reference leaves it"""
+        v = C.c_int32()
+        capi._check(_lib().eds_ini_get_sparsity(self._h, C.cast(C.byref(v), C.c_void_p)))
+        return v.value
+
+    @sparsity.setter
+    def sparsity(self, value):
+        capi._check(_lib().eds_ini_set_sparsity(self._h, int(value)))
+
+    def make_pixel_status(self, lvl, density, recursions_left=5, th_factor=1.0):
+        """``makePixelStatus`` of one level of the first frame; the map stays on the device.  Returns (n_good, passes)."""
+        n, passes = C.c_int32(), C.c_int32()
+        capi._check(_lib().eds_ini_make_pixel_status(self._h, int(lvl), float(density), int(recursions_left), float(th_factor),
+                                                     C.cast(C.byref(n), C.c_void_p), C.cast(C.byref(passes), C.c_void_p)))
+        return n.value, passes.value
+
+    def pixel_status(self, lvl):
+        """the level's map as (H >> lvl) x (W >> lvl) bytes, 0 / 1"""
+        out = np.zeros((self.H >> lvl, self.W >> lvl), np.uint8)
+        capi._check(_lib().eds_ini_get_pixel_status(self._h, int(lvl), _vp(out)))
+        return out
+
+    def set_points_status(self, lvl):
+        """the level's points from the map ``make_pixel_status`` left on the device (my_type 1); returns their number"""
+        n = C.c_int32()
+        capi._check(_lib().eds_ini_set_points_status(self._h, int(lvl), C.cast(C.byref(n), C.c_void_p)))
+        self.n[lvl] = n.value
+        return n.value
+
+    def make_neighbours(self, lvl=None):
+        """``makeNN`` on the device and everything ``set_neighbours`` does with its tables; lvl None: every level, top first"""
+        for l in (range(self.levels - 1, -1, -1) if lvl is None else [int(lvl)]):
+            capi._check(_lib().eds_ini_make_neighbours(self._h, l))
+
+    def neighbours(self, lvl):
+        """the tables ``make_neighbours`` made: (neighbours n x 10, parent n or None at the top level)"""
+        n, top = int(self.n[lvl]), int(lvl) == self.levels - 1
+        nb, par = np.full((max(n, 1), NEIGHBOURS), -1, np.int32), np.zeros(max(n, 1), np.int32)
+        capi._check(_lib().eds_ini_get_neighbours(self._h, int(lvl), _vp(nb), None if top else _vp(par)))
+        return nb[:n], None if top else par[:n]
+
+    def neighbours_kernel_ms(self):
+        """the device time of the last ``make_neighbours`` level's search kernel, in milliseconds"""
+        ms = C.c_float()
+        capi._check(_lib().eds_ini_get_neighbours_kernel_ms(self._h, C.cast(C.byref(ms), C.c_void_p)))
+        return ms.value
+
+    def setup_levels(self, selector, densities=None):
+        """setFirst's points and tables for every level, on the device: `selector` (a ``select.Selector`` of the same size) holds the
+        first frame; densities None: the reference's {0.03, 0.05, 0.15, 0.5, 1}.  Returns the points per level."""
+        d = None
+        if densities is not None:
+            d = np.ascontiguousarray(densities, dtype=np.float32).reshape(-1)
+            if len(d) < self.levels:
+                raise ValueError(f"one density per level: {self.levels}")
+        n = np.zeros(MAX_LEVELS, np.int32)
+        capi._check(_lib().eds_ini_setup_levels(self._h, selector._h, _vp(d), _vp(n)))
+        self.n[:] = n[:self.levels]
+        return self.n.copy()

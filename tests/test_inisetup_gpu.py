@@ -1,0 +1,247 @@
+"""include/eds_hip_inisetup.h on the device, BIT FOR BIT: the pixel status against csrc/eds_inisetup.hpp under g++
+(tests/inisetup_harness.py, which tests/test_inisetup_oracle.py holds to the reference's loop order), the neighbour tables against
+eds_ini_make_nn, and eds_ini_setup_levels against the long way — the selector's map, the oracle's maps through set_points and
+eds_ini_make_nn's tables through set_neighbours — on a second handle, through the next two trackFrames."""
+import functools
+import importlib
+
+import numpy as np
+import pytest
+
+import coarse_cases as cc
+import init_cases as ic
+import inisetup_cases as sc
+import inisetup_harness as sh
+import np_inisetup_oracle as nso
+from test_init_gpu import _assert_same_state, _same, _state
+
+pytestmark = pytest.mark.gpu
+
+capi = importlib.import_module("slam-eds_amd.capi")
+init = importlib.import_module("slam-eds_amd.init")
+select = importlib.import_module("slam-eds_amd.select")
+
+NN_TILE = 256                                   # EDS_INI_NN_TILE
+
+
+def _open(c, cap=4096, image=None):
+    t = init.CoarseInitializer(c.H, c.W, c.levels, max_points_per_level=cap)
+    t.set_calib(*c.K)
+    t.setFirst(c.image if image is None else image)
+    return t
+
+
+def _selector(c, image=None):
+    sel = select.Selector(c.H, c.W)
+    sel.set_random_pattern(np.random.default_rng(5).integers(0, 256, c.H * c.W).astype(np.uint8))
+    sel.set_image(c.image if image is None else image)
+    return sel
+
+
+def _same_points(a, b, what):
+    assert len(a) == len(b), what
+    for f in init.POINT.names:
+        assert _same(a[f], b[f]), (what, f)
+
+
+# ---- pixel status ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(sc.cases()))
+def test_pixel_status_equals_the_host_build_bit_for_bit(name):
+    c, want_np = sc.cases()[name], sc.expected(name)
+    with _open(c) as t, _open(c) as other:
+        assert t.sparsity == 5
+        sparsity = 5
+        for (lvl, dens, recs, th, set_first), w_np in zip(c.calls, want_np):
+            if set_first is not None:
+                t.sparsity = sparsity = set_first
+                assert t.sparsity == set_first
+            grads = t.level(init.FIRST, lvl)
+            assert _same(grads, sc.grads(name)[lvl])
+            n_good, passes = t.make_pixel_status(lvl, dens, recs, th)
+            status, h_good, h_passes, sparsity = sh.make_pixel_status(grads, dens, recs, th, sparsity)
+            got = t.pixel_status(lvl)
+            print(f"{name} level {lvl}: device n_good {n_good} passes {passes} sparsity {t.sparsity}; host {h_good} {h_passes} {sparsity}")
+            assert (n_good, passes, t.sparsity) == (h_good, h_passes, sparsity) == (w_np.n_good, w_np.passes, w_np.sparsity)
+            assert _same(got, status) and _same(got, w_np.map), np.argwhere(got != status)[:8]
+            n = t.set_points_status(lvl)
+            assert n == other.set_points(lvl, got.astype(np.float32)) == int(got[3:-4, 3:-4].sum())
+            _same_points(t.points(lvl), other.points(lvl), (name, lvl))
+            assert n == 0 or (t.points(lvl)["my_type"] == 1).all()
+
+
+def test_sparsity_is_state_of_the_handle():
+    c = sc.cases()["a"]
+    with _open(c) as t:
+        for given, held in ((7, 7), (0, 1), (-5, 1), (1 << 30, 1 << 30)):
+            t.sparsity = given
+            assert t.sparsity == held
+        t.sparsity = 13
+        t.setFirst(c.image)                                                  # the reference's global survives setFirst
+        assert t.sparsity == 13
+
+
+# ---- neighbours ----------------------------------------------------------------------------------------------------------------------------
+def _chosen_status(h, w, k, rng):
+    """a status map with exactly k points inside setFirst's rectangle"""
+    s = np.zeros((h, w), np.float32)
+    ys, xs = np.mgrid[3:h - 4, 3:w - 4]
+    pick = rng.choice(ys.size, size=k, replace=False)
+    s[ys.ravel()[pick], xs.ravel()[pick]] = 1
+    return s
+
+
+def test_neighbours_equal_the_exhaustive_host_search():
+    H, W = 80, 96
+    rng = np.random.default_rng(17)
+    full = np.ones((H, W), np.float32)                                           # 89 x 73 = 6 497 points: 26 workgroups
+    maps = [_chosen_status(H, W, k, rng) for k in (1, 9, 10, 11, 63, 65, NN_TILE + 1, 3 * NN_TILE + 1)] + [ic.cases()["a96"].status[0], full]
+    assert int(full[3:-4, 3:-4].sum()) >= 4097
+    with init.CoarseInitializer(H, W, 2, max_points_per_level=8192) as t, init.CoarseInitializer(H, W, 2, max_points_per_level=8192) as other:
+        for h in (t, other):
+            h.set_calib(*ic.K96)
+            h.setFirst(ic.cases()["a96"].first)
+        up = _chosen_status(H // 2, W // 2, 700, rng)
+        for s in maps:
+            for h in (t, other):
+                n = h.set_points(0, s)
+                n_up = h.set_points(1, up)
+            uv = [np.stack([t.points(l)["u"], t.points(l)["v"]], axis=1) for l in range(2)]
+            t.make_neighbours()
+            assert t.neighbours_kernel_ms() >= 0.0
+            for l in (1, 0):
+                nb, par = t.neighbours(l)
+                want_nb, want_par = init.make_nn(uv[l], uv[1] if l == 0 else None)
+                assert _same(nb, want_nb), (n, l, np.argwhere(nb != want_nb)[:8])
+                assert (par is None and want_par is None) if l == 1 else _same(par, want_par), (n, l)
+                assert nb.shape == ((n, n_up)[l], 10) and ((nb >= 0).sum(axis=1) == min(10, len(nb))).all()
+            for l in (0, 1):
+                other.set_neighbours(l, *init.make_nn(uv[l], uv[1] if l == 0 else None))
+            assert [t.schedule_depth(l) for l in range(2)] == [other.schedule_depth(l) for l in range(2)]
+        # a level without points below one with points: empty tables, no launch
+        assert t.set_points(0, np.zeros((H, W), np.float32)) == 0
+        t.make_neighbours(0)
+        nb, par = t.neighbours(0)
+        assert nb.shape == (0, 10) and par.shape == (0,) and t.schedule_depth(0) == 0
+
+
+# ---- the one call --------------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _one_call_case(name):
+    """(case, frames, the oracle's maps for levels 1 ..): computed once, shared, never changed"""
+    if name == "a96":
+        a = ic.cases()["a96"]
+        c, frames = sc.cases()["a"], a.frames[:2]
+    else:
+        c = sc.cases()["c"]
+        frames = [ic.frame_at(c.H, c.W, c.K, cc.se3(np.multiply(ic.STEP[0], k), np.multiply(ic.STEP[1], k))) for k in (1, 2)]
+    maps, sparsity = {}, 5
+    for l in range(1, c.levels):
+        maps[l], _, _, sparsity = nso.make_pixel_status(sc.grads(c.name)[l], sc.density(sc.REFERENCE_DENSITIES[l], c.W, c.H), 5, 1.0, sparsity)
+    return c, frames, maps, sparsity
+
+
+def _long_way(t, c, sel, maps):
+    """setFirst's points and tables as a caller of eds_hip_init.h alone makes them"""
+    sel.potential = 3
+    sel.make_maps(float(sc.density(sc.REFERENCE_DENSITIES[0], c.W, c.H)), 1, 2.0)
+    t.set_points(0, sel.map().astype(np.float32))
+    for l in range(1, c.levels):
+        t.set_points(l, maps[l].astype(np.float32))
+    uv = [np.stack([t.points(l)["u"], t.points(l)["v"]], axis=1) for l in range(c.levels)]
+    for l in range(c.levels):
+        t.set_neighbours(l, *init.make_nn(uv[l], uv[l + 1] if l + 1 < c.levels else None))
+
+
+@pytest.mark.parametrize("name", ["a96", "five"])
+def test_setup_levels_equals_the_long_way_through_two_frames(name):
+    c, frames, maps, sparsity = _one_call_case(name)
+    with _open(c) as t, _open(c) as long, _selector(c) as sel:
+        _long_way(long, c, sel, maps)
+        n = t.setup_levels(sel)
+        assert n.tolist() == [int(k) for k in long.n] and (n > 0).all() and t.sparsity == sparsity
+        for l in range(1, c.levels):
+            assert _same(t.pixel_status(l), maps[l])
+        assert [t.schedule_depth(l) for l in range(c.levels)] == [long.schedule_depth(l) for l in range(c.levels)]
+        _assert_same_state(_state(t, c, False), _state(long, c, False), (name, "set-up"))
+        for k, f in enumerate(frames):
+            r, want = t.trackFrame(f, 1.0, 1), long.trackFrame(f, 1.0, 1)
+            assert r.tobytes() == want.tobytes(), (name, k)
+            _assert_same_state(_state(t, c, True), _state(long, c, True), (name, "frame", k + 1))
+        # explicit densities: the reference's, given
+        with _open(c) as again:
+            assert again.setup_levels(sel, sc.REFERENCE_DENSITIES).tolist() == n.tolist()
+
+
+def test_a_second_set_first_and_setup_equals_a_fresh_handle_with_the_sparsity_carried():
+    c, frames, _, sparsity = _one_call_case("a96")
+    a96 = ic.cases()["a96"]
+    second = a96.frames[2]
+    with _open(c) as used, _selector(c) as sel:
+        used.setup_levels(sel)
+        used.trackFrame(frames[0], 1.0, 1)
+        left = used.sparsity
+        assert left == sparsity
+        used.setFirst(second)
+        with pytest.raises(capi.EdsError) as e:
+            used.set_points_status(1)                                            # the maps were of the frame before
+        assert e.value.code == capi.ERR_STATE
+        sel.set_image(second)
+        n = used.setup_levels(sel)
+        with _open(c, image=second) as fresh:
+            fresh.sparsity = left
+            assert fresh.setup_levels(sel).tolist() == n.tolist() and fresh.sparsity == used.sparsity
+            _assert_same_state(_state(used, c, False), _state(fresh, c, False), "second setFirst")
+            assert used.trackFrame(a96.frames[3], 1.0, 1).tobytes() == fresh.trackFrame(a96.frames[3], 1.0, 1).tobytes()
+            _assert_same_state(_state(used, c, True), _state(fresh, c, True), "second setFirst, frame")
+        assert left != 5                                                         # so the carried value is not the starting one
+
+
+# ---- the refused calls ---------------------------------------------------------------------------------------------------------------------
+def _code(call):
+    with pytest.raises(capi.EdsError) as e:
+        call()
+    return e.value.code
+
+
+def test_refused_calls_return_their_code_and_change_nothing():
+    c, _, maps, _ = _one_call_case("a96")
+    dens = float(sc.density(0.05, c.W, c.H))
+    with init.CoarseInitializer(c.H, c.W, c.levels, max_points_per_level=4096) as t:
+        t.set_calib(*c.K)
+        assert _code(lambda: t.make_pixel_status(1, dens)) == capi.ERR_STATE                    # before set_first
+        assert t.sparsity == 5
+        t.setFirst(c.image)
+        assert _code(lambda: t.set_points_status(1)) == capi.ERR_STATE                          # before a map
+        assert _code(lambda: t.pixel_status(1)) == capi.ERR_STATE
+        assert _code(lambda: t.make_neighbours(2)) == capi.ERR_STATE                            # before the level's points
+        for bad in (lambda: t.make_pixel_status(3, dens), lambda: t.make_pixel_status(-1, dens), lambda: t.make_pixel_status(1, 0.0),
+                    lambda: t.make_pixel_status(1, float("nan")), lambda: t.make_pixel_status(1, dens, -1), lambda: t.make_pixel_status(1, dens, 5, 0.0),
+                    lambda: t.make_neighbours(3), lambda: t.set_points_status(7)):
+            assert _code(bad) == capi.ERR_INVALID
+        assert t.sparsity == 5
+        t.set_points(2, np.zeros((c.H >> 2, c.W >> 2), np.float32))
+        t.set_points(1, maps[1].astype(np.float32))
+        assert _code(lambda: t.make_neighbours(1)) == capi.ERR_INVALID                          # below a level with 0 points
+        assert _code(lambda: t.make_neighbours(0)) == capi.ERR_STATE                            # level 0 has no points yet
+        assert _code(lambda: t.neighbours(1)) == capi.ERR_STATE
+        t.make_neighbours(2)
+        assert _code(lambda: t.schedule_depth(1)) == capi.ERR_STATE and t.schedule_depth(2) == 0
+    with _open(c, cap=16) as small:                                                              # more selected pixels than the handle holds
+        n_good, _ = small.make_pixel_status(1, dens)
+        assert n_good > 16 and _code(lambda: small.set_points_status(1)) == capi.ERR_INVALID
+        assert _same(small.pixel_status(1), maps[1])
+    with _open(c) as t, _selector(c) as sel, select.Selector(64, 64) as other_size, select.Selector(c.H, c.W) as no_image:
+        t.setup_levels(sel)
+        before, depths, sparsity = _state(t, c, False), [t.schedule_depth(l) for l in range(c.levels)], t.sparsity
+        L = init._lib()
+        assert _code(lambda: t.setup_levels(other_size)) == capi.ERR_INVALID                    # a selector of another size
+        assert _code(lambda: t.setup_levels(no_image)) == capi.ERR_STATE
+        assert _code(lambda: t.setup_levels(sel, [0.03, -1.0, 0.15])) == capi.ERR_INVALID
+        assert L.eds_ini_setup_levels(t._h, None, None, None) == capi.ERR_INVALID
+        assert L.eds_ini_get_neighbours(t._h, 0, None, None) == capi.ERR_INVALID
+        assert L.eds_ini_get_sparsity(t._h, None) == capi.ERR_INVALID
+        assert t.sparsity == sparsity and [t.schedule_depth(l) for l in range(c.levels)] == depths
+        _assert_same_state(_state(t, c, False), before, "after the refused calls")
+        nb, par = t.neighbours(0)
+        t.set_neighbours(0, nb, par)                                                             # tables from outside: the made ones no longer hold
+        assert _code(lambda: t.neighbours(0)) == capi.ERR_STATE
