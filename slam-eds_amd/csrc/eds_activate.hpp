@@ -13,12 +13,6 @@
 #pragma once
 #include "eds_immature.hpp"
 
-#if defined(__HIPCC__)
-#define EDS_ACT_HD __host__ __device__ inline
-#else
-#define EDS_ACT_HD inline
-#endif
-
 namespace edsact {
 
 using edsimm::finite_f;
@@ -50,24 +44,24 @@ struct Params {
 
 struct Calib { float fx, fy, cx, cy, fxli, fyli, wM3G, hM3G; int32_t W, H, w1, h1; };
 
-EDS_ACT_HD Params params_default() { Params p = {100.0f, 3, 3.0f, 8.0f, 1, 1.0f}; return p; }
-EDS_ACT_HD bool params_valid(const Params& p) {
+EDS_HD Params params_default() { Params p = {100.0f, 3, 3.0f, 8.0f, 1, 1.0f}; return p; }
+EDS_HD bool params_valid(const Params& p) {
     return finite_f(p.min_idepth_h_act) && finite_f(p.min_trace_quality) && finite_f(p.max_trace_pixel_interval) && finite_f(p.scale_idepth) &&
            p.scale_idepth > 0.0f && p.gn_its >= 0 && p.gn_its <= 16 && p.min_obs >= 0 && p.min_obs <= MAX_FRAMES;
 }
-EDS_ACT_HD Calib make_calib(int H, int W, float fx, float fy, float cx, float cy) {
+EDS_HD Calib make_calib(int H, int W, float fx, float fy, float cx, float cy) {
     Calib c;
     c.fx = fx; c.fy = fy; c.cx = cx; c.cy = cy; c.fxli = 1.0f / fx; c.fyli = 1.0f / fy;
     c.wM3G = (float)(W - 3); c.hM3G = (float)(H - 3); c.W = W; c.H = H; c.w1 = W >> 1; c.h1 = H >> 1;
     return c;
 }
 
-EDS_ACT_HD float map_value(uint8_t b) { return b == FAR ? 1000.0f : (float)b; }
-EDS_ACT_HD bool on_ring(int x, int y, int w1, int h1) { return x == 0 || y == 0 || x == w1 - 1 || y == h1 - 1; }
+EDS_HD float map_value(uint8_t b) { return b == FAR ? 1000.0f : (float)b; }
+EDS_HD bool on_ring(int x, int y, int w1, int h1) { return x == 0 || y == 0 || x == w1 - 1 || y == h1 - 1; }
 
 // ptp = KRKi (u, v, 1) + Kt idepth, every row summed left to right; the cell (int)(ptp0 / ptp2 + 0.5f), (int)(ptp1 / ptp2 + 0.5f) when it
 // lies inside the map.  A quotient that is not finite or beyond +-2^20 is outside: the conversion is never reached.
-EDS_ACT_HD bool map_cell(const float* K, const float* Kt, float u, float v, float idepth, int w1, int h1, int* u1, int* v1, float* ptp0) {
+EDS_HD bool map_cell(const float* K, const float* Kt, float u, float v, float idepth, int w1, int h1, int* u1, int* v1, float* ptp0) {
     const float p0 = ((K[0] * u + K[1] * v) + K[2] * 1.0f) + Kt[0] * idepth;
     const float p1 = ((K[3] * u + K[4] * v) + K[5] * 1.0f) + Kt[1] * idepth;
     const float p2 = ((K[6] * u + K[7] * v) + K[8] * 1.0f) + Kt[2] * idepth;
@@ -80,12 +74,12 @@ EDS_ACT_HD bool map_cell(const float* K, const float* Kt, float u, float v, floa
 }
 
 // the neighbourhood of round k: the first four offsets always, all eight when k is odd
-EDS_ACT_HD int nb_count(int k) { return (k & 1) ? 8 : 4; }
-EDS_ACT_HD int nb_x(int i) { const int t[8] = {1, -1, 0, 0, 1, -1, -1, 1}; return t[i]; }
-EDS_ACT_HD int nb_y(int i) { const int t[8] = {0, 0, 1, -1, 1, 1, -1, -1}; return t[i]; }
+EDS_HD int nb_count(int k) { return (k & 1) ? 8 : 4; }
+EDS_HD int nb_x(int i) { const int t[8] = {1, -1, 0, 0, 1, -1, -1, 1}; return t[i]; }
+EDS_HD int nb_y(int i) { const int t[8] = {0, 0, 1, -1, 1, 1, -1, -1}; return t[i]; }
 
 // round k after seeding: cell (x, y) is set to k when it is above k and a neighbour that is not on the ring holds k - 1
-EDS_ACT_HD bool grow_pull(const uint8_t* map, int w1, int h1, int k, int x, int y) {
+EDS_HD bool grow_pull(const uint8_t* map, int w1, int h1, int k, int x, int y) {
     if ((int)map[x + y * w1] <= k) return false;
     const int nn = nb_count(k);
     for (int i = 0; i < nn; ++i) {
@@ -97,7 +91,7 @@ EDS_ACT_HD bool grow_pull(const uint8_t* map, int w1, int h1, int k, int x, int 
 }
 
 // round k of one seed's grow: ... when it is above k and a neighbour that is not on the ring was taken in round k - 1 OF THIS GROW
-EDS_ACT_HD bool grow_takes(const uint8_t* map, const uint32_t* mark, int w1, int h1, int k, int x, int y, uint32_t prev_tag) {
+EDS_HD bool grow_takes(const uint8_t* map, const uint32_t* mark, int w1, int h1, int k, int x, int y, uint32_t prev_tag) {
     if ((int)map[x + y * w1] <= k) return false;
     const int nn = nb_count(k);
     for (int i = 0; i < nn; ++i) {
@@ -109,13 +103,13 @@ EDS_ACT_HD bool grow_takes(const uint8_t* map, const uint32_t* mark, int w1, int
 }
 
 // canActivate of the stated loop
-EDS_ACT_HD bool can_activate(const Point& p, const Params& s) {
+EDS_HD bool can_activate(const Point& p, const Params& s) {
     const bool st = p.status == edsimm::GOOD || p.status == edsimm::SKIPPED || p.status == edsimm::BADCONDITION || p.status == edsimm::OOB;
     return st && p.last_interval < s.max_trace_pixel_interval && p.quality > s.min_trace_quality && (p.idepth_max + p.idepth_min) > 0;
 }
 
 // rows a and b of the candidate rule; NONE: go on to the map
-EDS_ACT_HD int fate_before_map(const Point& p, const Params& s, bool host_flagged) {
+EDS_HD int fate_before_map(const Point& p, const Params& s, bool host_flagged) {
     if (!finite_f(p.idepth_max) || p.status == edsimm::OUTLIER) return DELETED_UNTRACED;
     if (!can_activate(p, s)) return (host_flagged || p.status == edsimm::OOB) ? DELETED_CANNOT : KEPT_CANNOT;
     return NONE;
@@ -132,7 +126,7 @@ struct SelectIn {
 // with one thread.  sync.barrier() orders the map's reads and writes; sync.any(b) is a barrier that returns whether any thread passed
 // true.  Every thread takes every decision from the same values, so control flow is uniform.
 template <class Sync>
-EDS_ACT_HD void select_body(const SelectIn& in, int tid, int nt, Sync& sync) {
+EDS_HD void select_body(const SelectIn& in, int tid, int nt, Sync& sync) {
     int cnt[NUM_FATES];
     for (int i = 0; i < NUM_FATES; ++i) cnt[i] = 0;
     const int w1 = in.w1, h1 = in.h1;
@@ -204,7 +198,7 @@ struct SerialSync {
 // Hdd and bd.  pre: PRE_RTll row-major, PRE_tTll, PRE_aff_mode.
 struct TapOut { int32_t fail; float e, h, b; };
 
-EDS_ACT_HD TapOut tap(const Calib& K, float scale_idepth, float huber, const float* pre, const Frame& f, const Point& p, float idepth, int idx) {
+EDS_HD TapOut tap(const Calib& K, float scale_idepth, float huber, const float* pre, const Frame& f, const Point& p, float idepth, int idx) {
     TapOut o;
     o.fail = 1; o.e = o.h = o.b = 0.0f;
     const float* R = pre;
@@ -235,10 +229,10 @@ EDS_ACT_HD TapOut tap(const Calib& K, float scale_idepth, float huber, const flo
 }
 
 // the target frame of residual r of a point hosted by `host`: the frames 0 ... n_hosts - 1 except the host, in that order
-EDS_ACT_HD int res_target(int host, int r) { return r < host ? r : r + 1; }
+EDS_HD int res_target(int host, int r) { return r < host ? r : r + 1; }
 
 // what linearizeResidual leaves after its last tap (:584-595)
-EDS_ACT_HD void verdict(float energy, float energyTH, float slack, int32_t* new_state, float* new_energy) {
+EDS_HD void verdict(float energy, float energyTH, float slack, int32_t* new_state, float* new_energy) {
     if (energy > energyTH * slack) { energy = energyTH * slack; *new_state = ST_OUTLIER; }
     else *new_state = ST_IN;
     *new_energy = energy;
@@ -250,7 +244,7 @@ struct Fit { int32_t fate; float idepth, E, Hdd, bd; };
 // The stated optimizeImmaturePoint loop over an evaluator: ev.eval(idepth, slack) runs linearizeResidual over the residuals in order,
 // ev.apply() is state = new_state, energy = new_energy for every residual, ev.count_in() the residuals whose state is IN.
 template <class Ev>
-EDS_ACT_HD Fit fit_loop(Ev& ev, const Params& s, const Point& p) {
+EDS_HD Fit fit_loop(Ev& ev, const Params& s, const Point& p) {
     float idepth = (p.idepth_max + p.idepth_min) * 0.5f;
     Sums c = ev.eval(idepth, 1000.0f);
     ev.apply();
@@ -277,7 +271,7 @@ EDS_ACT_HD Fit fit_loop(Ev& ev, const Params& s, const Point& p) {
 }
 
 // a fitted point leaves the immature set, as does everything the candidate rule deleted
-EDS_ACT_HD bool leaves(int fate, int status) {
+EDS_HD bool leaves(int fate, int status) {
     return fate == ACTIVATED || fate == DROPPED || (fate == KEPT_WEAK && status == edsimm::OOB) || fate == DELETED_UNTRACED ||
            fate == DELETED_CANNOT || fate == DELETED_OUT_OF_MAP;
 }

@@ -2,7 +2,7 @@
 // holds the kernels and the C entry points.  Built without contraction into FMAs (csrc/Makefile).
 //
 // k_ct_track runs the whole of trackNewestCoarse for one try in ONE workgroup of 512 threads (grid = the batch): the threads stride the
-// level's list, keep fp64 partials, fold them in the header's order (wavefront shuffles, then eight LDS words added left to right), and
+// level's list, keep fp64 partials, fold them in eds_dso_common.hpp's order (its wave_fold, then eight LDS words added by its add8), and
 // then EVERY thread runs the small solve, SE3::exp and the accept test on the same workgroup-uniform values — one code path with the
 // host, nothing to broadcast.  The 45 sums of calcGSSSE are formed only after an accept (and once per level), as the reference forms
 // them, by a second pass that recomputes the accepted pose's rows instead of parking them in HBM: the taps are L2-resident and a try
@@ -26,7 +26,7 @@ using edsct::Level;
 using edsct::Params;
 using edsct::Pc;
 using edsct::Photo;
-using edsct::Px;
+using edsdso::Px;
 using edsct::Term;
 using edsct::TrackOut;
 using edsct::Warp;
@@ -59,26 +59,6 @@ struct eds_ct {
 namespace {
 
 constexpr int TB = 256;
-
-__global__ void __launch_bounds__(TB) k_ct_pyramid(const float* __restrict__ img, Px* __restrict__ px, const Geo* __restrict__ g, int lvl) {
-    const Level L = g->l[lvl];
-    const int i = blockIdx.x * TB + threadIdx.x;
-    if (i >= L.w * L.h) return;
-    Px o;
-    o.c = lvl == 0 ? img[i] : edsct::down_at(px + g->l[lvl - 1].off, g->l[lvl - 1].w, i % L.w, i / L.w);
-    o.dx = 0.0f; o.dy = 0.0f; o.pad = 0.0f;
-    px[L.off + i] = o;
-}
-
-__global__ void __launch_bounds__(TB) k_ct_gradient(Px* px, const Geo* __restrict__ g, int lvl) {
-    const Level L = g->l[lvl];
-    const int i = blockIdx.x * TB + threadIdx.x;
-    if (i >= L.w * L.h) return;
-    float dx, dy;
-    edsct::gradient_at(px + L.off, L.w, L.h, i, &dx, &dy);
-    px[L.off + i].dx = dx;
-    px[L.off + i].dy = dy;
-}
 
 // The scatter into idepth[0] / weightSums[0], equal to the serial loop in input order.  Pass 0: every contribution finds its pixel
 // and weight and records, with INTEGER atomics, the smallest and the largest input index that lands on the pixel.  Pass 1: a pixel with
@@ -144,38 +124,30 @@ __global__ void __launch_bounds__(TB) k_ct_dilate(const float* __restrict__ idA,
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = c;
 }
 
-// the stable, row-major compaction: a workgroup's base is the sum of the counts before it, a wavefront's the counts of the wavefronts
-// before it (LDS), a lane's the set bits of the ballot below it.  An interior pixel is in the list exactly when its idepth is > 0.
+// the stable, row-major compaction: a workgroup's base is the sum of the counts before it (blocks_before), a pixel's place in the
+// workgroup block_rank's.  An interior pixel is in the list exactly when its idepth is > 0.
 __global__ void __launch_bounds__(TB) k_ct_select(const float* __restrict__ idB, const Px* __restrict__ ref, Pc* __restrict__ pc,
                                                   int32_t* __restrict__ pc_n, const int32_t* __restrict__ block_cnt, const Geo* __restrict__ g, int lvl) {
-    __shared__ int wsum[TB / 64], wcnt[TB / 64];
+    __shared__ int s_wave[TB / 64];
     const Level L = g->l[lvl];
-    const int i = blockIdx.x * TB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int before = 0;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += TB) before += block_cnt[b];
-    for (int s = 32; s >= 1; s >>= 1) before += __shfl_xor(before, s);
+    const int i = blockIdx.x * TB + threadIdx.x;
     const int x = i % L.w, y = i / L.w;
-    const bool sel = i < L.w * L.h && x >= 2 && x < L.w - 2 && y >= 2 && y < L.h - 2 && idB[L.off + i] > 0;
-    const unsigned long long m = __ballot(sel);
-    if (lane == 0) { wsum[wave] = before; wcnt[wave] = __popcll(m); }
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int k = 0; k < TB / 64; ++k) { base += wsum[k]; if (k < wave) base += wcnt[k]; total += wcnt[k]; }
+    const bool sel = i < L.w * L.h && x >= 2 && x < L.w - 2 && y >= 2 && y < L.h - 2 && idB[L.off + i] > 0;     // in flight with blocks_before's loads
+    const int base = edsdso::blocks_before<TB>(block_cnt, s_wave);
+    int total;
+    const int rank = edsdso::block_rank<TB>(sel, s_wave, &total);
     if (sel) {
         Pc e;
         e.u = (float)x; e.v = (float)y; e.idepth = idB[L.off + i]; e.color = ref[L.off + i].c;
-        pc[L.off + base + __popcll(m & ((1ull << lane) - 1ull))] = e;
+        pc[L.off + base + rank] = e;
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        int all = 0;
-        for (int k = 0; k < TB / 64; ++k) all += wsum[k];
-        pc_n[lvl] = all + total;
-    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) pc_n[lvl] = base + total;
 }
 
 // ---- the evaluator of edsct::track on the device --------------------------------------------------------------------------------------
-using edsct::wave_fold;
-using edsct::wave_fold_i;
+using edsdso::add8;
+using edsdso::wave_fold;
+using edsdso::wave_fold_i;
 
 // a Warp is the same in every lane: say so, and its 31 words live in scalar registers through the strided loops
 __device__ inline Warp uniform_warp(Warp w) {
@@ -213,7 +185,6 @@ struct DevEval {
 #pragma unroll
         for (int i = 0; i < 6; ++i) rs[i] = shP[12 + i];
     }
-    __device__ static double add8(const double* p) { return ((((((p[0] + p[1]) + p[2]) + p[3]) + p[4]) + p[5]) + p[6]) + p[7]; }
     __device__ static int add8i(const int* p) { return p[0] + p[1] + p[2] + p[3] + p[4] + p[5] + p[6] + p[7]; }
 
     __device__ void res(int lvl, const double* R, const double* t, double a, double bb, float cutoff, double* rs) {
@@ -345,10 +316,9 @@ int load_frame(eds_ct* h, Px* px, const float* image, int64_t rs, int on_device)
     const int H = h->geo.H, W = h->geo.W;
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (int rc = edscapi::upload_image(h->own, h->in_img, H, W, image, rs, on_device)) return rc;
+    const Level* L = h->geo.l;
     for (int l = 0; l < h->geo.levels; ++l) {
-        const unsigned nb = blocks(h->geo.l[l].w * h->geo.l[l].h);
-        hipLaunchKernelGGL(k_ct_pyramid, dim3(nb), dim3(TB), 0, h->own.st, h->in_img, px, h->d_geo, l);
-        hipLaunchKernelGGL(k_ct_gradient, dim3(nb), dim3(TB), 0, h->own.st, px, h->d_geo, l);
+        edscapi::queue_level(h->own.st, l == 0 ? h->in_img : nullptr, l == 0 ? nullptr : px + L[l - 1].off, l == 0 ? 0 : L[l - 1].w, px + L[l].off, L[l].w, L[l].h);
     }
     EDS_HIP_TRY(hipGetLastError());
     return EDS_OK;

@@ -2,14 +2,10 @@
 // level of makeImages, the pieces of makeCoarseDepthL0, the per-point term of calcRes, the Jacobian row and the 45 products of
 // calcGSSSE, the small solve, SE3::exp and the whole of trackNewestCoarse as a template over an EVALUATOR that supplies the two
 // reductions — and a serial evaluator (SerialEval, track_serial) that walks the device's sum order.  fp32 per point in the
-// reference's order, fp64 sums in the order stated below; every translation unit that includes this is built without contraction
-// into FMAs.  Plain C++ outside hipcc.
-//
-// THE SUM ORDER.  A sum over the list entries of a level (E, the two flow sums, each of the 45 products) is taken by LANES = 512
-// lanes.  Lane t adds, starting from 0.0 and in fp64, the terms of entries t, t + 512, t + 1024, ... in that order (an entry that
-// contributes nothing adds nothing).  Inside every 64 consecutive lanes the partials are folded by p[t] += p[t + s] for
-// (t mod 64) < s, s = 32, 16, 8, 4, 2, 1; the eight group totals are added left to right.  reduce_lanes() is that fold on the
-// host; the device does the same with wavefront shuffles and eight LDS words.  Counts are integers.
+// reference's order, fp64 sums (E, the two flow sums, each of the 45 products over the list entries of a level) in THE SUM ORDER stated at
+// the top of eds_dso_common.hpp, which also holds the pixel type, makeImages' level and gradient, the interpolation weights and the fold
+// inside 64 lanes on the device; every translation unit that includes this is built without contraction into FMAs.  Plain C++ outside
+// hipcc.
 //
 // sincos_d / exp_d are plain fp64 arithmetic (+, -, *, /, floor, integer bit moves), so g++ and gfx950 give the same bits.  The loop
 // does not bound their arguments (an increment's angle and a difference of affine a's are whatever the solve gives), so the bounds
@@ -25,20 +21,18 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define EDS_CT_HD __host__ __device__ inline
-#define EDS_CT_UNROLL _Pragma("unroll")          /* the device needs constant indices: a local array must stay in registers */
-#else
-#define EDS_CT_HD inline
-#define EDS_CT_UNROLL
-#endif
+#include "eds_dso_common.hpp"
 
 namespace edsct {
 
+using edsdso::finite_d;
+using edsdso::finite_f;
+using edsdso::LANES;
+using edsdso::nan_d;
+using edsdso::nan_f;
+using edsdso::Px;
+
 constexpr int MAX_LEVELS = 5;
-constexpr int LANES = 512;
-constexpr int WAVE = 64;
-constexpr int GROUPS = LANES / WAVE;
 constexpr int MAX_DECISIONS = 512;             // 10 + 20 + 3 * 100 iterations and one repeated level at the most
 constexpr int NUM_SUMS = 45;
 constexpr int SINCOS_MAX_ULP = 2;
@@ -51,7 +45,6 @@ struct Params { float huber_th, coarse_cutoff_th, affine_opt_mode_a, affine_opt_
 struct Level { int32_t w, h, off, pad; float fx, fy, cx, cy, fxi, fyi, cxi, cyi; };
 struct Geo { int32_t levels, W, H, total; Level l[MAX_LEVELS]; };
 
-struct alignas(16) Px { float c, dx, dy, pad; };                // one pixel of a frame level
 struct alignas(16) Pc { float u, v, idepth, color; };           // one entry of a level's pc_* lists
 
 // the two frames' photometric state: AffLight::fromToVecExposure's arguments that do not change during a track
@@ -73,20 +66,15 @@ struct Term {
     float t1, t2, rt1, rt2;                                     // the four flow addends when `flow`
 };
 
-EDS_CT_HD bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }
-EDS_CT_HD bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
-EDS_CT_HD float nan_f() { return __builtin_nanf(""); }
-EDS_CT_HD double nan_d() { return __builtin_nan(""); }
-
-EDS_CT_HD Params params_default() { Params p = {9.0f, 20.0f, 1e12f, 1e8f}; return p; }
-EDS_CT_HD bool params_valid(const Params& p) {
+EDS_HD Params params_default() { Params p = {9.0f, 20.0f, 1e12f, 1e8f}; return p; }
+EDS_HD bool params_valid(const Params& p) {
     return finite_f(p.huber_th) && finite_f(p.coarse_cutoff_th) && finite_f(p.affine_opt_mode_a) && finite_f(p.affine_opt_mode_b) &&
            p.huber_th > 0.0f && p.coarse_cutoff_th > 0.0f;
 }
 
 // ---- fp64 sin, cos and exp in plain arithmetic -------------------------------------------------------------------------------------
 // x = k pi/2 + r by a three-part pi/2 (k pio2_1 and k pio2_2 are exact for |k| < 2^20), Taylor to r^17 / r^16 on |r| <= pi/4.
-EDS_CT_HD void sincos_d(double x, double* s, double* c) {
+EDS_HD void sincos_d(double x, double* s, double* c) {
     if (!(fabs(x) <= 1048576.0)) { *s = nan_d(); *c = nan_d(); return; }
     const double kf = floor(x * 6.36619772367581382433e-01 + 0.5);
     const double r = ((x - kf * 1.57079632673412561417e+00) - kf * 6.07710050630396597660e-11) - kf * 2.02226624879595063154e-21;
@@ -114,7 +102,7 @@ EDS_CT_HD void sincos_d(double x, double* s, double* c) {
 }
 
 // x = k ln2 + r (k ln2_hi is exact), Taylor to r^13 on |r| <= ln2 / 2, times 2^k built from its bits.  Outside +-708: inf and 0.
-EDS_CT_HD double exp_d(double x) {
+EDS_HD double exp_d(double x) {
     if (!(x == x)) return x;
     if (x > 708.0) return 1.0 / 0.0;
     if (x < -708.0) return 0.0;
@@ -140,7 +128,7 @@ EDS_CT_HD double exp_d(double x) {
 }
 
 // ---- fp64 atan in plain arithmetic ---------------------------------------------------------------------------------------------------
-EDS_CT_HD double atan_d(double x) {
+EDS_HD double atan_d(double x) {
     if (!(x == x)) return x;
     const double ATAN_K[9] = {0.0, 0.12435499454676144, 0.24497866312686414, 0.35877067027057225, 0.46364760900080609,
                               0.55859931534356244, 0.64350110879328437, 0.71882999962162453, 0.78539816339744828};
@@ -160,7 +148,7 @@ EDS_CT_HD double atan_d(double x) {
     p = 1.0 / 3.0 - z * p;
     const int k = (int)kf;
     double base = 0.0;
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int q = 0; q < 9; ++q) if (q == k) base = ATAN_K[q];
     double a = base + (r - (r * z) * p);
     if (inv) a = (1.5707963267948966 - a) + 6.123233995736766e-17;
@@ -168,13 +156,13 @@ EDS_CT_UNROLL
 }
 
 // ---- makeK (CoarseTracker.cpp:93-122) -----------------------------------------------------------------------------------------------
-EDS_CT_HD bool shape_valid(int H, int W, int levels) {
+EDS_HD bool shape_valid(int H, int W, int levels) {
     if (levels < 1 || levels > MAX_LEVELS || H < 8 || W < 8 || H > 8192 || W > 8192) return false;
     const int m = 1 << (levels - 1);
     return H % m == 0 && W % m == 0 && (H >> (levels - 1)) >= 8 && (W >> (levels - 1)) >= 8;
 }
 
-EDS_CT_HD void make_shape(Geo& g, int H, int W, int levels) {
+EDS_HD void make_shape(Geo& g, int H, int W, int levels) {
     g.levels = levels; g.W = W; g.H = H;
     int off = 0;
     for (int l = 0; l < MAX_LEVELS; ++l) {
@@ -188,7 +176,7 @@ EDS_CT_HD void make_shape(Geo& g, int H, int W, int levels) {
 
 // fx_l = fx_{l-1} * 0.5 and c_l = (c_0 + 0.5) / 2^l - 0.5 are formed in fp64 from the fp32 operands and narrowed on assignment, as the
 // reference's float members make them; Ki is the closed form of the inverse of an upper-triangular K, in fp32.
-EDS_CT_HD void make_k(Geo& g, float fx, float fy, float cx, float cy) {
+EDS_HD void make_k(Geo& g, float fx, float fy, float cx, float cy) {
     g.l[0].fx = fx; g.l[0].fy = fy; g.l[0].cx = cx; g.l[0].cy = cy;
     for (int l = 1; l < g.levels; ++l) {
         g.l[l].fx = (float)(g.l[l - 1].fx * 0.5);
@@ -202,40 +190,24 @@ EDS_CT_HD void make_k(Geo& g, float fx, float fy, float cx, float cy) {
     }
 }
 
-// ---- makeImages (HessianBlocks.cpp:139-202) -----------------------------------------------------------------------------------------
-EDS_CT_HD float down_at(const Px* lm, int wlm1, int x, int y) {
-    const int b = 2 * x + 2 * y * wlm1;
-    return 0.25f * (((lm[b].c + lm[b + 1].c) + lm[b + wlm1].c) + lm[b + 1 + wlm1].c);
-}
-
-EDS_CT_HD void gradient_at(const Px* p, int w, int h, int i, float* dx_out, float* dy_out) {
-    *dx_out = 0.0f; *dy_out = 0.0f;
-    if (i < w || i >= w * (h - 1)) return;
-    float dx = 0.5f * (p[i + 1].c - p[i - 1].c);
-    float dy = 0.5f * (p[i + w].c - p[i - w].c);
-    if (!finite_f(dx)) dx = 0.0f;
-    if (!finite_f(dy)) dy = 0.0f;
-    *dx_out = dx; *dy_out = dy;
-}
-
 // ---- makeCoarseDepthL0 (CoarseTracker.cpp:126-283) ----------------------------------------------------------------------------------
 // u = (int)(x + 0.5f): truncation towards zero, so -1 < x + 0.5f < 0 is pixel 0.  false: the contribution is dropped.
-EDS_CT_HD bool splat_pixel(float x, float y, int W, int H, int* pix) {
+EDS_HD bool splat_pixel(float x, float y, int W, int H, int* pix) {
     const float xf = x + 0.5f, yf = y + 0.5f;
     if (!(xf > -1.0f && xf < (float)W && yf > -1.0f && yf < (float)H)) return false;
     *pix = (int)xf + W * (int)yf;
     return true;
 }
-EDS_CT_HD float splat_weight(float hdif) { return sqrtf((float)(1e-3 / (hdif + 1e-12))); }
+EDS_HD float splat_weight(float hdif) { return sqrtf((float)(1e-3 / (hdif + 1e-12))); }
 
-EDS_CT_HD float level_sum(const float* lm, int wlm1, int x, int y) {
+EDS_HD float level_sum(const float* lm, int wlm1, int x, int y) {
     const int b = 2 * x + 2 * y * wlm1;
     return ((lm[b] + lm[b + 1]) + lm[b + wlm1]) + lm[b + wlm1 + 1];
 }
 
 // one pixel of the dilation, read from the undilated planes (the reference's _bak): diagonal neighbours at levels 0 and 1, the cross
 // above.  A neighbour index outside 0 .. w h - 1 (the reference reads one element before and after the plane) counts as empty.
-EDS_CT_HD void dilate_at(const float* id_in, const float* ws_in, int w, int h, int lvl, int i, float* id_out, float* ws_out) {
+EDS_HD void dilate_at(const float* id_in, const float* ws_in, int w, int h, int lvl, int i, float* id_out, float* ws_out) {
     float id = id_in[i], ws = ws_in[i];
     if (i >= w && i < w * h - w && ws <= 0) {
         const int off[4] = {lvl < 2 ? 1 + w : 1, lvl < 2 ? -1 - w : -1, lvl < 2 ? w - 1 : w, lvl < 2 ? -w + 1 : -w};
@@ -250,7 +222,7 @@ EDS_CT_HD void dilate_at(const float* id_in, const float* ws_in, int w, int h, i
 }
 
 // the normalisation of one pixel; true: the pixel enters the level's list
-EDS_CT_HD bool normalise_at(int x, int y, int w, int h, float color, float* id, float* ws) {
+EDS_HD bool normalise_at(int x, int y, int w, int h, float color, float* id, float* ws) {
     if (x < 2 || x >= w - 2 || y < 2 || y >= h - 2) return false;
     if (*ws > 0) {
         *id = *id / *ws;
@@ -271,14 +243,14 @@ struct Warp {
 };
 
 // AffLight::fromToVecExposure (NumType.h:175-187)
-EDS_CT_HD void from_to_exposure(const Photo& ph, double a_new, double b_new, double* a, double* b) {
+EDS_HD void from_to_exposure(const Photo& ph, double a_new, double b_new, double* a, double* b) {
     float ef = ph.exposure_ref, et = ph.exposure_new;
     if (ef == 0 || et == 0) { et = 1; ef = 1; }
     *a = exp_d(a_new - ph.ref_a) * et / ef;
     *b = b_new - *a * ph.ref_b;
 }
 
-EDS_CT_HD Warp make_warp(const Level& L, int lvl, const Params& s, const Photo& ph, const double* R, const double* t, double a, double b,
+EDS_HD Warp make_warp(const Level& L, int lvl, const Params& s, const Photo& ph, const double* R, const double* t, double a, double b,
                          float cutoff) {
     Warp w;
     float r[9];
@@ -301,10 +273,10 @@ EDS_CT_HD Warp make_warp(const Level& L, int lvl, const Params& s, const Photo& 
     return w;
 }
 
-EDS_CT_HD float shift_sq(float ku, float kv, float x, float y) { return (ku - x) * (ku - x) + (kv - y) * (kv - y); }
+EDS_HD float shift_sq(float ku, float kv, float x, float y) { return (ku - x) * (ku - x) + (kv - y) * (kv - y); }
 
 // one list entry i of the level whose new-frame pixels are `img`
-EDS_CT_HD Term point_term(const Warp& w, const Px* img, const Pc& p, int i) {
+EDS_HD Term point_term(const Warp& w, const Px* img, const Pc& p, int i) {
     Term o;
     o.in_e = 0; o.warped = 0; o.flow = 0; o.e = 0.0f;
     o.idepth = o.u = o.v = o.dx = o.dy = o.residual = o.weight = o.ref_color = 0.0f;
@@ -330,15 +302,13 @@ EDS_CT_HD Term point_term(const Warp& w, const Px* img, const Pc& p, int i) {
         o.rt1 = shift_sq(Ku, Kv, x, y); o.rt2 = shift_sq(Ku3, Kv3, x, y);
     }
     if (!(Ku > 2 && Kv > 2 && Ku < w.wl3 && Kv < w.hl3 && new_idepth > 0)) return o;
-    // getInterpolatedElement33: ((w11 v11 + w01 v01) + w10 v10) + w00 v00 with w00 = ((1 - dx) - dy) + dxdy
-    const int ix = (int)Ku, iy = (int)Kv;
-    const float dx = Ku - ix, dy = Kv - iy, dxdy = dx * dy;
-    const Px* bp = img + ((size_t)iy * w.w + ix);
+    // getInterpolatedElement33
+    const edsdso::Bilin bw = edsdso::bilin(Ku, Kv);
+    const Px* bp = img + ((size_t)bw.iy * w.w + bw.ix);
     const Px v11 = bp[1 + w.w], v01 = bp[w.w], v10 = bp[1], v00 = bp[0];
-    const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-    const float h0 = w11 * v11.c + w01 * v01.c + w10 * v10.c + w00 * v00.c;
-    const float h1 = w11 * v11.dx + w01 * v01.dx + w10 * v10.dx + w00 * v00.dx;
-    const float h2 = w11 * v11.dy + w01 * v01.dy + w10 * v10.dy + w00 * v00.dy;
+    const float h0 = edsdso::mix(bw, v11.c, v01.c, v10.c, v00.c);
+    const float h1 = edsdso::mix(bw, v11.dx, v01.dx, v10.dx, v00.dx);
+    const float h2 = edsdso::mix(bw, v11.dy, v01.dy, v10.dy, v00.dy);
     if (!finite_f(h0)) return o;
     const float residual = h0 - (w.aff0 * p.color + w.aff1);
     const float ar = fabsf(residual);
@@ -352,7 +322,7 @@ EDS_CT_HD Term point_term(const Warp& w, const Px* img, const Pc& p, int i) {
 }
 
 // rs[0 .. 5] of calcRes from the sums
-EDS_CT_HD void rs_from_sums(double E, int nE, int nSat, double sT, double sRT, int nFlow, double* rs) {
+EDS_HD void rs_from_sums(double E, int nE, int nSat, double sT, double sRT, int nFlow, double* rs) {
     const double num = 2.0 * nFlow;
     rs[0] = E; rs[1] = (double)nE; rs[2] = sT / (num + 0.1); rs[3] = 0.0; rs[4] = sRT / (num + 0.1);
     rs[5] = (double)((float)nSat / (float)nE);
@@ -360,7 +330,7 @@ EDS_CT_HD void rs_from_sums(double E, int nE, int nSat, double sT, double sRT, i
 
 // ---- calcGSSSE (CoarseTracker.cpp:287-344) ------------------------------------------------------------------------------------------
 // J[0 .. 8] as the _mm_* calls nest them (J[7] = -1, J[8] = the residual), and the 45 products (J_a w) J_b, a <= b, row by row
-EDS_CT_HD void jacobian(const Warp& w, const Term& o, float* J) {
+EDS_HD void jacobian(const Warp& w, const Term& o, float* J) {
     const float dx = o.dx * w.fx, dy = o.dy * w.fy, u = o.u, v = o.v, id = o.idepth;
     J[0] = id * dx;
     J[1] = id * dy;
@@ -374,7 +344,7 @@ EDS_CT_HD void jacobian(const Warp& w, const Term& o, float* J) {
 }
 
 // H (8 x 8, row-major) and b from the 45 sums and the number of warped rows; n is padded to a multiple of 4 as the reference's buffer is
-EDS_CT_HD double h_entry(const double* S, int n_warped, int r, int c) {
+EDS_HD double h_entry(const double* S, int n_warped, int r, int c) {
     const int n = (n_warped + 3) & ~3;
     const double inv = (double)(1.0f / (float)n);
     const int a = r < c ? r : c, b = r < c ? c : r;
@@ -388,47 +358,47 @@ EDS_CT_HD double h_entry(const double* S, int n_warped, int r, int c) {
 // unpivoted L D L^T of the leading N x N of the damped system (A's diagonal times `damp`, rhs = -b), then L z = rhs, y = z / d,
 // L^T x = y.  STITCH: row and column 6 are A's row and column 7 and rhs[6] is -b[7] (the fixed-a case's HlStitch).
 template <int N, bool STITCH>
-EDS_CT_HD void ldlt_solve(const double* A, const double* b, double damp, double* x) {
+EDS_HD void ldlt_solve(const double* A, const double* b, double damp, double* x) {
     double L[N][N], d[N], z[N];
 #define EDS_CT_MAP(i) ((STITCH && (i) == 6) ? 7 : (i))
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int j = 0; j < N; ++j) {
         double dj = A[8 * EDS_CT_MAP(j) + EDS_CT_MAP(j)] * damp;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int k = 0; k < j; ++k) dj -= (L[j][k] * L[j][k]) * d[k];
         d[j] = dj;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int i = j + 1; i < N; ++i) {
             double v = A[8 * EDS_CT_MAP(i) + EDS_CT_MAP(j)];
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int k = 0; k < j; ++k) v -= (L[i][k] * L[j][k]) * d[k];
             L[i][j] = v / dj;
         }
     }
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = 0; i < N; ++i) {
         double v = -b[EDS_CT_MAP(i)];
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int k = 0; k < i; ++k) v -= L[i][k] * z[k];
         z[i] = v;
     }
 #undef EDS_CT_MAP
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = 0; i < N; ++i) z[i] = z[i] / d[i];
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = N - 1; i >= 0; --i) {
         double v = z[i];
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int k = i + 1; k < N; ++k) v -= L[k][i] * x[k];
         x[i] = v;
     }
 }
 
 // the increment of one iteration: the damped system in the four affineOptMode cases (CoarseTracker.cpp:579-605)
-EDS_CT_HD void solve_inc(const double* H, const double* b, float lambda, const Params& s, double* inc) {
+EDS_HD void solve_inc(const double* H, const double* b, float lambda, const Params& s, double* inc) {
     double x[8];
     const double damp = (double)(1 + lambda);
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = 0; i < 8; ++i) x[i] = 0.0;
     const bool fix_a = s.affine_opt_mode_a < 0, fix_b = s.affine_opt_mode_b < 0;
     if (fix_a && fix_b) {
@@ -443,14 +413,14 @@ EDS_CT_UNROLL
     } else {
         ldlt_solve<8, false>(H, b, damp, x);
     }
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = 0; i < 8; ++i) inc[i] = x[i];
 }
 
 // ---- SE3::exp(xi) * T (sophus/se3.hpp:406-428, so3.hpp:343-369) ---------------------------------------------------------------------
 // xi = [upsilon, omega].  The pose is carried as R (row-major 3 x 3) and t: the product is R' = Rinc R, t' = Rinc t + V upsilon with
 // Rinc the rotation matrix of the normalised quaternion, every 3-term sum left to right.
-EDS_CT_HD void se3_exp_mul(const double* xi, const double* R, const double* t, double* Rn, double* tn) {
+EDS_HD void se3_exp_mul(const double* xi, const double* R, const double* t, double* Rn, double* tn) {
     const double ox = xi[3], oy = xi[4], oz = xi[5];
     const double theta_sq = (ox * ox + oy * oy) + oz * oz;
     const double theta = sqrt(theta_sq), half = 0.5 * theta;
@@ -475,21 +445,21 @@ EDS_CT_HD void se3_exp_mul(const double* xi, const double* R, const double* t, d
     const double Om[9] = {0.0, -oz, oy, oz, 0.0, -ox, -oy, ox, 0.0};
     double V[9];
     if (small_angle) {
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int i = 0; i < 9; ++i) V[i] = Ri[i];
     } else {
         const double c1 = (1.0 - ct) / theta_sq, c2 = (theta - st) / (theta_sq * theta);
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int i = 0; i < 3; ++i)
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int j = 0; j < 3; ++j) {
                 const double o2 = (Om[3 * i] * Om[j] + Om[3 * i + 1] * Om[3 + j]) + Om[3 * i + 2] * Om[6 + j];
                 V[3 * i + j] = ((i == j ? 1.0 : 0.0) + c1 * Om[3 * i + j]) + c2 * o2;
             }
     }
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = 0; i < 3; ++i) {
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (Ri[3 * i] * R[j] + Ri[3 * i + 1] * R[3 + j]) + Ri[3 * i + 2] * R[6 + j];
         const double rt = (Ri[3 * i] * t[0] + Ri[3 * i + 1] * t[1]) + Ri[3 * i + 2] * t[2];
         const double vu = (V[3 * i] * xi[0] + V[3 * i + 1] * xi[1]) + V[3 * i + 2] * xi[2];
@@ -504,12 +474,12 @@ EDS_CT_UNROLL
 // fabsf(logf(x)) > 1.5 of the final affine check is restated without logf as x > e^1.5 or x < e^-1.5 (fp32 constants), NaN and
 // negative x passing as they do in the reference.
 template <class Ev>
-EDS_CT_HD void track(Ev& ev, const Params& s, const Photo& ph, const double* T_in, const double* aff_in, int coarsest, const double* min_res,
+EDS_HD void track(Ev& ev, const Params& s, const Photo& ph, const double* T_in, const double* aff_in, int coarsest, const double* min_res,
                      TrackOut* out, bool writer) {
     double R[9], t[3], a = aff_in[0], b = aff_in[1];
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = 0; i < 3; ++i) {
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int j = 0; j < 3; ++j) R[3 * i + j] = T_in[4 * i + j];
         t[i] = T_in[4 * i + 3];
     }
@@ -543,7 +513,7 @@ EDS_CT_UNROLL
             float extrap = 1;
             if (lambda < limit) extrap = sqrtf(sqrtf(limit / lambda));
             double sum = 0.0, sq = 0.0;
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int i = 0; i < 8; ++i) {
                 inc[i] = inc[i] * (double)extrap;
                 incs[i] = inc[i] * (i == 6 ? 10.0 : i == 7 ? 1000.0 : 1.0);
@@ -551,7 +521,7 @@ EDS_CT_UNROLL
                 sq += inc[i] * inc[i];
             }
             if (!finite_d(sum)) {
-EDS_CT_UNROLL
+EDS_UNROLL
                 for (int i = 0; i < 8; ++i) incs[i] = 0.0;
             }
             se3_exp_mul(incs, R, t, Rn, tn);
@@ -561,11 +531,11 @@ EDS_CT_UNROLL
             if (writer && nd < MAX_DECISIONS) out->decisions[nd] = (uint8_t)((accept ? 1 : 0) | (lvl << 1));
             ++nd; ++its;
             if (accept) {
-EDS_CT_UNROLL
+EDS_UNROLL
                 for (int i = 0; i < 6; ++i) rs_old[i] = rs_new[i];
-EDS_CT_UNROLL
+EDS_UNROLL
                 for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-EDS_CT_UNROLL
+EDS_UNROLL
                 for (int i = 0; i < 3; ++i) t[i] = tn[i];
                 a = an; b = bn;
                 lambda *= 0.5f;
@@ -591,9 +561,9 @@ EDS_CT_UNROLL
         if (rep > 1 && !have_repeated) { ++lvl; have_repeated = true; }
     }
     if (writer) {
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int i = 0; i < 3; ++i) {
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int j = 0; j < 3; ++j) out->T[4 * i + j] = R[3 * i + j];
             out->T[4 * i + 3] = t[i];
         }
@@ -612,42 +582,14 @@ EDS_CT_UNROLL
     }
 }
 
-#if defined(__HIPCC__)
-// the fold inside 64 lanes on the device (eds_coarse.hip, eds_init.hip): lane 0 of the wavefront holds the total
-__device__ inline double wave_fold(double v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
-__device__ inline int wave_fold_i(int v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
-#endif
-
 #if !defined(__HIP_DEVICE_COMPILE__)
 // ---- the serial side: the same pieces walked in the device's order -------------------------------------------------------------------
-inline double reduce_lanes(double* p) {
-    for (int g = 0; g < GROUPS; ++g)
-        for (int s = WAVE / 2; s >= 1; s >>= 1)
-            for (int t = 0; t < s; ++t) p[g * WAVE + t] += p[g * WAVE + t + s];
-    double r = p[0];
-    for (int g = 1; g < GROUPS; ++g) r += p[g * WAVE];
-    return r;
-}
 
 // a frame's pyramid: px[g.total]
 inline void make_pyramid(const Geo& g, const float* image, int64_t row_stride, Px* px) {
-    for (int l = 0; l < g.levels; ++l) {
-        const Level& L = g.l[l];
-        Px* p = px + L.off;
-        for (int y = 0; y < L.h; ++y)
-            for (int x = 0; x < L.w; ++x) {
-                Px& o = p[x + y * L.w];
-                o.c = l == 0 ? image[(int64_t)y * row_stride + x] : down_at(px + g.l[l - 1].off, g.l[l - 1].w, x, y);
-                o.dx = o.dy = o.pad = 0.0f;
-            }
-        for (int i = 0; i < L.w * L.h; ++i) gradient_at(p, L.w, L.h, i, &p[i].dx, &p[i].dy);
-    }
+    Px* lv[MAX_LEVELS];
+    for (int l = 0; l < g.levels; ++l) lv[l] = px + g.l[l].off;
+    edsdso::make_levels(image, row_stride, g.W, g.H, g.levels, lv);
 }
 
 // makeCoarseDepthL0: idepth[g.total], wsum[g.total], pc[g.total] (a level's list starts at its off), pc_n[levels]; returns the dropped count

@@ -1,6 +1,7 @@
 // What the host code of the DSO-side handles shares (eds_imm, eds_ct, eds_win, eds_sel and the eds_act / eds_wsv / eds_wed states that hang
 // off them): one owner for a handle's device, stream and device memory, the check and upload of caller images, the read-back, and the
-// small argument checks.  Host code only, no kernel; nothing here is part of the ABI.
+// small argument checks.  Host code only; the one kernel pair the handles share, a level of makeImages, is eds_dso_image.hip's and is
+// queued through queue_level below.  Nothing here is part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,8 @@
 
 #include "../../include/eds_hip.h"
 #include "../../include/eds_hip_device.h"
+
+namespace edsdso { struct Px; }
 
 namespace edscapi {
 
@@ -153,6 +156,12 @@ inline int upload_image(const DeviceOwner& o, float* dst, int H, int W, const fl
                                  on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, o.st));
     return EDS_OK;
 }
+
+// eds_dso_image.hip: one level of makeImages (w x h, at `out`) queued into st, nothing waited for: its colours from the dense image `img`
+// (level 0, lm NULL) or from the level below (lm, wlm1 wide), then its gradients.  Two launches of blocks(w * h) workgroups;
+// queue_colours is the first alone, for eds_sel, whose own gradient kernel also writes absSquaredGrad.
+void queue_colours(hipStream_t st, const float* img, const edsdso::Px* lm, int wlm1, edsdso::Px* out, int w, int h);
+void queue_level(hipStream_t st, const float* img, const edsdso::Px* lm, int wlm1, edsdso::Px* out, int w, int h);
 
 // device memory into the caller's, waited for; a NULL dst or no bytes is no work
 inline int read_back(const DeviceOwner& o, void* dst, const void* src, size_t bytes) {

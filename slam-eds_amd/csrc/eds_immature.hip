@@ -68,8 +68,7 @@ __global__ void __launch_bounds__(256) k_imm_construct(Point* __restrict__ pts, 
 __global__ void __launch_bounds__(256) k_imm_filter_rect(const int32_t* __restrict__ uv, const float* __restrict__ type, int n, int x_min, int y_min,
                                                          int x_max, int y_max, int cap, int32_t* __restrict__ out_uv, float* __restrict__ out_type,
                                                          int32_t* __restrict__ n_out) {
-    __shared__ int wcnt[256 / WAVE];
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    __shared__ int s_wave[256 / WAVE];
     int base = 0;
     for (int i0 = 0; i0 < n; i0 += 256) {
         const int i = i0 + (int)threadIdx.x;
@@ -79,15 +78,10 @@ __global__ void __launch_bounds__(256) k_imm_filter_rect(const int32_t* __restri
             u = uv[2 * i]; v = uv[2 * i + 1];
             in = u >= x_min && u <= x_max && v >= y_min && v <= y_max;
         }
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int k = 0; k < 256 / WAVE; ++k) { if (k < wave) before += wcnt[k]; total += wcnt[k]; }
-        const int pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
+        int total;
+        const int pos = base + edsdso::block_rank<256>(in, s_wave, &total);
         if (in && pos < cap) { out_uv[2 * pos] = u; out_uv[2 * pos + 1] = v; out_type[pos] = type[i]; }
         base += total;
-        __syncthreads();
     }
     if (threadIdx.x == 0) *n_out = base;
 }

@@ -8,11 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define EDS_IMM_HD __host__ __device__ inline
-#else
-#define EDS_IMM_HD inline
-#endif
+#include "eds_dso_common.hpp"
 
 namespace edsimm {
 
@@ -52,14 +48,14 @@ struct Pre {                               // one host's hostToFrame_* and the t
 };
 
 // staticPattern[8] (reference settings.cpp:276)
-EDS_IMM_HD int pat_x(int i) { const int t[PATTERN] = {0, -1, 1, -2, 0, 2, -1, 0}; return t[i]; }
-EDS_IMM_HD int pat_y(int i) { const int t[PATTERN] = {-2, -1, -1, 0, 0, 0, 1, 2}; return t[i]; }
+EDS_HD int pat_x(int i) { const int t[PATTERN] = {0, -1, 1, -2, 0, 2, -1, 0}; return t[i]; }
+EDS_HD int pat_y(int i) { const int t[PATTERN] = {-2, -1, -1, 0, 0, 0, 1, 2}; return t[i]; }
 
-EDS_IMM_HD bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }      // false for NaN and +-inf
-EDS_IMM_HD float nan_f() { return __builtin_nanf(""); }
+using edsdso::finite_f;
+using edsdso::nan_f;
 
 // the sample rule of the header: the cell of a VALID sample, or false
-EDS_IMM_HD bool tap_cell(float x, float y, int W, int H, int* ix, int* iy) {
+EDS_HD bool tap_cell(float x, float y, int W, int H, int* ix, int* iy) {
     if (!(fabsf(x) <= 1048576.0f && fabsf(y) <= 1048576.0f)) return false;
     const int a = (int)x, b = (int)y;
     if (a < 0 || b < 0 || a > W - 2 || b > H - 2) return false;
@@ -68,42 +64,37 @@ EDS_IMM_HD bool tap_cell(float x, float y, int W, int H, int* ix, int* iy) {
 }
 
 // makeImages level 0 at flat index i of an H x W colour plane
-EDS_IMM_HD Grad gradient_at(const float* c, int W, int H, int i) {
+EDS_HD Grad gradient_at(const float* c, int W, int H, int i) {
     Grad g = {0.0f, 0.0f};
-    if (i < W || i >= W * (H - 1)) return g;
-    float dx = 0.5f * (c[i + 1] - c[i - 1]);
-    float dy = 0.5f * (c[i + W] - c[i - W]);
-    if (!finite_f(dx)) dx = 0.0f;
-    if (!finite_f(dy)) dy = 0.0f;
-    g.x = dx; g.y = dy;
+    if (edsdso::border_row(W, H, i)) return g;
+    g.x = edsdso::half_diff(c[i + 1], c[i - 1]);
+    g.y = edsdso::half_diff(c[i + W], c[i - W]);
     return g;
 }
 
 // getInterpolatedElement31; NaN for an invalid sample
-EDS_IMM_HD float interp31(const float* c, int W, int H, float x, float y) {
+EDS_HD float interp31(const float* c, int W, int H, float x, float y) {
     int ix, iy;
     if (!tap_cell(x, y, W, H, &ix, &iy)) return nan_f();
-    const float dx = x - ix, dy = y - iy, dxdy = dx * dy;
     const float* bp = c + ((size_t)iy * W + ix);
-    return dxdy * bp[1 + W] + (dy - dxdy) * bp[W] + (dx - dxdy) * bp[1] + (1 - dx - dy + dxdy) * bp[0];
+    return edsdso::mix(edsdso::bilin(x, y), bp[1 + W], bp[W], bp[1], bp[0]);
 }
 
 // getInterpolatedElement33; out[0] = NaN for an invalid sample
-EDS_IMM_HD void interp33(const Frame& f, int W, int H, float x, float y, float out[3]) {
+EDS_HD void interp33(const Frame& f, int W, int H, float x, float y, float out[3]) {
     int ix, iy;
     if (!tap_cell(x, y, W, H, &ix, &iy)) { out[0] = nan_f(); out[1] = 0.0f; out[2] = 0.0f; return; }
-    const float dx = x - ix, dy = y - iy, dxdy = dx * dy;
+    const edsdso::Bilin bw = edsdso::bilin(x, y);
     const size_t o = (size_t)iy * W + ix;
-    const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
     const float* bp = f.c + o;
     const Grad* gp = f.g + o;
-    out[0] = w11 * bp[1 + W] + w01 * bp[W] + w10 * bp[1] + w00 * bp[0];
-    out[1] = w11 * gp[1 + W].x + w01 * gp[W].x + w10 * gp[1].x + w00 * gp[0].x;
-    out[2] = w11 * gp[1 + W].y + w01 * gp[W].y + w10 * gp[1].y + w00 * gp[0].y;
+    out[0] = edsdso::mix(bw, bp[1 + W], bp[W], bp[1], bp[0]);
+    out[1] = edsdso::mix(bw, gp[1 + W].x, gp[W].x, gp[1].x, gp[0].x);
+    out[2] = edsdso::mix(bw, gp[1 + W].y, gp[W].y, gp[1].y, gp[0].y);
 }
 
 // Both constructors (ImmaturePoint.cpp:27-114): has_depth selects the second.
-EDS_IMM_HD void construct(Point& p, const float* c, int W, int H, const Params& s, int u, int v, float type, bool has_depth, float idepth,
+EDS_HD void construct(Point& p, const float* c, int W, int H, const Params& s, int u, int v, float type, bool has_depth, float idepth,
                           double distance) {
     p.u = (float)u; p.v = (float)v; p.type = type;
     p.idepth_min = 0.0f; p.idepth_max = nan_f(); p.status = UNINITIALIZED;
@@ -149,11 +140,11 @@ struct Line {
     int numSteps;
 };
 
-EDS_IMM_HD void set_oob(Point& p, int status) { p.last_u = -1.0f; p.last_v = -1.0f; p.last_interval = 0.0f; p.status = status; }
-EDS_IMM_HD bool inside(float u, float v, int W, int H) { return u > 4 && v > 4 && u < W - 5 && v < H - 5; }
+EDS_HD void set_oob(Point& p, int status) { p.last_u = -1.0f; p.last_v = -1.0f; p.last_interval = 0.0f; p.status = status; }
+EDS_HD bool inside(float u, float v, int W, int H) { return u > 4 && v > 4 && u < W - 5 && v < H - 5; }
 
 // traceOn up to the discrete search (:130-310).  false: the point has its result; true: L describes the search.
-EDS_IMM_HD bool trace_prologue(Point& p, const Params& s, int W, int H, const Pre& m, Line& L) {
+EDS_HD bool trace_prologue(Point& p, const Params& s, int W, int H, const Pre& m, Line& L) {
     if (p.status == OOB) return false;
     const float maxPixSearch = (W + H) * s.max_pix_search;
     const float* K = m.KRKi;
@@ -228,7 +219,7 @@ EDS_IMM_HD bool trace_prologue(Point& p, const Params& s, int W, int H, const Pr
 }
 
 // the energy of one search step at (ptx, pty) (:314-326)
-EDS_IMM_HD float step_energy(const Point& p, const Params& s, const float* c, int W, int H, const Pre& m, const Line& L, float ptx, float pty) {
+EDS_HD float step_energy(const Point& p, const Params& s, const float* c, int W, int H, const Pre& m, const Line& L, float ptx, float pty) {
     float energy = 0;
     for (int idx = 0; idx < PATTERN; ++idx) {
         const float hitColor = interp31(c, W, H, ptx + L.rot[idx][0], pty + L.rot[idx][1]);
@@ -241,12 +232,12 @@ EDS_IMM_HD float step_energy(const Point& p, const Params& s, const float* c, in
 }
 
 // an energy the reference's `energy < bestEnergy` can ever accept (bestEnergy starts at 1e10)
-EDS_IMM_HD bool can_be_best(float e) { return e < 1e10f; }
+EDS_HD bool can_be_best(float e) { return e < 1e10f; }
 // step i counts for the second-best score (:346-350)
-EDS_IMM_HD bool outside_radius(int i, int bestIdx, int radius) { return i < bestIdx - radius || i > bestIdx + radius; }
+EDS_HD bool outside_radius(int i, int bestIdx, int radius) { return i < bestIdx - radius || i > bestIdx + radius; }
 
 // traceOn after the search (:351-467): quality, the Gauss-Newton steps, the outlier test, the new interval
-EDS_IMM_HD void trace_epilogue(Point& p, const Params& s, const Frame& f, int W, int H, const Pre& m, const Line& L, float bestU, float bestV,
+EDS_HD void trace_epilogue(Point& p, const Params& s, const Frame& f, int W, int H, const Pre& m, const Line& L, float bestU, float bestV,
                                float bestEnergy, float secondBest) {
     const float newQuality = secondBest / bestEnergy;
     if (newQuality < p.quality || L.numSteps > 10) p.quality = newQuality;

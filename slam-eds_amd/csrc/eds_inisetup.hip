@@ -33,7 +33,7 @@
 
 using edscapi::fail;
 using edsct::Level;
-using edsct::Px;
+using edsdso::Px;
 using edsini::Pnt;
 
 static_assert(edsini::NN == EDS_INI_NEIGHBOURS && edsini::SPARSITY_START == EDS_INI_SPARSITY_START, "header constants");

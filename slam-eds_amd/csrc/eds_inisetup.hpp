@@ -17,7 +17,7 @@ constexpr int32_t SPARSITY_START = 5;             // settings.cpp:212
 constexpr int32_t SPARSITY_MAX = 1 << 30;         // where the reference's float-to-int conversion would be undefined, the value is this
 
 // H:108-123: false where the pixel is below the gradient threshold; s = |dx|, |dy|, |dx - dy|, |dx + dy|
-EDS_CT_HD bool gms_scores(const Px& g, float THFac, float* s) {
+EDS_HD bool gms_scores(const Px& g, float THFac, float* s) {
     const float sqgd = g.dx * g.dx + g.dy * g.dy;
     const float TH = (THFac * 10.0f) * 0.75f;
     if (!(sqgd > TH * TH)) return false;
@@ -26,10 +26,10 @@ EDS_CT_HD bool gms_scores(const Px& g, float THFac, float* s) {
 }
 
 // the cells of one axis: x = 1, 1 + pot, ... while x < w - pot (H:91-93)
-EDS_CT_HD int gms_cells(int w, int pot) { return w - pot > 1 ? (w - pot - 2) / pot + 1 : 0; }
+EDS_HD int gms_cells(int w, int pot) { return w - pot > 1 ? (w - pot - 2) / pot + 1 : 0; }
 
 // candidate (s, rank) against the held (bs, brank): the larger score, then the smaller rank; rank < 0 is "none", whose score is 0
-EDS_CT_HD bool gms_better(float s, int rank, float bs, int brank) { return s > bs || (s == bs && rank >= 0 && brank >= 0 && rank < brank); }
+EDS_HD bool gms_better(float s, int rank, float bs, int brank) { return s > bs || (s == bs && rank >= 0 && brank >= 0 && rank < brank); }
 
 // gridMaxSelection (H:84-240; the templates 1 .. 11 and the generic form compute the same): map is w x h bytes, 0 / 1
 inline int grid_max_selection(const Px* grads, uint8_t* map, int w, int h, int pot, float THFac) {

@@ -22,7 +22,7 @@
 using edscapi::fail;
 using edsct::Geo;
 using edsct::Level;
-using edsct::Px;
+using edsdso::Px;
 using edsini::Carry;
 using edsini::Frame;
 using edsini::Lv;
@@ -42,7 +42,7 @@ static_assert(edsini::MAX_DECISIONS == EDS_INI_MAX_DECISIONS && edsini::MAX_LEVE
 
 namespace {
 
-constexpr int LANES = edsct::LANES;
+using edsdso::LANES;
 
 // the evaluator of eds_init.hpp's templates on the device
 struct DevEv {
@@ -88,13 +88,12 @@ struct DevEv {
         for (int i = threadIdx.x; i < n; i += LANES) f(i, acc);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-            const double v = edsct::wave_fold(acc[q]);
+            const double v = edsdso::wave_fold(acc[q]);
             if (lane == 0) part[8 * q + wave] = v;
         }
         __syncthreads();
         if ((int)threadIdx.x < NQ) {
-            const double* p = part + 8 * threadIdx.x;
-            S[threadIdx.x] = ((((((p[0] + p[1]) + p[2]) + p[3]) + p[4]) + p[5]) + p[6]) + p[7];
+            S[threadIdx.x] = edsdso::add8(part + 8 * threadIdx.x);
         }
         __syncthreads();
     }
@@ -106,26 +105,20 @@ __global__ void __launch_bounds__(LANES) k_ini_pyramid(Geo g, const float* __res
     edsini::build_pyramid(ev, g, img, px);
 }
 
-// one level's points: the rectangle in row-major order, 512 pixels a trip; a selected pixel's place is the count before its trip, plus the
-// wavefronts before its own (LDS), plus the set bits of the ballot below its lane.  Places past `cap` are counted and not written.
+// one level's points: the rectangle in row-major order, 512 pixels a trip; a selected pixel's place is the count before its trip plus
+// its rank in the trip (block_rank).  Places past `cap` are counted and not written.
 template <class T>
 __global__ void __launch_bounds__(LANES) k_ini_points(const T* __restrict__ status, int w, int h, Params s, Pnt* __restrict__ out, int cap,
                                                       int32_t* __restrict__ count) {
-    __shared__ int wcnt[LANES / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_wave[LANES / 64];
     int base = 0;
     for (int start = 0; start < w * h; start += LANES) {
         const int i = start + threadIdx.x, x = i % w, y = i / w;
         const bool sel = i < w * h && edsini::in_rect(x, y, w, h) && status[i] != 0;
-        const unsigned long long m = __ballot(sel);
-        if (lane == 0) wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int k = 0; k < LANES / 64; ++k) { if (k < wave) before += wcnt[k]; total += wcnt[k]; }
-        const int at = base + before + __popcll(m & ((1ull << lane) - 1ull));
+        int total;
+        const int at = base + edsdso::block_rank<LANES>(sel, s_wave, &total);
         if (sel && at < cap) out[at] = edsini::make_point(x, y, (float)status[i], s);
         base += total;
-        __syncthreads();
     }
     if (threadIdx.x == 0) *count = base;
 }

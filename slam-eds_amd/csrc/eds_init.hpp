@@ -2,13 +2,13 @@
 // per-tap term of calcResAndGS with its Jacobian buffer row, doStep, applyStep, optReg, resetPoints, propagateDown / propagateUp, calcEC,
 // the damped loop of trackFrame and SE3::log's translation part — written ONCE over an EVALUATOR that supplies three things: a loop over
 // the points of a level (each), a loop over a level's dependency schedule, depth by depth (each_sched), and the lane-strided fp64 sums
-// (reduce).  SerialEv walks the device's order on the host; eds_init.hip's evaluator is one workgroup of edsct::LANES lanes.  fp32 per tap
+// (reduce).  SerialEv walks the device's order on the host; eds_init.hip's evaluator is one workgroup of edsdso::LANES lanes.  fp32 per tap
 // and per point in the reference's order (src/init/CoarseInitializer.cpp, lines quoted as :n), fp64 sums in the order stated at the top
-// of eds_coarse.hpp; every translation unit that includes this is built without contraction into FMAs.  Plain C++ outside hipcc.
+// of eds_dso_common.hpp; every translation unit that includes this is built without contraction into FMAs.  Plain C++ outside hipcc.
 //
 // THE SUMS.  Lane t adds, in fp64 and starting from 0.0, the terms of points t, t + 512, ... in that order; a point's terms are added
 // one by one (for acc9: tap 0's 45 products row by row, then tap 1's, ...; the point's addend to E after them in slot 45).  The fold and
-// the left-to-right addition of the eight group totals are edsct's.  Results are cast to float where the reference holds one.
+// the left-to-right addition of the eight group totals are edsdso's.  Results are cast to float where the reference holds one.
 //
 // THE THREE ORDER DEPENDENCIES.  optReg (:564-585), resetPoints at the top level (:785-800) and propagateUp's += (:609-617) read what
 // earlier iterations of the same loop wrote.  For the first two the level carries a schedule: depth[i] = 1 + max(depth[j] : j a
@@ -24,9 +24,9 @@
 namespace edsini {
 
 using edsct::Geo;
-using edsct::LANES;
 using edsct::Level;
-using edsct::Px;
+using edsdso::LANES;
+using edsdso::Px;
 
 constexpr int MAX_LEVELS = edsct::MAX_LEVELS;
 constexpr int NN = 10;                            // neighbours per point
@@ -88,14 +88,14 @@ struct Sys { float H[64], b[8], Hsc[64], bsc[8], res[3], pad; };
 // the uniform state of one trackFrame (LDS on the device): two systems and two poses (current and tried), the increment, the sums
 struct Shared { Sys sys[2]; double R[2][9], t[2][3], ab[2][2]; float inc[8]; double S[46]; };
 
-EDS_CT_HD Params params_default() {
+EDS_HD Params params_default() {
     Params p = {9.0f, 144.0f, 6.25f, 22500.0f, 0.8f, 1.0f, 1, {5, 5, 10, 30, 50}, 1.0f, 1.0f, 10.0f, 1000.0f};
     return p;
 }
-EDS_CT_HD bool params_valid(const Params& p) {
+EDS_HD bool params_valid(const Params& p) {
     const float f[10] = {p.huber_th, p.outlier_th, p.alpha_k, p.alpha_w, p.reg_weight, p.coupling_weight, p.scale_xi_rot, p.scale_xi_trans,
                          p.scale_a, p.scale_b};
-    for (int i = 0; i < 10; ++i) if (!edsct::finite_f(f[i])) return false;
+    for (int i = 0; i < 10; ++i) if (!edsdso::finite_f(f[i])) return false;
     for (int i = 0; i < MAX_LEVELS; ++i) if (p.max_iterations[i] < 0 || p.max_iterations[i] > MAX_ITERATIONS) return false;
     return p.huber_th > 0.0f && p.outlier_th > 0.0f && p.scale_xi_rot > 0.0f && p.scale_xi_trans > 0.0f && p.scale_a > 0.0f &&
            p.scale_b > 0.0f && (p.fix_affine == 0 || p.fix_affine == 1);
@@ -105,7 +105,7 @@ EDS_CT_HD bool params_valid(const Params& p) {
 // edsct keeps R, not a quaternion: the quaternion is Eigen's from a rotation matrix (trace > 0: s = sqrt(trace + 1), w = s / 2, the
 // vector part the antisymmetric differences times 1 / (2 s); otherwise the branch of the largest diagonal entry).  logAndTheta's three
 // cases are restated (n < 1e-10; |w| < 1e-10; 2 atan(n / w) / n), and tan(theta / 2) of V^-1 is sin / cos of edsct::sincos_d.
-EDS_CT_HD void se3_log_upsilon(const double* R, const double* t, double* ups) {
+EDS_HD void se3_log_upsilon(const double* R, const double* t, double* ups) {
     double q[3], qw;
     const double tr = (R[0] + R[4]) + R[8];
     if (tr > 0.0) {
@@ -122,7 +122,7 @@ EDS_CT_HD void se3_log_upsilon(const double* R, const double* t, double* ups) {
         s = 0.5 / s;
         qw = (R[3 * k + j] - R[3 * j + k]) * s;
         const double vj = (R[3 * j + i] + R[3 * i + j]) * s, vk = (R[3 * k + i] + R[3 * i + k]) * s;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int m = 0; m < 3; ++m) qq[m] = m == i ? h : m == j ? vj : vk;
         q[0] = qq[0]; q[1] = qq[1]; q[2] = qq[2];
     }
@@ -140,10 +140,10 @@ EDS_CT_UNROLL
         edsct::sincos_d(theta / 2.0, &sh, &ch);
         c2 = (1.0 - theta / (2.0 * (sh / ch))) / (theta * theta);
     }
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int i = 0; i < 3; ++i) {
         double row[3];
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int j = 0; j < 3; ++j) {
             const double o2 = (Om[3 * i] * Om[j] + Om[3 * i + 1] * Om[3 + j]) + Om[3 * i + 2] * Om[6 + j];
             row[j] = ((i == j ? 1.0 : 0.0) - 0.5 * Om[3 * i + j]) + c2 * o2;
@@ -154,8 +154,8 @@ EDS_CT_UNROLL
 
 // ---- setFirst: one point (:725-749) ---------------------------------------------------------------------------------------------------
 // the rectangle of :718-719
-EDS_CT_HD bool in_rect(int x, int y, int w, int h) { return x >= 3 && x < w - 4 && y >= 3 && y < h - 4; }
-EDS_CT_HD Pnt make_point(int x, int y, float type, const Params& s) {
+EDS_HD bool in_rect(int x, int y, int w, int h) { return x >= 3 && x < w - 4 && y >= 3 && y < h - 4; }
+EDS_HD Pnt make_point(int x, int y, float type, const Params& s) {
     Pnt p;
     p.u = (float)(x + 0.1); p.v = (float)(y + 0.1);
     p.idepth = 1.0f; p.idepth_new = 1.0f; p.iR = 1.0f;
@@ -171,7 +171,7 @@ struct Warp { float RKi[9], t[3], a, b, fx, fy, cx, cy, huber, wl2, hl2; int32_t
 
 // Ki is the closed form of the inverse of an upper-triangular K in fp64 (the reference inverts the fp64 K with Eigen); cx of a level is
 // the fp64 value makeK forms, not its fp32 narrowing; R Ki is summed left to right in fp64 and then narrowed, as :275 does
-EDS_CT_HD Warp make_warp(const Geo& g, int lvl, const Params& s, const double* R, const double* t, double a, double b) {
+EDS_HD Warp make_warp(const Geo& g, int lvl, const Params& s, const double* R, const double* t, double a, double b) {
     const Level& L = g.l[lvl];
     Warp w;
     const double fx = (double)L.fx, fy = (double)L.fy;
@@ -192,18 +192,17 @@ EDS_CT_HD Warp make_warp(const Geo& g, int lvl, const Params& s, const double* R
     return w;
 }
 
-EDS_CT_HD float interp_c(const Px* img, float x, float y, int w) {
-    const int ix = (int)x, iy = (int)y;
-    const float dx = x - ix, dy = y - iy, dxdy = dx * dy;
-    const Px* bp = img + ((size_t)iy * w + ix);
-    return dxdy * bp[1 + w].c + (dy - dxdy) * bp[w].c + (dx - dxdy) * bp[1].c + (1 - dx - dy + dxdy) * bp[0].c;
+EDS_HD float interp_c(const Px* img, float x, float y, int w) {
+    const edsdso::Bilin bw = edsdso::bilin(x, y);
+    const Px* bp = img + ((size_t)bw.iy * w + bw.ix);
+    return edsdso::mix(bw, bp[1 + w].c, bp[w].c, bp[1].c, bp[0].c);
 }
 
-EDS_CT_HD int sum_index(int a, int b) { return a * 9 - a * (a - 1) / 2 + (b - a); }     // (a, b), a <= b, of the 45
+EDS_HD int sum_index(int a, int b) { return a * 9 - a * (a - 1) / 2 + (b - a); }     // (a, b), a <= b, of the 45
 
 // one point of the first loop (:292-428): its state, its JbBuffer_new row (before the alphaOpt terms), its 45 x 8 products and its
 // addend to E (slot 45).  A tap that fails ends the point as the reference's break does: later taps change nothing.
-EDS_CT_HD void point_calc(const Warp& w, const Px* ref, const Px* nw, Pnt& p, float* jb, double* acc, float* taps = nullptr) {
+EDS_HD void point_calc(const Warp& w, const Px* ref, const Px* nw, Pnt& p, float* jb, double* acc, float* taps = nullptr) {
     p.maxstep = 1e10f;
     if (!p.isGood) {
         acc[45] += (double)p.energy[0];
@@ -217,7 +216,7 @@ EDS_CT_HD void point_calc(const Warp& w, const Px* ref, const Px* nw, Pnt& p, fl
     bool good = true;
     float energy = 0, pmax = 1e10f;
     const float id = p.idepth_new;
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int k = 0; k < TAPS; ++k) {
         if (!good) continue;
         const float x = p.u + PX[k], y = p.v + PY[k];
@@ -228,16 +227,14 @@ EDS_CT_UNROLL
         const float Ku = w.fx * u + w.cx, Kv = w.fy * v + w.cy;
         const float new_idepth = id / pt2;
         if (!(Ku > 1 && Kv > 1 && Ku < w.wl2 && Kv < w.hl2 && new_idepth > 0)) { good = false; continue; }
-        const int ix = (int)Ku, iy = (int)Kv;
-        const float dx = Ku - ix, dy = Kv - iy, dxdy = dx * dy;
-        const Px* bp = nw + ((size_t)iy * w.w + ix);
+        const edsdso::Bilin bw = edsdso::bilin(Ku, Kv);
+        const Px* bp = nw + ((size_t)bw.iy * w.w + bw.ix);
         const Px v11 = bp[1 + w.w], v01 = bp[w.w], v10 = bp[1], v00 = bp[0];
-        const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-        const float h0 = w11 * v11.c + w01 * v01.c + w10 * v10.c + w00 * v00.c;
-        const float h1 = w11 * v11.dx + w01 * v01.dx + w10 * v10.dx + w00 * v00.dx;
-        const float h2 = w11 * v11.dy + w01 * v01.dy + w10 * v10.dy + w00 * v00.dy;
+        const float h0 = edsdso::mix(bw, v11.c, v01.c, v10.c, v00.c);
+        const float h1 = edsdso::mix(bw, v11.dx, v01.dx, v10.dx, v00.dx);
+        const float h2 = edsdso::mix(bw, v11.dy, v01.dy, v10.dy, v00.dy);
         const float rlR = interp_c(ref, x, y, w.w);
-        if (!edsct::finite_f(rlR) || !edsct::finite_f(h0)) { good = false; continue; }
+        if (!edsdso::finite_f(rlR) || !edsdso::finite_f(h0)) { good = false; continue; }
         const float residual = h0 - w.a * rlR - w.b;
         float hw = fabsf(residual) < w.huber ? 1 : w.huber / fabsf(residual);
         if (taps) { taps[2 * k] = residual; taps[2 * k + 1] = hw; }          // the host's tests read them; the device passes none
@@ -258,12 +255,12 @@ EDS_CT_UNROLL
         const float sx = dxdd * w.fx, sy = dydd * w.fy;
         const float maxstep = 1.0f / sqrtf(sx * sx + sy * sy);
         if (maxstep < pmax) pmax = maxstep;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int q = 0; q < 9; ++q) row[q] += J[q][k] * dd;
         row[9] += dd * dd;
     }
     p.maxstep = pmax;
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int q = 0; q < 10; ++q) jb[q] = row[q];
     if (!good || energy > p.outlierTH * 20) {
         acc[45] += (double)p.energy[0];
@@ -273,12 +270,12 @@ EDS_CT_UNROLL
     }
     p.isGood_new = 1;
     p.energy_new[0] = energy;
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int k = 0; k < TAPS; ++k) {
         int q = 0;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int a = 0; a < 9; ++a)
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int b = a; b < 9; ++b) { acc[q] += (double)(J[a][k] * J[b][k]); ++q; }
     }
     acc[45] += (double)energy;
@@ -286,7 +283,7 @@ EDS_CT_UNROLL
 
 // one point of the third loop (:474-496), with the second loop's energy_new[1] (:450): the alphaOpt and coupling terms of the row,
 // 1 / (1 + x), and the 45 weighted products of updateSingleWeighted ((Ja Ja) w on the diagonal, Jb (Ja w) beside it)
-EDS_CT_HD void point_sc(Pnt& p, float* r, float alphaOpt, float coupling, double* acc) {
+EDS_HD void point_sc(Pnt& p, float* r, float alphaOpt, float coupling, double* acc) {
     if (!p.isGood_new) return;
     p.energy_new[1] = (p.idepth_new - 1) * (p.idepth_new - 1);
     p.lastHessian_new = r[9];
@@ -298,22 +295,22 @@ EDS_CT_HD void point_sc(Pnt& p, float* r, float alphaOpt, float coupling, double
     }
     r[9] = 1 / (1 + r[9]);
     float J[9];
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int a = 0; a < 9; ++a) J[a] = r[a];
     const float wgt = r[9];
     int q = 0;
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int a = 0; a < 9; ++a) {
         acc[q] += (double)(J[a] * J[a] * wgt); ++q;
         const float jw = J[a] * wgt;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int b = a + 1; b < 9; ++b) { acc[q] += (double)(J[b] * jw); ++q; }
     }
 }
 
 // the whole of calcResAndGS at pose `which` into sys[which]; jb: the level's JbBuffer_new
 template <class Ev>
-EDS_CT_HD void calc(Ev& ev, const Frame& f, Shared* sh, int lvl, int which, float* jb) {
+EDS_HD void calc(Ev& ev, const Frame& f, Shared* sh, int lvl, int which, float* jb) {
     const Lv& L = f.lv[lvl];
     const int n = L.n;
     const Px *ref = f.ref + f.g.l[lvl].off, *nw = f.nw + f.g.l[lvl].off;
@@ -353,7 +350,7 @@ EDS_CT_HD void calc(Ev& ev, const Frame& f, Shared* sh, int lvl, int which, floa
 
 // ---- calcEC (:531-551): old and new coupling energy and the number of terms, into out[3] -------------------------------------------------
 template <class Ev>
-EDS_CT_HD void calc_ec(Ev& ev, const Frame& f, Shared* sh, int lvl, int snapped, float* out) {
+EDS_HD void calc_ec(Ev& ev, const Frame& f, Shared* sh, int lvl, int snapped, float* out) {
     const Lv& L = f.lv[lvl];
     if (!snapped) { out[0] = 0; out[1] = 0; out[2] = (float)L.n; return; }
     ev.template reduce<3>(L.n, sh->S, [&](int i, double* acc) {
@@ -367,12 +364,12 @@ EDS_CT_HD void calc_ec(Ev& ev, const Frame& f, Shared* sh, int lvl, int snapped,
 
 // ---- optReg (:552-587) -------------------------------------------------------------------------------------------------------------------
 // the nnn / 2-th smallest of v[0 .. nnn) by counting ranks: no array is permuted and every index is a constant
-EDS_CT_HD float nth_smallest(const float* v, int nnn, int k) {
+EDS_HD float nth_smallest(const float* v, int nnn, int k) {
     float r = 0.0f;
-EDS_CT_UNROLL
+EDS_UNROLL
     for (int a = 0; a < NN; ++a) {
         int rank = 0;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int b = 0; b < NN; ++b) rank += (b < nnn && (v[b] < v[a] || (v[b] == v[a] && b < a))) ? 1 : 0;
         if (a < nnn && rank == k) r = v[a];
     }
@@ -380,7 +377,7 @@ EDS_CT_UNROLL
 }
 
 template <class Ev>
-EDS_CT_HD void opt_reg(Ev& ev, const Frame& f, int lvl, int snapped) {
+EDS_HD void opt_reg(Ev& ev, const Frame& f, int lvl, int snapped) {
     const Lv& L = f.lv[lvl];
     if (!snapped) {
         ev.each(L.n, [&](int i) { L.p[i].iR = 1; });
@@ -394,7 +391,7 @@ EDS_CT_HD void opt_reg(Ev& ev, const Frame& f, int lvl, int snapped) {
         Pnt& p = L.p[i];
         int32_t good[NN];
         float live[NN], snap[NN];
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int j = 0; j < NN; ++j) {
             const int o = row[j] < 0 ? i : row[j];
             good[j] = L.p[o].isGood; live[j] = L.p[o].iR; snap[j] = old[o];
@@ -402,11 +399,11 @@ EDS_CT_UNROLL
         if (!p.isGood) return;
         float idnn[NN] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         int nnn = 0;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int j = 0; j < NN; ++j) {
             if (row[j] == -1 || !good[j]) continue;
             const float val = row[j] < i ? live[j] : snap[j];
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int q = 0; q < NN; ++q) if (q == nnn) idnn[q] = val;
             ++nnn;
         }
@@ -416,7 +413,7 @@ EDS_CT_UNROLL
 
 // ---- resetPoints (:775-802) --------------------------------------------------------------------------------------------------------------
 template <class Ev>
-EDS_CT_HD void reset_points(Ev& ev, const Frame& f, int lvl) {
+EDS_HD void reset_points(Ev& ev, const Frame& f, int lvl) {
     const Lv& L = f.lv[lvl];
     float* old = f.iR_old;
     int32_t* gold = f.good_old;
@@ -431,7 +428,7 @@ EDS_CT_HD void reset_points(Ev& ev, const Frame& f, int lvl) {
         Pnt& p = L.p[i];
         int32_t good[NN];
         float val[NN];
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int j = 0; j < NN; ++j) {
             const int o = row[j] < 0 ? i : row[j];
             const int32_t gl = L.p[o].isGood, gs = gold[o];
@@ -440,7 +437,7 @@ EDS_CT_UNROLL
         }
         if (p.isGood) return;
         float snd = 0, sn = 0;
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int j = 0; j < NN; ++j) {
             if (row[j] == -1 || !good[j]) continue;
             snd += val[j];
@@ -455,7 +452,7 @@ EDS_CT_UNROLL
 
 // ---- propagateDown (:632-660), propagateUp (:591-630) --------------------------------------------------------------------------------------
 template <class Ev>
-EDS_CT_HD void propagate_down(Ev& ev, const Frame& f, int src, int snapped) {
+EDS_HD void propagate_down(Ev& ev, const Frame& f, int src, int snapped) {
     const Lv &S = f.lv[src], &T = f.lv[src - 1];
     ev.each(T.n, [&](int i) {
         Pnt& p = T.p[i];
@@ -474,7 +471,7 @@ EDS_CT_HD void propagate_down(Ev& ev, const Frame& f, int src, int snapped) {
 }
 
 template <class Ev>
-EDS_CT_HD void propagate_up(Ev& ev, const Frame& f, int src, int snapped) {
+EDS_HD void propagate_up(Ev& ev, const Frame& f, int src, int snapped) {
     const Lv &S = f.lv[src], &T = f.lv[src + 1];
     ev.each(T.n, [&](int i) {
         Pnt& par = T.p[i];
@@ -497,14 +494,14 @@ EDS_CT_HD void propagate_up(Ev& ev, const Frame& f, int src, int snapped) {
 // ---- doStep (:804-832), applyStep (:834-851) ---------------------------------------------------------------------------------------------
 // the dot product of :816 is summed left to right
 template <class Ev>
-EDS_CT_HD void do_step(Ev& ev, const Frame& f, int lvl, float lambda, const float* inc, const float* jb) {
+EDS_HD void do_step(Ev& ev, const Frame& f, int lvl, float lambda, const float* inc, const float* jb) {
     const Lv& L = f.lv[lvl];
     ev.each(L.n, [&](int i) {
         Pnt& p = L.p[i];
         if (!p.isGood) return;
         const float* r = jb + (size_t)i * 10;
         float dot = r[0] * inc[0];
-EDS_CT_UNROLL
+EDS_UNROLL
         for (int q = 1; q < 8; ++q) dot += r[q] * inc[q];
         const float b = r[8] + dot;
         float step = -b * r[9] / (1 + lambda);
@@ -520,7 +517,7 @@ EDS_CT_UNROLL
 }
 
 template <class Ev>
-EDS_CT_HD void apply_step(Ev& ev, const Frame& f, int lvl) {
+EDS_HD void apply_step(Ev& ev, const Frame& f, int lvl) {
     const Lv& L = f.lv[lvl];
     ev.each(L.n, [&](int i) {
         Pnt& p = L.p[i];
@@ -532,23 +529,18 @@ EDS_CT_HD void apply_step(Ev& ev, const Frame& f, int lvl) {
     });
 }
 
-// ---- a frame's pyramid (edsct's down_at and gradient_at) -----------------------------------------------------------------------------------
+// ---- a frame's pyramid (edsdso's level_pixel and gradient_at) -----------------------------------------------------------------------------------
 template <class Ev>
-EDS_CT_HD void build_pyramid(Ev& ev, const Geo& g, const float* img, Px* px) {
+EDS_HD void build_pyramid(Ev& ev, const Geo& g, const float* img, Px* px) {
     for (int l = 0; l < g.levels; ++l) {
         const Level L = g.l[l];
         Px* p = px + L.off;
-        const Px* lm = l ? px + g.l[l - 1].off : px;
+        const Px* lm = l ? px + g.l[l - 1].off : nullptr;
         const int wlm1 = l ? g.l[l - 1].w : 0;
-        ev.each(L.w * L.h, [&](int i) {
-            Px o;
-            o.c = l == 0 ? img[i] : edsct::down_at(lm, wlm1, i % L.w, i / L.w);
-            o.dx = 0.0f; o.dy = 0.0f; o.pad = 0.0f;
-            p[i] = o;
-        });
+        ev.each(L.w * L.h, [&](int i) { p[i] = edsdso::level_pixel(img, lm, wlm1, L.w, i); });
         ev.each(L.w * L.h, [&](int i) {
             float dx, dy;
-            edsct::gradient_at(p, L.w, L.h, i, &dx, &dy);
+            edsdso::gradient_at(p, L.w, L.h, i, &dx, &dy);
             p[i].dx = dx; p[i].dy = dy;
         });
     }
@@ -557,7 +549,7 @@ EDS_CT_HD void build_pyramid(Ev& ev, const Geo& g, const float* img, Px* px) {
 // ---- the damped system and its solve (:148-164) ----------------------------------------------------------------------------------------------
 // fp32 in the reference's order up to Hl and bl; the solve is edsct's unpivoted fp64 L D L^T of the widened system, its solution narrowed
 // to float before wM multiplies it (the reference: Eigen's pivoted fp32 ldlt)
-EDS_CT_HD void solve_inc(const Sys& y, const Params& s, float lambda, int wh, float* inc) {
+EDS_HD void solve_inc(const Sys& y, const Params& s, float lambda, int wh, float* inc) {
     const float wM[8] = {s.scale_xi_rot, s.scale_xi_rot, s.scale_xi_rot, s.scale_xi_trans, s.scale_xi_trans, s.scale_xi_trans, s.scale_a, s.scale_b};
     const float k = 1 / (1 + lambda), sc = 0.01f / wh;
     double A[64], bb[8], x[8];
@@ -579,7 +571,7 @@ EDS_CT_HD void solve_inc(const Sys& y, const Params& s, float lambda, int wh, fl
 // ---- trackFrame (:75-262) --------------------------------------------------------------------------------------------------------------------
 // Every caller of one evaluator runs this on the same values; the writer (lane 0, or the host) alone stores the uniform state.
 template <class Ev>
-EDS_CT_HD void track_frame(Ev& ev, const Frame& f, Shared* sh, Carry* carry, Result* out) {
+EDS_HD void track_frame(Ev& ev, const Frame& f, Shared* sh, Carry* carry, Result* out) {
     const Params& s = f.s;
     const int levels = f.g.levels;
     int snapped = carry->snapped, frame_id = carry->frame_id, snapped_at = carry->snapped_at;
@@ -628,7 +620,7 @@ EDS_CT_HD void track_frame(Ev& ev, const Frame& f, Shared* sh, Carry* carry, Res
             }
             ev.sync();
             float inc[8];
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int i = 0; i < 8; ++i) inc[i] = sh->inc[i];
             do_step(ev, f, lvl, lambda, inc, L.jb + (size_t)((jbm >> lvl) & 1) * L.cap * 10);
             calc(ev, f, sh, lvl, nxt, L.jb + (size_t)(1 - ((jbm >> lvl) & 1)) * L.cap * 10);
@@ -657,7 +649,7 @@ EDS_CT_UNROLL
                 if (lambda > 10000) lambda = 10000;
             }
             float nrm = 0;
-EDS_CT_UNROLL
+EDS_UNROLL
             for (int i = 0; i < 8; ++i) nrm += inc[i] * inc[i];
             nrm = sqrtf(nrm);
             if (!(nrm > eps) || iteration >= s.max_iterations[lvl] || fails >= 2) break;
@@ -786,7 +778,7 @@ struct SerialEv {
             f(i, acc);
             for (int q = 0; q < NQ; ++q) part[q][i % LANES] = acc[q];
         }
-        for (int q = 0; q < NQ; ++q) S[q] = edsct::reduce_lanes(part[q]);
+        for (int q = 0; q < NQ; ++q) S[q] = edsdso::reduce_lanes(part[q]);
     }
 };
 #endif

@@ -18,7 +18,7 @@ struct eds_ini {
     int32_t n[edsini::MAX_LEVELS] = {0, 0, 0, 0, 0}, nd[edsini::MAX_LEVELS] = {0, 0, 0, 0, 0};
     float exposure_first = 1.0f;
     edsini::Carry carry;                                   // the host's copy of what the device hands from frame to frame
-    edsct::Px *first_px = nullptr, *new_px = nullptr;      // [geo.total]
+    edsdso::Px *first_px = nullptr, *new_px = nullptr;      // [geo.total]
     float *in_img = nullptr, *in_status = nullptr;         // [H * W]
     edsini::Pnt* pts = nullptr;                            // [levels][cap]
     int32_t *sched = nullptr, *parent = nullptr, *doff = nullptr, *coff = nullptr, *child = nullptr;

@@ -95,20 +95,6 @@ struct DepthArgs {
     double T[12 * edsmap::MAX_FRAMES];
 };
 
-// the rank of this lane's kept point among the workgroup's, and the workgroup's total; every lane of the workgroup calls it
-__device__ __forceinline__ int block_rank(bool keep, int* s_wave, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < CT / 64; ++w) { const int n = s_wave[w]; before += w < wave ? n : 0; sum += n; }
-    __syncthreads();                                            // s_wave is written again by the next sweep
-    *total = sum;
-    return before + __popcll(m & ((1ull << lane) - 1ull));
-}
-
 // map b = blockIdx.x: par + 16 b holds T_dst_w (12) and K_dst (4); n_out[b], and xy / idp / src from b * stride
 __global__ __launch_bounds__(CT) void k_map_depth(DepthArgs a, const edswin::Point* __restrict__ pts, const float* __restrict__ ids,
                                                   const double* __restrict__ par, int* __restrict__ n_out, double* __restrict__ xy,
@@ -135,7 +121,7 @@ __global__ __launch_bounds__(CT) void k_map_depth(DepthArgs a, const edswin::Poi
                 keep = edsmap::project(s_par + 12, a.dW, a.dH, d, &px, &py, &ip);
             }
             int total;
-            const int rank = block_rank(keep, s_wave, &total);
+            const int rank = edsdso::block_rank<CT>(keep, s_wave, &total);
             if (keep) {
                 const size_t dst = ob + (size_t)(run + rank);
                 xy[2 * dst] = px; xy[2 * dst + 1] = py;
@@ -199,7 +185,7 @@ __global__ __launch_bounds__(CT) void k_map_immature(ImmArgs a, const edsimm::Po
                 u = row[p].u; v = row[p].v; st = row[p].status;
             }
             int total;
-            const int rank = block_rank(keep, s_wave, &total);
+            const int rank = edsdso::block_rank<CT>(keep, s_wave, &total);
             if (keep) {
                 const size_t q0 = (size_t)(run + rank) * a.fan;
                 double col[4];

@@ -9,11 +9,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define EDS_MAP_HD __host__ __device__ inline
-#else
-#define EDS_MAP_HD inline
-#endif
+#include "eds_dso_common.hpp"
 
 namespace edsmap {
 
@@ -29,11 +25,11 @@ struct Calib { float fx, fy, cx, cy; };                         // hcalib->fxl()
 struct Runs { int32_t first[MAX_FRAMES + 1]; };
 
 // getMap's eight points (:55-84): the centre, then (0,+2) (-1,+1) (-2,0) (-1,-1) (0,-2) (+1,-1) (+2,0)
-EDS_MAP_HD int fan_dx(int k) { const int t[FAN] = {0, 0, -1, -2, -1, 0, 1, 2}; return t[k]; }
-EDS_MAP_HD int fan_dy(int k) { const int t[FAN] = {0, 2, 1, 0, -1, -2, -1, 0}; return t[k]; }
+EDS_HD int fan_dx(int k) { const int t[FAN] = {0, 0, -1, -2, -1, 0, 1, 2}; return t[k]; }
+EDS_HD int fan_dy(int k) { const int t[FAN] = {0, 2, 1, 0, -1, -2, -1, 0}; return t[k]; }
 
 // p->u - 1 - cx and its kin: fp32, left to right; an offset of 0 is not added (p->u - cx)
-EDS_MAP_HD float fan_coord(float u, int d, float c) {
+EDS_HD float fan_coord(float u, int d, float c) {
     float a = u;
     if (d != 0) a = a + (float)d;
     return a - c;
@@ -41,7 +37,7 @@ EDS_MAP_HD float fan_coord(float u, int d, float c) {
 
 // ::base::Point(d_i * (p->u - cx) / fx, d_i * (p->v - cy) / fy, d_i) for point k of the fan: the difference in fp32, the product and the
 // quotient in fp64, (d_i * a) / fx
-EDS_MAP_HD void back_project(const Calib& c, float u, float v, double d_i, int k, double* P) {
+EDS_HD void back_project(const Calib& c, float u, float v, double d_i, int k, double* P) {
     const float a = fan_coord(u, fan_dx(k), c.cx), b = fan_coord(v, fan_dy(k), c.cy);
     P[0] = (d_i * (double)a) / (double)c.fx;
     P[1] = (d_i * (double)b) / (double)c.fy;
@@ -49,16 +45,16 @@ EDS_MAP_HD void back_project(const Calib& c, float u, float v, double d_i, int k
 }
 
 // T * p, T the rows of [R | t]: R_i0 X + R_i1 Y + R_i2 Z + t_i summed left to right (the order include/eds_hip_kfpoints.h states)
-EDS_MAP_HD void transform(const double* T, const double* p, double* o) {
+EDS_HD void transform(const double* T, const double* p, double* o) {
     for (int i = 0; i < 3; ++i) o[i] = T[4 * i] * p[0] + T[4 * i + 1] * p[1] + T[4 * i + 2] * p[2] + T[4 * i + 3];
 }
 
 // getMap: d_i = 1.0 / p->idepth_scaled (:51); no test, a zero, negative or NaN inverse depth gives the point it gives
-EDS_MAP_HD double window_depth(float idepth_scaled) { return 1.0 / (double)idepth_scaled; }
+EDS_HD double window_depth(float idepth_scaled) { return 1.0 / (double)idepth_scaled; }
 
 // getImmatureMap: d_i = 1.0 / (0.5 * (idepth_max + idepth_min)) (:107), the sum in fp32; false where the reference skips the point
 // (:109), and for a point that is not alive: it is no longer in immaturePoints
-EDS_MAP_HD bool immature_depth(int32_t alive, float idepth_min, float idepth_max, double* d_i) {
+EDS_HD bool immature_depth(int32_t alive, float idepth_min, float idepth_max, double* d_i) {
     const float s = idepth_max + idepth_min;
     const double d = 1.0 / (0.5 * (double)s);
     *d_i = d;
@@ -69,14 +65,14 @@ EDS_MAP_HD bool immature_depth(int32_t alive, float idepth_min, float idepth_max
 
 // getImmatureMap's colour by lastTraceStatus (:112-123): GOOD green, OOB red, OUTLIER blue, SKIPPED cyan, BADCONDITION white,
 // UNINITIALIZED black.  A code outside the table leaves the reference's colour uninitialised; here it is four zeros.
-EDS_MAP_HD void status_color(int32_t status, double* c) {
+EDS_HD void status_color(int32_t status, double* c) {
     const double t[NUM_STATUS][4] = {{0, 1, 0, 1}, {1, 0, 0, 1}, {0, 0, 1, 1}, {0, 1, 1, 1}, {1, 1, 1, 1}, {0, 0, 0, 1}};
     for (int i = 0; i < 4; ++i) c[i] = status >= 0 && status < NUM_STATUS ? t[status][i] : 0.0;
 }
 
 // IDepthMap::fromPoints (Types.hpp:264-267): px = fx (X / Z) + cx, py likewise, idp = 1 / Z; kept iff 0 <= px < W and 0 <= py < H,
 // written so that a NaN fails.  K: fx, fy, cx, cy.  Z <= 0 is not tested, as there.
-EDS_MAP_HD bool project(const double* K, double W, double H, const double* P, double* px, double* py, double* idp) {
+EDS_HD bool project(const double* K, double W, double H, const double* P, double* px, double* py, double* idp) {
     *px = K[0] * (P[0] / P[2]) + K[2];
     *py = K[1] * (P[1] / P[2]) + K[3];
     *idp = 1.0 / P[2];
@@ -84,22 +80,21 @@ EDS_MAP_HD bool project(const double* K, double W, double H, const double* P, do
 }
 
 // point k of window point (u, v, idepth_scaled) of a host with pose T_w_c, in the world
-EDS_MAP_HD void window_point(const Calib& c, const double* T_w_c, float u, float v, float idepth_scaled, int k, double* o) {
+EDS_HD void window_point(const Calib& c, const double* T_w_c, float u, float v, float idepth_scaled, int k, double* o) {
     double P[3];
     back_project(c, u, v, window_depth(idepth_scaled), k, P);
     transform(T_w_c, P, o);
 }
 
 // KeyFrame::getMap (:1260-1262): T_w_kf * (d x_n, d y_n, d), d = 1.0 / idp
-EDS_MAP_HD void slot_point(const double* T_w_kf, double xn, double yn, double idp, double* o) {
+EDS_HD void slot_point(const double* T_w_kf, double xn, double yn, double idp, double* o) {
     const double d = 1.0 / idp;
     const double P[3] = {d * xn, d * yn, d};
     transform(T_w_kf, P, o);
 }
 
-EDS_MAP_HD bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
 inline bool finite_all(const double* p, int64_t n) {
-    for (int64_t i = 0; i < n; ++i) if (!finite_d(p[i])) return false;
+    for (int64_t i = 0; i < n; ++i) if (!edsdso::finite_d(p[i])) return false;
     return true;
 }
 

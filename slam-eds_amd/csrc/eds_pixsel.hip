@@ -47,16 +47,6 @@ constexpr int SCAN = 1024;
 constexpr int PICK = 64;
 enum { C_N2 = 0, C_N3 = 1, C_N4 = 2, C_AMBIGUOUS = 3, C_N2_CERTAIN = 4, C_LIST = 5, C_COUNTS = 8 };
 
-__global__ void __launch_bounds__(TB) k_sel_level(const float* __restrict__ img, const Px* __restrict__ lm, Px* __restrict__ out, int w, int h,
-                                                  int wlm1) {
-    const int i = blockIdx.x * TB + threadIdx.x;
-    if (i >= w * h) return;
-    Px o;
-    o.c = lm ? edsct::down_at(lm, wlm1, i % w, i / w) : img[i];
-    o.dx = 0.0f; o.dy = 0.0f; o.pad = 0.0f;
-    out[i] = o;
-}
-
 __global__ void __launch_bounds__(TB) k_sel_gradient(Px* p, int w, int h, const float* __restrict__ B) {
     const int i = blockIdx.x * TB + threadIdx.x;
     if (i >= w * h) return;
@@ -173,24 +163,18 @@ __global__ void __launch_bounds__(TB) k_sel_count(const uint8_t* __restrict__ ma
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = c;
 }
 
-// The stable rank of the non-zero map pixels in flat order (k_ct_select's compaction).  sub = 1: the sub-selection, pixel of rank rn is
+// The stable rank of the non-zero map pixels in flat order (blocks_before, then block_rank).  sub = 1: the sub-selection, pixel of rank rn is
 // cleared when table[rn] > char_th, and what is left is counted per 256 into cnt_out.  sub = 0: the selection list.
 __global__ void __launch_bounds__(TB) k_sel_rank(uint8_t* __restrict__ map, const int32_t* __restrict__ block_cnt, const uint8_t* __restrict__ table,
                                                  int sub, int char_th, int32_t* __restrict__ cnt_out, int32_t* __restrict__ uv, float* __restrict__ type,
                                                  int32_t* __restrict__ counts, int wh, int w) {
-    __shared__ int wsum[TB / 64], wcnt[TB / 64];
-    const int i = blockIdx.x * TB + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int before = 0;
-    for (int b = threadIdx.x; b < (int)blockIdx.x; b += TB) before += block_cnt[b];
-    for (int s = 32; s >= 1; s >>= 1) before += __shfl_xor(before, s);
-    const uint8_t v = i < wh ? map[i] : (uint8_t)0;
+    __shared__ int s_wave[TB / 64];
+    const int i = blockIdx.x * TB + threadIdx.x;
+    const uint8_t v = i < wh ? map[i] : (uint8_t)0;              // in flight together with the counts blocks_before reads
     const bool nz = v != 0;
-    const unsigned long long m = __ballot(nz);
-    if (lane == 0) { wsum[wave] = before; wcnt[wave] = __popcll(m); }
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int k = 0; k < TB / 64; ++k) { base += wsum[k]; if (k < wave) base += wcnt[k]; total += wcnt[k]; }
-    const int rank = base + __popcll(m & ((1ull << lane) - 1ull));
+    const int base = edsdso::blocks_before<TB>(block_cnt, s_wave);
+    int total;
+    const int rank = base + edsdso::block_rank<TB>(nz, s_wave, &total);
     bool keep = nz;
     if (nz) {
         if (sub) {
@@ -204,9 +188,7 @@ __global__ void __launch_bounds__(TB) k_sel_rank(uint8_t* __restrict__ map, cons
         const int c = __syncthreads_count(keep);
         if (threadIdx.x == 0) cnt_out[blockIdx.x] = c;
     } else if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        int all = 0;
-        for (int k = 0; k < TB / 64; ++k) all += wsum[k];
-        counts[C_LIST] = all + total;
+        counts[C_LIST] = base + total;
     }
 }
 
@@ -350,8 +332,7 @@ int eds_sel_set_image(eds_sel* h, const float* image, int64_t rs, int on_device,
     h->hist_valid = false;
     for (int l = 0; l < edspix::LEVELS; ++l) {
         const int w = edspix::level_w(h->g, l), hh = edspix::level_h(h->g, l);
-        hipLaunchKernelGGL(k_sel_level, dim3(blocks((int64_t)w * hh)), dim3(TB), 0, h->own.st, h->in_img, l ? h->lv[l - 1] : (const Px*)nullptr, h->lv[l], w,
-                           hh, l ? edspix::level_w(h->g, l - 1) : 0);
+        edscapi::queue_colours(h->own.st, l ? nullptr : h->in_img, l ? h->lv[l - 1] : nullptr, l ? edspix::level_w(h->g, l - 1) : 0, h->lv[l], w, hh);
         hipLaunchKernelGGL(k_sel_gradient, dim3(blocks((int64_t)w * hh)), dim3(TB), 0, h->own.st, h->lv[l], w, hh, B ? h->B : (const float*)nullptr);
     }
     EDS_HIP_TRY(hipGetLastError());

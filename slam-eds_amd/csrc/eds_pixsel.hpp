@@ -51,19 +51,14 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "eds_coarse.hpp"
-
-#if defined(__HIPCC__)
-#define EDS_PX_HD __host__ __device__ inline
-#else
-#define EDS_PX_HD inline
-#endif
 #include <cstdlib>
 #include <vector>
 
+#include "eds_dso_common.hpp"
+
 namespace edspix {
 
-using edsct::Px;                                   // {c, dx, dy, pad}: pad holds absSquaredGrad here
+using edsdso::Px;                                  // {c, dx, dy, pad}: pad holds absSquaredGrad here
 typedef unsigned long long Key;
 
 constexpr int LEVELS = 3;
@@ -81,29 +76,28 @@ struct Geo { int32_t w, h, w1, h1, w2, h2, w32, h32; };
 
 struct Pass { int32_t potential, n2, n3, n4; };    // eds_sel_pass
 
-EDS_PX_HD Params params_default() { Params p = {0.5f, 7.0f, 0.75f, 1}; return p; }
-EDS_PX_HD bool finite_f(float x) { return fabsf(x) <= 3.402823466e38f; }
-EDS_PX_HD bool params_valid(const Params& p) {
-    return finite_f(p.min_grad_hist_cut) && finite_f(p.min_grad_hist_add) && finite_f(p.grad_downweight_per_level) &&
+EDS_HD Params params_default() { Params p = {0.5f, 7.0f, 0.75f, 1}; return p; }
+EDS_HD bool params_valid(const Params& p) {
+    return edsdso::finite_f(p.min_grad_hist_cut) && edsdso::finite_f(p.min_grad_hist_add) && edsdso::finite_f(p.grad_downweight_per_level) &&
            p.min_grad_hist_cut >= 0.0f && p.min_grad_hist_cut <= 1.0f;
 }
 
-EDS_PX_HD Geo make_geo(int H, int W) {
+EDS_HD Geo make_geo(int H, int W) {
     Geo g = {W, H, W >> 1, H >> 1, W >> 2, H >> 2, W / 32, H / 32};
     return g;
 }
-EDS_PX_HD int level_w(const Geo& g, int l) { return l == 0 ? g.w : l == 1 ? g.w1 : g.w2; }
-EDS_PX_HD int level_h(const Geo& g, int l) { return l == 0 ? g.h : l == 1 ? g.h1 : g.h2; }
+EDS_HD int level_w(const Geo& g, int l) { return l == 0 ? g.w : l == 1 ? g.w1 : g.w2; }
+EDS_HD int level_h(const Geo& g, int l) { return l == 0 ? g.h : l == 1 ? g.h1 : g.h2; }
 
 // ---- makeImages: absSquaredGrad (HessianBlocks.cpp:193-199, getBGradOnly HessianBlocks.h:384-390) -------------------------------------
-EDS_PX_HD int gamma_index(float colour) {
+EDS_HD int gamma_index(float colour) {
     const float t = colour + 0.5f;
     if (!(t >= 5.0f)) return 5;
     if (!(t < 250.0f)) return 250;
     return (int)t;
 }
 // B: the 256 floats of CalibHessian::B, or NULL for HCalib == 0
-EDS_PX_HD float abs_grad(float dx, float dy, float colour, const float* B) {
+EDS_HD float abs_grad(float dx, float dy, float colour, const float* B) {
     float dabs = dx * dx + dy * dy;
     if (B) {
         const int c = gamma_index(colour);
@@ -112,24 +106,24 @@ EDS_PX_HD float abs_grad(float dx, float dy, float colour, const float* B) {
     }
     return dabs;
 }
-// one pixel of a level after its colours are there: dx, dy by edsct's restatement, absSquaredGrad into pad
-EDS_PX_HD void gradient_pixel(Px* p, int w, int h, int i, const float* B) {
+// one pixel of a level after its colours are there: dx, dy by edsdso's restatement, absSquaredGrad into pad
+EDS_HD void gradient_pixel(Px* p, int w, int h, int i, const float* B) {
     float dx, dy;
-    edsct::gradient_at(p, w, h, i, &dx, &dy);
+    edsdso::gradient_at(p, w, h, i, &dx, &dy);
     p[i].dx = dx; p[i].dy = dy;
-    p[i].pad = (i < w || i >= w * (h - 1)) ? 0.0f : abs_grad(dx, dy, p[i].c, B);
+    p[i].pad = edsdso::border_row(w, h, i) ? 0.0f : abs_grad(dx, dy, p[i].c, B);
 }
 
 // ---- computeHistQuantil, makeHists (:60-135) ------------------------------------------------------------------------------------------
-EDS_PX_HD bool hist_counted(int it, int jt, int w, int h) { return !(it > w - 2 || jt > h - 2 || it < 1 || jt < 1); }
-EDS_PX_HD int hist_bin(float v) {
+EDS_HD bool hist_counted(int it, int jt, int w, int h) { return !(it > w - 2 || jt > h - 2 || it < 1 || jt < 1); }
+EDS_HD int hist_bin(float v) {
     const float r = sqrtf(v);
     if (!(r < 49.0f)) return 48;
     const int g = (int)r;
     return g > 48 ? 48 : g;
 }
 // hist[0]: the number of pixels; hist[1 + g]: those of bin g, g = 0 .. 48
-EDS_PX_HD int hist_quantile(const int* hist, float below) {
+EDS_HD int hist_quantile(const int* hist, float below) {
     int th = (int)(hist[0] * below + 0.5f);
     for (int i = 0; i < 90; ++i) {
         if (i + 1 < 50) th -= hist[i + 1];
@@ -137,9 +131,9 @@ EDS_PX_HD int hist_quantile(const int* hist, float below) {
     }
     return 90;
 }
-EDS_PX_HD float block_threshold(const int* hist, const Params& s) { return hist_quantile(hist, s.min_grad_hist_cut) + s.min_grad_hist_add; }
+EDS_HD float block_threshold(const int* hist, const Params& s) { return hist_quantile(hist, s.min_grad_hist_cut) + s.min_grad_hist_add; }
 
-EDS_PX_HD float smooth_at(const float* ths, int w32, int h32, int x, int y) {
+EDS_HD float smooth_at(const float* ths, int w32, int h32, int x, int y) {
     float sum = 0, num = 0;
     if (x > 0) {
         if (y > 0) { num++; sum += ths[x - 1 + (y - 1) * w32]; }
@@ -158,19 +152,19 @@ EDS_PX_HD float smooth_at(const float* ths, int w32, int h32, int x, int y) {
 }
 
 // defined behaviour 1
-EDS_PX_HD int ths_index(int xf, int yf, int w32, int h32) {
+EDS_HD int ths_index(int xf, int yf, int w32, int h32) {
     const int bx = xf >> 5, by = yf >> 5, flat = bx + by * w32;
     if (flat < w32 * h32) return flat;
     return (bx < w32 - 1 ? bx : w32 - 1) + (by < h32 - 1 ? by : h32 - 1) * w32;
 }
 
 // ---- select (:231-374) ----------------------------------------------------------------------------------------------------------------
-EDS_PX_HD float dir_x(int i) {
+EDS_HD float dir_x(int i) {
     const float t[16] = {(float)0, (float)0.3827, (float)0.1951, (float)0.9239, (float)0.7071, (float)0.3827, (float)0.8315, (float)0.8315,
                          (float)0.5556, (float)0.9808, (float)0.9239, (float)0.7071, (float)0.5556, (float)0.9808, (float)1.0000, (float)0.1951};
     return t[i];
 }
-EDS_PX_HD float dir_y(int i) {
+EDS_HD float dir_y(int i) {
     const float t[16] = {(float)1.0000, (float)0.9239, (float)0.9808, (float)0.3827, (float)0.7071, (float)-0.9239, (float)0.5556, (float)-0.5556,
                          (float)-0.8315, (float)0.1951, (float)-0.3827, (float)-0.7071, (float)0.8315, (float)-0.1951, (float)0.0000, (float)-0.9808};
     return t[i];
@@ -187,7 +181,7 @@ struct Sel {
     int32_t nbx, nby;                              // 4 pot blocks per row and column
 };
 
-EDS_PX_HD Sel make_sel(const Px* l0, const Px* l1, const Px* l2, const float* ths_s, const Geo& g, const Params& s, float thf, int potential) {
+EDS_HD Sel make_sel(const Px* l0, const Px* l1, const Px* l2, const float* ths_s, const Geo& g, const Params& s, float thf, int potential) {
     Sel S;
     S.l0 = l0; S.l1 = l1; S.l2 = l2; S.ths_s = ths_s; S.g = g;
     S.dw1 = s.grad_downweight_per_level;
@@ -201,12 +195,12 @@ EDS_PX_HD Sel make_sel(const Px* l0, const Px* l1, const Px* l2, const float* th
     return S;
 }
 
-EDS_PX_HD bool pixel_in(int xf, int yf, int w, int h) { return !(xf < 4 || xf >= w - 5 || yf < 4 || yf > h - 4); }
+EDS_HD bool pixel_in(int xf, int yf, int w, int h) { return !(xf < 4 || xf >= w - 5 || yf < 4 || yf > h - 4); }
 
 // a pot cell: origin and extent; mx < 1 or my < 1: the image clips it away
 struct Cell { int x0, y0, mx, my; };
-EDS_PX_HD int min_i(int a, int b) { return a < b ? a : b; }
-EDS_PX_HD Cell cell_of(const Sel& S, int b4, int slot) {
+EDS_HD int min_i(int a, int b) { return a < b ? a : b; }
+EDS_HD Cell cell_of(const Sel& S, int b4, int slot) {
     const int p = S.pot, w = S.g.w, h = S.g.h;
     const int x4 = (b4 % S.nbx) * 4 * p, y4 = (b4 / S.nbx) * 4 * p;
     const int b3 = slot >> 2, c2 = slot & 3;
@@ -220,10 +214,10 @@ EDS_PX_HD Cell cell_of(const Sel& S, int b4, int slot) {
     return c;
 }
 
-EDS_PX_HD float dir_norm(const Px& q, int d) { return fabsf(q.dx * dir_x(d) + q.dy * dir_y(d)); }
+EDS_HD float dir_norm(const Px& q, int d) { return fabsf(q.dx * dir_x(d) + q.dy * dir_y(d)); }
 
 // (a) the directions under which the level-0 pixel (xf, yf) makes its cell select
-EDS_PX_HD unsigned pixel_mask(const Sel& S, int xf, int yf) {
+EDS_HD unsigned pixel_mask(const Sel& S, int xf, int yf) {
     if (!pixel_in(xf, yf, S.g.w, S.g.h)) return 0u;
     const float pixelTH0 = S.ths_s[ths_index(xf, yf, S.g.w32, S.g.h32)];
     const Px q = S.l0[xf + S.g.w * yf];
@@ -235,7 +229,7 @@ EDS_PX_HD unsigned pixel_mask(const Sel& S, int xf, int yf) {
         if (dir_norm(q, d) > 0.0f) m |= 1u << d;
     return m;
 }
-EDS_PX_HD unsigned cell_mask(const Sel& S, const Cell& c) {
+EDS_HD unsigned cell_mask(const Sel& S, const Cell& c) {
     unsigned m = 0u;
     for (int y = 0; y < c.my; ++y)
         for (int x = 0; x < c.mx; ++x) m |= pixel_mask(S, c.x0 + x, c.y0 + y);
@@ -243,9 +237,9 @@ EDS_PX_HD unsigned cell_mask(const Sel& S, const Cell& c) {
 }
 
 // (b)
-EDS_PX_HD bool mask_certain(unsigned m) { return m == 0u || m == 0xFFFFu; }
-EDS_PX_HD int table_dir(const uint8_t* table, int n2, int wh) { return table[n2 < wh ? n2 : wh - 1] & 0xF; }
-EDS_PX_HD int cell_selected(unsigned mask, const uint8_t* table, int n2, int wh) { return (int)((mask >> table_dir(table, n2, wh)) & 1u); }
+EDS_HD bool mask_certain(unsigned m) { return m == 0u || m == 0xFFFFu; }
+EDS_HD int table_dir(const uint8_t* table, int n2, int wh) { return table[n2 < wh ? n2 : wh - 1] & 0xF; }
+EDS_HD int cell_selected(unsigned mask, const uint8_t* table, int n2, int wh) { return (int)((mask >> table_dir(table, n2, wh)) & 1u); }
 
 // (c) what a 4 pot block knows when its pixels are read: which cells select, and the directions drawn at the three levels
 struct Block {
@@ -253,7 +247,7 @@ struct Block {
     uint32_t sel;                                  // bit slot: the cell selects at level 0
     uint8_t d2[SLOTS], d3[4], d4;
 };
-EDS_PX_HD void make_block(const Sel& S, int b4, const int32_t* n2_start, const uint8_t* cell_sel, const uint8_t* table, Block& B) {
+EDS_HD void make_block(const Sel& S, int b4, const int32_t* n2_start, const uint8_t* cell_sel, const uint8_t* table, Block& B) {
     const int p = S.pot, wh = S.g.w * S.g.h;
     B.x4 = (b4 % S.nbx) * 4 * p; B.y4 = (b4 / S.nbx) * 4 * p;
     B.bw = min_i(4 * p, S.g.w - B.x4); B.bh = min_i(4 * p, S.g.h - B.y4);
@@ -265,15 +259,15 @@ EDS_PX_HD void make_block(const Sel& S, int b4, const int32_t* n2_start, const u
     for (int b = 0; b < 4; ++b) B.d3[b] = B.d2[4 * b];
     B.d4 = B.d2[0];
 }
-EDS_PX_HD bool block3_hit(const Block& B, int b3) { return ((B.sel >> (4 * b3)) & 0xFu) != 0u; }
+EDS_HD bool block3_hit(const Block& B, int b3) { return ((B.sel >> (4 * b3)) & 0xFu) != 0u; }
 
-EDS_PX_HD uint32_t float_bits(float v) { uint32_t u; __builtin_memcpy(&u, &v, 4); return u; }
+EDS_HD uint32_t float_bits(float v) { uint32_t u; __builtin_memcpy(&u, &v, 4); return u; }
 // v > 0 (+inf included): larger v, then the earlier visiting rank, is the larger key; 0 is "no candidate"
-EDS_PX_HD Key make_key(float v, uint32_t ord) { return ((Key)float_bits(v) << 32) | (Key)(0xFFFFFFFFu - ord); }
-EDS_PX_HD uint32_t key_ord(Key k) { return 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull); }
+EDS_HD Key make_key(float v, uint32_t ord) { return ((Key)float_bits(v) << 32) | (Key)(0xFFFFFFFFu - ord); }
+EDS_HD uint32_t key_ord(Key k) { return 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull); }
 
 // the pixel (lx, ly) of block B: its slot and its three keys (0: it does not compete at that level)
-EDS_PX_HD int pixel_keys(const Sel& S, const Block& B, int lx, int ly, Key* k2, Key* k3, Key* k4) {
+EDS_HD int pixel_keys(const Sel& S, const Block& B, int lx, int ly, Key* k2, Key* k3, Key* k4) {
     const int p = S.pot;
     const int b3 = ((ly >= 2 * p) << 1) | (lx >= 2 * p);
     const int rx = lx - (b3 & 1) * 2 * p, ry = ly - (b3 >> 1) * 2 * p;
@@ -311,7 +305,7 @@ EDS_PX_HD int pixel_keys(const Sel& S, const Block& B, int lx, int ly, Key* k2, 
 }
 
 // the flat index of the pixel a key names
-EDS_PX_HD int key_pixel(const Sel& S, const Block& B, Key k) {
+EDS_HD int key_pixel(const Sel& S, const Block& B, Key k) {
     const uint32_t ord = key_ord(k), p = (uint32_t)S.pot;
     const int x1 = (int)(ord % p), y1 = (int)((ord / p) % p), slot = (int)(ord / p / p);
     const int b3 = slot >> 2, c2 = slot & 3;
@@ -321,7 +315,7 @@ EDS_PX_HD int key_pixel(const Sel& S, const Block& B, Key k) {
 
 // what item `item` of a block's 21 writes: 0 .. 15 a cell (map value 1), 16 .. 19 a 2 pot block (2), 20 the 4 pot block (4).
 // K2[16], K3[4], K4[1] are the arg-max keys.  Returns the map value written, 0 for none.
-EDS_PX_HD int finish_item(const Sel& S, const Block& B, const Key* K2, const Key* K3, const Key* K4, int item, uint8_t* map) {
+EDS_HD int finish_item(const Sel& S, const Block& B, const Key* K2, const Key* K3, const Key* K4, int item, uint8_t* map) {
     if (item < SLOTS) {
         if (!((B.sel >> item) & 1u) || K2[item] == 0) return 0;
         map[key_pixel(S, B, K2[item])] = 1;
@@ -348,7 +342,7 @@ struct Decision {
     int32_t char_th;
     float quotia;
 };
-EDS_PX_HD Decision decide(int n2, int n3, int n4, float density, int recursionsLeft, int currentPotential) {
+EDS_HD Decision decide(int n2, int n3, int n4, float density, int recursionsLeft, int currentPotential) {
     Decision D;
     const float numHave = (float)(n2 + n3 + n4);
     const float numWant = density;
@@ -373,7 +367,7 @@ EDS_PX_HD Decision decide(int n2, int n3, int n4, float density, int recursionsL
     return D;
 }
 // the sub-selection's rule for the non-zero pixel of rank rn
-EDS_PX_HD bool sub_removed(const uint8_t* table, int rn, int char_th) { return (int)table[rn] > char_th; }
+EDS_HD bool sub_removed(const uint8_t* table, int rn, int char_th) { return (int)table[rn] > char_th; }
 
 // ---- the serial driver (host only) -----------------------------------------------------------------------------------------------------------------
 // the constructor's table (:37-39).  Reseeds the C library's generator.
@@ -409,17 +403,10 @@ inline void serial_init(Serial& s, int H, int W) {
 }
 
 inline void serial_set_image(Serial& s, const float* image, int64_t row_stride, const float* B) {
-    for (int l = 0; l < LEVELS; ++l) {
-        const int w = level_w(s.g, l), h = level_h(s.g, l);
-        Px* p = s.lv[l].data();
-        for (int y = 0; y < h; ++y)
-            for (int x = 0; x < w; ++x) {
-                Px& o = p[x + y * w];
-                o.c = l == 0 ? image[(int64_t)y * row_stride + x] : edsct::down_at(s.lv[l - 1].data(), level_w(s.g, l - 1), x, y);
-                o.dx = o.dy = o.pad = 0.0f;
-            }
-        for (int i = 0; i < w * h; ++i) gradient_pixel(p, w, h, i, B);
-    }
+    Px* lv[LEVELS] = {s.lv[0].data(), s.lv[1].data(), s.lv[2].data()};
+    edsdso::make_levels(image, row_stride, s.g.w, s.g.h, LEVELS, lv);
+    for (int l = 0; l < LEVELS; ++l)
+        for (int i = 0; i < level_w(s.g, l) * level_h(s.g, l); ++i) gradient_pixel(lv[l], level_w(s.g, l), level_h(s.g, l), i, B);
     s.hist_valid = false;
 }
 

@@ -12,14 +12,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define EDS_UND_HD __host__ __device__ inline
-#else
-#define EDS_UND_HD inline
-#endif
-
 #include <cmath>
 #include <vector>
+
+#include "eds_dso_common.hpp"
 
 namespace edsund {
 
@@ -54,20 +50,20 @@ inline bool settings_valid(const Settings& s) {
 
 // processFrame<T> (:214-234) for one pixel: `phot` is valid && exposure > 0 && setting_photometricCalibration != 0, `vig` is
 // setting_photometricCalibration == 2.  One fp32 product of two table reads, so a tap corrected on the fly has the plane's bits.
-EDS_UND_HD float corrected(int raw, bool phot, bool vig, const float* G, const float* vinv, int64_t i, float factor) {
+EDS_HD float corrected(int raw, bool phot, bool vig, const float* G, const float* vinv, int64_t i, float factor) {
     if (!phot) return factor * (float)raw;
     float v = G[raw];
     if (vig) v = v * vinv[i];
     return v;
 }
 // processFrame's branch for one frame; NaN is not <= 0
-EDS_UND_HD bool photometric_branch(bool valid, float exposure, int mode) { return !(!valid || exposure <= 0 || mode == 0); }
+EDS_HD bool photometric_branch(bool valid, float exposure, int mode) { return !(!valid || exposure <= 0 || mode == 0); }
 
 // :437: the reference tests xx < 0; a NaN, which no checked map holds, counts as outside here
-EDS_UND_HD bool outside(float xx) { return !(xx >= 0.0f); }
+EDS_HD bool outside(float xx) { return !(xx >= 0.0f); }
 
 // :452-455 from the four taps: src[0], src[1], src[wOrg], src[1 + wOrg] and the fractions; every sum left to right
-EDS_UND_HD float bilinear(float xx, float yy, float s0, float s1, float sw, float sw1) {
+EDS_HD float bilinear(float xx, float yy, float s0, float s1, float sw, float sw1) {
     const float xxyy = xx * yy;
     return ((xxyy * sw1 + (yy - xxyy) * sw) + (xx - xxyy) * s1) + (((1.0f - xx) - yy) + xxyy) * s0;
 }

@@ -46,23 +46,6 @@ struct Dev {
     float *energy, *new_energy, *new_energy_wo, *ret, *cp, *proj, *J, *efJ, *JpJdF;
 };
 
-__global__ void __launch_bounds__(TB) k_win_image(const float* __restrict__ img, Px* __restrict__ px, int n) {
-    const int i = blockIdx.x * TB + threadIdx.x;
-    if (i >= n) return;
-    Px o;
-    o.c = img[i]; o.dx = 0.0f; o.dy = 0.0f; o.pad = 0.0f;
-    px[i] = o;
-}
-
-__global__ void __launch_bounds__(TB) k_win_gradient(Px* px, int W, int H) {
-    const int i = blockIdx.x * TB + threadIdx.x;
-    if (i >= W * H) return;
-    float dx, dy;
-    edsct::gradient_at(px, W, H, i, &dx, &dy);
-    px[i].dx = dx;
-    px[i].dy = dy;
-}
-
 __device__ inline float pick8(int j, float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7) {
     return j == 0 ? a0 : j == 1 ? a1 : j == 2 ? a2 : j == 3 ? a3 : j == 4 ? a4 : j == 5 ? a5 : j == 6 ? a6 : a7;
 }
@@ -135,14 +118,8 @@ __global__ void __launch_bounds__(TB) k_win_linearize(Calib K, Params s, int F, 
     }
 }
 
-__device__ inline double wave_fold(double v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
-__device__ inline int wave_fold_i(int v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
+using edsdso::wave_fold;                                        // the fold inside 64 lanes is eds_dso_common.hpp's, as is add8
+using edsdso::wave_fold_i;
 
 // the energy in the header's sum order and the counts of the new states, one workgroup
 __global__ void __launch_bounds__(edswin::LANES) k_win_energy(const float* __restrict__ ret, const int32_t* __restrict__ new_state, int m, Sum* out) {
@@ -170,7 +147,7 @@ __global__ void __launch_bounds__(edswin::LANES) k_win_energy(const float* __res
     if (lane == 0) { part[wave] = e; ipart[wave] = c0; ipart[8 + wave] = c1; ipart[16 + wave] = c2; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        out->energy = ((((((part[0] + part[1]) + part[2]) + part[3]) + part[4]) + part[5]) + part[6]) + part[7];
+        out->energy = edsdso::add8(part);
         for (int k = 0; k < 3; ++k) {
             int c = 0;
             for (int w = 0; w < 8; ++w) c += ipart[8 * k + w];
@@ -233,7 +210,7 @@ __global__ void __launch_bounds__(edswin::LANES) k_win_acc(edswin::AccIn in, dou
     v = wave_fold(v);
     if (lane == 0) part[wave] = v;
     __syncthreads();
-    if (threadIdx.x == 0) acc[j] = ((((((part[0] + part[1]) + part[2]) + part[3]) + part[4]) + part[5]) + part[6]) + part[7];
+    if (threadIdx.x == 0) acc[j] = edsdso::add8(part);
 }
 
 // both stitches, one thread per output entry (edswin::stitch_entry: the addends and their order are stitch_serial's)
@@ -427,8 +404,7 @@ int eds_win_set_frames(eds_win* h, int first, int count, const float* images, in
         h->frames_set &= ~(1u << (first + f));
         Px* dst = h->frames + (size_t)(first + f) * px;
         if (int rc = edscapi::upload_image(h->own, h->in_img, H, W, images + (int64_t)f * frame_stride, row_stride, on_device)) return rc;
-        hipLaunchKernelGGL(k_win_image, dim3(blocks(px)), dim3(TB), 0, h->own.st, h->in_img, dst, (int)px);
-        hipLaunchKernelGGL(k_win_gradient, dim3(blocks(px)), dim3(TB), 0, h->own.st, dst, W, H);
+        edscapi::queue_level(h->own.st, h->in_img, nullptr, 0, dst, W, H);
         EDS_HIP_TRY(hipGetLastError());
         EDS_HIP_TRY(hipStreamSynchronize(h->own.st));                // the host image may be pageable, and in_img is reused by the next frame
         h->frames_set |= 1u << (first + f);

@@ -4,7 +4,7 @@
 // of AccumulatedSCHessianSSE::addPoint, every accumulator term of the two addPoint()s and both stitches — and a serial evaluator
 // (linearize_serial, apply_serial, points_serial, accumulate_serial, stitch_serial) that strings them
 // together in the reference's loop order.  fp32 per residual and per point in the reference's operand order; every translation unit
-// that includes this is built without contraction into FMAs.  Plain C++ outside hipcc.  Level 0 of makeImages is edsct's (one frame is
+// that includes this is built without contraction into FMAs.  Plain C++ outside hipcc.  Level 0 of makeImages is edsdso's (one frame is
 // one Px {c, dx, dy, 0} per pixel); nothing of it is written twice.
 //
 // WHAT J HOLDS AFTER AN OOB.  The reference leaves the RawResidualJacobian half-written when linearize returns OOB from inside the
@@ -16,25 +16,19 @@
 //
 // THE SUM ORDER.  The energy eds_win_linearize returns is the sum, in fp64, of the fp32 values linearize returns per residual, taken
 // by LANES = 512 lanes: lane t adds, from 0.0, the returns of residuals t, t + 512, ... in that order; inside every 64 consecutive lanes
-// the partials are folded by p[t] += p[t + s] for (t mod 64) < s, s = 32 ... 1; the eight totals are added left to right (edsct's
+// the partials are folded by p[t] += p[t + s] for (t mod 64) < s, s = 32 ... 1; the eight totals are added left to right (edsdso's
 // reduce_lanes).  Counts are integers.  No floating-point atomic anywhere.
 #pragma once
-#include "eds_coarse.hpp"
-
-#if defined(__HIPCC__)
-#define EDS_WIN_HD __host__ __device__ inline
-#else
-#define EDS_WIN_HD inline
-#endif
+#include "eds_dso_common.hpp"
 
 namespace edswin {
 
-using edsct::finite_f;
-using edsct::Px;
+using edsdso::finite_f;
+using edsdso::Px;
 
 constexpr int MAX_FRAMES = 8;
 constexpr int PATTERN = 8;
-constexpr int LANES = edsct::LANES;
+using edsdso::LANES;
 constexpr int J_WORDS = 74;
 enum { ST_IN = 0, ST_OOB = 1, ST_OUTLIER = 2 };                 // ResState (Residuals.h:47)
 
@@ -52,19 +46,19 @@ struct Precalc { float KRKi[9], Kt[3], R0[9], t0[3], aff[2], b0; };
 // a point's constant part; its two inverse depths change every iteration and are arrays of their own (one plain copy per step)
 struct Point { int32_t host; float u, v, color[PATTERN], weights[PATTERN]; };
 
-EDS_WIN_HD int pat_x(int i) { const int t[PATTERN] = {0, -1, 1, -2, 0, 2, -1, 0}; return t[i]; }
-EDS_WIN_HD int pat_y(int i) { const int t[PATTERN] = {-2, -1, -1, 0, 0, 0, 1, 2}; return t[i]; }
+EDS_HD int pat_x(int i) { const int t[PATTERN] = {0, -1, 1, -2, 0, 2, -1, 0}; return t[i]; }
+EDS_HD int pat_y(int i) { const int t[PATTERN] = {-2, -1, -1, 0, 0, 0, 1, 2}; return t[i]; }
 
-EDS_WIN_HD Params params_default() { Params p = {50.0f * 50.0f, 9.0f, 1e12f, 1e8f, 1.0f, 1.0f, 1.0f, 0.0f}; return p; }
-EDS_WIN_HD bool params_valid(const Params& p) {
+EDS_HD Params params_default() { Params p = {50.0f * 50.0f, 9.0f, 1e12f, 1e8f, 1.0f, 1.0f, 1.0f, 0.0f}; return p; }
+EDS_HD bool params_valid(const Params& p) {
     return finite_f(p.outlier_th_sum_component) && finite_f(p.huber_th) && finite_f(p.affine_opt_mode_a) && finite_f(p.affine_opt_mode_b) &&
            finite_f(p.scale_idepth) && finite_f(p.scale_f) && finite_f(p.scale_c) && p.outlier_th_sum_component > 0.0f && p.huber_th > 0.0f &&
            p.scale_idepth > 0.0f && p.scale_f > 0.0f && p.scale_c > 0.0f;
 }
-EDS_WIN_HD bool shape_valid(int H, int W) { return H >= 8 && W >= 8 && H <= 8192 && W <= 8192; }
+EDS_HD bool shape_valid(int H, int W) { return H >= 8 && W >= 8 && H <= 8192 && W <= 8192; }
 
 // CalibHessian's fxl() ... fyli() (HessianBlocks.h:350-366: value_scaledi[0] = 1 / fx) and globalCalib's wM3G, hM3G
-EDS_WIN_HD Calib make_calib(int H, int W, float fx, float fy, float cx, float cy) {
+EDS_HD Calib make_calib(int H, int W, float fx, float fy, float cx, float cy) {
     Calib c;
     c.fx = fx; c.fy = fy; c.cx = cx; c.cy = cy; c.fxi = 1.0f / fx; c.fyi = 1.0f / fy;
     c.wM3 = (float)(W - 3); c.hM3 = (float)(H - 3); c.W = W; c.H = H;
@@ -74,7 +68,7 @@ EDS_WIN_HD Calib make_calib(int H, int W, float fx, float fy, float cx, float cy
 // ---- the geometric part of linearize (Residuals.cpp:94-148) with projectPoint's long overload (ResidualProjections.h:60-86) ------------
 struct Geo { int32_t ok; float cp[3], Jpdxi[12], Jpdc[8], Jpdd[2]; };
 
-EDS_WIN_HD Geo geo(const Calib& K, const Params& s, const Precalc& pc, float u_pt, float v_pt, float idepth_zero) {
+EDS_HD Geo geo(const Calib& K, const Params& s, const Precalc& pc, float u_pt, float v_pt, float idepth_zero) {
     Geo g;
     g.ok = 0;
     g.cp[0] = g.cp[1] = g.cp[2] = 0.0f;
@@ -118,7 +112,7 @@ EDS_WIN_HD Geo geo(const Calib& K, const Params& s, const Precalc& pc, float u_p
 // _10, JabJIdx_00, _01, _10, _11, JabJab_00, _01, _11.  No address is formed before the bounds test passes; a NaN fails it.
 struct Tap { int32_t fail; float Ku, Kv, resF, jx, jy, ja, jb, e, wji2, s[10]; };
 
-EDS_WIN_HD Tap tap(const Calib& K, const Params& s, const Precalc& pc, const Px* img, const Point& pt, float idepth_scaled, int idx) {
+EDS_HD Tap tap(const Calib& K, const Params& s, const Precalc& pc, const Px* img, const Point& pt, float idepth_scaled, int idx) {
     Tap o;
     o.fail = 1;
     o.Ku = o.Kv = o.resF = o.jx = o.jy = o.ja = o.jb = o.e = o.wji2 = 0.0f;
@@ -130,15 +124,13 @@ EDS_WIN_HD Tap tap(const Calib& K, const Params& s, const Precalc& pc, const Px*
     const float Ku = p0 / p2, Kv = p1 / p2;
     if (!(Ku > 1.1f && Kv > 1.1f && Ku < K.wM3 && Kv < K.hM3)) return o;
     o.Ku = Ku; o.Kv = Kv;
-    // getInterpolatedElement33 (globalFuncs.h:78-92): ((dxdy v11 + (dy - dxdy) v01) + (dx - dxdy) v10) + (((1 - dx) - dy) + dxdy) v00
-    const int ix = (int)Ku, iy = (int)Kv;
-    const float dx = Ku - ix, dy = Kv - iy, dxdy = dx * dy;
-    const Px* bp = img + ((size_t)iy * K.W + ix);
+    // getInterpolatedElement33 (globalFuncs.h:78-92)
+    const edsdso::Bilin bw = edsdso::bilin(Ku, Kv);
+    const Px* bp = img + ((size_t)bw.iy * K.W + bw.ix);
     const Px v11 = bp[1 + K.W], v01 = bp[K.W], v10 = bp[1], v00 = bp[0];
-    const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-    const float h0 = w11 * v11.c + w01 * v01.c + w10 * v10.c + w00 * v00.c;
-    float h1 = w11 * v11.dx + w01 * v01.dx + w10 * v10.dx + w00 * v00.dx;
-    float h2 = w11 * v11.dy + w01 * v01.dy + w10 * v10.dy + w00 * v00.dy;
+    const float h0 = edsdso::mix(bw, v11.c, v01.c, v10.c, v00.c);
+    float h1 = edsdso::mix(bw, v11.dx, v01.dx, v10.dx, v00.dx);
+    float h2 = edsdso::mix(bw, v11.dy, v01.dy, v10.dy, v00.dy);
     const float residual = h0 - (pc.aff[0] * pt.color[idx] + pc.aff[1]);
     const float drdA = pt.color[idx] - pc.b0;
     if (!finite_f(h0)) { o.fail = 2; return o; }
@@ -163,15 +155,15 @@ EDS_WIN_HD Tap tap(const Calib& K, const Params& s, const Precalc& pc, const Px*
 
 // the running sums of the loop, added in pattern order 0 ... 7 from 0: energyLeft, wJI2_sum and the ten products
 struct Sums { float e, wji2, s[10]; };
-EDS_WIN_HD Sums sums_zero() { Sums a; a.e = 0.0f; a.wji2 = 0.0f; for (int i = 0; i < 10; ++i) a.s[i] = 0.0f; return a; }
-EDS_WIN_HD void sums_add(Sums& a, float e, float wji2, const float* s) {
+EDS_HD Sums sums_zero() { Sums a; a.e = 0.0f; a.wji2 = 0.0f; for (int i = 0; i < 10; ++i) a.s[i] = 0.0f; return a; }
+EDS_HD void sums_add(Sums& a, float e, float wji2, const float* s) {
     a.e += e; a.wji2 += wji2;
     for (int i = 0; i < 10; ++i) a.s[i] += s[i];
 }
 
 // the outlier rule (Residuals.cpp:251-263): std::max<float>(host, target) is (host < target) ? target : host
 struct Verdict { int32_t state; float energy, energy_with_outlier; };
-EDS_WIN_HD Verdict verdict(const Sums& a, float th_host, float th_target) {
+EDS_HD Verdict verdict(const Sums& a, float th_host, float th_target) {
     Verdict v;
     const float th = th_host < th_target ? th_target : th_host;
     v.energy_with_outlier = a.e;
@@ -181,14 +173,14 @@ EDS_WIN_HD Verdict verdict(const Sums& a, float th_host, float th_target) {
 }
 
 // the twelve words of JIdx2, JabJIdx and Jab2 (row-major 2 x 2 each) from the sums (Residuals.cpp:238-249)
-EDS_WIN_HD float block_word(const Sums& a, int k) {
+EDS_HD float block_word(const Sums& a, int k) {
     const int m[12] = {0, 2, 2, 1, 3, 4, 5, 6, 7, 8, 8, 9};
     return a.s[m[k]];
 }
 
 // ---- applyRes (Residuals.cpp:298-320) with EFResidual::takeDataF (EnergyFunctionalStructs.cpp:38-48) ---------------------------------------
 // JpJdF from a J: JI_JI_Jd = JIdx2 * Jpdd, JpJdF[i] = Jpdxi[0][i] JI_JI_Jd[0] + Jpdxi[1][i] JI_JI_Jd[1], JpJdF[6 .. 7] = JabJIdx * Jpdd
-EDS_WIN_HD void jpjdf(const float* J, float* out) {
+EDS_HD void jpjdf(const float* J, float* out) {
     const float d0 = J[J_JPDD], d1 = J[J_JPDD + 1];
     const float a = J[J_JIDX2] * d0 + J[J_JIDX2 + 1] * d1, b = J[J_JIDX2 + 2] * d0 + J[J_JIDX2 + 3] * d1;
     for (int i = 0; i < 6; ++i) out[i] = J[J_JPDXI + i] * a + J[J_JPDXI + 6 + i] * b;
@@ -199,7 +191,7 @@ EDS_WIN_HD void jpjdf(const float* J, float* out) {
 // one residual's applyRes.  takeDataF swaps two J pointers; here the linearized J is COPIED into the energy functional's, which gives the
 // functional the same words (the swapped-out buffer is overwritten by the next linearize that does not end OOB, and read by nothing).
 struct ResState { int32_t* state; float* energy; int32_t* active; const int32_t* new_state; const float* new_energy; const float* J; float* efJ; float* JpJdF; };
-EDS_WIN_HD void apply_one(const ResState& r, int i, bool copy_jacobians) {
+EDS_HD void apply_one(const ResState& r, int i, bool copy_jacobians) {
     if (copy_jacobians) {
         if (r.state[i] == ST_OOB) return;                       // can never go back from OOB
         if (r.new_state[i] == ST_IN) {
@@ -221,7 +213,7 @@ struct PointOut { float Hdd_accAF, bd_accAF, Hcd_accAF[4], HdiF, bdSumF, idepth_
 // Mode 0 of the top accumulator skips residuals with isLinearized while the Schur complement's ngoodres counts every active one.  The
 // flags live beside the table (lin[r], NULL: none is set; include/eds_hip_winsolve.h sets them); PointOut::nres is ngoodres.
 // One residual's addends to bd_acc, Hdd_acc and Hcd_acc (AccumulatedTopHessian.cpp:102-137); res: the eight words of resApprox
-EDS_WIN_HD void top_point_term(const float* J, const float* res, float& bd, float& Hdd, float* Hcd) {
+EDS_HD void top_point_term(const float* J, const float* res, float& bd, float& Hdd, float* Hcd) {
     float jr0 = 0, jr1 = 0;
     for (int i = 0; i < PATTERN; ++i) {
         jr0 += res[i] * J[J_JIDX + i];
@@ -234,11 +226,11 @@ EDS_WIN_HD void top_point_term(const float* J, const float* res, float& bd, floa
     for (int k = 0; k < 4; ++k) Hcd[k] += J[J_JPDC + k] * q0 + J[J_JPDC + 4 + k] * q1;
 }
 // the residual filter of addPoint<mode>: 0 active and not linearized, 1 active and linearized, 2 active
-EDS_WIN_HD bool top_filter(int mode, int is_active, int is_lin) { return is_active && (mode == 2 || (mode == 1) == (is_lin != 0)); }
+EDS_HD bool top_filter(int mode, int is_active, int is_lin) { return is_active && (mode == 2 || (mode == 1) == (is_lin != 0)); }
 
 // the point's residuals are [r0, r1) of the table; prior, delta and the linearized sums Hdd_accLF, bd_accLF, Hcd_accLF[4] are inputs.
 // mode 0: the A sums over the residuals that are active and not linearized; mode 2: the A sums are zero (addPoint<2> zeroes them)
-EDS_WIN_HD PointOut point_sums_mode(const int32_t* active, const int32_t* lin, const float* efJ, int r0, int r1, float priorF, float deltaF,
+EDS_HD PointOut point_sums_mode(const int32_t* active, const int32_t* lin, const float* efJ, int r0, int r1, float priorF, float deltaF,
                                     const float* lf, bool shift_prior_to_zero, int mode, int* added) {
     PointOut o;
     float bd = 0, Hdd = 0, Hcd[4] = {0, 0, 0, 0};
@@ -263,7 +255,7 @@ EDS_WIN_HD PointOut point_sums_mode(const int32_t* active, const int32_t* lin, c
     if (shift_prior_to_zero) o.bdSumF += priorF * deltaF;
     return o;
 }
-EDS_WIN_HD PointOut point_sums(const int32_t* active, const float* efJ, int r0, int r1, float priorF, float deltaF, const float* lf,
+EDS_HD PointOut point_sums(const int32_t* active, const float* efJ, int r0, int r1, float priorF, float deltaF, const float* lf,
                                bool shift_prior_to_zero) {
     int added;
     return point_sums_mode(active, nullptr, efJ, r0, r1, priorF, deltaF, lf, shift_prior_to_zero, 0, &added);
@@ -279,11 +271,7 @@ struct Tables {
 };
 
 // one frame's level 0: px[H * W]
-inline void make_frame(int H, int W, const float* image, int64_t row_stride, Px* px) {
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) { Px& o = px[x + y * W]; o.c = image[(int64_t)y * row_stride + x]; o.dx = o.dy = o.pad = 0.0f; }
-    for (int i = 0; i < W * H; ++i) edsct::gradient_at(px, W, H, i, &px[i].dx, &px[i].dy);
-}
+inline void make_frame(int H, int W, const float* image, int64_t row_stride, Px* px) { edsdso::make_levels(image, row_stride, W, H, 1, &px); }
 
 // PointFrameResidual::linearize for residual i; returns what the reference returns
 inline float linearize_one(const Calib& K, const Params& s, int F, const Precalc* pcs, const float* th, const Px* frames, const Point* pts,
@@ -331,7 +319,7 @@ inline double linearize_serial(const Calib& K, const Params& s, int F, const Pre
         part[i % LANES] += (double)t.ret[i];
         ++counts[t.new_state[i]];
     }
-    return edsct::reduce_lanes(part);
+    return edsdso::reduce_lanes(part);
 }
 
 inline void apply_serial(const Tables& t, bool copy_jacobians) {
@@ -369,20 +357,20 @@ inline int points_serial(int n, const int32_t* res_first, const Tables& t, const
 //   D    [F F F][65] accD[h + F t1 + F^2 t2] (8 x 8 row-major), then num
 //   C    [F][20]    per host: accHcc (4 x 4 row-major), then accbc (4)
 constexpr int TOP_WORDS = 92, E_WORDS = 40, D_WORDS = 65, C_WORDS = 20;
-EDS_WIN_HD int acc_off_e(int F) { return F * F * TOP_WORDS; }
-EDS_WIN_HD int acc_off_d(int F) { return acc_off_e(F) + F * F * E_WORDS; }
-EDS_WIN_HD int acc_off_c(int F) { return acc_off_d(F) + F * F * F * D_WORDS; }
-EDS_WIN_HD int acc_size(int F) { return acc_off_c(F) + F * C_WORDS; }
+EDS_HD int acc_off_e(int F) { return F * F * TOP_WORDS; }
+EDS_HD int acc_off_d(int F) { return acc_off_e(F) + F * F * E_WORDS; }
+EDS_HD int acc_off_c(int F) { return acc_off_d(F) + F * F * F * D_WORDS; }
+EDS_HD int acc_size(int F) { return acc_off_c(F) + F * C_WORDS; }
 
 // x4 | x6 and y4 | y6 of the update calls: Jpdc[0], Jpdxi[0] and Jpdc[1], Jpdxi[1]
-EDS_WIN_HD float jx(const float* J, int k) { return k < 4 ? J[J_JPDC + k] : J[J_JPDXI + k - 4]; }
-EDS_WIN_HD float jy(const float* J, int k) { return k < 4 ? J[J_JPDC + 4 + k] : J[J_JPDXI + 6 + k - 4]; }
+EDS_HD float jx(const float* J, int k) { return k < 4 ? J[J_JPDC + k] : J[J_JPDXI + k - 4]; }
+EDS_HD float jy(const float* J, int k) { return k < 4 ? J[J_JPDC + 4 + k] : J[J_JPDXI + 6 + k - 4]; }
 // sum_i a[i] b[i] from 0 in index order (JI_r, Jab_r, rr of AccumulatedTopHessian.cpp:102-112)
-EDS_WIN_HD float dot8(const float* a, const float* b) { float r = 0; for (int i = 0; i < PATTERN; ++i) r += a[i] * b[i]; return r; }
+EDS_HD float dot8(const float* a, const float* b) { float r = 0; for (int i = 0; i < PATTERN; ++i) r += a[i] * b[i]; return r; }
 
 // entry e of what one active residual adds to acc[h + F t] (AccumulatedTopHessian.cpp:115-129); res: the eight words of resApprox (mode 0:
 // the J's own resF)
-EDS_WIN_HD float top_term(const float* J, const float* res, int e) {
+EDS_HD float top_term(const float* J, const float* res, int e) {
     if (e < 55) {                                               // Data: column c, rows r = c ... 9
         int c = 0, base = 0;
         while (e >= base + (10 - c)) { base += 10 - c; ++c; }
@@ -407,7 +395,7 @@ EDS_WIN_HD float top_term(const float* J, const float* res, int e) {
         default: return 1.0f;
     }
 }
-EDS_WIN_HD float top_term(const float* J, int e) { return top_term(J, J + J_RESF, e); }
+EDS_HD float top_term(const float* J, int e) { return top_term(J, J + J_RESF, e); }
 
 // what a term reads; res_of[p F + t]: the residual of point p towards target t, or -1
 // The trailing members are zero in every brace list that ends at lf: mode 0, no linearized flag, every point.  lin[r]: isLinearized;
@@ -415,27 +403,27 @@ EDS_WIN_HD float top_term(const float* J, int e) { return top_term(J, J + J_RESF
 struct AccIn { int32_t F, has_lf; const int32_t* first; const int32_t* res_of; const int32_t* active; const float* efJ; const float* JpJdF; const PointOut* pout; const float* lf;
                int32_t mode; const int32_t* lin; const float* res_approx; const int32_t* sel; };
 
-EDS_WIN_HD int active_res(const AccIn& in, int p, int t) {
+EDS_HD int active_res(const AccIn& in, int p, int t) {
     const int r = in.res_of[p * in.F + t];
     return r >= 0 && in.active[r] ? r : -1;
 }
 // the residual of point p towards target t that addPoint<mode> of the top accumulator takes, or -1
-EDS_WIN_HD int top_res(const AccIn& in, int p, int t) {
+EDS_HD int top_res(const AccIn& in, int p, int t) {
     const int r = in.res_of[p * in.F + t];
     return r >= 0 && top_filter(in.mode, in.active[r], in.lin ? in.lin[r] : 0) ? r : -1;
 }
 // Hcd = Hcd_accAF + Hcd_accLF (AccumulatedSCHessian.cpp:55)
-EDS_WIN_HD float hcd(const AccIn& in, int p, int k) { return in.pout[p].Hcd_accAF[k] + (in.has_lf ? in.lf[6 * p + 2 + k] : 0.0f); }
+EDS_HD float hcd(const AccIn& in, int p, int k) { return in.pout[p].Hcd_accAF[k] + (in.has_lf ? in.lf[6 * p + 2 + k] : 0.0f); }
 
 // the host frame of accumulator word j, and what point p adds to it.  AccumulatorXX::update(L, R, w) adds (w L[i]) R[j],
 // AccumulatorX::update(L, w) adds w L[i] (MatrixAccumulators.h); the weights are HdiF, bdSumF * HdiF (accbc) and HdiF * bdSumF (accEB).
-EDS_WIN_HD int acc_host(int F, int j) {
+EDS_HD int acc_host(int F, int j) {
     if (j < acc_off_e(F)) return (j / TOP_WORDS) % F;
     if (j < acc_off_d(F)) return ((j - acc_off_e(F)) / E_WORDS) % F;
     if (j < acc_off_c(F)) return ((j - acc_off_d(F)) / D_WORDS) % F;
     return (j - acc_off_c(F)) / C_WORDS;
 }
-EDS_WIN_HD double acc_value(const AccIn& in, int j, int p) {
+EDS_HD double acc_value(const AccIn& in, int j, int p) {
     const int F = in.F;
     if (in.sel && !in.sel[p]) return 0.0;
     if (j < acc_off_e(F)) {
@@ -475,7 +463,7 @@ inline void accumulate_serial(const AccIn& in, double* acc) {
         double part[LANES];
         for (int l = 0; l < LANES; ++l) part[l] = 0.0;
         for (int p = in.first[h]; p < in.first[h + 1]; ++p) part[(p - in.first[h]) % LANES] += acc_value(in, j, p);
-        acc[j] = edsct::reduce_lanes(part);
+        acc[j] = edsdso::reduce_lanes(part);
     }
 }
 
@@ -574,7 +562,7 @@ inline void stitch_serial(int F, const double* acc, const double* adH, const dou
 // Every entry receives the same addends in the same order as in stitch_serial: a block product's entry is sum_k (sum_l A(r,l) M(l,k)) B(c,k)
 // with both sums from 0.0 left to right, and the products are added into the entry in the loop and statement order of the reference.
 // entry (r, c) of the 13 x 13 H of AccumulatorApprox::finish, straight from the 91 words
-EDS_WIN_HD double h13_at(const double* w, int r, int c) {
+EDS_HD double h13_at(const double* w, int r, int c) {
     const int a = r < c ? r : c, b = r < c ? c : r;
     if (b < 10) return w[a * 10 - a * (a - 1) / 2 + (b - a)];
     if (a < 10) return w[55 + 3 * a + (b - 10)];
@@ -582,19 +570,19 @@ EDS_WIN_HD double h13_at(const double* w, int r, int c) {
 }
 // sum_l A(r, l) M(l, c) with M given by a word array and a (row, column) -> word rule: kind 0 the 13 x 13 H at offset (4 + l, c0 + c),
 // kind 1 a dense row-major matrix with `ms` columns
-EDS_WIN_HD double m_at(const double* w, int kind, int ms, int c0, int l, int c) { return kind == 0 ? h13_at(w, 4 + l, c0 + c) : w[ms * l + c]; }
-EDS_WIN_HD double row_dot(const double* A, int r, const double* w, int kind, int ms, int c0, int c) {
+EDS_HD double m_at(const double* w, int kind, int ms, int c0, int l, int c) { return kind == 0 ? h13_at(w, 4 + l, c0 + c) : w[ms * l + c]; }
+EDS_HD double row_dot(const double* A, int r, const double* w, int kind, int ms, int c0, int c) {
     double v = 0.0;
     for (int l = 0; l < 8; ++l) v += A[8 * r + l] * m_at(w, kind, ms, c0, l, c);
     return v;
 }
-EDS_WIN_HD double tri_at(const double* A, const double* w, int kind, int ms, int c0, const double* B, int r, int c) {
+EDS_HD double tri_at(const double* A, const double* w, int kind, int ms, int c0, const double* B, int r, int c) {
     double v = 0.0;
     for (int k = 0; k < 8; ++k) v += row_dot(A, r, w, kind, ms, c0, k) * B[8 * c + k];
     return v;
 }
 // H_A before the transposed copies: i a pose row or a calibration row, j a column or N for b; only the entries the accumulation writes
-EDS_WIN_HD double top_raw(int F, const double* acc, const double* adH, const double* adT, int i, int j) {
+EDS_HD double top_raw(int F, const double* acc, const double* adH, const double* adT, int i, int j) {
     const int N = 4 + 8 * F;
     const bool pi = i >= 4, pj = j >= 4 && j < N;
     const int I = pi ? (i - 4) / 8 : -1, r = pi ? (i - 4) % 8 : i, J = pj ? (j - 4) / 8 : -1, c = pj ? (j - 4) % 8 : j;
@@ -622,7 +610,7 @@ EDS_WIN_HD double top_raw(int F, const double* acc, const double* adH, const dou
         }
     return v;
 }
-EDS_WIN_HD double top_entry(int F, const double* acc, const double* adH, const double* adT, int i, int j) {
+EDS_HD double top_entry(int F, const double* acc, const double* adH, const double* adT, int i, int j) {
     const int N = 4 + 8 * F;
     if (j == N) return top_raw(F, acc, adH, adT, i, j);
     if (i < 4 && j >= 4) return top_raw(F, acc, adH, adT, j, i);
@@ -633,7 +621,7 @@ EDS_WIN_HD double top_entry(int F, const double* acc, const double* adH, const d
     }
     return top_raw(F, acc, adH, adT, i, j);
 }
-EDS_WIN_HD double sc_entry(int F, const double* acc, const double* adH, const double* adT, int i, int j) {
+EDS_HD double sc_entry(int F, const double* acc, const double* adH, const double* adT, int i, int j) {
     const int N = 4 + 8 * F;
     if (i < 4 && j >= 4 && j < N) { const int t = i; i = j; j = t; }          // the calibration rows are the transposed copies
     if (i < 4) {                                                                 // accHcc, accbc: hosts left to right
@@ -675,8 +663,8 @@ EDS_WIN_HD double sc_entry(int F, const double* acc, const double* adH, const do
     return v;
 }
 // out: H_A (N N), b_A (N), H_sc (N N), b_sc (N), one after the other; entry e of 2 N (N + 1)
-EDS_WIN_HD int stitch_words(int F) { const int N = 4 + 8 * F; return 2 * N * (N + 1); }
-EDS_WIN_HD void stitch_entry(int F, const double* acc, const double* adH, const double* adT, int e, double* out) {
+EDS_HD int stitch_words(int F) { const int N = 4 + 8 * F; return 2 * N * (N + 1); }
+EDS_HD void stitch_entry(int F, const double* acc, const double* adH, const double* adT, int e, double* out) {
     const int N = 4 + 8 * F, half = N * (N + 1), q = e % half;
     const int i = q < N * N ? q / N : q - N * N, j = q < N * N ? q % N : N;
     out[e] = e < half ? top_entry(F, acc, adH, adT, i, j) : sc_entry(F, acc, adH, adT, i, j);

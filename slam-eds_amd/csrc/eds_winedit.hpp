@@ -11,11 +11,7 @@
 #include <cstdint>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define EDS_WED_HD __host__ __device__ inline
-#else
-#define EDS_WED_HD inline
-#endif
+#include "eds_dso_common.hpp"
 
 namespace edswed {
 
@@ -39,10 +35,10 @@ inline void cols_add(Cols& t, const void* src, void* dst, int words) {
 
 // ---- which rows stay ---------------------------------------------------------------------------------------------------------------------
 // eds_wed_remove_residuals: select given, the residuals it marks go; select == NULL, every residual whose state is not IN goes
-EDS_WED_HD int32_t keep_residual(const int32_t* select, const int32_t* state, int r) { return select ? select[r] == 0 : state[r] == ST_IN; }
+EDS_HD int32_t keep_residual(const int32_t* select, const int32_t* state, int r) { return select ? select[r] == 0 : state[r] == ST_IN; }
 // eds_wed_remove_points: a flagged point goes, and a residual goes with its point
-EDS_WED_HD int32_t keep_point(const int32_t* flag, int p) { return flag[p] == 0; }
-EDS_WED_HD int32_t keep_residual_of(const int32_t* keep_point_, const int32_t* res_point, int r) { return keep_point_[res_point[r]]; }
+EDS_HD int32_t keep_point(const int32_t* flag, int p) { return flag[p] == 0; }
+EDS_HD int32_t keep_residual_of(const int32_t* keep_point_, const int32_t* res_point, int r) { return keep_point_[res_point[r]]; }
 
 // excl[i] = the kept rows before row i, excl[n] = all of them; map[excl[i]] = i for every kept row.  Returns excl[n].
 inline int scan_serial(const int32_t* keep, int n, int32_t* excl, int32_t* map) {
@@ -57,14 +53,14 @@ inline int scan_serial(const int32_t* keep, int n, int32_t* excl, int32_t* map) 
 
 // ---- moving the rows -----------------------------------------------------------------------------------------------------------------------
 // both sides copy through the compiler's memcpy with a constant size: no pointer is read through another type
-template <int BYTES, int ALIGN> EDS_WED_HD void copy_bytes(char* dst, const char* src) {
+template <int BYTES, int ALIGN> EDS_HD void copy_bytes(char* dst, const char* src) {
     __builtin_memcpy(__builtin_assume_aligned(dst, ALIGN), __builtin_assume_aligned(src, ALIGN), BYTES);
 }
-template <int BYTES, int ALIGN> EDS_WED_HD void zero_bytes(char* dst) { __builtin_memset(__builtin_assume_aligned(dst, ALIGN), 0, BYTES); }
+template <int BYTES, int ALIGN> EDS_HD void zero_bytes(char* dst) { __builtin_memset(__builtin_assume_aligned(dst, ALIGN), 0, BYTES); }
 // map[i] < 0: row i is new (eds_wed_insert_activated): every word of it starts as 0
 
 // word g of the narrow columns: new row g / t.words, word g % t.words of the row, counted over the columns one after the other
-EDS_WED_HD void move_word(const Cols& t, const int32_t* map, int64_t g) {
+EDS_HD void move_word(const Cols& t, const int32_t* map, int64_t g) {
     const int64_t i = g / t.words;
     const int w = (int)(g % t.words);
     int k = 0;
@@ -76,7 +72,7 @@ EDS_WED_HD void move_word(const Cols& t, const int32_t* map, int64_t g) {
 }
 
 // piece g of a 74-word column: new row g / 19, piece g % 19.  A row starts at a multiple of 296 bytes, so a piece is aligned to 8.
-EDS_WED_HD void move_wide(const char* src, char* dst, const int32_t* map, int64_t g) {
+EDS_HD void move_wide(const char* src, char* dst, const int32_t* map, int64_t g) {
     const int64_t i = g / WIDE_PIECES;
     const int c = (int)(g % WIDE_PIECES);
     char* d = dst + 4 * (i * WIDE_WORDS) + 16 * c;
@@ -91,12 +87,12 @@ EDS_WED_HD void move_wide(const char* src, char* dst, const int32_t* map, int64_
 }
 
 // the point of new residual i: its old point's new index (new_point == NULL: the points did not move)
-EDS_WED_HD int32_t moved_res_point(const int32_t* res_point, const int32_t* map_r, const int32_t* new_point, int i) {
+EDS_HD int32_t moved_res_point(const int32_t* res_point, const int32_t* map_r, const int32_t* new_point, int i) {
     const int32_t p = res_point[map_r[i]];
     return new_point ? new_point[p] : p;
 }
 // the first residual of new point q (q = n_new: the end of the table): the kept residuals before its old first one
-EDS_WED_HD int32_t moved_res_first(const int32_t* res_first, const int32_t* map_p, const int32_t* excl_r, int q, int n_new, int m_new) {
+EDS_HD int32_t moved_res_first(const int32_t* res_first, const int32_t* map_p, const int32_t* excl_r, int q, int n_new, int m_new) {
     if (q >= n_new) return m_new;
     return excl_r[res_first[map_p ? map_p[q] : q]];
 }
@@ -138,10 +134,10 @@ inline void per_host_counts(const std::vector<int32_t>& host_of, int32_t* per_ho
 // points come first, in order, then the host's activated points in index order; a new point's residuals in ascending target.
 constexpr int ST_OUTLIER = 2, FATE_ACTIVATED = 9;
 struct ImmCounts { int32_t n[MAX_FRAMES]; };                    // immature points per host
-EDS_WED_HD int32_t ins_keep_candidate(const ImmCounts& nn, const int32_t* fate, int mp, int c) {
+EDS_HD int32_t ins_keep_candidate(const ImmCounts& nn, const int32_t* fate, int mp, int c) {
     return c % mp < nn.n[c / mp] && fate[c] == FATE_ACTIVATED;
 }
-EDS_WED_HD int32_t ins_keep_cell(const ImmCounts& nn, const int32_t* fate, const int32_t* res_state, int F, int mp, int stride, int64_t g) {
+EDS_HD int32_t ins_keep_cell(const ImmCounts& nn, const int32_t* fate, const int32_t* res_state, int F, int mp, int stride, int64_t g) {
     const int c = (int)(g / F), t = (int)(g % F);
     return ins_keep_candidate(nn, fate, mp, c) && res_state[(int64_t)c * stride + t] == ST_IN;
 }
@@ -150,15 +146,15 @@ struct Ins {
     const int32_t *first, *res_first;                           // the window's hosts' runs [9] and res_first [n + 1] BEFORE the insert
     const int32_t *excl_c, *excl_g;
 };
-EDS_WED_HD int ins_old_point(const Ins& s, int p, int host) { return p + s.excl_c[host * s.mp]; }
-EDS_WED_HD int ins_new_point(const Ins& s, int c) { return s.first[c / s.mp + 1] + s.excl_c[c]; }
-EDS_WED_HD int ins_old_res(const Ins& s, int r, int host) { return r + s.excl_g[(int64_t)host * s.mp * s.F]; }
-EDS_WED_HD int ins_new_res(const Ins& s, int64_t g) { return s.res_first[s.first[(int)(g / s.F) / s.mp + 1]] + s.excl_g[g]; }
+EDS_HD int ins_old_point(const Ins& s, int p, int host) { return p + s.excl_c[host * s.mp]; }
+EDS_HD int ins_new_point(const Ins& s, int c) { return s.first[c / s.mp + 1] + s.excl_c[c]; }
+EDS_HD int ins_old_res(const Ins& s, int r, int host) { return r + s.excl_g[(int64_t)host * s.mp * s.F]; }
+EDS_HD int ins_new_res(const Ins& s, int64_t g) { return s.res_first[s.first[(int)(g / s.F) / s.mp + 1]] + s.excl_g[g]; }
 
 // ---- a frame leaves: the tables ----------------------------------------------------------------------------------------------------------------
 // every residual towards the frame goes (FullSystem drops them before marginalizeFrame); hosts and targets above it go down by one
-EDS_WED_HD int32_t keep_residual_not_towards(const int32_t* res_target, int frame, int r) { return res_target[r] != frame; }
-EDS_WED_HD int32_t frame_after(int32_t f, int frame) { return f > frame ? f - 1 : f; }
+EDS_HD int32_t keep_residual_not_towards(const int32_t* res_target, int frame, int r) { return res_target[r] != frame; }
+EDS_HD int32_t frame_after(int32_t f, int frame) { return f > frame ? f - 1 : f; }
 
 // ---- a frame leaves: EnergyFunctional::marginalizeFrame's arithmetic (EnergyFunctional.cpp:516-576), fp64 -----------------------------------
 // N = 4 + 8 F, nd = N - 8.  In the order of the reference's lines, every step by the thread that owns its entry:
@@ -189,11 +185,11 @@ struct MargIo {
     double *HM_out, *bM_out;                                    // (N - 8) x (N - 8), N - 8; may be HM, bM: everything is read before anything is written
     int32_t* flag;                                              // set to 1 where the header says EDS_ERR_NOT_USABLE
 };
-EDS_WED_HD bool finite_d(double v) { return v - v == 0.0; }
-EDS_WED_HD int marg_perm(int i, int io, int nd) { return i < io ? i : i < nd ? i + 8 : io + (i - nd); }
+EDS_HD bool finite_d(double v) { return v - v == 0.0; }
+EDS_HD int marg_perm(int i, int io, int nd) { return i < io ? i : i < nd ? i + 8 : io + (i - nd); }
 
 // step 5, by one thread: a[64] row-major in (the LU overwrites it), hpi[64] out; false for a zero pivot or a result that is not finite
-EDS_WED_HD bool inverse8(double* a, double* hpi) {
+EDS_HD bool inverse8(double* a, double* hpi) {
     int perm[8];
     for (int i = 0; i < 8; ++i) perm[i] = i;
     for (int k = 0; k < 8; ++k) {
@@ -234,7 +230,7 @@ EDS_WED_HD bool inverse8(double* a, double* hpi) {
     return true;
 }
 
-template <class Sync> EDS_WED_HD void marg_frame_body(const MargIo& io, MargMem& m, int tid, int nt, Sync sync) {
+template <class Sync> EDS_HD void marg_frame_body(const MargIo& io, MargMem& m, int tid, int nt, Sync sync) {
     const int N = io.N, nd = N - 8, fo = 4 + 8 * io.frame;
     if (tid == 0) m.bad = 0;
     for (int e = tid; e < N * N; e += nt) m.H[e] = io.HM[(size_t)marg_perm(e / N, fo, nd) * N + marg_perm(e % N, fo, nd)];
@@ -298,8 +294,7 @@ template <class Sync> EDS_WED_HD void marg_frame_body(const MargIo& io, MargMem&
     for (int e = tid; e < nd * nd; e += nt) { const int i = e / nd, j = e % nd; io.HM_out[e] = 0.5 * (m.H[i * N + j] + m.H[j * N + i]); }
     for (int i = tid; i < nd; i += nt) io.bM_out[i] = m.b[i];
 }
-struct NoSync { EDS_WED_HD void operator()() const {} };
-inline void marg_frame_serial(const MargIo& io, MargMem& m) { marg_frame_body(io, m, 0, 1, NoSync()); }
+inline void marg_frame_serial(const MargIo& io, MargMem& m) { marg_frame_body(io, m, 0, 1, edsdso::NoSync()); }
 
 // ---- the serial evaluator: what the kernels do, row by row --------------------------------------------------------------------------------
 inline void gather_serial(const Cols& narrow, const Cols& wide, const int32_t* map, int rows_new) {

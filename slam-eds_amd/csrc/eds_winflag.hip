@@ -116,10 +116,6 @@ __global__ void __launch_bounds__(TB) k_wfl_select(int n, const int32_t* __restr
     if (p < n) sel[p] = value < 0 ? fate[p] != edswfl::KEEP : fate[p] == value;
 }
 
-__device__ inline int wave_sum(int v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
 __global__ void __launch_bounds__(TB) k_wfl_apply_fixed(Hist h, int n, int F, const edswin::Precalc* __restrict__ pcs, const edswin::Point* __restrict__ pts,
                                                         const float* __restrict__ ids, const int32_t* __restrict__ res_first,
                                                         const int32_t* __restrict__ res_target, const int32_t* __restrict__ state,
@@ -132,7 +128,7 @@ __global__ void __launch_bounds__(TB) k_wfl_apply_fixed(Hist h, int n, int F, co
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int total = wave_sum(c[k]);
+        const int total = edsdso::wave_fold_i(c[k]);
         if ((threadIdx.x & 63) == 0 && total) atomicAdd(counts + k, total);
     }
 }

@@ -10,11 +10,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define EDS_WFL_HD __host__ __device__ inline
-#else
-#define EDS_WFL_HD inline
-#endif
+#include "eds_dso_common.hpp"
 
 namespace edswfl {
 
@@ -29,7 +25,7 @@ struct Hist {
 };
 
 // ---- a point's and a residual's first values (PointHessian's and PointFrameResidual's constructors) -------------------------------------
-EDS_WFL_HD void default_point(const Hist& h, int p) {
+EDS_HD void default_point(const Hist& h, int p) {
     h.num_good[p] = 0;
     h.max_rel_baseline[p] = 0.0f;
     h.last_target[2 * p] = h.last_target[2 * p + 1] = -1;
@@ -37,7 +33,7 @@ EDS_WFL_HD void default_point(const Hist& h, int p) {
 }
 // an activated point enters a window of F frames: lastResiduals[0] is its residual towards frame F - 1 and [1] the one towards F - 2,
 // where the fit gave it one (state IN); a null pointer with state OOB otherwise
-EDS_WFL_HD void activated_point(const Hist& h, int q, int F, int got_last, int got_prev) {
+EDS_HD void activated_point(const Hist& h, int q, int F, int got_last, int got_prev) {
     h.num_good[q] = 0;
     h.max_rel_baseline[q] = 0.0f;
     h.last_target[2 * q] = got_last ? F - 1 : -1;
@@ -48,26 +44,26 @@ EDS_WFL_HD void activated_point(const Hist& h, int q, int F, int got_last, int g
 
 // ---- the edits -----------------------------------------------------------------------------------------------------------------------------
 // the residual (p, target) leaves: lastResiduals[k].first = 0 where it named that residual; the state stays
-EDS_WFL_HD void forget_residual(int32_t* last_target, int p, int target) {
+EDS_HD void forget_residual(int32_t* last_target, int p, int target) {
     for (int k = 0; k < 2; ++k)
         if (last_target[2 * p + k] == target) last_target[2 * p + k] = -1;
 }
 // frame `frame` left the window: the frames above it are one lower; -1 stays
-EDS_WFL_HD int32_t target_after(int32_t t, int frame) { return t > frame ? t - 1 : t; }
+EDS_HD int32_t target_after(int32_t t, int frame) { return t > frame ? t - 1 : t; }
 
 // ---- makeKeyFrame's loop: every point not hosted by `frame` and without a residual towards it gets one, at the END of its run -------------
-EDS_WFL_HD int32_t needs_residual(const int32_t* res_first, const int32_t* res_target, int host, int p, int frame) {
+EDS_HD int32_t needs_residual(const int32_t* res_first, const int32_t* res_target, int host, int p, int frame) {
     if (host == frame) return 0;
     for (int r = res_first[p]; r < res_first[p + 1]; ++r)
         if (res_target[r] == frame) return 0;
     return 1;
 }
 // excl[p]: the new residuals of the points before p.  Old residual r of point p moves to r + excl[p]; p's new one sits behind its run
-EDS_WFL_HD int moved_row(const int32_t* excl, int p, int r) { return r + excl[p]; }
-EDS_WFL_HD int new_row(const int32_t* res_first, const int32_t* excl, int p) { return res_first[p + 1] + excl[p]; }
-EDS_WFL_HD int32_t moved_first(const int32_t* res_first, const int32_t* excl, int q) { return res_first[q] + excl[q]; }   // q = n: the table's end
+EDS_HD int moved_row(const int32_t* excl, int p, int r) { return r + excl[p]; }
+EDS_HD int new_row(const int32_t* res_first, const int32_t* excl, int p) { return res_first[p + 1] + excl[p]; }
+EDS_HD int32_t moved_first(const int32_t* res_first, const int32_t* excl, int q) { return res_first[q] + excl[q]; }   // q = n: the table's end
 // p->lastResiduals[1] = p->lastResiduals[0]; p->lastResiduals[0] = (r, IN)
-EDS_WFL_HD void shift_last(const Hist& h, int p, int frame) {
+EDS_HD void shift_last(const Hist& h, int p, int frame) {
     h.last_target[2 * p + 1] = h.last_target[2 * p];
     h.last_state[2 * p + 1] = h.last_state[2 * p];
     h.last_target[2 * p] = frame;
@@ -76,7 +72,7 @@ EDS_WFL_HD void shift_last(const Hist& h, int p, int frame) {
 
 // ---- the fixLinearization half of linearizeAll, after applyRes(true) ---------------------------------------------------------------------
 // relBS of one residual: pc is the (host, target) precalc record; every row of PRE_KRKiTll (u, v, 1) is summed left to right
-EDS_WFL_HD float rel_baseline(const float* pc, float u, float v, float idepth_scaled) {
+EDS_HD float rel_baseline(const float* pc, float u, float v, float idepth_scaled) {
     const float i0 = (pc[0] * u + pc[1] * v) + pc[2] * 1.0f;
     const float i1 = (pc[3] * u + pc[4] * v) + pc[5] * 1.0f;
     const float i2 = (pc[6] * u + pc[7] * v) + pc[8] * 1.0f;
@@ -85,7 +81,7 @@ EDS_WFL_HD float rel_baseline(const float* pc, float u, float v, float idepth_sc
     return (float)(0.01 * (double)sqrtf(dx * dx + dy * dy));
 }
 // One point, its residuals in table order.  pcs: F x F records, [host F + target].  counts[state] += 1 for every residual.
-EDS_WFL_HD void apply_fixed_point(const Hist& h, int p, const int32_t* res_first, const int32_t* res_target, const int32_t* state, const int32_t* active,
+EDS_HD void apply_fixed_point(const Hist& h, int p, const int32_t* res_first, const int32_t* res_target, const int32_t* state, const int32_t* active,
                                   const float* pcs, int F, int host, float u, float v, float idepth_scaled, int clear_is_new, int32_t* counts) {
     int32_t good = h.num_good[p], t0 = h.last_target[2 * p], t1 = h.last_target[2 * p + 1], s0 = h.last_state[2 * p], s1 = h.last_state[2 * p + 1];
     float best = h.max_rel_baseline[p];
@@ -111,10 +107,10 @@ EDS_WFL_HD void apply_fixed_point(const Hist& h, int p, const int32_t* res_first
 constexpr int KEEP = 0, MARGINALIZE = 1, DROP = 2, CANDIDATE = 3;   // CANDIDATE: between the two phases only — to be re-linearized, then 1 or 2
 // setting_minGoodActiveResForMarg, setting_minGoodResForMarg, setting_minIdepthH_marg (settings.cpp:68, 106-107)
 struct Params { int32_t min_good_active_res_for_marg, min_good_res_for_marg; float min_idepth_h_marg; int32_t reserved; };
-EDS_WFL_HD Params params_default() { Params p = {3, 4, 50.0f, 0}; return p; }
+EDS_HD Params params_default() { Params p = {3, 4, 50.0f, 0}; return p; }
 
 // PointHessian::isOOB (HessianBlocks.h:474-497) with toMarg as a bit mask of frames; the run length plays residuals.size()
-EDS_WFL_HD bool is_oob(const Params& s, const Hist& h, int p, const int32_t* res_first, const int32_t* res_target, const int32_t* state, uint32_t frames_to_marg) {
+EDS_HD bool is_oob(const Params& s, const Hist& h, int p, const int32_t* res_first, const int32_t* res_target, const int32_t* state, uint32_t frames_to_marg) {
     const int size = res_first[p + 1] - res_first[p];
     int vis_in_to_marg = 0;
     for (int r = res_first[p]; r < res_first[p + 1]; ++r) {
@@ -128,11 +124,11 @@ EDS_WFL_HD bool is_oob(const Params& s, const Hist& h, int p, const int32_t* res
     return false;
 }
 // PointHessian::isInlierNew (HessianBlocks.h:500-504)
-EDS_WFL_HD bool is_inlier_new(const Params& s, const Hist& h, int p, const int32_t* res_first) {
+EDS_HD bool is_inlier_new(const Params& s, const Hist& h, int p, const int32_t* res_first) {
     return res_first[p + 1] - res_first[p] >= s.min_good_active_res_for_marg && h.num_good[p] >= s.min_good_res_for_marg;
 }
 // phase one: KEEP, DROP, or CANDIDATE (its residuals are re-linearized before finish_fate decides between MARGINALIZE and DROP)
-EDS_WFL_HD int32_t first_fate(const Params& s, const Hist& h, int p, int host, float idepth_scaled, const int32_t* res_first, const int32_t* res_target,
+EDS_HD int32_t first_fate(const Params& s, const Hist& h, int p, int host, float idepth_scaled, const int32_t* res_first, const int32_t* res_target,
                               const int32_t* state, uint32_t frames_to_marg, int only_empty) {
     const bool empty = res_first[p + 1] == res_first[p];
     if (only_empty) return empty ? DROP : KEEP;
@@ -141,14 +137,14 @@ EDS_WFL_HD int32_t first_fate(const Params& s, const Hist& h, int p, int host, f
     return KEEP;
 }
 // resetOOB (Residuals.h:92-98) and isLinearized = false for one residual of a candidate
-EDS_WFL_HD void reset_oob(int r, int32_t* state, int32_t* new_state, float* energy, float* new_energy, int32_t* lin) {
+EDS_HD void reset_oob(int r, int32_t* state, int32_t* new_state, float* energy, float* new_energy, int32_t* lin) {
     new_energy[r] = 0.0f; energy[r] = 0.0f;
     new_state[r] = ST_OUTLIER;
     state[r] = ST_IN;
     lin[r] = 0;
 }
 // phase two's end: the Hessian the last eds_win_point_hessians / eds_win_accumulate left decides
-EDS_WFL_HD int32_t finish_fate(const Params& s, int32_t fate, float idepth_hessian) {
+EDS_HD int32_t finish_fate(const Params& s, int32_t fate, float idepth_hessian) {
     if (fate != CANDIDATE) return fate;
     return idepth_hessian > s.min_idepth_h_marg ? MARGINALIZE : DROP;
 }

@@ -97,10 +97,6 @@ __global__ void __launch_bounds__(TB) k_wsv_delta_of_idepths(int n, float scale,
     if (p < n) delta[p] = edswsv::delta_of_idepths(ids[p], idz[p], scale);
 }
 
-__device__ inline double wave_fold(double v) {
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_down(v, s);
-    return v;
-}
 // calcLEnergyF_MT: per host frame the 512 lanes stride its points and fold as csrc/eds_window.hpp says, hosts left to right, then the priors
 __global__ void __launch_bounds__(edswin::LANES) k_wsv_l_energy(Lin t, const int32_t* __restrict__ first, const double* __restrict__ vec, const float* __restrict__ cF,
                                                                double* out) {
@@ -110,10 +106,10 @@ __global__ void __launch_bounds__(edswin::LANES) k_wsv_l_energy(Lin t, const int
     for (int h = 0; h < t.F; ++h) {
         double v = 0.0;
         for (int p = first[h] + (int)threadIdx.x; p < first[h + 1]; p += edswin::LANES) v += edswsv::lenergy_point(t, p);
-        v = wave_fold(v);
+        v = edsdso::wave_fold(v);
         if (lane == 0) part[wave] = v;
         __syncthreads();
-        if (threadIdx.x == 0) total += ((((((part[0] + part[1]) + part[2]) + part[3]) + part[4]) + part[5]) + part[6]) + part[7];
+        if (threadIdx.x == 0) total += edsdso::add8(part);
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = edswsv::lenergy_priors(t.F, vec, cF) + total;

@@ -19,12 +19,6 @@
 #pragma once
 #include "eds_window.hpp"
 
-#if defined(__HIPCC__)
-#define EDS_WSV_HD __host__ __device__ inline
-#else
-#define EDS_WSV_HD inline
-#endif
-
 namespace edswsv {
 
 using edswin::J_WORDS;
@@ -38,18 +32,18 @@ enum { SOLVER_SVD = 1, SOLVER_ORTHOGONALIZE_SYSTEM = 2, SOLVER_ORTHOGONALIZE_POI
        SOLVER_STEPMOMENTUM = 1024, SOLVER_ORTHOGONALIZE_X_LATER = 2048 };
 constexpr int MODE_HONOURED = SOLVER_ORTHOGONALIZE_SYSTEM | SOLVER_USE_GN | SOLVER_FIX_LAMBDA | SOLVER_ORTHOGONALIZE_X | SOLVER_ORTHOGONALIZE_X_LATER |
                               SOLVER_REMOVE_POSEPRIOR;
-EDS_WSV_HD bool mode_valid(int mode) { return (mode & ~MODE_HONOURED) == 0; }
-EDS_WSV_HD double mode_lambda(int mode, double lambda) {
+EDS_HD bool mode_valid(int mode) { return (mode & ~MODE_HONOURED) == 0; }
+EDS_HD double mode_lambda(int mode, double lambda) {
     if (mode & SOLVER_USE_GN) lambda = 0;
     if (mode & SOLVER_FIX_LAMBDA) lambda = 1e-5;
     return lambda;
 }
-EDS_WSV_HD bool mode_orth_x(int mode, int iteration) { return (mode & SOLVER_ORTHOGONALIZE_X) || (iteration >= 2 && (mode & SOLVER_ORTHOGONALIZE_X_LATER)); }
-EDS_WSV_HD bool finite_d(double v) { return v - v == 0.0; }
+EDS_HD bool mode_orth_x(int mode, int iteration) { return (mode & SOLVER_ORTHOGONALIZE_X) || (iteration >= 2 && (mode & SOLVER_ORTHOGONALIZE_X_LATER)); }
+EDS_HD bool finite_d(double v) { return v - v == 0.0; }
 
 // ---- setDeltaF (EnergyFunctional.cpp:171-194) ---------------------------------------------------------------------------------------------
 // adHTdeltaF[h + F t][j] = sum_k (float)delta_h[k] adHostF(k, j), from 0 with k = 0 ... 7, the same for the target, the two added
-EDS_WSV_HD void adht_delta(const float* adHostF, const float* adTargetF, const double* delta_h, const double* delta_t, float* out) {
+EDS_HD void adht_delta(const float* adHostF, const float* adTargetF, const double* delta_h, const double* delta_t, float* out) {
     for (int j = 0; j < 8; ++j) {
         float a = 0, b = 0;
         for (int k = 0; k < 8; ++k) a += (float)delta_h[k] * adHostF[8 * k + j];
@@ -60,20 +54,20 @@ EDS_WSV_HD void adht_delta(const float* adHostF, const float* adTargetF, const d
 
 // ---- fixLinearizationF (EnergyFunctionalStructs.cpp:87-113), mode 1's resApprox (AccumulatedTopHessian.cpp:78-96) --------------------------
 // Jp_delta of row q (0: x, 1: y): the 6-term dot, the 4-term dot, the Jpdd product, each dot from 0 in index order, added left to right
-EDS_WSV_HD float jp_delta(const float* J, int q, const float* dp, const float* dc, float dd) {
+EDS_HD float jp_delta(const float* J, int q, const float* dp, const float* dc, float dd) {
     float a = 0, b = 0;
     for (int i = 0; i < 6; ++i) a += J[edswin::J_JPDXI + 6 * q + i] * dp[i];
     for (int i = 0; i < 4; ++i) b += J[edswin::J_JPDC + 4 * q + i] * dc[i];
     return (a + b) + J[edswin::J_JPDD + q] * dd;
 }
-EDS_WSV_HD float rtz_tap(const float* J, int i, float jx, float jy, float da, float db) {
+EDS_HD float rtz_tap(const float* J, int i, float jx, float jy, float da, float db) {
     return (((J[edswin::J_RESF + i] - J[edswin::J_JIDX + i] * jx) - J[edswin::J_JIDX + 8 + i] * jy) - J[edswin::J_JABF + i] * da) - J[edswin::J_JABF + 8 + i] * db;
 }
-EDS_WSV_HD float approx_tap(const float* J, float rtz, int i, float jx, float jy, float da, float db) {
+EDS_HD float approx_tap(const float* J, float rtz, int i, float jx, float jy, float da, float db) {
     return (((rtz + J[edswin::J_JIDX + i] * jx) + J[edswin::J_JIDX + 8 + i] * jy) + J[edswin::J_JABF + i] * da) + J[edswin::J_JABF + 8 + i] * db;
 }
 // calcLEnergyPt's term of one tap (EnergyFunctional.cpp:366-379): Jdelta ((rtz + rtz) + Jdelta)
-EDS_WSV_HD float lenergy_tap(const float* J, float rtz, int i, float jx, float jy, float da, float db) {
+EDS_HD float lenergy_tap(const float* J, float rtz, int i, float jx, float jy, float da, float db) {
     const float jd = ((J[edswin::J_JIDX + i] * jx + J[edswin::J_JIDX + 8 + i] * jy) + J[edswin::J_JABF + i] * da) + J[edswin::J_JABF + 8 + i] * db;
     return jd * ((rtz + rtz) + jd);
 }
@@ -87,20 +81,20 @@ struct Lin {
 };
 
 // one tap of one residual: fixLinearizationF's res_toZeroF, and resApprox of mode 1 (2: res_toZeroF itself)
-EDS_WSV_HD void res_deltas(const Lin& t, int r, float* jx, float* jy, const float** dp) {
+EDS_HD void res_deltas(const Lin& t, int r, float* jx, float* jy, const float** dp) {
     const int p = t.res_point[r];
     const float* J = t.efJ + (size_t)r * J_WORDS;
     *dp = t.adHTdeltaF + (size_t)(t.pts[p].host + t.F * t.res_target[r]) * 8;
     *jx = jp_delta(J, 0, *dp, t.cDeltaF, t.deltaF[p]);
     *jy = jp_delta(J, 1, *dp, t.cDeltaF, t.deltaF[p]);
 }
-EDS_WSV_HD float fix_tap(const Lin& t, int r, int i) {
+EDS_HD float fix_tap(const Lin& t, int r, int i) {
     float jx, jy;
     const float* dp;
     res_deltas(t, r, &jx, &jy, &dp);
     return rtz_tap(t.efJ + (size_t)r * J_WORDS, i, jx, jy, dp[6], dp[7]);
 }
-EDS_WSV_HD float res_approx_tap(const Lin& t, int mode, int r, int i) {
+EDS_HD float res_approx_tap(const Lin& t, int mode, int r, int i) {
     const float rtz = t.rtz[(size_t)r * PATTERN + i];
     if (mode != 1) return rtz;
     float jx, jy;
@@ -110,7 +104,7 @@ EDS_WSV_HD float res_approx_tap(const Lin& t, int mode, int r, int i) {
 }
 
 // the sums addPoint<1> / <2> leave in Hdd_accLF, bd_accLF, Hcd_accLF[4] (out[0 .. 5]), residuals in table order; returns the residuals added
-EDS_WSV_HD int lf_sums(const Lin& t, int mode, int p, float* out) {
+EDS_HD int lf_sums(const Lin& t, int mode, int p, float* out) {
     float bd = 0, Hdd = 0, Hcd[4] = {0, 0, 0, 0};
     int n = 0;
     for (int r = t.res_first[p]; r < t.res_first[p + 1]; ++r) {
@@ -124,7 +118,7 @@ EDS_WSV_HD int lf_sums(const Lin& t, int mode, int p, float* out) {
 }
 
 // calcLEnergyPt for one point, in fp64 from 0.0: its linearized active residuals in table order, taps 0 ... 7, then deltaF deltaF priorF
-EDS_WSV_HD double lenergy_point(const Lin& t, int p) {
+EDS_HD double lenergy_point(const Lin& t, int p) {
     double e = 0.0;
     const float dd = t.deltaF[p];
     const int host = t.pts[p].host;
@@ -140,7 +134,7 @@ EDS_WSV_HD double lenergy_point(const Lin& t, int p) {
 }
 // the frames' and the calibration's prior terms of calcLEnergyF_MT (EnergyFunctional.cpp:398-403): vec = delta[68], prior[68],
 // prior * delta_prior[68], delta_prior[68] with the calibration in 0 ... 3; cF = cDeltaF[4], cPriorF[4]
-EDS_WSV_HD double lenergy_priors(int F, const double* vec, const float* cF) {
+EDS_HD double lenergy_priors(int F, const double* vec, const float* cF) {
     double E = 0;
     for (int f = 0; f < F; ++f) {
         double d = 0.0;
@@ -154,7 +148,7 @@ EDS_WSV_HD double lenergy_priors(int F, const double* vec, const float* cF) {
 }
 
 // calcMEnergyF: delta . (2 bM + HM delta), every row and the final dot from 0.0 in index order
-EDS_WSV_HD double menergy_row(int N, const double* HM, const double* bM, const double* delta, int i) {
+EDS_HD double menergy_row(int N, const double* HM, const double* bM, const double* delta, int i) {
     double v = 0.0;
     for (int j = 0; j < N; ++j) v += HM[(size_t)i * N + j] * delta[j];
     return 2 * bM[i] + v;
@@ -164,7 +158,7 @@ EDS_WSV_HD double menergy_row(int N, const double* HM, const double* bM, const d
 // work: the solve's matrices on the device, N N each unless noted, in this order
 enum { W_HM = 0, W_P, W_HT, W_T1, W_T2, W_HF, W_LASTH, W_MATS };
 enum { V_BM = 0, V_BT, V_TB, V_BF, V_LASTB, V_X, V_BMTOP, V_VECS };
-EDS_WSV_HD int work_words() { return W_MATS * MAX_N * MAX_N + V_VECS * MAX_N; }
+EDS_HD int work_words() { return W_MATS * MAX_N * MAX_N + V_VECS * MAX_N; }
 struct Sys {
     int32_t N, system, orth_system;
     double lambda;
@@ -172,14 +166,14 @@ struct Sys {
     const double *HL, *bL;                                      // mode 1's stitch, before the priors
     const double* vec;                                          // delta, prior, prior * delta_prior, delta_prior
     double* work;
-    EDS_WSV_HD double* mat(int k) const { return work + (size_t)k * MAX_N * MAX_N; }
-    EDS_WSV_HD double* v(int k) const { return work + (size_t)W_MATS * MAX_N * MAX_N + (size_t)k * MAX_N; }
+    EDS_HD double* mat(int k) const { return work + (size_t)k * MAX_N * MAX_N; }
+    EDS_HD double* v(int k) const { return work + (size_t)W_MATS * MAX_N * MAX_N + (size_t)k * MAX_N; }
 };
 // stage 0: entry e < N N is (i, j), e >= N N is row i of the right-hand side.  H_L and b_L get usePrior's adds (AccumulatedTopHessian.cpp:
 // 227-237) here, after the stitch.  Without SOLVER_ORTHOGONALIZE_SYSTEM this finishes HFinal_top, bFinal_top, lastHS, lastbS; with it, it
 // leaves HT_act, bT_act.  stages 1 and 2 (only when the system is orthogonalised): T1 = P HT, tb = P bT; T2 = T1 P.  stage 3: the rest of
 // the SYSTEM branch.  Every statement adds left to right as the reference writes it.
-EDS_WSV_HD void assemble(const Sys& s, int stage, int e) {
+EDS_HD void assemble(const Sys& s, int stage, int e) {
     const int N = s.N;
     const bool vecrow = e >= N * N;
     const int i = vecrow ? e - N * N : e / N, j = vecrow ? 0 : e % N;
@@ -238,7 +232,7 @@ struct SolveMem {
     double L[MAX_N * MAX_N], A[MAX_N * (MAX_N + 1) / 2], S[MAX_N], y[MAX_N], acc[MAX_N], dg[MAX_N], W[MAX_N], w[MAX_N], x[MAX_N];
     int32_t perm[MAX_N], pos[MAX_N], bad;
 };
-EDS_WSV_HD int tri(int r, int k) { return r >= k ? r * (r + 1) / 2 + k : k * (k + 1) / 2 + r; }
+EDS_HD int tri(int r, int k) { return r >= k ? r * (r + 1) / 2 + k : k * (k + 1) / 2 + r; }
 
 struct SolveIo {
     int32_t N, F, orth_x;
@@ -250,7 +244,7 @@ struct SolveIo {
     double *L_out, *d_out;                                      // may be NULL: the factors, L (N N, row r, step j), d then perm as doubles (2 N)
 };
 
-template <class Sync> EDS_WSV_HD void solve_body(const SolveIo& io, SolveMem& m, int tid, int nt, Sync sync) {
+template <class Sync> EDS_HD void solve_body(const SolveIo& io, SolveMem& m, int tid, int nt, Sync sync) {
     const int N = io.N;
     for (int r = tid; r < N; r += nt) m.S[r] = 1.0 / sqrt(io.H[(size_t)r * N + r] + 10.0);
     sync();
@@ -346,7 +340,7 @@ template <class Sync> EDS_WSV_HD void solve_body(const SolveIo& io, SolveMem& m,
 
 // ---- resubstituteFPt (EnergyFunctional.cpp:284-317) and setIdepth (HessianBlocks.h:445-448) ---------------------------------------------------
 // xAd: [F host + target][8] then cstep[4]; lf: the point's six linearized sums (Hcd_accLF is lf[2 .. 5])
-EDS_WSV_HD float point_step(const Lin& t, const PointOut& o, const float* lf, const float* JpJdF, const float* xAd, int p) {
+EDS_HD float point_step(const Lin& t, const PointOut& o, const float* lf, const float* JpJdF, const float* xAd, int p) {
     if (o.nres == 0) return 0.0f;
     const float* xc = xAd + t.F * t.F * 8;
     float b = o.bdSumF;
@@ -364,17 +358,16 @@ EDS_WSV_HD float point_step(const Lin& t, const PointOut& o, const float* lf, co
     return -b * o.HdiF;
 }
 // idepth = SCALE_IDEPTH_INVERSE idepth_scaled (setIdepthScaled), and back after the step
-EDS_WSV_HD float idepth_of(float idepth_scaled, float scale_idepth) { return (1.0f / scale_idepth) * idepth_scaled; }
+EDS_HD float idepth_of(float idepth_scaled, float scale_idepth) { return (1.0f / scale_idepth) * idepth_scaled; }
 // setDeltaF's per-point line (EnergyFunctional.cpp:190): deltaF = idepth - idepth_zero, each the scaled value times 1 / SCALE_IDEPTH
-EDS_WSV_HD float delta_of_idepths(float idepth_scaled, float idepth_zero_scaled, float scale_idepth) {
+EDS_HD float delta_of_idepths(float idepth_scaled, float idepth_zero_scaled, float scale_idepth) {
     const float inv = 1.0f / scale_idepth;
     return inv * idepth_scaled - inv * idepth_zero_scaled;
 }
-EDS_WSV_HD float stepped_idepth_scaled(float backup, float fac, float step, float scale_idepth) { return scale_idepth * (backup + fac * step); }
+EDS_HD float stepped_idepth_scaled(float backup, float fac, float step, float scale_idepth) { return scale_idepth * (backup + fac * step); }
 
 #if !defined(__HIP_DEVICE_COMPILE__)
-struct NoSync { void operator()() const {} };
-inline void solve_serial(const SolveIo& io, SolveMem& m) { solve_body(io, m, 0, 1, NoSync()); }
+inline void solve_serial(const SolveIo& io, SolveMem& m) { solve_body(io, m, 0, 1, edsdso::NoSync()); }
 #endif
 
 }  // namespace edswsv

@@ -86,7 +86,7 @@ def test_activate_sources_are_build_inputs():
     import inspect
     assert "eds_hip_activate.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_activate.hip", "eds_hip_activate.h", "eds_activate.hpp", "eds_immature_internal.hpp", "eds_device_owner.hpp"):
+    for f in ("eds_activate.hip", "eds_hip_activate.h", "eds_activate.hpp", "eds_immature_internal.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp"):
         assert f in mk, f
     assert "eds_activate.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-c eds_activate.hip -o /dev/null" in mk

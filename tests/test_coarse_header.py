@@ -89,7 +89,7 @@ def test_coarse_sources_are_build_inputs():
     import inspect
     assert "eds_hip_coarse.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_coarse.hip", "eds_hip_coarse.h", "eds_coarse.hpp", "eds_device_owner.hpp"):
+    for f in ("eds_coarse.hip", "eds_hip_coarse.h", "eds_coarse.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp", "eds_dso_image.hip"):
         assert f in mk, f
     assert "eds_coarse.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_coarse.hip" in mk

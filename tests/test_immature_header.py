@@ -96,6 +96,6 @@ def test_immature_sources_are_build_inputs():
     import inspect
     assert "eds_hip_immature.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_immature.hip", "eds_hip_immature.h", "eds_immature.hpp", "eds_device_owner.hpp"):
+    for f in ("eds_immature.hip", "eds_hip_immature.h", "eds_immature.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp"):
         assert f in mk, f
     assert "eds_immature.o: HIPFLAGS += -ffp-contract=off" in mk

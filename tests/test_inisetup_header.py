@@ -69,7 +69,7 @@ def test_inisetup_sources_are_build_inputs():
     import inspect
     assert "eds_hip_inisetup.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_inisetup.hip", "eds_hip_inisetup.h", "eds_inisetup.hpp", "eds_init_internal.hpp"):
+    for f in ("eds_inisetup.hip", "eds_hip_inisetup.h", "eds_inisetup.hpp", "eds_init_internal.hpp", "eds_dso_common.hpp"):
         assert f in mk, f
     assert "eds_inisetup.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_inisetup.hip" in mk

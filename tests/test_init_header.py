@@ -103,7 +103,7 @@ def test_init_sources_are_build_inputs():
     import inspect
     assert "eds_hip_init.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_init.hip", "eds_hip_init.h", "eds_init.hpp"):
+    for f in ("eds_init.hip", "eds_hip_init.h", "eds_init.hpp", "eds_dso_common.hpp"):
         assert f in mk, f
     assert "eds_init.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_init.hip" in mk

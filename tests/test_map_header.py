@@ -93,6 +93,6 @@ def test_map_sources_are_build_inputs():
     srcs = re.search(r"^SRCS\s*:=(.*)$", mk, re.M).group(1).split()
     hdrs = re.search(r"^HDRS\s*:=(.*)$", mk, re.M).group(1).split()
     assert "eds_map.hip" in srcs
-    assert "eds_map.hpp" in hdrs and "eds_map_internal.hpp" in hdrs and "../../include/eds_hip_map.h" in hdrs
+    assert "eds_map.hpp" in hdrs and "eds_map_internal.hpp" in hdrs and "../../include/eds_hip_map.h" in hdrs and "eds_dso_common.hpp" in hdrs
     assert "eds_map.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-c eds_map.hip -o /dev/null" in mk

@@ -114,7 +114,7 @@ def test_select_sources_are_build_inputs():
     import inspect
     assert "eds_hip_select.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_pixsel.hip", "eds_hip_select.h", "eds_pixsel.hpp", "eds_pixsel_internal.hpp", "eds_device_owner.hpp"):
+    for f in ("eds_pixsel.hip", "eds_hip_select.h", "eds_pixsel.hpp", "eds_pixsel_internal.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp", "eds_dso_image.hip"):
         assert f in mk, f
     assert "eds_pixsel.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-c eds_pixsel.hip -o /dev/null" in mk

@@ -140,6 +140,6 @@ def test_undistort_sources_are_build_inputs():
     srcs = re.search(r"^SRCS\s*:=(.*)$", mk, re.M).group(1).split()
     hdrs = re.search(r"^HDRS\s*:=(.*)$", mk, re.M).group(1).split()
     assert "eds_undistort.hip" in srcs
-    assert "eds_undistort.hpp" in hdrs and "../../include/eds_hip_undistort.h" in hdrs and "eds_device_owner.hpp" in hdrs
+    assert "eds_undistort.hpp" in hdrs and "../../include/eds_hip_undistort.h" in hdrs and "eds_device_owner.hpp" in hdrs and "eds_dso_common.hpp" in hdrs
     assert "eds_undistort.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-c eds_undistort.hip -o /dev/null" in mk

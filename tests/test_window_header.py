@@ -96,7 +96,7 @@ def test_window_sources_are_build_inputs():
     import inspect
     assert "eds_hip_window.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_window.hip", "eds_hip_window.h", "eds_window.hpp", "eds_device_owner.hpp"):
+    for f in ("eds_window.hip", "eds_hip_window.h", "eds_window.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp", "eds_dso_image.hip"):
         assert f in mk, f
     assert "eds_window.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_window.hip" in mk

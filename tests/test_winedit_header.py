@@ -94,7 +94,7 @@ def test_winedit_sources_are_build_inputs():
     import inspect
     assert "eds_hip_winedit.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_winedit.hip", "eds_hip_winedit.h", "eds_winedit.hpp", "eds_window_internal.hpp", "eds_device_owner.hpp"):
+    for f in ("eds_winedit.hip", "eds_hip_winedit.h", "eds_winedit.hpp", "eds_window_internal.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp"):
         assert f in mk, f
     assert "eds_winedit.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_winedit.hip" in mk

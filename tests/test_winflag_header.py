@@ -83,7 +83,7 @@ def test_winflag_c_program_links_every_declared_function(tmp_path):
 def test_winflag_sources_are_build_inputs():
     assert "eds_hip_winflag.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_winflag.hip", "eds_hip_winflag.h", "eds_winflag.hpp"):
+    for f in ("eds_winflag.hip", "eds_hip_winflag.h", "eds_winflag.hpp", "eds_dso_common.hpp"):
         assert f in mk, f
     assert "eds_winflag.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_winflag.hip" in mk

@@ -93,7 +93,7 @@ def test_winsolve_sources_are_build_inputs():
     import inspect
     assert "eds_hip_winsolve.h" in inspect.getsource(capi.build)
     mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    for f in ("eds_winsolve.hip", "eds_hip_winsolve.h", "eds_winsolve.hpp", "eds_window_internal.hpp", "eds_device_owner.hpp"):
+    for f in ("eds_winsolve.hip", "eds_hip_winsolve.h", "eds_winsolve.hpp", "eds_window_internal.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp"):
         assert f in mk, f
     assert "eds_winsolve.o: HIPFLAGS += -ffp-contract=off" in mk
     assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_winsolve.hip" in mk
