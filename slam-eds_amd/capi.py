@@ -128,6 +128,10 @@ UND_EXPORTS = ("eds_und_abi_version", "eds_und_settings_default", "eds_und_creat
 MAP_EXPORTS = ("eds_map_abi_version", "eds_map_window_cloud", "eds_map_window_depth_maps", "eds_map_immature_cloud", "eds_map_set_immature_trace",
                "eds_map_slot_cloud")
 
+# every symbol include/eds_hip_immdepth.h declares: immature points seeded from a depth map on the device, state beside an eds_imm (bound in immdepth.py)
+IMD_EXPORTS = ("eds_imd_abi_version", "eds_imd_set_depth_map", "eds_imd_create_points_selected", "eds_imd_create_points", "eds_imd_get_nearest",
+               "eds_imd_get_tree", "eds_imd_set_debug", "eds_imd_get_info")
+
 # every symbol include/eds_hip_device.h declares: inputs that already live in device memory (its own header and ABI version)
 DEV_EXPORTS = (
     "eds_dev_abi_version", "eds_dev_check_range", "eds_dev_malloc", "eds_dev_free", "eds_dev_upload", "eds_dev_download",
@@ -251,6 +255,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_inisetup.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_undistort.h"))
     srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_map.h"))
+    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_immdepth.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
     rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]

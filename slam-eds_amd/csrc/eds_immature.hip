@@ -273,6 +273,7 @@ void eds_imm_destroy(eds_imm* h) {
     h->own.close();
     edsimm_internal::act_release(h);
     edsmap_internal::release(h->map);
+    edsimm_internal::imd_release(h);
     delete h;
 }
 

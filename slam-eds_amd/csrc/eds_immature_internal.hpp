@@ -1,5 +1,5 @@
-// What eds_immature.hip and eds_activate.hip share: the definition of the opaque eds_imm of include/eds_hip_immature.h and the state
-// include/eds_hip_activate.h keeps beside it.
+// What eds_immature.hip, eds_activate.hip and eds_immdepth.hip share: the definition of the opaque eds_imm of include/eds_hip_immature.h
+// and the state include/eds_hip_activate.h and include/eds_hip_immdepth.h keep beside it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,6 +33,8 @@ struct eds_act_state {
     int active_cap = 0;
 };
 
+struct eds_imd_state;                                  // include/eds_hip_immdepth.h's part, defined in eds_immdepth.hip
+
 struct eds_imm {
     edscapi::DeviceOwner own;
     int H = 0, W = 0, max_hosts = 0, max_points = 0, max_targets = 0;
@@ -50,10 +52,13 @@ struct eds_imm {
     std::vector<uint8_t> host_set, target_set;
     eds_act_state* act = nullptr;
     eds_map_state* map = nullptr;                      // include/eds_hip_map.h's scratch, allocated by the first eds_map_immature_cloud
+    eds_imd_state* imd = nullptr;                      // the depth map, its tree and the nearest points, allocated by the first eds_imd_* call
 };
 
 namespace edsimm_internal {
 // eds_activate.hip
 void act_release(eds_imm* h);
 void act_invalidate(eds_imm* h);                       // a host's image or points were replaced: map, selection and fit no longer hold
+// eds_immdepth.hip
+void imd_release(eds_imm* h);                          // after the owner closed: deletes the struct and its events
 }  // namespace edsimm_internal

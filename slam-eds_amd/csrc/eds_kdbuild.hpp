@@ -11,7 +11,7 @@
 // the OTHER axis' list is partitioned stably by side into [lo, mid) | mid | [mid + 1, hi).  Sub-range bounds follow from m alone
 // (segment_of).  After levels(m) levels every position is a node and both lists are the tree.
 //
-// This header holds what the device kernel (k_kd_build, eds_kfswitch.hip) and the host share — the bounds arithmetic, the order of the
+// This header holds what the device kernel (k_kd_build, eds_kdbuild_kernel.hpp) and the host share — the bounds arithmetic, the order of the
 // two sorts, the ambiguity rule, the LDS layout — and a serial restatement of the kernel's steps (build_sorted) that the CPU tests compare
 // with edskd::build_tree.  Plain C++ outside hipcc.
 #pragma once

@@ -1,7 +1,8 @@
 """ctypes binding of include/eds_hip_map.h: the map as EDS publishes it and as the tracker takes it — ``dso::io::getMap`` over a
 ``window.Window``, ``getImmatureMap`` over an ``immature.ImmaturePoints``, ``KeyFrame::getMap``'s points over a tracker ``capi.Handle``,
 and the depth maps the next event keyframes are created from (the window's points moved into each new keyframe and pushed through
-``IDepthMap::fromPoints``), which ``build_keyframes_from_window`` hands to ``eds_kfs_build_keyframes_dev`` without leaving the device.
+``IDepthMap::fromPoints``), which ``build_keyframes_from_window`` hands to ``eds_kfs_build_keyframes_dev`` and
+``seed_immature_from_window`` to ``eds_imd_set_depth_map`` (include/eds_hip_immdepth.h) without leaving the device.
 
 Plumbing only: every point is computed by the HIP kernels behind the C ABI (csrc/eds_map.hip); there is no CPU fallback.
 
@@ -157,3 +158,16 @@ def build_keyframes_from_window(trk, images, K, win, T_w_c, T_dst_w, first=0, fr
     maps = window_depth_maps(win, T_w_c, T_dst_w, K, trk.H, trk.W, frame_mask=frame_mask, src_index=False, device=device)
     out = trk.build_keyframes(images, K, first=first, depth=maps["depth_xy"], depth_idp=maps["depth_idp"], depth_n=maps["n"], **kw)
     return out, maps
+
+
+def seed_immature_from_window(imm_depth, host, selector, win, T_w_c, T_kf_w, K, H, W, rect=None, frame_mask=None):
+    """The new keyframe's immature points end to end on the device: ``window_depth_maps(device=...)`` of `win` for the one keyframe at
+    `T_kf_w` with intrinsics `K` (fx, fy, cx, cy) and size H x W, into ``imm_depth.set_depth_map`` (an ``immdepth.ImmatureDepth``), then
+    ``create_points_selected`` for the pixels `selector` chose on host frame `host`.  Returns (alive mask, (GOOD, UNINITIALIZED), the
+    maps, tree_on_host)."""
+    device = True if capi.torch_loaded_first else "array"
+    maps = window_depth_maps(win, T_w_c, [T_kf_w], np.asarray(K, dtype=np.float64).reshape(1, 4), H, W, frame_mask=frame_mask, src_index=False,
+                             device=device)
+    on_host = imm_depth.set_depth_map(maps["depth_xy"], maps["depth_idp"], n=int(maps["n"][0]))
+    alive, counts = imm_depth.create_points_selected(host, selector, rect=rect)
+    return alive, counts, maps, on_host
