@@ -28,20 +28,22 @@
  *     0.7f), the THFac = 0.5 switch, the three-way stop test.  sqrtf is taken on the host.  One 4-byte count comes back per pass, and
  *     there are at most recursions_left + 1 passes.  The reference's global sparsityFactor (settings.cpp:212, initial value 5) is
  *     state of the handle.  Where the reference's float-to-int conversion would overflow, the new sparsity is 2^30.
- *  3. makeNN (:884-958) as eds_ini_make_nn states it: an exhaustive search, smaller fp32 squared distance (d0 d0 + d1 d1 of the fp32
- *     u, v, without contraction) first, then the lower index; the parent is the nearest point of the level above to 0.5f u - 0.25f;
- *     fewer than 10 points leave -1.  A query per lane, the candidates broadcast from LDS in tiles of EDS_INI_NN_TILE, the ten best
- *     in registers.  That order is total, so the table does not depend on the order of the visit: a workgroup walks outwards from
- *     its queries' own tile and skips a tile whose bounding box is farther from every query than the query's tenth best.
+ *  3. makeNN (:884-958) with the reference's tables, ties included — eds_ini_make_nn's (eds_hip_init.h item 4): the k-d tree
+ *     nanoflann builds over the level (leaf size 5) and over the level above, walked as nanoflann walks it, the ten neighbours in
+ *     nanoflann's order; the parent is nanoflann's one nearest point of the level above to 0.5f u - 0.25f; fewer than 10 points
+ *     leave -1.  The build is host code (csrc/eds_nntree.hpp): eds_ini_make_neighbours READS BACK THE PACKED (u, v) of the level and
+ *     of the level above (8 n + 8 n_up bytes), builds the two trees, and uploads their nodes and index arrays (at most 52 bytes a
+ *     point).  The walk is the same header's on the device, a query per lane, its stack of pending far sides (one per level of the
+ *     tree, at most 64) in the lane's private memory; distances are d0 d0 + d1 d1 of the fp32 u, v without contraction.  A level
+ *     whose tree is deeper than 64 — points on the pixel lattice never give one — is walked on the host and its table uploaded.
  *  4. What eds_ini_set_neighbours derives from the tables — the dependency schedule and the child lists — stays host code
  *     (csrc/eds_init.hpp, unchanged).  For it eds_ini_make_neighbours READS THE TABLES BACK ONCE per level (n x 11 int32) and uploads
- *     the schedule as eds_ini_set_neighbours does.  That is the one set-up read-back besides the counts.
+ *     the schedule as eds_ini_set_neighbours does.  With item 3's (u, v) these are the set-up's read-backs besides the counts.
  *
  * The host restatement (csrc/eds_inisetup.hpp: edsini::grid_max_selection, edsini::make_pixel_status in the reference's loop order;
- * edsini::make_nn of csrc/eds_init.hpp) and the device agree bit for bit on everything this header returns.
+ * edsini::make_nn of csrc/eds_init.hpp over csrc/eds_nntree.hpp) and the device agree bit for bit on everything this header returns.
  *
- * Out of scope.  nanoflann's visiting order for ties: the tables are eds_ini_make_nn's, lower index first.
- * FullSystem::initializeFromInitializer, which is not in the reference tree.  An LDS-resident optReg.  Deriving the schedule on the
+ * Out of scope.  Building the tree on the device.  FullSystem::initializeFromInitializer, which is not in the reference tree.  An LDS-resident optReg.  Deriving the schedule on the
  * device.
  */
 #ifndef EDS_HIP_INISETUP_H_
@@ -57,7 +59,7 @@ extern "C" {
 int eds_ini_setup_abi_version(void);
 
 #define EDS_INI_SPARSITY_START 5
-#define EDS_INI_NN_TILE 256                    /* candidates per LDS tile of the neighbour search */
+#define EDS_INI_NN_TILE 256                    /* queries per workgroup of the neighbour search */
 
 /* the reference's global `sparsityFactor`: it starts at 5, every eds_ini_make_pixel_status reads it and leaves what the reference
  * leaves, across levels and across a second eds_ini_set_first.  Neither call touches the device. */
@@ -76,7 +78,7 @@ int eds_ini_get_pixel_status(eds_ini* ini, int lvl, uint8_t* map_out);
  * n_out may be NULL. */
 int eds_ini_set_points_status(eds_ini* ini, int lvl, int32_t* n_out);
 
-/* makeNN for one level from the points on the device: the tables eds_ini_make_nn would fill for the same points, then everything
+/* makeNN for one level from the points on the device: the tables eds_ini_make_nn would fill for the same points (nanoflann's), then everything
  * eds_ini_set_neighbours does with them.  The level above must have points (and at least one) unless lvl is the top level. */
 int eds_ini_make_neighbours(eds_ini* ini, int lvl);
 /* those tables: neighbours n x 10, parent n (NULL at the top level) */

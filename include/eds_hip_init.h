@@ -26,9 +26,15 @@
  *     eds_ini_set_points_status); a caller's own maps remain inputs here.
  *  4. makeNN's tables (:884-958) are inputs here (eds_ini_set_neighbours); eds_hip_inisetup.h makes them on the device from the
  *     level's points (eds_ini_make_neighbours).  neighboursDist and parentDist, which the reference writes and
- *     never reads, have no counterpart.  eds_ini_make_nn fills the tables on the host by an exhaustive search: smaller fp32 squared distance first,
- *     then the lower index — which is not nanoflann's order: with every point at an integer pixel + 0.1 ties are common, and nanoflann
- *     resolves them by the order its tree is visited in.
+ *     never reads, have no counterpart.  eds_ini_make_nn fills the tables on the host AS THE REFERENCE'S NANOFLANN DOES, ties
+ *     included: with every point at an integer pixel + 0.1 equal fp32 distances are the normal case, and nanoflann decides them by
+ *     the order its tree is visited in.  Restated from src/utils/nanoflann.h (csrc/eds_nntree.hpp): the build (:985-991, :1024-1046
+ *     the root box, :1056-1104 divideTree with leaf size 5, :1118-1157 middleSplit_, :1169-1196 planeSplit), the walk (:1198-1215,
+ *     :1222-1269 searchLevel: near child by diff1 + diff2 < 0, the fp32 running mindistsq with its <= prune, a leaf's dist <
+ *     worst_dist against the worst distance on entry) and KNNResultSet::addPoint without NANOFLANN_FIRST_MATCH (:124-145); the
+ *     distance is FLANNPointcloud::kdtree_distance, d0 d0 + d1 d1 in fp32 without contraction.  Coordinates must be finite and a
+ *     parent table needs n_up >= 1 (EDS_ERR_INVALID otherwise); a parent search in which every squared distance overflows answers 0.
+ *     tests/test_nn_pin.py holds this to the reference's own nanoflann (tests/golden/nn/).
  *  5. trackFrame (:75-262), whole, in ONE kernel launch and one wait: the new frame's pyramid, the un-snapped reset, the exposure guess
  *     (its logf is taken on the host), per level propagateDown, resetPoints, calcResAndGS, applyStep and the damped loop with doStep,
  *     calcEC, the accept test, the float equality that sets `snapped`, optReg, the lambda schedule and the three exits; propagateUp;
@@ -135,8 +141,8 @@ int eds_ini_set_points_selected(eds_ini* ini, eds_sel* sel, int32_t* n_out);
 /* makeNN's tables of one level: neighbours n x 10 (indices into the level, -1: none), parent n (indices into level lvl + 1; NULL at
  * the top level).  Every index is checked on the host. */
 int eds_ini_set_neighbours(eds_ini* ini, int lvl, const int32_t* neighbours, const int32_t* parent);
-/* fills such tables on the host, exactly: uv n x {u, v} of the level, uv_up n_up x {u, v} of the level above (NULL / 0 and parent
- * NULL at the top level).  Fewer than 10 points: the rest of a row is -1. */
+/* fills such tables on the host — nanoflann's, ties included (item 4): uv n x {u, v} of the level, uv_up n_up x {u, v} of the level
+ * above (NULL / 0 and parent NULL at the top level).  Fewer than 10 points: the rest of a row is -1. */
 int eds_ini_make_nn(int n, const float* uv, int n_up, const float* uv_up, int32_t* neighbours, int32_t* parent);
 /* the depths of a level's dependency schedule (what optReg and resetPoints cost in barriers) */
 int eds_ini_get_schedule_depth(const eds_ini* ini, int lvl, int32_t* depth_out);

@@ -11,6 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 DRIVER = os.path.join(os.path.dirname(HERE), "_ref", "ref_driver")
 KDTREE = os.path.join(os.path.dirname(HERE), "_ref", "kdtree_nn")
+NANOFLANN = os.path.join(os.path.dirname(HERE), "_ref", "nanoflann_nn")
 
 
 def available() -> bool:
@@ -35,6 +36,32 @@ def kdtree_nn(depth_xy, queries):
         raw = open(cout, "rb").read()
     n = len(q)
     return np.frombuffer(raw[:4 * n], dtype=np.int32).astype(np.int64), np.frombuffer(raw[4 * n:], dtype=np.float64).copy()
+
+
+def nanoflann_available() -> bool:
+    """oracle/_ref/nanoflann_nn: the reference's nanoflann.h, unmodified, with the reference's flags (built wherever the tree exists)."""
+    return os.path.isfile(NANOFLANN) and os.access(NANOFLANN, os.X_OK)
+
+
+def nanoflann_nn(uv, uv_up=None):
+    """CoarseInitializer::makeNN's two searches (CoarseInitializer.cpp:888-946) for every point of uv (n x 2 fp32): the ten neighbours
+    in uv and the nearest point of uv_up (None or empty: no level above) to 0.5f pt - 0.25f.  Returns dict(nb int32 n x 10, dist
+    float32 n x 10 (squared, 0 where nb is -1), parent int32 n (-1 without a level above), parent_dist float32 n)."""
+    p = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    u = np.zeros((0, 2), np.float32) if uv_up is None else np.ascontiguousarray(uv_up, dtype=np.float32).reshape(-1, 2)
+    with tempfile.TemporaryDirectory() as t:
+        cin, cout = os.path.join(t, "case.bin"), os.path.join(t, "out.bin")
+        with open(cin, "wb") as f:
+            np.array([len(p)], dtype=np.int32).tofile(f); p.tofile(f)
+            np.array([len(u)], dtype=np.int32).tofile(f); u.tofile(f)
+        subprocess.run([NANOFLANN, cin, cout], check=True, stdout=subprocess.DEVNULL)
+        raw = open(cout, "rb").read()
+    n = len(p)
+    assert len(raw) == 4 * (22 * n), (len(raw), n)
+    return dict(nb=np.frombuffer(raw[:40 * n], dtype=np.int32).reshape(n, 10).copy(),
+                dist=np.frombuffer(raw[40 * n:80 * n], dtype=np.float32).reshape(n, 10).copy(),
+                parent=np.frombuffer(raw[80 * n:84 * n], dtype=np.int32).copy(),
+                parent_dist=np.frombuffer(raw[84 * n:], dtype=np.float32).copy())
 
 
 def build() -> str:

@@ -8,14 +8,10 @@
 // candidates under gms_better (larger score, then smaller rank), which is a total order on the candidates that have a score: the fold's
 // winner is the serial loop's.  Cells are disjoint, so the cell's leader sets its pixels without a race and numGood is their number.
 //
-// k_ini_nn: a query per lane.  The candidates pass through LDS in tiles of NN_TILE, every lane reading the same address (a broadcast);
-// the ten best stay in registers by an unrolled insertion under the total order (fp32 squared distance, index) of edsini::make_nn.
-// Because that order is total the table does not depend on the order the candidates are visited in, and the kernel uses that twice:
-// a workgroup starts at the tile of its own queries and walks outwards (the points are in row-major order, so near indices are near
-// pixels and the ten best are nearly final after a few tiles), and a tile whose bounding box (k_ini_uv) is farther from every query
-// of the workgroup than the query's tenth best is not read at all.  The box bound is formed with the candidates' own fp32 operations —
-// the gap to the box squared and added, each rounding monotone — so it never exceeds the distance of a candidate inside the box.
-// The parent is the same walk over the level above with one best.
+// k_ini_nn: a query per lane walks the k-d tree nanoflann would build over the level (csrc/eds_nntree.hpp, shared with the host), so the
+// table is the reference's, ties included.  The trees of the level and of the level above are built on the host from a read-back of their packed (u, v) and
+// uploaded as nodes + vind; the walk's stack of pending far sides is private memory of the lane (no LDS).  A level whose tree is deeper than
+// the stack — no level of lattice points is — gets its table from the host walk instead.
 //
 // No kernel here waits on another workgroup, and every loop is bounded by a size passed in: nothing can spin.
 #include <hip/hip_runtime.h>
@@ -44,9 +40,8 @@ constexpr int BLOCK = 256;
 constexpr int NN_TILE = EDS_INI_NN_TILE;
 constexpr int NN_ROW = edsini::NN + 1;                 // ten neighbours and the parent
 constexpr int GMS_SERIAL_MAX_POT = 8;                  // up to here a lane walks its cell alone
-constexpr float INF = __builtin_huge_valf();
 
-static_assert(NN_TILE == BLOCK, "a lane stages one candidate of a tile");
+static_assert(NN_TILE == BLOCK, "the header's name for the queries of a workgroup");
 
 // gridMaxSelection.  G lanes per cell; ncx x ncy cells; map is zero on entry; *count is zero on entry.
 template <int G>
@@ -100,138 +95,44 @@ __global__ void __launch_bounds__(BLOCK) k_grid_max(const Px* __restrict__ grads
     if ((threadIdx.x & 63) == 0 && good > 0) atomicAdd(count, good);
 }
 
-// the points' (u, v) packed — the search reads 8 bytes a candidate and not a point's 64 — and the bounding box of every tile of
-// NN_TILE consecutive points: (min u, min v, max u, max v).  A workgroup per tile.
-__global__ void __launch_bounds__(BLOCK) k_ini_uv(const Pnt* __restrict__ p, int n, float2* __restrict__ uv, float4* __restrict__ box) {
-    __shared__ float4 part[BLOCK / 64];
+// the points' (u, v) packed: what the host builds the level's tree from, and what the walk reads — 8 bytes a candidate, not a point's 64
+__global__ void __launch_bounds__(BLOCK) k_ini_uv(const Pnt* __restrict__ p, int n, float2* __restrict__ uv) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
-    float4 b = make_float4(INF, INF, -INF, -INF);
-    if (i < n) {
-        const float2 c = make_float2(p[i].u, p[i].v);
-        uv[i] = c;
-        b = make_float4(c.x, c.y, c.x, c.y);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        b.x = fminf(b.x, __shfl_xor(b.x, off)); b.y = fminf(b.y, __shfl_xor(b.y, off));
-        b.z = fmaxf(b.z, __shfl_xor(b.z, off)); b.w = fmaxf(b.w, __shfl_xor(b.w, off));
-    }
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < BLOCK / 64; ++k) {
-            b.x = fminf(b.x, part[k].x); b.y = fminf(b.y, part[k].y); b.z = fmaxf(b.z, part[k].z); b.w = fmaxf(b.w, part[k].w);
-        }
-        box[blockIdx.x] = b;
-    }
+    if (i < n) uv[i] = make_float2(p[i].u, p[i].v);
 }
 
-// (d, j) before (bd, bi) in the total order: the smaller distance, then the lower index
-__device__ __forceinline__ bool nn_before(float d, int32_t j, float bd, int32_t bi) { return d < bd || (d == bd && j < bi); }
-
-// held (bd, bi) ascending in that order; (d, j) enters before the first held entry it precedes.  Constant indices only: registers.
-__device__ __forceinline__ void nn_insert(float (&bd)[edsini::NN], int32_t (&bi)[edsini::NN], float d, int32_t j) {
-#pragma unroll
-    for (int k = edsini::NN - 1; k >= 1; --k) {
-        const bool here = nn_before(d, j, bd[k], bi[k]), above = nn_before(d, j, bd[k - 1], bi[k - 1]);
-        bi[k] = here ? (above ? bi[k - 1] : j) : bi[k];
-        bd[k] = here ? (above ? bd[k - 1] : d) : bd[k];
-    }
-    if (nn_before(d, j, bd[0], bi[0])) { bd[0] = d; bi[0] = j; }
-}
-
-// what no candidate inside `box` can be nearer to (qx, qy) than: the gaps to the box through the candidates' own operations
-__device__ __forceinline__ float nn_box_bound(float qx, float qy, const float4 box) {
-    const float gx = fmaxf(fmaxf(box.x - qx, qx - box.z), 0.0f), gy = fmaxf(fmaxf(box.y - qy, qy - box.w), 0.0f);
-    return gx * gx + gy * gy;
-}
-
-// the s-th tile of a walk outwards from tile `start`: start, start + 1, start - 1, ... with the side that ran out skipped
-struct TileWalk {
-    int lo, hi, ntiles, s;
-    __device__ TileWalk(int start, int nt) : lo(start - 1), hi(start), ntiles(nt), s(0) {}
-    __device__ bool more() const { return s < ntiles; }
-    __device__ int next() {
-        const bool up = hi < ntiles && (lo < 0 || (s & 1) == 0);
-        ++s;
-        return up ? hi++ : lo--;
-    }
+// one level's tree in device memory: nodes and vind as edsnn::build left them, uv the level's n points, box the root box
+struct NnTree {
+    const edsnn::Node* nodes;
+    const int32_t* vind;
+    const float* uv;
+    edsnn::Box box;
+    int n;
 };
 
-// one tile of `pts` (n of them) into LDS, two candidates to a float4; the places past the last point hold (inf, inf), whose distance is
-// inf and never enters.  Every lane writes.
-__device__ __forceinline__ void nn_stage(float4* tile, const float2* __restrict__ pts, int base, int n) {
-    const int j = base + (int)threadIdx.x;
-    reinterpret_cast<float2*>(tile)[threadIdx.x] = j < n ? pts[j] : make_float2(INF, INF);
-}
-
-// makeNN for one level: uv[n] its points with their tiles' boxes, up[n_up] those of the level above (n_up = 0 at the top level);
-// out[n][NN_ROW].  A workgroup's queries are the points of tile blockIdx.x.  Four candidates a step: two 16-byte LDS reads, four
-// distances, and one test of the nearest of them against the tenth best before any insertion is looked at.
-__global__ void __launch_bounds__(BLOCK) k_ini_nn(const float2* __restrict__ uv, const float4* __restrict__ box, int n,
-                                                  const float2* __restrict__ up, const float4* __restrict__ box_up, int n_up,
-                                                  int32_t* __restrict__ out) {
-    __shared__ float4 tile[NN_TILE / 2];
+// makeNN for one level: out[n][NN_ROW].  A query per lane walks the level's tree for its ten neighbours and, with a level above
+// (up.n > 0), that level's tree for its parent — edsnn::knn, the code the host runs, with its stack in the lane's private memory.
+// The host launches this only for trees no deeper than edsnn::STACK.  Every index the walk follows was written by edsnn::build:
+// nodes < 2 n, vind < n, a leaf's [left, right) inside [0, n].
+__global__ void __launch_bounds__(BLOCK) k_ini_nn(const NnTree lvl, const NnTree up, int32_t* __restrict__ out) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
-    const bool live = i < n;
-    const float2 q = live ? uv[i] : make_float2(0.0f, 0.0f);
-    const int ntiles = (n + NN_TILE - 1) / NN_TILE;
-    float bd[edsini::NN];
+    if (i >= lvl.n) return;
+    const float q0 = lvl.uv[2 * (size_t)i], q1 = lvl.uv[2 * (size_t)i + 1];
     int32_t bi[edsini::NN];
+    float bd[edsini::NN];
 #pragma unroll
-    for (int k = 0; k < edsini::NN; ++k) { bd[k] = INF; bi[k] = -1; }
-    for (TileWalk walk(blockIdx.x, ntiles); walk.more();) {
-        const int t = walk.next(), base = t * NN_TILE;
-        const bool need = live && nn_box_bound(q.x, q.y, box[t]) <= bd[edsini::NN - 1];
-        if (!__syncthreads_or(need)) continue;                 // uniform; also the barrier before the tile is written again
-        const int m = n - base < NN_TILE ? n - base : NN_TILE;
-        nn_stage(tile, uv, base, n);
-        __syncthreads();
-        if (!__any(need)) continue;                            // this wavefront has nothing to find here
-        for (int j = 0; j < m; j += 4) {                       // j <= NN_TILE - 4: the reads stay inside the tile
-            const float4 a = tile[j >> 1], b = tile[(j >> 1) + 1];
-            const float cx[4] = {a.x, a.z, b.x, b.z}, cy[4] = {a.y, a.w, b.y, b.w};
-            float d[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const float d0 = q.x - cx[k], d1 = q.y - cy[k]; d[k] = d0 * d0 + d1 * d1; }
-            if (!(fminf(fminf(d[0], d[1]), fminf(d[2], d[3])) <= bd[edsini::NN - 1])) continue;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (nn_before(d[k], base + j + k, bd[edsini::NN - 1], bi[edsini::NN - 1])) nn_insert(bd, bi, d[k], base + j + k);
-        }
-    }
+    for (int k = 0; k < edsini::NN; ++k) { bi[k] = -1; bd[k] = 0.0f; }
+    edsnn::knn<edsini::NN>(lvl.nodes, lvl.vind, lvl.uv, lvl.box, q0, q1, bi, bd);
     int32_t parent = -1;
-    if (n_up > 0) {
-        const float qx = q.x * 0.5f - 0.25f, qy = q.y * 0.5f - 0.25f;
-        const int ntiles_up = (n_up + NN_TILE - 1) / NN_TILE;
-        float bestd = INF;
-        for (TileWalk walk((int)((long long)blockIdx.x * ntiles_up / ntiles), ntiles_up); walk.more();) {
-            const int t = walk.next(), base = t * NN_TILE;
-            const bool need = live && nn_box_bound(qx, qy, box_up[t]) <= bestd;
-            if (!__syncthreads_or(need)) continue;
-            const int m = n_up - base < NN_TILE ? n_up - base : NN_TILE;
-            nn_stage(tile, up, base, n_up);
-            __syncthreads();
-            if (!__any(need)) continue;
-            for (int j = 0; j < m; j += 4) {
-                const float4 a = tile[j >> 1], b = tile[(j >> 1) + 1];
-                const float cx[4] = {a.x, a.z, b.x, b.z}, cy[4] = {a.y, a.w, b.y, b.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float d0 = qx - cx[k], d1 = qy - cy[k], d = d0 * d0 + d1 * d1;
-                    if (nn_before(d, base + j + k, bestd, parent)) { bestd = d; parent = base + j + k; }
-                }
-            }
-        }
-        if (parent < 0) parent = 0;                            // no finite distance: edsini::make_nn's answer
+    if (up.n > 0) {
+        float pd = 0.0f;
+        edsnn::knn<1>(up.nodes, up.vind, up.uv, up.box, q0 * 0.5f - 0.25f, q1 * 0.5f - 0.25f, &parent, &pd);
+        if (parent < 0) parent = 0;                            // no squared distance below FLT_MAX: edsini::make_nn's answer
     }
-    if (live) {
-        int32_t* row = out + (size_t)i * NN_ROW;
+    int32_t* row = out + (size_t)i * NN_ROW;
 #pragma unroll
-        for (int k = 0; k < edsini::NN; ++k) row[k] = bi[k];
-        row[edsini::NN] = parent;
-    }
+    for (int k = 0; k < edsini::NN; ++k) row[k] = bi[k];
+    row[edsini::NN] = parent;
 }
 
 // every launch and wait of this file is counted on the handle, as eds_init.hip counts its own
@@ -251,8 +152,6 @@ int check_level(const eds_ini* h, int lvl) {
     return EDS_OK;
 }
 
-size_t box_stride(const eds_ini* h) { return (size_t)(h->cap + NN_TILE - 1) / NN_TILE; }      // tiles of one level
-
 // the set-up's device memory, at the first call that needs it
 int setup_alloc(eds_ini* h) {
     if (h->status) return EDS_OK;
@@ -260,7 +159,8 @@ int setup_alloc(eds_ini* h) {
     const size_t lc = (size_t)h->geo.levels * h->cap;
     if (!h->own.alloc({{(void**)&h->status, (size_t)h->geo.total},
                        {(void**)&h->uv, lc * sizeof(float2)},
-                       {(void**)&h->box, (size_t)h->geo.levels * box_stride(h) * sizeof(float4)},
+                       {(void**)&h->tree_nodes, 2 * 2 * (size_t)h->cap * sizeof(edsnn::Node)},
+                       {(void**)&h->tree_vind, 2 * (size_t)h->cap * sizeof(int32_t)},
                        {(void**)&h->nn, lc * NN_ROW * sizeof(int32_t)}}))
         return fail(EDS_ERR_HIP, "eds_ini: the device refused an allocation for the set-up");
     return EDS_OK;
@@ -321,6 +221,19 @@ int check_neighbours_state(const eds_ini* h, int lvl) {
     return EDS_OK;
 }
 
+// a level's tree into slot 0 (the level) or 1 (the level above) of the handle's tree memory; the host arrays must outlive the copies
+int upload_tree(eds_ini* h, int slot, const edsnn::Tree& t, const float2* uv, int n, NnTree* out) {
+    edsnn::Node* nodes = h->tree_nodes + (size_t)slot * 2 * h->cap;
+    int32_t* vind = h->tree_vind + (size_t)slot * h->cap;
+    if (t.nodes.size() > 2 * (size_t)h->cap || t.vind.size() != (size_t)n) return fail(EDS_ERR_HIP, "eds_ini: a tree larger than its points allow");
+    if (n > 0) {
+        EDS_HIP_TRY(hipMemcpyAsync(nodes, t.nodes.data(), t.nodes.size() * sizeof(edsnn::Node), hipMemcpyHostToDevice, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(vind, t.vind.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
+    }
+    *out = NnTree{nodes, vind, reinterpret_cast<const float*>(uv), t.box, n};
+    return EDS_OK;
+}
+
 int make_neighbours(eds_ini* h, int lvl) {
     if (int rc = setup_alloc(h)) return rc;
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
@@ -329,22 +242,42 @@ int make_neighbours(eds_ini* h, int lvl) {
     const size_t o = (size_t)lvl * h->cap;
     h->nn_made[lvl] = false;
     std::vector<int32_t> rows((size_t)n * NN_ROW + 1), nb((size_t)n * edsini::NN + 1), parent((size_t)n + 1);
+    std::vector<float> uv(2 * (size_t)n + 2), uv_up(2 * (size_t)n_up + 2);
+    edsnn::Tree tree, tree_up;
     h->nn_kernel_ms = 0.0f;
+    bool on_device = false;
     if (n > 0) {
-        const size_t ob = (size_t)lvl * box_stride(h), up = top ? 0 : 1;       // the level above is the next one in every array
-        SETUP_LAUNCH(h, k_ini_uv, edscapi::blocks(n, BLOCK), h->pts + o, n, h->uv + o, h->box + ob);
-        if (n_up > 0) SETUP_LAUNCH(h, k_ini_uv, edscapi::blocks(n_up, BLOCK), h->pts + o + h->cap, n_up, h->uv + o + h->cap, h->box + ob + box_stride(h));
+        SETUP_LAUNCH(h, k_ini_uv, edscapi::blocks(n, BLOCK), h->pts + o, n, h->uv + o);
+        if (n_up > 0) SETUP_LAUNCH(h, k_ini_uv, edscapi::blocks(n_up, BLOCK), h->pts + o + h->cap, n_up, h->uv + o + h->cap);
+        EDS_HIP_TRY(hipGetLastError());
+        if (int rc = setup_read_back(h, uv.data(), h->uv + o, (size_t)n * sizeof(float2))) return rc;
+        if (int rc = setup_read_back(h, uv_up.data(), h->uv + o + h->cap, (size_t)n_up * sizeof(float2))) return rc;
+        edsnn::build(uv.data(), n, tree);
+        edsnn::build(uv_up.data(), n_up, tree_up);
+        on_device = tree.depth <= edsnn::STACK && tree_up.depth <= edsnn::STACK;
+    }
+    if (on_device) {
+        NnTree d_lvl, d_up;
+        if (int rc = upload_tree(h, 0, tree, h->uv + o, n, &d_lvl)) return rc;
+        if (int rc = upload_tree(h, 1, tree_up, h->uv + o + h->cap, n_up, &d_up)) return rc;
         EDS_HIP_TRY(hipEventRecord(h->ev0, h->own.st));
-        SETUP_LAUNCH(h, k_ini_nn, edscapi::blocks(n, BLOCK), h->uv + o, h->box + ob, n, h->uv + o + up * h->cap, h->box + ob + up * box_stride(h), n_up,
-                     h->nn + o * NN_ROW);
+        SETUP_LAUNCH(h, k_ini_nn, edscapi::blocks(n, BLOCK), d_lvl, d_up, h->nn + o * NN_ROW);
         EDS_HIP_TRY(hipEventRecord(h->ev1, h->own.st));
         EDS_HIP_TRY(hipGetLastError());
         if (int rc = setup_read_back(h, rows.data(), h->nn + o * NN_ROW, (size_t)n * NN_ROW * sizeof(int32_t))) return rc;
         if (hipEventElapsedTime(&h->nn_kernel_ms, h->ev0, h->ev1) != hipSuccess) { (void)hipGetLastError(); h->nn_kernel_ms = -1.0f; }
-    }
-    for (int i = 0; i < n; ++i) {
-        for (int k = 0; k < edsini::NN; ++k) nb[(size_t)i * edsini::NN + k] = rows[(size_t)i * NN_ROW + k];
-        parent[i] = rows[(size_t)i * NN_ROW + edsini::NN];
+        for (int i = 0; i < n; ++i) {
+            for (int k = 0; k < edsini::NN; ++k) nb[(size_t)i * edsini::NN + k] = rows[(size_t)i * NN_ROW + k];
+            parent[i] = rows[(size_t)i * NN_ROW + edsini::NN];
+        }
+    } else if (n > 0) {
+        // a tree deeper than the device walk's stack: the host walks (edsini::make_nn, by recursion) and the device gets the rows
+        edsini::make_nn(n, uv.data(), n_up, uv_up.data(), nb.data(), n_up > 0 ? parent.data() : nullptr);
+        for (int i = 0; i < n; ++i) {
+            for (int k = 0; k < edsini::NN; ++k) rows[(size_t)i * NN_ROW + k] = nb[(size_t)i * edsini::NN + k];
+            rows[(size_t)i * NN_ROW + edsini::NN] = n_up > 0 ? parent[i] : -1;
+        }
+        EDS_HIP_TRY(hipMemcpyAsync(h->nn + o * NN_ROW, rows.data(), (size_t)n * NN_ROW * sizeof(int32_t), hipMemcpyHostToDevice, h->own.st));
     }
     if (int rc = eds_ini_set_neighbours(h, lvl, nb.data(), top ? nullptr : parent.data())) return rc;
     h->nn_made[lvl] = true;

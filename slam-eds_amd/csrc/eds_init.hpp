@@ -20,6 +20,7 @@
 // SE3::log's atan is edsct::atan_d, beside sincos_d / exp_d in eds_coarse.hpp (within ATAN_MAX_ULP = 2 ulps of libm).
 #pragma once
 #include "eds_coarse.hpp"
+#include "eds_nntree.hpp"
 
 namespace edsini {
 
@@ -730,10 +731,11 @@ inline bool derive_tables(int n, const int32_t* nb, const int32_t* parent, int n
     return true;
 }
 
-// makeNN (:884-958) by exhaustive search: the 10 nearest points of the level (the point itself among them) and, with `up`, the nearest
-// point of the level above to 0.5 pt - 0.25.  Squared distances are fp32 as FLANNPointcloud::kdtree_distance forms them; ties go to
-// the lower index.  (nanoflann resolves ties by its tree's visiting order, which is not restated.)  Fewer than 10 points: -1 fills.
-inline void make_nn(int n, const float* uv, int n_up, const float* uv_up, int32_t* nb, int32_t* parent) {
+// makeNN (:884-958) by exhaustive search — NOT the reference's tables where distances tie, kept for the tests that show the difference:
+// the 10 nearest points of the level (the point itself among them) and, with `up`, the nearest point of the level above to 0.5 pt -
+// 0.25.  Squared distances are fp32 as FLANNPointcloud::kdtree_distance forms them; ties go to the lower index.  Fewer than 10
+// points: -1 fills.
+inline void make_nn_exhaustive(int n, const float* uv, int n_up, const float* uv_up, int32_t* nb, int32_t* parent) {
     for (int i = 0; i < n; ++i) {
         float bd[NN];
         int32_t bi[NN];
@@ -755,6 +757,32 @@ inline void make_nn(int n, const float* uv, int n_up, const float* uv_up, int32_
                 if (j == 0 || d < bestd) { bestd = d; best = j; }
             }
             parent[i] = best;
+        }
+    }
+}
+
+// makeNN (:884-958) with the reference's tables, ties included: nanoflann's build and walk as csrc/eds_nntree.hpp restates them.  Per
+// point the ten neighbours in nanoflann's order (the point itself among them; fewer than 10 points: -1 fills) and, with `parent`, the
+// one nearest point of the level above to 0.5f pt - 0.25f.  A tree deeper than `stack` (at most edsnn::STACK) is walked by recursion.
+// Coordinates are finite and n_up >= 1 with `parent` (eds_ini_make_nn refuses anything else); a parent search that finds no point —
+// every squared distance overflows — answers 0.  nb_dist (n x 10) / parent_dist (n), for tests: the squared distances, 0 where no
+// index was written.
+inline void make_nn(int n, const float* uv, int n_up, const float* uv_up, int32_t* nb, int32_t* parent, int stack = edsnn::STACK,
+                    float* nb_dist = nullptr, float* parent_dist = nullptr, int* depth_out = nullptr) {
+    edsnn::Tree t, tu;
+    edsnn::build(uv, n, t);
+    if (parent) edsnn::build(uv_up, n_up, tu);
+    if (depth_out) { depth_out[0] = t.depth; depth_out[1] = tu.depth; }
+    for (int i = 0; i < n; ++i) {
+        float d[NN];
+        edsnn::knn_host<NN>(t, uv, uv[2 * i], uv[2 * i + 1], nb + (size_t)i * NN, d, stack);
+        for (int k = 0; nb_dist && k < NN; ++k) nb_dist[(size_t)i * NN + k] = d[k];
+        if (parent) {
+            int32_t pi;
+            float pd;
+            edsnn::knn_host<1>(tu, uv_up, uv[2 * i] * 0.5f - 0.25f, uv[2 * i + 1] * 0.5f - 0.25f, &pi, &pd, stack);
+            parent[i] = pi < 0 ? 0 : pi;
+            if (parent_dist) parent_dist[i] = pd;
         }
     }
 }

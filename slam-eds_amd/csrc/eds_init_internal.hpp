@@ -37,7 +37,8 @@ struct eds_ini {
     bool nn_made[edsini::MAX_LEVELS] = {false, false, false, false, false};       // nn holds the tables the level's schedule was derived from
     uint8_t* status = nullptr;                             // [geo.total] one byte per pixel, the levels at geo.l[].off
     float2* uv = nullptr;                                  // [levels][cap] the points' (u, v), packed for the search
-    float4* box = nullptr;                                 // [levels][tiles of cap] the bounding box of every tile of uv
+    edsnn::Node* tree_nodes = nullptr;                     // [2][2 cap] the k-d tree of the level eds_ini_make_neighbours works on, and of the level above
+    int32_t* tree_vind = nullptr;                          // [2][cap] their permuted point indices
     int32_t* nn = nullptr;                                 // [levels][cap][11] ten neighbours and the parent
     float nn_kernel_ms = -1.0f;
 };

@@ -89,8 +89,9 @@ def default_params(**over) -> Params:
 
 
 def make_nn(uv, uv_up=None):
-    """``makeNN``'s tables by exhaustive search (ties: smaller squared distance, then lower index — not nanoflann's order): the 10
-    nearest points of the level, and with `uv_up` (the level above) every point's parent; returns (neighbours n x 10, parent or None)"""
+    """``makeNN``'s tables as the reference's nanoflann fills them, ties included (its k-d tree with leaf size 5 and its walk, restated
+    in csrc/eds_nntree.hpp and pinned by tests/test_nn_pin.py): the 10 nearest points of the level in nanoflann's order, and with
+    `uv_up` (the level above) every point's parent; returns (neighbours n x 10, parent or None)"""
     uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
     nb = np.full((len(uv), NEIGHBOURS), -1, np.int32)
     if uv_up is None:

@@ -1,6 +1,6 @@
 """include/eds_hip_inisetup.h on the device, BIT FOR BIT: the pixel status against csrc/eds_inisetup.hpp under g++
 (tests/inisetup_harness.py, which tests/test_inisetup_oracle.py holds to the reference's loop order), the neighbour tables against
-eds_ini_make_nn, and eds_ini_setup_levels against the long way — the selector's map, the oracle's maps through set_points and
+eds_ini_make_nn (the host walk of nanoflann's tree, which tests/test_nn_pin.py pins to the reference's own nanoflann), and eds_ini_setup_levels against the long way — the selector's map, the oracle's maps through set_points and
 eds_ini_make_nn's tables through set_neighbours — on a second handle, through the next two trackFrames."""
 import functools
 import importlib
@@ -21,7 +21,7 @@ capi = importlib.import_module("slam-eds_amd.capi")
 init = importlib.import_module("slam-eds_amd.init")
 select = importlib.import_module("slam-eds_amd.select")
 
-NN_TILE = 256                                   # EDS_INI_NN_TILE
+NN_TILE = 256                                   # EDS_INI_NN_TILE: the queries of a workgroup
 
 
 def _open(c, cap=4096, image=None):
@@ -90,7 +90,7 @@ def _chosen_status(h, w, k, rng):
     return s
 
 
-def test_neighbours_equal_the_exhaustive_host_search():
+def test_neighbours_equal_the_pinned_host_walk():
     H, W = 80, 96
     rng = np.random.default_rng(17)
     full = np.ones((H, W), np.float32)                                           # 89 x 73 = 6 497 points: 26 workgroups

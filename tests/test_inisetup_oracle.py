@@ -76,4 +76,5 @@ def test_the_controller_at_its_edges():
 def test_standalone_program_builds_and_survives_the_hostile_inputs():
     out = sh.run_standalone()
     m = re.search(r"inisetup standalone: (\d+) calls, (\d+) points", out)
-    assert m and int(m.group(1)) >= 100 and int(m.group(2)) > 100, out
+    # 4 shapes x (13 + 16) calls of the pixel status, then makeNN over every pair of 10 clouds (level, level above)
+    assert m and int(m.group(1)) == 4 * 29 + 10 * 10 and int(m.group(2)) > 100000, out

@@ -15,6 +15,7 @@ import pytest
 
 import init_cases as ic
 import init_harness as ih
+import inisetup_harness as sh
 import np_init_oracle as no
 
 POSE_BOUND, AFF_BOUND = 4 * 4.0e-7, 4 * 4.0e-6
@@ -51,9 +52,9 @@ def test_cases_have_the_sizes_the_issue_asks_for():
     e = ic.cases()["edges"]
     assert e.pose_guess is not None and any((nb == -1).any() for nb in e.nb)
     assert any(((nb != -1).sum(axis=1) <= 2).any() for nb in e.nb)
-    for c in ic.cases().values():                                                   # the tables in numpy equal eds_ini_make_nn's
-        for l in range(c.levels):
-            nb, par = ih.make_nn(c.uv[l], c.uv[l + 1] if l + 1 < c.levels else None)
+    for c in ic.cases().values():                            # the cases' tables in numpy equal edsini::make_nn_exhaustive's (any valid
+        for l in range(c.levels):                            # table is an input here; tests/test_nn_pin.py holds make_nn to nanoflann)
+            nb, par = sh.make_nn_exhaustive(c.uv[l], c.uv[l + 1] if l + 1 < c.levels else None)
             enb, epar = ic.exact_nn(c.uv[l], c.uv[l + 1] if l + 1 < c.levels else None)
             assert np.array_equal(nb, enb) and (par is None or np.array_equal(par, epar))
 

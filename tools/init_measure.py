@@ -3,7 +3,7 @@ reference's density (0.03 W H, one recursion, th_factor 2), level 1 from a gradi
 above at full density; exact tables from eds_ini_make_nn.  A 10-frame sequence along a growing motion over a textured plane.
 
   set-up      eds_ini_set_first, the five eds_ini_set_points* and the five eds_ini_set_neighbours (the tables are made before, untimed
-              and reported on their own: eds_ini_make_nn is an exhaustive host search)
+              and reported on their own: eds_ini_make_nn is a host search)
   trackFrame  per frame the call (host clock around it: upload, one launch, one wait) and the kernel (two events around the launch)
   serial      csrc/eds_init.hpp under g++ -O2 on the same input, one thread (tests/init_harness.py)
 
