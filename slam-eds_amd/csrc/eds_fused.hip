@@ -33,6 +33,9 @@
 #ifndef EDS_TILE_REFETCH
 #define EDS_TILE_REFETCH 1       // the first-solve tile kernels (pairs, one CU per alignment): toroidal patch cache, only the NEW taps of a shifted patch are fetched (0: every tap of a patch whose cell changed)
 #endif
+#ifndef EDS_TILE_STAGES
+#define EDS_TILE_STAGES 4        // groups those tile kernels consume a lane's points in, each behind its own counted wait on that group's rows, issued branch-free (1: predicated loads and one wait for all rows)
+#endif
 #include "eds_handle.hpp"
 #include "eds_launch_rule.hpp"
 #include "eds_math.hpp"
@@ -409,6 +412,9 @@ __global__ __launch_bounds__(MAXT, (TEAM > 1 && PPT == 1) ? EDS_TEAM_P1_WAVES_PE
             // ---- the same gather on pairs with a TOROIDAL cache and incremental refetch (eds_device.hpp, torus_*) ----
             // phase A: every point compares its clamped origin with the cached one and sends origin and refetch word round the quad; lane
             // jr, which owns the patch row of frame row = jr (mod 4), puts in flight only the tile pieces that hold a tap it lacks
+            // (EDS_TILE_STAGES > 1: the loads are issued without a branch, in point order, and phase B consumes point j behind a counted
+            // wait on point j's own rows while the later points' rows are still in flight — profiles/tile_stages_isa.txt;
+            // tests/test_tile_stages_gpu.py compares against an EDS_TILE_STAGES=1 build)
             const int jr = lane & 3;
             float* __restrict__ cache = &s_patch[0][0] + 16 * (tid & ~3) + 4 * jr;
             const int swz = (tid >> 2) & 3;
@@ -443,13 +449,29 @@ __global__ __launch_bounds__(MAXT, (TEAM > 1 && PPT == 1) ? EDS_TEAM_P1_WAVES_PE
                     const int oq[4] = {o0, o1, o2, o3}, wq[4] = {w0, w1, w2, w3};
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        asm("" : "=v"(ra[j][q].x), "=v"(ra[j][q].y), "=v"(ra[j][q].z), "=v"(ra[j][q].w));      // content does not matter where nothing is fetched: no instruction
-                        asm("" : "=v"(rb[j][q].x), "=v"(rb[j][q].y), "=v"(rb[j][q].z));
-                        const int m = torus_lane_mask(wq[q], rowbit);
-                        const char* __restrict__ src = tbase + torus_row_offset(oq[q], rowc, tile_row_bytes);
-                        if (m & 0x000f0000) ra[j][q] = *reinterpret_cast<const float4*>(src);
-                        if (m & 0x00700000) rb[j][q] = *reinterpret_cast<const float3v*>(src + 64);      // (asked for only where a tap lies in it: inside the allocation)
+                        if (EDS_TILE_STAGES > 1) {
+                            const int m = torus_lane_mask(wq[q], rowbit);
+                            // branch-free issue: EVERY lane issues both pieces — a lane that needs nothing of one reads this lane's row of
+                            // the slot's first tile (piece b: of the tile beside it) instead: offset 0, always inside the allocation,
+                            // always hot; the merge ignores what it brought.  No load sits behind a branch, so the compiler counts vmcnt
+                            // exactly and phase B waits per first use, not once for everything.  (The 32-bit offset is selected, not the
+                            // 64-bit pointer; piece b's + 64 stays the instruction's immediate.)
+                            const unsigned off = torus_row_offset(oq[q], rowc, tile_row_bytes);
+                            const unsigned offa = (m & 0x000f0000) ? off : 0u, offb = (m & 0x00700000) ? off : 0u;
+                            ra[j][q] = *reinterpret_cast<const float4*>(tbase + offa);
+                            rb[j][q] = *reinterpret_cast<const float3v*>(tbase + offb + 64);
+                        } else {
+                            asm("" : "=v"(ra[j][q].x), "=v"(ra[j][q].y), "=v"(ra[j][q].z), "=v"(ra[j][q].w));      // content does not matter where nothing is fetched: no instruction
+                            asm("" : "=v"(rb[j][q].x), "=v"(rb[j][q].y), "=v"(rb[j][q].z));
+                            const int m = torus_lane_mask(wq[q], rowbit);
+                            const char* __restrict__ src = tbase + torus_row_offset(oq[q], rowc, tile_row_bytes);
+                            if (m & 0x000f0000) ra[j][q] = *reinterpret_cast<const float4*>(src);
+                            if (m & 0x00700000) rb[j][q] = *reinterpret_cast<const float3v*>(src + 64);      // (asked for only where a tap lies in it: inside the allocation)
+                        }
                     }
+                    // a point's rows go out as soon as its origin is known, in point order: without the barrier the scheduler collects
+                    // all 32 loads behind the last projection, and the first rows leave 250 instructions later than they could
+                    if (EDS_TILE_STAGES > 1) asm volatile("" ::: "memory");
                 }
             }
             // phase B (branch-free): the new taps into the cached unit, the unit back to the cache, its taps into patch order, the row
@@ -460,6 +482,10 @@ __global__ __launch_bounds__(MAXT, (TEAM > 1 && PPT == 1) ? EDS_TEAM_P1_WAVES_PE
 #pragma unroll
             for (int j = 0; j < NREG; ++j) {
                 const int g = j >> 1;
+                // staged consumption: the group of points before this one is computed before this group's rows are waited for (without
+                // the tie the scheduler sinks its arithmetic below the later waits and reads every group's rows up front)
+                if (EDS_TILE_STAGES > 1 && j > 0 && j % (NREG / (EDS_TILE_STAGES < NREG ? EDS_TILE_STAGES : NREG)) == 0)
+                    asm volatile("" : "+v"(rcand[j - 1]) :: "memory");
                 const float ax_j = (j & 1) ? pg[g].ax.y : pg[g].ax.x, ay_j = (j & 1) ? pg[g].ay.y : pg[g].ay.x;
                 // (the lane masks are formed again, not kept from phase A: sixteen registers less while every load is in flight)
                 asm volatile("" : "+v"(ref[j]));
