@@ -8,11 +8,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB_PATH = os.environ.get("EDS_HIP_LIB") or os.path.join(CSRC, "libeds_hip.so")   # env override: diagnostic builds only
 
 # enums of include/eds_hip.h
@@ -139,6 +141,39 @@ DEV_EXPORTS = (
     "eds_dev_set_idepths",
 )
 
+
+class Header(NamedTuple):
+    """one public header of include/: the names it declares, its ABI macro and the version this binding is written against"""
+    file: str
+    exports: tuple
+    abi_macro: str
+    abi_version: int
+
+
+# the public headers of libeds_hip.so (eds_hip_rccl.h belongs to libeds_hip_rccl.so): a new module adds its line here
+HEADERS = (
+    Header("eds_hip.h", EXPORTS, "EDS_HIP_ABI_VERSION", 6),
+    Header("eds_hip_depth.h", DEPTH_EXPORTS, "EDS_HIP_DEPTH_ABI_VERSION", 2),
+    Header("eds_hip_klt.h", KLT_EXPORTS, "EDS_HIP_KLT_ABI_VERSION", 1),
+    Header("eds_hip_epiline.h", EPI_EXPORTS, "EDS_HIP_EPILINE_ABI_VERSION", 1),
+    Header("eds_hip_device.h", DEV_EXPORTS, "EDS_HIP_DEVICE_ABI_VERSION", 1),
+    Header("eds_hip_kfpoints.h", KFP_EXPORTS, "EDS_HIP_KFPOINTS_ABI_VERSION", 1),
+    Header("eds_hip_kfswitch.h", KFS_EXPORTS, "EDS_HIP_KFSWITCH_ABI_VERSION", 1),
+    Header("eds_hip_immature.h", IMM_EXPORTS, "EDS_HIP_IMMATURE_ABI_VERSION", 1),
+    Header("eds_hip_coarse.h", CT_EXPORTS, "EDS_HIP_COARSE_ABI_VERSION", 1),
+    Header("eds_hip_window.h", WIN_EXPORTS, "EDS_HIP_WINDOW_ABI_VERSION", 1),
+    Header("eds_hip_winsolve.h", WSV_EXPORTS, "EDS_HIP_WINSOLVE_ABI_VERSION", 1),
+    Header("eds_hip_winedit.h", WED_EXPORTS, "EDS_HIP_WINEDIT_ABI_VERSION", 1),
+    Header("eds_hip_winflag.h", WFL_EXPORTS, "EDS_HIP_WINFLAG_ABI_VERSION", 1),
+    Header("eds_hip_activate.h", ACT_EXPORTS, "EDS_HIP_ACTIVATE_ABI_VERSION", 1),
+    Header("eds_hip_select.h", SEL_EXPORTS, "EDS_HIP_SELECT_ABI_VERSION", 1),
+    Header("eds_hip_init.h", INI_EXPORTS, "EDS_HIP_INIT_ABI_VERSION", 1),
+    Header("eds_hip_inisetup.h", INISETUP_EXPORTS, "EDS_HIP_INISETUP_ABI_VERSION", 1),
+    Header("eds_hip_undistort.h", UND_EXPORTS, "EDS_HIP_UNDISTORT_ABI_VERSION", 1),
+    Header("eds_hip_map.h", MAP_EXPORTS, "EDS_HIP_MAP_ABI_VERSION", 1),
+    Header("eds_hip_immdepth.h", IMD_EXPORTS, "EDS_HIP_IMMDEPTH_ABI_VERSION", 1),
+)
+
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -233,32 +268,18 @@ class EdsError(RuntimeError):
         self.code = code
 
 
+def build_inputs() -> list:
+    """The files whose age decides whether libeds_hip.so is stale: every .hip and .hpp of csrc, every header of HEADERS."""
+    return ([os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))] +
+            [os.path.join(INCLUDE, h.file) for h in HEADERS])
+
+
 def build(force: bool = False) -> str:
     """Compile libeds_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_depth.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_klt.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_epiline.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_device.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfpoints.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_kfswitch.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_immature.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_coarse.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_window.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winsolve.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winedit.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_winflag.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_activate.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_select.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_init.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_inisetup.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_undistort.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_map.h"))
-    srcs.append(os.path.join(_HERE, "..", "include", "eds_hip_immdepth.h"))
+    srcs = build_inputs()
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     rccl_lib = os.path.join(CSRC, "libeds_hip_rccl.so")       # include/eds_hip_rccl.h: the RCCL gather for a C / C++ caller (its own library)
-    rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(_HERE, "..", "include", "eds_hip_rccl.h")]
+    rccl_src = [os.path.join(CSRC, "eds_gather.hip"), os.path.join(INCLUDE, "eds_hip_rccl.h")]
     stale_rccl = (not os.path.exists(rccl_lib)) or any(os.path.getmtime(s) > os.path.getmtime(rccl_lib) for s in rccl_src)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-j4", "-s", "libeds_hip.so"])

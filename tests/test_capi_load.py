@@ -3,29 +3,20 @@ symbols include/eds_hip.h declares, and refuses to work without a GPU (no CPU fa
 No compute entry point is called here."""
 import ctypes as C
 import os
-import re
 import subprocess
 
-import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "eds_hip.h")
-
-
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_[a-z0-9_]+)\s*\(", src)))
+from header_checks import ROOT, declared
 
 
 def test_header_and_binding_agree(capi):
-    assert _declared_functions() == sorted(capi.EXPORTS)
+    assert declared("eds_hip.h") == sorted(capi.EXPORTS)
 
 
 def test_library_exports_every_declared_symbol(capi):
     L = capi.lib()
-    for name in _declared_functions():
+    for name in declared("eds_hip.h"):
         assert hasattr(L, name), f"libeds_hip.so does not export {name}"
     assert L.eds_abi_version() == 6
 

@@ -7,74 +7,37 @@ import importlib
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import coarse_cases as cc
 import coarse_harness as ch
+import header_checks as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_coarse.h")
-capi = importlib.import_module("slam-eds_amd.capi")
+capi = hc.capi
 coarse = importlib.import_module("slam-eds_amd.coarse")
 
 # reference src/utils/settings.cpp:119-138
 REFERENCE_SETTINGS = dict(huber_th=9.0, coarse_cutoff_th=20.0, affine_opt_mode_a=1e12, affine_opt_mode_b=1e8)
 
 
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_ct_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_coarse_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc_, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_coarse.h"\nint main(void) { return EDS_HIP_COARSE_ABI_VERSION == 1 ? 0 : 1; }\n')
-        subprocess.check_call([cc_, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
-
-
-def test_coarse_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.CT_EXPORTS)
-    others = (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS) |
-              set(capi.KFP_EXPORTS) | set(capi.KFS_EXPORTS) | set(capi.IMM_EXPORTS))
-    assert not set(capi.CT_EXPORTS) & others
-    assert len(set(capi.CT_EXPORTS)) == len(capi.CT_EXPORTS)
-
-
 def test_coarse_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared_functions()
-    lines = ['#include <stdio.h>', '#include "eds_hip_coarse.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    eds_ct_params p; eds_ct_result r;", "    float x = 0; double d[12] = {0}; int32_t m = 0;",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_ct_abi_version() != EDS_HIP_COARSE_ABI_VERSION || EDS_HIP_COARSE_ABI_VERSION != 1) return 3;",
-              "    if (eds_abi_version() != 6) return 4;",
-              "    eds_ct_params_default(&p);",
-              "    if (p.huber_th != 9.0f || p.coarse_cutoff_th != 20.0f || p.affine_opt_mode_a != 1e12f || p.affine_opt_mode_b != 1e8f) return 5;",
-              "    if (eds_ct_set_params(0, &p) != EDS_ERR_INVALID || eds_ct_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_ct_create(0, 64, 64, 5, 1, 1, 0) != EDS_ERR_INVALID) return 7;",
-              "    if (eds_ct_set_calib(0, 1, 1, 0, 0) != EDS_ERR_INVALID || eds_ct_get_k(0, 0, &x) != EDS_ERR_INVALID) return 8;",
-              "    if (eds_ct_set_ref(0, &x, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID || eds_ct_set_new(0, &x, 0, 0, 1) != EDS_ERR_INVALID) return 9;",
-              "    if (eds_ct_track(0, 1, d, d, 0, d, &r) != EDS_ERR_INVALID || eds_ct_calc_res(0, 0, d, d, 20, 0, 0, 0, 0) != EDS_ERR_INVALID) return 10;",
-              "    if (eds_ct_get_level(0, EDS_CT_PC, 0, &x, &m) != EDS_ERR_INVALID) return 11;",
-              "    if (sizeof(eds_ct_row) != 64 || sizeof(eds_ct_result) != 744 || EDS_CT_MAX_LEVELS != 5 || EDS_CT_PC != 4) return 12;",
-              "    eds_ct_destroy(0);",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run("eds_hip_coarse.h", hc.declared("eds_hip_coarse.h"), [
+        "    eds_ct_params p; eds_ct_result r;",
+        "    float x = 0; double d[12] = {0}; int32_t m = 0;",
+        "    if (eds_ct_abi_version() != EDS_HIP_COARSE_ABI_VERSION || EDS_HIP_COARSE_ABI_VERSION != 1) return 3;",
+        "    if (eds_abi_version() != 6) return 4;",
+        "    eds_ct_params_default(&p);",
+        "    if (p.huber_th != 9.0f || p.coarse_cutoff_th != 20.0f || p.affine_opt_mode_a != 1e12f || p.affine_opt_mode_b != 1e8f) return 5;",
+        "    if (eds_ct_set_params(0, &p) != EDS_ERR_INVALID || eds_ct_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_ct_create(0, 64, 64, 5, 1, 1, 0) != EDS_ERR_INVALID) return 7;",
+        "    if (eds_ct_set_calib(0, 1, 1, 0, 0) != EDS_ERR_INVALID || eds_ct_get_k(0, 0, &x) != EDS_ERR_INVALID) return 8;",
+        "    if (eds_ct_set_ref(0, &x, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID || eds_ct_set_new(0, &x, 0, 0, 1) != EDS_ERR_INVALID) return 9;",
+        "    if (eds_ct_track(0, 1, d, d, 0, d, &r) != EDS_ERR_INVALID || eds_ct_calc_res(0, 0, d, d, 20, 0, 0, 0, 0) != EDS_ERR_INVALID) return 10;",
+        "    if (eds_ct_get_level(0, EDS_CT_PC, 0, &x, &m) != EDS_ERR_INVALID) return 11;",
+        "    if (sizeof(eds_ct_row) != 64 || sizeof(eds_ct_result) != 744 || EDS_CT_MAX_LEVELS != 5 || EDS_CT_PC != 4) return 12;",
+        "    eds_ct_destroy(0);"], tmp_path)
 
 
 def test_defaults_equal_the_reference_settings():
@@ -86,13 +49,9 @@ def test_defaults_equal_the_reference_settings():
 
 
 def test_coarse_sources_are_build_inputs():
-    import inspect
-    assert "eds_hip_coarse.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
     for f in ("eds_coarse.hip", "eds_hip_coarse.h", "eds_coarse.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp", "eds_dso_image.hip"):
-        assert f in mk, f
-    assert "eds_coarse.o: HIPFLAGS += -ffp-contract=off" in mk
-    assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_coarse.hip" in mk
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_coarse.o")) and hc.contraction_off(hc.resources_line("eds_coarse.hip"))
 
 
 def _ulps(got, want):

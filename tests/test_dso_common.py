@@ -6,15 +6,14 @@ tests/cpp/dso_common_check.hip, a stand-alone program, once: block_rank<T> in sw
 two-kernel grid compaction with blocks_before, wave_fold + add8 against reduce_lanes, wave_fold_i."""
 import ctypes as C
 import importlib
-import inspect
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import harness_build as hb
+import header_checks as hc
 import np_coarse_oracle as nco
 import np_window_oracle as nwo
 
@@ -96,15 +95,10 @@ def test_bilin_and_mix_are_the_window_oracles_interpolation(lib, H, W):
 
 
 def test_dso_common_sources_are_build_inputs():
-    """a header-only edit must rebuild the library (capi.build lists every .hip and .hpp of csrc); the shared level kernels are fp32 in the
+    """a header-only edit must rebuild the library (capi.build_inputs lists every .hip and .hpp of csrc); the shared level kernels are fp32 in the
     reference's order, so their translation unit is built without FMA contraction"""
-    assert 'f.endswith((".hip", ".hpp"))' in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    srcs = re.search(r"^SRCS\s*:=(.*)$", mk, re.M).group(1).split()
-    hdrs = re.search(r"^HDRS\s*:=(.*)$", mk, re.M).group(1).split()
-    assert "eds_dso_image.hip" in srcs and "eds_dso_common.hpp" in hdrs
-    assert "eds_dso_image.o: HIPFLAGS += -ffp-contract=off" in mk
-    assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_dso_image.hip" in mk
+    assert hc.is_build_input("eds_dso_image.hip") and hc.is_build_input("eds_dso_common.hpp")
+    assert hc.contraction_off(hc.compile_line("eds_dso_image.o")) and hc.contraction_off(hc.resources_line("eds_dso_image.hip"))
     for f in ("eds_window.hpp", "eds_pixsel.hpp"):                   # the coarse tracker's header is no longer where pixels come from
         assert '#include "eds_coarse.hpp"' not in open(os.path.join(capi.CSRC, f)).read(), f
 

@@ -1,63 +1,29 @@
 """include/eds_hip_epiline.h, the epiline tracker's companion header: plain C like eds_hip.h, its border numbers are OpenCV's, and every
 function it declares is exported by libeds_hip.so and bound in capi.EPI_EXPORTS (no GPU needed: nothing here launches anything)."""
-import importlib
-import os
-import re
-import subprocess
+import header_checks as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_epiline.h")
-capi = importlib.import_module("slam-eds_amd.capi")
-
-
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_[a-z0-9_]+)\s*\(", text)))
+capi = hc.capi
 
 
 def test_epiline_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_epiline.h"\nint main(void) { return EDS_EPI_BORDER_REFLECT_101 == 4 ? 0 : 1; }\n')
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
+    hc.compiles_clean("eds_hip_epiline.h", "EDS_EPI_BORDER_REFLECT_101 == 4 ? 0 : 1", tmp_path)
 
 
 def test_epiline_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.EPI_EXPORTS)
-    assert not set(capi.EPI_EXPORTS) & (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS))
     # cv::BORDER_CONSTANT, REPLICATE, REFLECT, REFLECT_101 (= BORDER_DEFAULT)
     assert (capi.EPI_BORDER_CONSTANT, capi.EPI_BORDER_REPLICATE, capi.EPI_BORDER_REFLECT, capi.EPI_BORDER_REFLECT_101) == (0, 1, 2, 4)
 
 
 def test_epiline_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared_functions()
-    lines = ['#include <stdio.h>', '#include "eds_hip_epiline.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_epi_abi_version() != EDS_HIP_EPILINE_ABI_VERSION || EDS_HIP_EPILINE_ABI_VERSION != 1) return 3;",
-              "    if (EDS_EPI_BORDER_CONSTANT != 0 || EDS_EPI_BORDER_REPLICATE != 1 || EDS_EPI_BORDER_REFLECT != 2) return 4;",
-              "    if (eds_epi_track_points(0, 0, 1, 7, 4, 0, 1, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID) return 5;",
-              "    if (eds_epi_get(0, 0, 0) != EDS_ERR_INVALID || eds_epi_get_model(0, 0, 0) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_epi_depth_update(0, 0, 1, 0, 0, 0) != EDS_ERR_INVALID) return 7;",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run("eds_hip_epiline.h", hc.declared("eds_hip_epiline.h"), [
+        "    if (eds_epi_abi_version() != EDS_HIP_EPILINE_ABI_VERSION || EDS_HIP_EPILINE_ABI_VERSION != 1) return 3;",
+        "    if (EDS_EPI_BORDER_CONSTANT != 0 || EDS_EPI_BORDER_REPLICATE != 1 || EDS_EPI_BORDER_REFLECT != 2) return 4;",
+        "    if (eds_epi_track_points(0, 0, 1, 7, 4, 0, 1, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID) return 5;",
+        "    if (eds_epi_get(0, 0, 0) != EDS_ERR_INVALID || eds_epi_get_model(0, 0, 0) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_epi_depth_update(0, 0, 1, 0, 0, 0) != EDS_ERR_INVALID) return 7;"], tmp_path)
 
 
 def test_epiline_header_is_a_build_input():
     """a header-only edit must rebuild the library (capi.build's staleness check)"""
-    import inspect
-    assert "eds_hip_epiline.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    assert "eds_epiline.hip" in mk and "eds_hip_epiline.h" in mk and "eds_epiline.o: HIPFLAGS += -ffp-contract=off" in mk
+    assert hc.is_build_input("eds_hip_epiline.h") and hc.is_build_input("eds_epiline.hip")
+    assert hc.contraction_off(hc.compile_line("eds_epiline.o"))

@@ -3,13 +3,11 @@ exported by libeds_hip.so and listed in capi.IMM_EXPORTS, and its defaults are t
 here launches anything)."""
 import ctypes as C
 import importlib
-import os
-import re
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_immature.h")
-capi = importlib.import_module("slam-eds_amd.capi")
+import header_checks as hc
+
+capi = hc.capi
 immature = importlib.import_module("slam-eds_amd.immature")
 
 # reference src/utils/settings.cpp:90-165
@@ -18,57 +16,21 @@ REFERENCE_SETTINGS = dict(max_pix_search=0.027, trace_stepsize=1.0, trace_gn_ite
                           outlier_th=12.0 * 12.0, outlier_th_sum_component=50.0 * 50.0, overall_energy_th_weight=1.0)
 
 
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_imm_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_immature_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_immature.h"\nint main(void) { return EDS_HIP_IMMATURE_ABI_VERSION == 1 ? 0 : 1; }\n')
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
-
-
-def test_immature_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.IMM_EXPORTS)
-    others = (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS) |
-              set(capi.KFP_EXPORTS) | set(capi.KFS_EXPORTS))
-    assert not set(capi.IMM_EXPORTS) & others
-    assert len(set(capi.IMM_EXPORTS)) == len(capi.IMM_EXPORTS)
-
-
 def test_immature_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared_functions()
-    lines = ['#include <stdio.h>', '#include "eds_hip_immature.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    eds_imm_params p;", "    float x = 0; int32_t t = 0; int m = 0;",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_imm_abi_version() != EDS_HIP_IMMATURE_ABI_VERSION || EDS_HIP_IMMATURE_ABI_VERSION != 1) return 3;",
-              "    if (eds_abi_version() != 6) return 4;",
-              "    eds_imm_params_default(&p);",
-              "    if (p.trace_gn_iterations != 3 || p.min_trace_test_radius != 2 || p.outlier_th != 144.0f) return 5;",
-              "    if (eds_imm_set_params(0, &p) != EDS_ERR_INVALID || eds_imm_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_imm_create(0, 4, 4, 1, 1, 1, 0) != EDS_ERR_INVALID) return 7;",
-              "    if (eds_imm_set_host_images(0, 0, 1, &x, 0, 0, 0) != EDS_ERR_INVALID) return 8;",
-              "    if (eds_imm_trace(0, 0, 1, &t, &x, &x, &x, 0) != EDS_ERR_INVALID) return 9;",
-              "    if (eds_imm_num_points(0, 0, &m) != EDS_ERR_INVALID || eds_imm_get_image(0, EDS_IMM_HOST_IMAGE, 0, &x) != EDS_ERR_INVALID) return 10;",
-              "    if (EDS_IMM_GOOD != 0 || EDS_IMM_OOB != 1 || EDS_IMM_OUTLIER != 2 || EDS_IMM_SKIPPED != 3 || EDS_IMM_BADCONDITION != 4 ||",
-              "        EDS_IMM_UNINITIALIZED != 5 || EDS_IMM_NUM_STATUS != 6) return 11;",
-              "    eds_imm_destroy(0);",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run("eds_hip_immature.h", hc.declared("eds_hip_immature.h"), [
+        "    eds_imm_params p;", "    float x = 0; int32_t t = 0; int m = 0;",
+        "    if (eds_imm_abi_version() != EDS_HIP_IMMATURE_ABI_VERSION || EDS_HIP_IMMATURE_ABI_VERSION != 1) return 3;",
+        "    if (eds_abi_version() != 6) return 4;",
+        "    eds_imm_params_default(&p);",
+        "    if (p.trace_gn_iterations != 3 || p.min_trace_test_radius != 2 || p.outlier_th != 144.0f) return 5;",
+        "    if (eds_imm_set_params(0, &p) != EDS_ERR_INVALID || eds_imm_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_imm_create(0, 4, 4, 1, 1, 1, 0) != EDS_ERR_INVALID) return 7;",
+        "    if (eds_imm_set_host_images(0, 0, 1, &x, 0, 0, 0) != EDS_ERR_INVALID) return 8;",
+        "    if (eds_imm_trace(0, 0, 1, &t, &x, &x, &x, 0) != EDS_ERR_INVALID) return 9;",
+        "    if (eds_imm_num_points(0, 0, &m) != EDS_ERR_INVALID || eds_imm_get_image(0, EDS_IMM_HOST_IMAGE, 0, &x) != EDS_ERR_INVALID) return 10;",
+        "    if (EDS_IMM_GOOD != 0 || EDS_IMM_OOB != 1 || EDS_IMM_OUTLIER != 2 || EDS_IMM_SKIPPED != 3 || EDS_IMM_BADCONDITION != 4 ||",
+        "        EDS_IMM_UNINITIALIZED != 5 || EDS_IMM_NUM_STATUS != 6) return 11;",
+        "    eds_imm_destroy(0);"], tmp_path)
 
 
 def test_defaults_equal_the_reference_settings():
@@ -84,7 +46,7 @@ def test_ctypes_struct_matches_the_header(tmp_path):
                    '(int)sizeof(eds_imm_params), (int)offsetof(eds_imm_params, min_trace_test_radius), '
                    '(int)offsetof(eds_imm_params, overall_energy_th_weight)); return 0; }\n')
     exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    subprocess.check_call(["gcc", "-std=c99", "-I", capi.INCLUDE, str(src), "-o", str(exe)])
     got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
     P = immature.Params
     assert got == [C.sizeof(P), P.min_trace_test_radius.offset, P.overall_energy_th_weight.offset]
@@ -93,9 +55,6 @@ def test_ctypes_struct_matches_the_header(tmp_path):
 def test_immature_sources_are_build_inputs():
     """a header-only edit must rebuild the library (capi.build's staleness check); the trace is fp32 in the reference's order, so its
     translation unit is built without FMA contraction; the shared header is a prerequisite of every object"""
-    import inspect
-    assert "eds_hip_immature.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
     for f in ("eds_immature.hip", "eds_hip_immature.h", "eds_immature.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp"):
-        assert f in mk, f
-    assert "eds_immature.o: HIPFLAGS += -ffp-contract=off" in mk
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_immature.o"))

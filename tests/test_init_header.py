@@ -7,15 +7,13 @@ import importlib
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 
 import init_harness as ih
+import header_checks as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_init.h")
-capi = importlib.import_module("slam-eds_amd.capi")
+capi = hc.capi
 init = importlib.import_module("slam-eds_amd.init")
 
 # reference src/init/CoarseInitializer.cpp:58-61, :79-86; src/utils/settings.cpp:90, :127; src/tracking/HessianBlocks.h:59-65
@@ -23,25 +21,7 @@ REFERENCE = dict(huber_th=9.0, outlier_th=144.0, alpha_k=6.25, alpha_w=22500.0, 
                  max_iterations=[5, 5, 10, 30, 50], scale_xi_rot=1.0, scale_xi_trans=1.0, scale_a=10.0, scale_b=1000.0)
 
 
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_ini_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_init_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc_, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_init.h"\nint main(void) { return EDS_HIP_INIT_ABI_VERSION == 1 ? 0 : 1; }\n')
-        subprocess.check_call([cc_, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
-
-
 def test_init_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.INI_EXPORTS)
-    others = (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS) |
-              set(capi.KFP_EXPORTS) | set(capi.KFS_EXPORTS) | set(capi.IMM_EXPORTS) | set(capi.CT_EXPORTS) | set(capi.SEL_EXPORTS))
-    assert not set(capi.INI_EXPORTS) & others
-    assert len(set(capi.INI_EXPORTS)) == len(capi.INI_EXPORTS)
     capi.build()
     L = init._lib()
     for name in capi.INI_EXPORTS:
@@ -50,41 +30,27 @@ def test_init_declarations_equal_binding():
 
 def test_init_c_program_links_every_function_and_arguments_are_refused_before_the_device(tmp_path):
     """a C program calls every setter and creator with arguments that must be refused: no device is needed to be told so"""
-    capi.build()
-    names = _declared_functions()
-    lines = ['#include <stdio.h>', '#include "eds_hip_init.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    eds_ini_params p; eds_ini_result r; eds_ini_point pt; eds_ini* h = 0;",
-              "    float x = 0, uv[4] = {3.1f, 3.1f, 4.1f, 3.1f}; double d[12] = {0}; int32_t m = 0, nb[20], par[2];",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_ini_abi_version() != EDS_HIP_INIT_ABI_VERSION || EDS_HIP_INIT_ABI_VERSION != 1) return 3;",
-              "    eds_ini_params_default(&p);",
-              "    if (p.huber_th != 9.0f || p.outlier_th != 144.0f || p.alpha_k != 6.25f || p.alpha_w != 22500.0f || p.reg_weight != 0.8f) return 4;",
-              "    if (p.coupling_weight != 1.0f || p.fix_affine != 1 || p.max_iterations[4] != 50 || p.scale_a != 10.0f || p.scale_b != 1000.0f) return 5;",
-              "    if (eds_ini_create(0, 64, 64, 5, 100, 0) != EDS_ERR_INVALID || eds_ini_create(0, 64, 64, 6, 100, &h) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_ini_create(0, 50, 64, 3, 100, &h) != EDS_ERR_INVALID || eds_ini_create(0, 48, 64, 3, 0, &h) != EDS_ERR_INVALID) return 7;",
-              "    if (eds_ini_create(0, 48, 64, 3, EDS_INI_MAX_POINTS + 1, &h) != EDS_ERR_INVALID || h) return 8;",
-              "    if (eds_ini_set_params(0, &p) != EDS_ERR_INVALID || eds_ini_get_params(0, &p) != EDS_ERR_INVALID) return 9;",
-              "    if (eds_ini_set_calib(0, 1, 1, 0, 0) != EDS_ERR_INVALID || eds_ini_set_first(0, &x, 0, 0, 1) != EDS_ERR_INVALID) return 10;",
-              "    if (eds_ini_set_pose(0, d, d) != EDS_ERR_INVALID || eds_ini_set_points(0, 0, &x, 0, 0, &m) != EDS_ERR_INVALID) return 11;",
-              "    if (eds_ini_set_points_selected(0, 0, &m) != EDS_ERR_INVALID || eds_ini_set_neighbours(0, 0, nb, par) != EDS_ERR_INVALID) return 12;",
-              "    if (eds_ini_track_frame(0, &x, 0, 0, 1, 5, &r) != EDS_ERR_INVALID || eds_ini_get_schedule_depth(0, 0, &m) != EDS_ERR_INVALID) return 13;",
-              "    if (eds_ini_get_points(0, 0, &pt, &m) != EDS_ERR_INVALID || eds_ini_get_jb(0, 0, 0, &x) != EDS_ERR_INVALID) return 14;",
-              "    if (eds_ini_get_level(0, 0, 0, &x) != EDS_ERR_INVALID || eds_ini_get_kernel_ms(0, &x) != EDS_ERR_INVALID) return 15;",
-              "    if (eds_ini_make_nn(2, 0, 0, 0, nb, 0) != EDS_ERR_INVALID || eds_ini_make_nn(2, uv, 0, 0, nb, par) != EDS_ERR_INVALID) return 16;",
-              "    if (eds_ini_make_nn(2, uv, 0, 0, nb, 0) != EDS_OK || nb[0] != 0 || nb[1] != 1 || nb[2] != -1 || nb[10] != 1 || nb[11] != 0) return 17;",
-              "    if (sizeof(eds_ini_point) != 64 || sizeof(eds_ini_result) != 712 || sizeof(eds_ini_params) != 64 || EDS_INI_MAX_LEVELS != 5) return 18;",
-              "    eds_ini_destroy(0);",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    assert set(names) <= set(re.findall(r"\s[TW]\s+(\S+)", out))
+    hc.link_and_run("eds_hip_init.h", hc.declared("eds_hip_init.h"), [
+        "    eds_ini_params p; eds_ini_result r; eds_ini_point pt; eds_ini* h = 0;",
+        "    float x = 0, uv[4] = {3.1f, 3.1f, 4.1f, 3.1f}; double d[12] = {0}; int32_t m = 0, nb[20], par[2];",
+        "    if (eds_ini_abi_version() != EDS_HIP_INIT_ABI_VERSION || EDS_HIP_INIT_ABI_VERSION != 1) return 3;",
+        "    eds_ini_params_default(&p);",
+        "    if (p.huber_th != 9.0f || p.outlier_th != 144.0f || p.alpha_k != 6.25f || p.alpha_w != 22500.0f || p.reg_weight != 0.8f) return 4;",
+        "    if (p.coupling_weight != 1.0f || p.fix_affine != 1 || p.max_iterations[4] != 50 || p.scale_a != 10.0f || p.scale_b != 1000.0f) return 5;",
+        "    if (eds_ini_create(0, 64, 64, 5, 100, 0) != EDS_ERR_INVALID || eds_ini_create(0, 64, 64, 6, 100, &h) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_ini_create(0, 50, 64, 3, 100, &h) != EDS_ERR_INVALID || eds_ini_create(0, 48, 64, 3, 0, &h) != EDS_ERR_INVALID) return 7;",
+        "    if (eds_ini_create(0, 48, 64, 3, EDS_INI_MAX_POINTS + 1, &h) != EDS_ERR_INVALID || h) return 8;",
+        "    if (eds_ini_set_params(0, &p) != EDS_ERR_INVALID || eds_ini_get_params(0, &p) != EDS_ERR_INVALID) return 9;",
+        "    if (eds_ini_set_calib(0, 1, 1, 0, 0) != EDS_ERR_INVALID || eds_ini_set_first(0, &x, 0, 0, 1) != EDS_ERR_INVALID) return 10;",
+        "    if (eds_ini_set_pose(0, d, d) != EDS_ERR_INVALID || eds_ini_set_points(0, 0, &x, 0, 0, &m) != EDS_ERR_INVALID) return 11;",
+        "    if (eds_ini_set_points_selected(0, 0, &m) != EDS_ERR_INVALID || eds_ini_set_neighbours(0, 0, nb, par) != EDS_ERR_INVALID) return 12;",
+        "    if (eds_ini_track_frame(0, &x, 0, 0, 1, 5, &r) != EDS_ERR_INVALID || eds_ini_get_schedule_depth(0, 0, &m) != EDS_ERR_INVALID) return 13;",
+        "    if (eds_ini_get_points(0, 0, &pt, &m) != EDS_ERR_INVALID || eds_ini_get_jb(0, 0, 0, &x) != EDS_ERR_INVALID) return 14;",
+        "    if (eds_ini_get_level(0, 0, 0, &x) != EDS_ERR_INVALID || eds_ini_get_kernel_ms(0, &x) != EDS_ERR_INVALID) return 15;",
+        "    if (eds_ini_make_nn(2, 0, 0, 0, nb, 0) != EDS_ERR_INVALID || eds_ini_make_nn(2, uv, 0, 0, nb, par) != EDS_ERR_INVALID) return 16;",
+        "    if (eds_ini_make_nn(2, uv, 0, 0, nb, 0) != EDS_OK || nb[0] != 0 || nb[1] != 1 || nb[2] != -1 || nb[10] != 1 || nb[11] != 0) return 17;",
+        "    if (sizeof(eds_ini_point) != 64 || sizeof(eds_ini_result) != 712 || sizeof(eds_ini_params) != 64 || EDS_INI_MAX_LEVELS != 5) return 18;",
+        "    eds_ini_destroy(0);"], tmp_path)
 
 
 def test_defaults_equal_the_reference_and_the_records_agree():
@@ -100,13 +66,9 @@ def test_defaults_equal_the_reference_and_the_records_agree():
 
 
 def test_init_sources_are_build_inputs():
-    import inspect
-    assert "eds_hip_init.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
     for f in ("eds_init.hip", "eds_hip_init.h", "eds_init.hpp", "eds_dso_common.hpp"):
-        assert f in mk, f
-    assert "eds_init.o: HIPFLAGS += -ffp-contract=off" in mk
-    assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_init.hip" in mk
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_init.o")) and hc.contraction_off(hc.resources_line("eds_init.hip"))
     hip = open(os.path.join(capi.CSRC, "eds_init.hip")).read()
     assert "eds_device_owner.hpp" in open(os.path.join(capi.CSRC, "eds_capi_internal.hpp")).read() or "eds_device_owner.hpp" in hip
     assert "edscapi::DeviceOwner own;" in hip and "hipMalloc" not in hip and "hipFree" not in hip

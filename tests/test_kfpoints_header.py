@@ -1,65 +1,22 @@
 """include/eds_hip_kfpoints.h, the companion header of the keyframe's own point set: plain C like eds_hip.h, and every function it declares
 is exported by libeds_hip.so and bound in capi.KFP_EXPORTS (no GPU needed: nothing here launches anything)."""
-import importlib
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_kfpoints.h")
-capi = importlib.import_module("slam-eds_amd.capi")
-
-
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_kfpoints_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_kfpoints.h"\nint main(void) { return EDS_HIP_KFPOINTS_ABI_VERSION == 1 ? 0 : 1; }\n')
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
-
-
-def test_kfpoints_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.KFP_EXPORTS)
-    others = set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS)
-    assert not set(capi.KFP_EXPORTS) & others
+import header_checks as hc
 
 
 def test_kfpoints_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared_functions()
-    lines = ['#include <stdio.h>', '#include "eds_hip_kfpoints.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    uint8_t flag = 1;", "    int k = 0;",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_kfp_abi_version() != EDS_HIP_KFPOINTS_ABI_VERSION || EDS_HIP_KFPOINTS_ABI_VERSION != 1) return 3;",
-              "    if (eds_abi_version() != 6) return 4;",
-              "    if (eds_kfp_refine_points(0, 0, 1, 1.0, 11, 4, 255, 1, 0, 0, 0, 0) != EDS_ERR_INVALID) return 5;",
-              "    if (eds_kfp_clean_points(0, 0, 1, 0.2, 0, 0, 0) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_kfp_erase_points(0, 0, 1, 1, &flag, 0, 0) != EDS_ERR_INVALID) return 7;",
-              "    if (eds_kfp_counts(0, 0, 1, &k, &k) != EDS_ERR_INVALID) return 8;",
-              "    if (eds_kfp_project_depth_map(0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID) return 9;",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run("eds_hip_kfpoints.h", hc.declared("eds_hip_kfpoints.h"), [
+        "    uint8_t flag = 1;", "    int k = 0;",
+        "    if (eds_kfp_abi_version() != EDS_HIP_KFPOINTS_ABI_VERSION || EDS_HIP_KFPOINTS_ABI_VERSION != 1) return 3;",
+        "    if (eds_abi_version() != 6) return 4;",
+        "    if (eds_kfp_refine_points(0, 0, 1, 1.0, 11, 4, 255, 1, 0, 0, 0, 0) != EDS_ERR_INVALID) return 5;",
+        "    if (eds_kfp_clean_points(0, 0, 1, 0.2, 0, 0, 0) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_kfp_erase_points(0, 0, 1, 1, &flag, 0, 0) != EDS_ERR_INVALID) return 7;",
+        "    if (eds_kfp_counts(0, 0, 1, &k, &k) != EDS_ERR_INVALID) return 8;",
+        "    if (eds_kfp_project_depth_map(0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID) return 9;"], tmp_path)
 
 
 def test_kfpoints_header_and_flag_are_build_inputs():
     """a header-only edit must rebuild the library (capi.build's staleness check), and the projection is built without FMA contraction"""
-    import inspect
-    assert "eds_hip_kfpoints.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    assert "eds_kfpoints.hip" in mk and "eds_hip_kfpoints.h" in mk and "eds_kfpoints.hpp" in mk
-    assert "eds_kfpoints.o: HIPFLAGS += -ffp-contract=off" in mk
+    for f in ("eds_kfpoints.hip", "eds_hip_kfpoints.h", "eds_kfpoints.hpp"):
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_kfpoints.o"))

@@ -4,15 +4,13 @@ select.Params and select.Pass, its defaults are the reference's settings, and it
 launches anything)."""
 import ctypes as C
 import importlib
-import os
-import re
 import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_select.h")
-capi = importlib.import_module("slam-eds_amd.capi")
+import header_checks as hc
+
+capi = hc.capi
 select = importlib.import_module("slam-eds_amd.select")
 immature = importlib.import_module("slam-eds_amd.immature")
 
@@ -20,64 +18,36 @@ immature = importlib.import_module("slam-eds_amd.immature")
 REFERENCE_SETTINGS = dict(min_grad_hist_cut=0.5, min_grad_hist_add=7.0, grad_downweight_per_level=0.75, select_direction_distribution=1)
 
 
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_sel_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_select_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_select.h"\n#include "eds_hip_immature.h"\n'
-                       "int main(void) { return EDS_HIP_SELECT_ABI_VERSION == 1 && EDS_HIP_IMMATURE_ABI_VERSION == 1 ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
+    hc.compiles_clean(("eds_hip_select.h", "eds_hip_immature.h"),
+                      "EDS_HIP_SELECT_ABI_VERSION == 1 && EDS_HIP_IMMATURE_ABI_VERSION == 1 ? 0 : 1", tmp_path)
 
 
 def test_select_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.SEL_EXPORTS)
-    others = (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS) |
-              set(capi.KFP_EXPORTS) | set(capi.KFS_EXPORTS) | set(capi.IMM_EXPORTS) | set(capi.CT_EXPORTS) | set(capi.WIN_EXPORTS) |
-              set(capi.WSV_EXPORTS) | set(capi.ACT_EXPORTS))
-    assert not set(capi.SEL_EXPORTS) & others
-    assert len(set(capi.SEL_EXPORTS)) == len(capi.SEL_EXPORTS)
     assert "eds_imm_create_points_selected" in capi.IMM_EXPORTS
 
 
 def test_select_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared_functions() + ["eds_imm_create_points_selected"]
-    lines = ['#include <stdio.h>', '#include "eds_hip_select.h"', '#include "eds_hip_immature.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    eds_sel_params p;", "    eds_sel_pass ps;", "    float x = 0; int m = 0; uint8_t b = 0; int32_t t = 0;",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_sel_abi_version() != EDS_HIP_SELECT_ABI_VERSION || EDS_HIP_SELECT_ABI_VERSION != 1) return 3;",
-              "    if (eds_abi_version() != 6 || eds_imm_abi_version() != 1) return 4;",
-              "    eds_sel_params_default(&p);",
-              "    if (p.min_grad_hist_cut != 0.5f || p.min_grad_hist_add != 7.0f || p.grad_downweight_per_level != 0.75f || p.select_direction_distribution != 1) return 5;",
-              "    if (eds_sel_set_params(0, &p) != EDS_ERR_INVALID || eds_sel_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_sel_create(0, 16, 16, 0) != EDS_ERR_INVALID) return 7;",
-              "    if (eds_sel_set_random_pattern(0, &b, 1) != EDS_ERR_INVALID || eds_sel_fill_reference_pattern(0, 1) != EDS_ERR_INVALID) return 8;",
-              "    if (eds_sel_set_potential(0, 3) != EDS_ERR_INVALID || eds_sel_get_potential(0, &m) != EDS_ERR_INVALID) return 9;",
-              "    if (eds_sel_set_image(0, &x, 0, 0, 0) != EDS_ERR_INVALID) return 10;",
-              "    if (eds_sel_make_maps(0, 100.0f, 1, 1.0f, &m, &ps, 1, &m, 0) != EDS_ERR_INVALID) return 11;",
-              "    if (eds_sel_get_map(0, &b) != EDS_ERR_INVALID || eds_sel_get_selection(0, &m, &t, &x) != EDS_ERR_INVALID) return 12;",
-              "    if (eds_sel_get_level(0, 0, &x) != EDS_ERR_INVALID || eds_sel_get_thresholds(0, EDS_SEL_THS, &x) != EDS_ERR_INVALID) return 13;",
-              "    if (eds_sel_get_scan_info(0, &m, &m) != EDS_ERR_INVALID) return 14;",
-              "    if (eds_imm_create_points_selected(0, 0, 0, 0, 0, 1, 1, &b, &m) != EDS_ERR_INVALID) return 15;",
-              "    if (EDS_SEL_THS != 0 || EDS_SEL_THS_SMOOTHED != 1 || EDS_SEL_MAX_POTENTIAL != 1073741824) return 16;",
-              "    eds_sel_destroy(0);",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run(("eds_hip_select.h", "eds_hip_immature.h"), hc.declared("eds_hip_select.h") + ["eds_imm_create_points_selected"], [
+        "    eds_sel_params p;",
+        "    eds_sel_pass ps;",
+        "    float x = 0; int m = 0; uint8_t b = 0; int32_t t = 0;",
+        "    if (eds_sel_abi_version() != EDS_HIP_SELECT_ABI_VERSION || EDS_HIP_SELECT_ABI_VERSION != 1) return 3;",
+        "    if (eds_abi_version() != 6 || eds_imm_abi_version() != 1) return 4;",
+        "    eds_sel_params_default(&p);",
+        "    if (p.min_grad_hist_cut != 0.5f || p.min_grad_hist_add != 7.0f || p.grad_downweight_per_level != 0.75f || p.select_direction_distribution != 1) return 5;",
+        "    if (eds_sel_set_params(0, &p) != EDS_ERR_INVALID || eds_sel_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_sel_create(0, 16, 16, 0) != EDS_ERR_INVALID) return 7;",
+        "    if (eds_sel_set_random_pattern(0, &b, 1) != EDS_ERR_INVALID || eds_sel_fill_reference_pattern(0, 1) != EDS_ERR_INVALID) return 8;",
+        "    if (eds_sel_set_potential(0, 3) != EDS_ERR_INVALID || eds_sel_get_potential(0, &m) != EDS_ERR_INVALID) return 9;",
+        "    if (eds_sel_set_image(0, &x, 0, 0, 0) != EDS_ERR_INVALID) return 10;",
+        "    if (eds_sel_make_maps(0, 100.0f, 1, 1.0f, &m, &ps, 1, &m, 0) != EDS_ERR_INVALID) return 11;",
+        "    if (eds_sel_get_map(0, &b) != EDS_ERR_INVALID || eds_sel_get_selection(0, &m, &t, &x) != EDS_ERR_INVALID) return 12;",
+        "    if (eds_sel_get_level(0, 0, &x) != EDS_ERR_INVALID || eds_sel_get_thresholds(0, EDS_SEL_THS, &x) != EDS_ERR_INVALID) return 13;",
+        "    if (eds_sel_get_scan_info(0, &m, &m) != EDS_ERR_INVALID) return 14;",
+        "    if (eds_imm_create_points_selected(0, 0, 0, 0, 0, 1, 1, &b, &m) != EDS_ERR_INVALID) return 15;",
+        "    if (EDS_SEL_THS != 0 || EDS_SEL_THS_SMOOTHED != 1 || EDS_SEL_MAX_POTENTIAL != 1073741824) return 16;",
+        "    eds_sel_destroy(0);"], tmp_path)
 
 
 def test_defaults_equal_the_reference_settings():
@@ -93,7 +63,7 @@ def test_ctypes_structs_match_the_header(tmp_path):
                    '(int)sizeof(eds_sel_params), (int)offsetof(eds_sel_params, select_direction_distribution), (int)sizeof(eds_sel_pass), '
                    '(int)offsetof(eds_sel_pass, n4)); return 0; }\n')
     exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    subprocess.check_call(["gcc", "-std=c99", "-I", capi.INCLUDE, str(src), "-o", str(exe)])
     got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
     P, S = select.Params, select.Pass
     assert got == [C.sizeof(P), P.select_direction_distribution.offset, C.sizeof(S), S.n4.offset]
@@ -111,10 +81,6 @@ def test_the_reference_pattern_is_the_constructors():
 def test_select_sources_are_build_inputs():
     """a header-only edit must rebuild the library (capi.build's staleness check); the selector is fp32 in the reference's order, so its
     translation unit is built without FMA contraction; the shared headers are prerequisites of every object"""
-    import inspect
-    assert "eds_hip_select.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
     for f in ("eds_pixsel.hip", "eds_hip_select.h", "eds_pixsel.hpp", "eds_pixsel_internal.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp", "eds_dso_image.hip"):
-        assert f in mk, f
-    assert "eds_pixsel.o: HIPFLAGS += -ffp-contract=off" in mk
-    assert "-c eds_pixsel.hip -o /dev/null" in mk
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_pixsel.o")) and hc.resources_line("eds_pixsel.hip")

@@ -8,75 +8,43 @@ import os
 import re
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_undistort.h")
+import header_checks as hc
+
 REFERENCE_SETTINGS_CPP = "/root/reference/src/utils/settings.cpp"
-capi = importlib.import_module("slam-eds_amd.capi")
+capi = hc.capi
 und = importlib.import_module("slam-eds_amd.undistort")
 
 # reference src/utils/settings.cpp:117-118
 REFERENCE_SETTINGS = dict(photometric_calibration=2, use_exposure=1)
 
 
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_und_[a-z0-9_A-Z]+)\s*\(", text)))
-
-
 def test_undistort_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_undistort.h"\n#include "eds_hip_select.h"\n'
-                       "int main(void) { return EDS_HIP_UNDISTORT_ABI_VERSION == 1 && EDS_HIP_SELECT_ABI_VERSION == 1 ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
-
-
-def test_undistort_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.UND_EXPORTS)
-    others = (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS) |
-              set(capi.KFP_EXPORTS) | set(capi.KFS_EXPORTS) | set(capi.IMM_EXPORTS) | set(capi.CT_EXPORTS) | set(capi.WIN_EXPORTS) |
-              set(capi.WSV_EXPORTS) | set(capi.WED_EXPORTS) | set(capi.WFL_EXPORTS) | set(capi.ACT_EXPORTS) | set(capi.SEL_EXPORTS) |
-              set(capi.INI_EXPORTS))
-    assert not set(capi.UND_EXPORTS) & others
-    assert len(set(capi.UND_EXPORTS)) == len(capi.UND_EXPORTS)
+    hc.compiles_clean(("eds_hip_undistort.h", "eds_hip_select.h"),
+                      "EDS_HIP_UNDISTORT_ABI_VERSION == 1 && EDS_HIP_SELECT_ABI_VERSION == 1 ? 0 : 1", tmp_path)
 
 
 def test_undistort_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared_functions()
-    lines = ['#include <stdio.h>', '#include "eds_hip_undistort.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    eds_und_settings s;", "    eds_und_geometry g;", "    eds_und* u = (eds_und*)&g;",
-              "    double K[9]; float x = 0; int m = 0; uint8_t b = 0; const float* d = 0; int64_t rs = 0;",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_und_abi_version() != EDS_HIP_UNDISTORT_ABI_VERSION || EDS_HIP_UNDISTORT_ABI_VERSION != 1) return 3;",
-              "    if (eds_abi_version() != 6) return 4;",
-              "    eds_und_settings_default(&s);",
-              "    if (s.photometric_calibration != 2 || s.use_exposure != 1) return 5;",
-              "    if (eds_und_create(0, 0, 1, &u) != EDS_ERR_INVALID || u != 0 || eds_und_create(0, &g, 1, 0) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_und_get_K(0, K) != EDS_ERR_INVALID || eds_und_get_map(0, &x, &x) != EDS_ERR_INVALID) return 7;",
-              "    if (eds_und_is_passthrough(0, &m) != EDS_ERR_INVALID || eds_und_set_map(0, &x, &x) != EDS_ERR_INVALID) return 8;",
-              "    if (eds_und_set_photometric(0, &x, 256, &b, EDS_UND_U8) != EDS_ERR_INVALID) return 9;",
-              "    if (eds_und_set_settings(0, &s) != EDS_ERR_INVALID || eds_und_get_settings(0, &s) != EDS_ERR_INVALID) return 10;",
-              "    if (eds_und_set_form(0, EDS_UND_FORM_FUSED) != EDS_ERR_INVALID || eds_und_get_form(0, &m) != EDS_ERR_INVALID) return 11;",
-              "    if (eds_und_process(0, 0, 1, &b, EDS_UND_U8, 0, 0, 0, &x, 1.0f, &x) != EDS_ERR_INVALID) return 12;",
-              "    if (eds_und_image(0, 0, &d, &rs) != EDS_ERR_INVALID || eds_und_get_image(0, 0, &x) != EDS_ERR_INVALID) return 13;",
-              "    if (EDS_UND_MODEL_FOV != 0 || EDS_UND_MODEL_RADTAN != 1 || EDS_UND_MODEL_EQUIDISTANT != 2 || EDS_UND_MODEL_KB != 3 || EDS_UND_MODEL_PINHOLE != 4) return 14;",
-              "    if (EDS_UND_OUT_CROP != 0 || EDS_UND_OUT_NONE != 1 || EDS_UND_OUT_GIVEN != 2 || EDS_UND_OUT_FULL != 3) return 15;",
-              "    if (EDS_UND_U8 != 0 || EDS_UND_U16 != 1 || EDS_UND_FORM_FUSED != 0 || EDS_UND_FORM_TWO_PASS != 1 || EDS_UND_FORM_AUTO != 2 || EDS_UND_MAX_SLOTS != 16) return 16;",
-              "    eds_und_destroy(0);",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run("eds_hip_undistort.h", hc.declared("eds_hip_undistort.h"), [
+        "    eds_und_settings s;",
+        "    eds_und_geometry g;",
+        "    eds_und* u = (eds_und*)&g;",
+        "    double K[9]; float x = 0; int m = 0; uint8_t b = 0; const float* d = 0; int64_t rs = 0;",
+        "    if (eds_und_abi_version() != EDS_HIP_UNDISTORT_ABI_VERSION || EDS_HIP_UNDISTORT_ABI_VERSION != 1) return 3;",
+        "    if (eds_abi_version() != 6) return 4;",
+        "    eds_und_settings_default(&s);",
+        "    if (s.photometric_calibration != 2 || s.use_exposure != 1) return 5;",
+        "    if (eds_und_create(0, 0, 1, &u) != EDS_ERR_INVALID || u != 0 || eds_und_create(0, &g, 1, 0) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_und_get_K(0, K) != EDS_ERR_INVALID || eds_und_get_map(0, &x, &x) != EDS_ERR_INVALID) return 7;",
+        "    if (eds_und_is_passthrough(0, &m) != EDS_ERR_INVALID || eds_und_set_map(0, &x, &x) != EDS_ERR_INVALID) return 8;",
+        "    if (eds_und_set_photometric(0, &x, 256, &b, EDS_UND_U8) != EDS_ERR_INVALID) return 9;",
+        "    if (eds_und_set_settings(0, &s) != EDS_ERR_INVALID || eds_und_get_settings(0, &s) != EDS_ERR_INVALID) return 10;",
+        "    if (eds_und_set_form(0, EDS_UND_FORM_FUSED) != EDS_ERR_INVALID || eds_und_get_form(0, &m) != EDS_ERR_INVALID) return 11;",
+        "    if (eds_und_process(0, 0, 1, &b, EDS_UND_U8, 0, 0, 0, &x, 1.0f, &x) != EDS_ERR_INVALID) return 12;",
+        "    if (eds_und_image(0, 0, &d, &rs) != EDS_ERR_INVALID || eds_und_get_image(0, 0, &x) != EDS_ERR_INVALID) return 13;",
+        "    if (EDS_UND_MODEL_FOV != 0 || EDS_UND_MODEL_RADTAN != 1 || EDS_UND_MODEL_EQUIDISTANT != 2 || EDS_UND_MODEL_KB != 3 || EDS_UND_MODEL_PINHOLE != 4) return 14;",
+        "    if (EDS_UND_OUT_CROP != 0 || EDS_UND_OUT_NONE != 1 || EDS_UND_OUT_GIVEN != 2 || EDS_UND_OUT_FULL != 3) return 15;",
+        "    if (EDS_UND_U8 != 0 || EDS_UND_U16 != 1 || EDS_UND_FORM_FUSED != 0 || EDS_UND_FORM_TWO_PASS != 1 || EDS_UND_FORM_AUTO != 2 || EDS_UND_MAX_SLOTS != 16) return 16;",
+        "    eds_und_destroy(0);"], tmp_path)
 
 
 def test_invalid_geometries_are_refused_before_any_device_is_touched():
@@ -122,7 +90,7 @@ def test_ctypes_structs_match_the_header(tmp_path):
                    '\\n", (int)sizeof(eds_und_geometry), (int)sizeof(eds_und_settings), (int)offsetof(eds_und_settings, photometric_calibration), '
                    "(int)offsetof(eds_und_settings, use_exposure), " + ", ".join(f"(int)offsetof(eds_und_geometry, {f})" for f in fields) + "); return 0; }\n")
     exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    subprocess.check_call(["gcc", "-std=c99", "-I", capi.INCLUDE, str(src), "-o", str(exe)])
     got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
     G, S = und.Geometry, und.Settings
     assert [k for k, _ in G._fields_] == fields
@@ -134,12 +102,6 @@ def test_ctypes_structs_match_the_header(tmp_path):
 def test_undistort_sources_are_build_inputs():
     """a header-only edit must rebuild the library (capi.build's staleness check); the per-frame path is fp32 in the reference's order, so
     its translation unit is built without FMA contraction; the shared headers are prerequisites of every object"""
-    import inspect
-    assert "eds_hip_undistort.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
-    srcs = re.search(r"^SRCS\s*:=(.*)$", mk, re.M).group(1).split()
-    hdrs = re.search(r"^HDRS\s*:=(.*)$", mk, re.M).group(1).split()
-    assert "eds_undistort.hip" in srcs
-    assert "eds_undistort.hpp" in hdrs and "../../include/eds_hip_undistort.h" in hdrs and "eds_device_owner.hpp" in hdrs and "eds_dso_common.hpp" in hdrs
-    assert "eds_undistort.o: HIPFLAGS += -ffp-contract=off" in mk
-    assert "-c eds_undistort.hip -o /dev/null" in mk
+    for f in ("eds_undistort.hip", "eds_hip_undistort.h", "eds_undistort.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp"):
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_undistort.o")) and hc.resources_line("eds_undistort.hip")

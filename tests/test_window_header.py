@@ -4,16 +4,13 @@ build inputs; and the stand-alone program of csrc/eds_window.hpp under g++ (test
 inputs (no GPU needed: nothing here launches anything)."""
 import ctypes as C
 import importlib
-import os
 import re
-import subprocess
 
 import window_cases as wc
 import window_harness as wh
+import header_checks as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_window.h")
-capi = importlib.import_module("slam-eds_amd.capi")
+capi = hc.capi
 window = importlib.import_module("slam-eds_amd.window")
 
 # reference src/utils/settings.cpp:91-127 and src/tracking/HessianBlocks.h:58-62
@@ -21,65 +18,29 @@ REFERENCE_SETTINGS = dict(outlier_th_sum_component=50.0 * 50.0, huber_th=9.0, af
                           scale_f=1.0, scale_c=1.0)
 
 
-def _declared_functions():
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(eds_win_[a-z0-9_]+)\s*\(", text)))
-
-
-def test_window_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc_, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_window.h"\nint main(void) { return EDS_HIP_WINDOW_ABI_VERSION == 1 ? 0 : 1; }\n')
-        subprocess.check_call([cc_, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
-
-
-def test_window_declarations_equal_binding():
-    assert _declared_functions() == sorted(capi.WIN_EXPORTS)
-    others = (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS) |
-              set(capi.KFP_EXPORTS) | set(capi.KFS_EXPORTS) | set(capi.IMM_EXPORTS) | set(capi.CT_EXPORTS))
-    assert not set(capi.WIN_EXPORTS) & others
-    assert len(set(capi.WIN_EXPORTS)) == len(capi.WIN_EXPORTS)
-
-
 def test_window_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared_functions()
-    lines = ['#include <stdio.h>', '#include "eds_hip_window.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    eds_win_params p; eds_win_residual_out ro; eds_win_point_out po;",
-              "    float x = 0; double d = 0; int32_t m[3] = {0, 0, 0};",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_win_abi_version() != EDS_HIP_WINDOW_ABI_VERSION || EDS_HIP_WINDOW_ABI_VERSION != 1) return 3;",
-              "    if (eds_abi_version() != 6) return 4;",
-              "    eds_win_params_default(&p);",
-              "    if (p.outlier_th_sum_component != 2500.0f || p.huber_th != 9.0f || p.affine_opt_mode_a != 1e12f || p.affine_opt_mode_b != 1e8f) return 5;",
-              "    if (p.scale_idepth != 1.0f || p.scale_f != 1.0f || p.scale_c != 1.0f) return 5;",
-              "    if (eds_win_set_params(0, &p) != EDS_ERR_INVALID || eds_win_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_win_create(0, 48, 64, 8, 1, 1, 0) != EDS_ERR_INVALID) return 7;",
-              "    if (eds_win_set_calib(0, 1, 1, 0, 0) != EDS_ERR_INVALID) return 8;",
-              "    if (eds_win_set_frames(0, 0, 1, &x, 0, 0, 0) != EDS_ERR_INVALID || eds_win_get_frame(0, 0, &x) != EDS_ERR_INVALID) return 9;",
-              "    if (eds_win_set_points(0, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID || eds_win_set_idepths(0, &x, &x) != EDS_ERR_INVALID) return 10;",
-              "    if (eds_win_set_residuals(0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID) return 11;",
-              "    if (eds_win_linearize(0, 2, &x, &x, &d, m) != EDS_ERR_INVALID || eds_win_apply(0, 1) != EDS_ERR_INVALID) return 12;",
-              "    if (eds_win_point_hessians(0, 0, 0, 0, 0, m) != EDS_ERR_INVALID) return 13;",
-              "    if (eds_win_accumulate(0, 2, &d, &d, 0, 0, 0, 0, &d, &d, &d, &d, &d, m) != EDS_ERR_INVALID) return 13;",
-              "    if (eds_win_acc_size(8) != 41888 || eds_win_acc_size(1) != 0 || eds_win_acc_size(9) != 0) return 13;",
-              "    if (eds_win_get_residuals(0, &ro) != EDS_ERR_INVALID || eds_win_get_points(0, &po) != EDS_ERR_INVALID) return 14;",
-              "    if (sizeof(eds_win_params) != 32 || EDS_WIN_MAX_FRAMES != 8 || EDS_WIN_PRECALC_FLOATS != 27 || EDS_WIN_J_WORDS != 74) return 15;",
-              "    if (EDS_WIN_IN != 0 || EDS_WIN_OOB != 1 || EDS_WIN_OUTLIER != 2) return 16;",
-              "    eds_win_destroy(0);",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run("eds_hip_window.h", hc.declared("eds_hip_window.h"), [
+        "    eds_win_params p; eds_win_residual_out ro; eds_win_point_out po;",
+        "    float x = 0; double d = 0; int32_t m[3] = {0, 0, 0};",
+        "    if (eds_win_abi_version() != EDS_HIP_WINDOW_ABI_VERSION || EDS_HIP_WINDOW_ABI_VERSION != 1) return 3;",
+        "    if (eds_abi_version() != 6) return 4;",
+        "    eds_win_params_default(&p);",
+        "    if (p.outlier_th_sum_component != 2500.0f || p.huber_th != 9.0f || p.affine_opt_mode_a != 1e12f || p.affine_opt_mode_b != 1e8f) return 5;",
+        "    if (p.scale_idepth != 1.0f || p.scale_f != 1.0f || p.scale_c != 1.0f) return 5;",
+        "    if (eds_win_set_params(0, &p) != EDS_ERR_INVALID || eds_win_get_params(0, &p) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_win_create(0, 48, 64, 8, 1, 1, 0) != EDS_ERR_INVALID) return 7;",
+        "    if (eds_win_set_calib(0, 1, 1, 0, 0) != EDS_ERR_INVALID) return 8;",
+        "    if (eds_win_set_frames(0, 0, 1, &x, 0, 0, 0) != EDS_ERR_INVALID || eds_win_get_frame(0, 0, &x) != EDS_ERR_INVALID) return 9;",
+        "    if (eds_win_set_points(0, 0, 0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID || eds_win_set_idepths(0, &x, &x) != EDS_ERR_INVALID) return 10;",
+        "    if (eds_win_set_residuals(0, 0, 0, 0, 0, 0) != EDS_ERR_INVALID) return 11;",
+        "    if (eds_win_linearize(0, 2, &x, &x, &d, m) != EDS_ERR_INVALID || eds_win_apply(0, 1) != EDS_ERR_INVALID) return 12;",
+        "    if (eds_win_point_hessians(0, 0, 0, 0, 0, m) != EDS_ERR_INVALID) return 13;",
+        "    if (eds_win_accumulate(0, 2, &d, &d, 0, 0, 0, 0, &d, &d, &d, &d, &d, m) != EDS_ERR_INVALID) return 13;",
+        "    if (eds_win_acc_size(8) != 41888 || eds_win_acc_size(1) != 0 || eds_win_acc_size(9) != 0) return 13;",
+        "    if (eds_win_get_residuals(0, &ro) != EDS_ERR_INVALID || eds_win_get_points(0, &po) != EDS_ERR_INVALID) return 14;",
+        "    if (sizeof(eds_win_params) != 32 || EDS_WIN_MAX_FRAMES != 8 || EDS_WIN_PRECALC_FLOATS != 27 || EDS_WIN_J_WORDS != 74) return 15;",
+        "    if (EDS_WIN_IN != 0 || EDS_WIN_OOB != 1 || EDS_WIN_OUTLIER != 2) return 16;",
+        "    eds_win_destroy(0);"], tmp_path)
 
 
 def test_defaults_equal_the_reference_settings():
@@ -93,13 +54,9 @@ def test_defaults_equal_the_reference_settings():
 
 
 def test_window_sources_are_build_inputs():
-    import inspect
-    assert "eds_hip_window.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
     for f in ("eds_window.hip", "eds_hip_window.h", "eds_window.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp", "eds_dso_image.hip"):
-        assert f in mk, f
-    assert "eds_window.o: HIPFLAGS += -ffp-contract=off" in mk
-    assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_window.hip" in mk
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_window.o")) and hc.contraction_off(hc.resources_line("eds_window.hip"))
 
 
 def test_precalc_helper_forms_the_records_of_the_cases():

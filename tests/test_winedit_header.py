@@ -5,44 +5,25 @@ build inputs, the two window headers declare what they declared before; and the 
 import importlib
 import os
 import re
-import subprocess
 
 import winedit_harness as weh
 import winsolve_cases as wsc
+import header_checks as hc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "eds_hip_winedit.h")
-capi = importlib.import_module("slam-eds_amd.capi")
+capi = hc.capi
 winedit = importlib.import_module("slam-eds_amd.winedit")
 
 
-def _declared(path, prefix):
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(" + prefix + r"[a-z0-9_]+)\s*\(", text)))
-
-
 def test_winedit_header_is_c99_and_cxx11_clean(tmp_path):
-    for std, cc_, ext in (("-std=c99", "gcc", "c"), ("-std=c++11", "g++", "cpp")):
-        src = tmp_path / ("inc." + ext)
-        src.write_text('#include "eds_hip_winedit.h"\nint main(void) { return EDS_HIP_WINEDIT_ABI_VERSION == 1 && EDS_HIP_WINSOLVE_ABI_VERSION == 1 ? 0 : 1; }\n')
-        subprocess.check_call([cc_, std, "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                               "-o", str(tmp_path / "inc.o")])
+    hc.compiles_clean("eds_hip_winedit.h", "EDS_HIP_WINEDIT_ABI_VERSION == 1 && EDS_HIP_WINSOLVE_ABI_VERSION == 1 ? 0 : 1", tmp_path)
 
 
 def test_winedit_declarations_equal_binding():
-    assert _declared(HDR, "eds_wed_") == sorted(capi.WED_EXPORTS)
-    others = (set(capi.EXPORTS) | set(capi.DEPTH_EXPORTS) | set(capi.KLT_EXPORTS) | set(capi.EPI_EXPORTS) | set(capi.DEV_EXPORTS) |
-              set(capi.KFP_EXPORTS) | set(capi.KFS_EXPORTS) | set(capi.IMM_EXPORTS) | set(capi.CT_EXPORTS) | set(capi.WIN_EXPORTS) |
-              set(capi.WSV_EXPORTS) | set(capi.ACT_EXPORTS) | set(capi.SEL_EXPORTS))
-    assert not set(capi.WED_EXPORTS) & others
-    assert len(set(capi.WED_EXPORTS)) == len(capi.WED_EXPORTS)
     # the two window headers declare exactly what they declared: nothing of this header leaked into them
-    for name, prefix, exports in (("eds_hip_window.h", "eds_win_", capi.WIN_EXPORTS), ("eds_hip_winsolve.h", "eds_wsv_", capi.WSV_EXPORTS)):
-        path = os.path.join(ROOT, "include", name)
-        assert _declared(path, prefix) == sorted(exports)
-        assert not _declared(path, "eds_wed_")
+    for name, exports in (("eds_hip_window.h", capi.WIN_EXPORTS), ("eds_hip_winsolve.h", capi.WSV_EXPORTS)):
+        assert hc.declared(name) == sorted(exports)
     # the header says what it must: the stable order, and that the swap-with-back is not restated
-    text = open(HDR).read()
+    text = open(os.path.join(capi.INCLUDE, "eds_hip_winedit.h")).read()
     assert "STABLE" in text and "swap-with-back" in text and "NOT restated" in text
     # ... and every step of marginalizeFrame's arithmetic, the stated inverse and its tie rule included
     for phrase in ("sqrt(|H_ii| + 10)", "exact no-ops", "partial pivoting", "LOWEST r on", "ONE subtraction", "0.5 * (H_ij + H_ji)", "EDS_ERR_NOT_USABLE"):
@@ -50,40 +31,25 @@ def test_winedit_declarations_equal_binding():
 
 
 def test_winedit_c_program_links_every_declared_function(tmp_path):
-    capi.build()
-    names = _declared(HDR, "eds_wed_")
-    lines = ['#include <stdio.h>', '#include "eds_hip_winedit.h"', "int main(void) {", "    const void* f[] = {"]
-    lines += [f"        (const void*)(size_t)&{n}," for n in names]
-    lines += ["    };", "    size_t i, n = sizeof(f) / sizeof(f[0]);", "    eds_wed_out out; int32_t m[8] = {0, 0, 0, 0, 0, 0, 0, 0};",
-              "    for (i = 0; i < n; ++i) if (!f[i]) return 2;",
-              "    if (eds_wed_abi_version() != EDS_HIP_WINEDIT_ABI_VERSION || EDS_HIP_WINEDIT_ABI_VERSION != 1) return 3;",
-              "    if (eds_abi_version() != 6 || eds_win_abi_version() != 1 || eds_wsv_abi_version() != 1) return 4;",
-              "    if (eds_wed_remove_residuals(0, m, 0, m) != EDS_ERR_INVALID || eds_wed_remove_residuals(0, 0, 0, 0) != EDS_ERR_INVALID) return 5;",
-              "    if (eds_wed_remove_points(0, m, 0, m, m) != EDS_ERR_INVALID) return 6;",
-              "    if (eds_wed_counts(0, m, m, m) != EDS_ERR_INVALID) return 7;",
-              "    { double d[8] = {0, 0, 0, 0, 0, 0, 0, 0};",
-              "      if (eds_wed_marginalize_frame(0, 0, d, d, d, d, d, d) != EDS_ERR_INVALID) return 10;",
-              "      if (eds_wed_set_state(0, 2, d, d, d, d, d, d, d) != EDS_ERR_INVALID) return 11; }",
-              "    if (eds_wed_insert_activated(0, 0, m, m) != EDS_ERR_INVALID) return 12;",
-              "    if (eds_wed_get(0, &out) != EDS_ERR_INVALID) return 8;",
-              "    if (sizeof(eds_wed_out) != 10 * sizeof(void*)) return 9;",
-              '    printf("%d functions\\n", (int)n);', "    return 0;", "}"]
-    src = tmp_path / "link.c"
-    src.write_text("\n".join(lines) + "\n")
-    libdir = os.path.dirname(capi.LIB_PATH)
-    exe = tmp_path / "link"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                           "-L", libdir, "-leds_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    assert f"{len(names)} functions" in subprocess.check_output([str(exe)], text=True)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", capi.LIB_PATH], text=True)
-    exported = set(re.findall(r"\s[TW]\s+(\S+)", out))
-    assert set(names) <= exported
+    hc.link_and_run("eds_hip_winedit.h", hc.declared("eds_hip_winedit.h"), [
+        "    eds_wed_out out; int32_t m[8] = {0, 0, 0, 0, 0, 0, 0, 0};",
+        "    if (eds_wed_abi_version() != EDS_HIP_WINEDIT_ABI_VERSION || EDS_HIP_WINEDIT_ABI_VERSION != 1) return 3;",
+        "    if (eds_abi_version() != 6 || eds_win_abi_version() != 1 || eds_wsv_abi_version() != 1) return 4;",
+        "    if (eds_wed_remove_residuals(0, m, 0, m) != EDS_ERR_INVALID || eds_wed_remove_residuals(0, 0, 0, 0) != EDS_ERR_INVALID) return 5;",
+        "    if (eds_wed_remove_points(0, m, 0, m, m) != EDS_ERR_INVALID) return 6;",
+        "    if (eds_wed_counts(0, m, m, m) != EDS_ERR_INVALID) return 7;",
+        "    { double d[8] = {0, 0, 0, 0, 0, 0, 0, 0};",
+        "      if (eds_wed_marginalize_frame(0, 0, d, d, d, d, d, d) != EDS_ERR_INVALID) return 10;",
+        "      if (eds_wed_set_state(0, 2, d, d, d, d, d, d, d) != EDS_ERR_INVALID) return 11; }",
+        "    if (eds_wed_insert_activated(0, 0, m, m) != EDS_ERR_INVALID) return 12;",
+        "    if (eds_wed_get(0, &out) != EDS_ERR_INVALID) return 8;",
+        "    if (sizeof(eds_wed_out) != 10 * sizeof(void*)) return 9;"], tmp_path)
 
 
 def test_winedit_binding_matches_the_harness():
     assert [k for k, _, _ in winedit.OUT_FIELDS] == [k for k, _, _ in weh.OUT_FIELDS] == [k for k, _ in winedit.Out._fields_]
     assert winedit.STATE_FIELDS == weh.STATE_FIELDS
-    text = re.sub(r"/\*.*?\*/", " ", open(HDR).read(), flags=re.S)
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(capi.INCLUDE, "eds_hip_winedit.h")).read(), flags=re.S)
     body = re.search(r"typedef struct eds_wed_out \{(.*?)\} eds_wed_out;", text, flags=re.S).group(1)
     assert re.findall(r"\*\s*([a-zA-Z_]+);", body) == [k for k, _, _ in winedit.OUT_FIELDS]
     for method in ("remove_residuals", "remove_points", "marginalize_frame", "insert_activated", "set_state", "counts", "rows"):
@@ -91,13 +57,9 @@ def test_winedit_binding_matches_the_harness():
 
 
 def test_winedit_sources_are_build_inputs():
-    import inspect
-    assert "eds_hip_winedit.h" in inspect.getsource(capi.build)
-    mk = open(os.path.join(capi.CSRC, "Makefile")).read()
     for f in ("eds_winedit.hip", "eds_hip_winedit.h", "eds_winedit.hpp", "eds_window_internal.hpp", "eds_device_owner.hpp", "eds_dso_common.hpp"):
-        assert f in mk, f
-    assert "eds_winedit.o: HIPFLAGS += -ffp-contract=off" in mk
-    assert "-ffp-contract=off -Rpass-analysis=kernel-resource-usage -c eds_winedit.hip" in mk
+        assert hc.is_build_input(f), f
+    assert hc.contraction_off(hc.compile_line("eds_winedit.o")) and hc.contraction_off(hc.resources_line("eds_winedit.hip"))
     text = open(os.path.join(capi.CSRC, "eds_winedit.hip")).read()
     assert '#include "eds_window_internal.hpp"' in text and '#include "eds_winedit.hpp"' in text and "struct eds_win {" not in text
     # no sum of floats anywhere, so nothing to reorder: the kernels hold no floating-point atomic
