@@ -14,10 +14,15 @@
 #include <memory>
 
 #include "../../slam-eds_amd/csrc/eds_winedit.hpp"
+#include "../../slam-eds_amd/csrc/eds_winflag.hpp"
 
 struct WedOut { int32_t *point, *target, *res_first, *host; float *uv, *color, *weights, *idz, *deltaF, *backup; };
 
 namespace {
+
+// where the last wed_insert_activated put the rows: new point row -> old row, or -2 - k for the k-th activated point; new residual row
+// -> old row, or -1 for a new residual
+std::vector<int32_t> g_insert_map_p, g_insert_map_r;
 
 // the states whose rows a frame's marginalisation left in place though the state is no longer valid (eds_wsv_state::rows_live on the device)
 std::vector<HostWsv*> g_rows_live;
@@ -208,7 +213,9 @@ int wed_insert_activated(HostWin* h, HostWsv* s, int F, int mp, int K, const int
         for (int j = 0; j < 8; ++j) { o.color[j] = color[8 * k + j]; o.weights[j] = weights[8 * k + j]; }
         h->ids[q] = h->idz[q] = idepth[k];
         res_first[q] = edswed::ins_new_res(si, (int64_t)c * F);
+        map_p[q] = -2 - k;
     }
+    g_insert_map_p = map_p; g_insert_map_r = map_r;
     for (int j = 0; j < R; ++j) {
         const int64_t g = map_g[j];
         const int r = edswed::ins_new_res(si, g);
@@ -219,6 +226,62 @@ int wed_insert_activated(HostWin* h, HostWsv* s, int F, int mp, int K, const int
     h->n = n2; h->m = m2;
     if (inserted_points) *inserted_points = K;
     if (inserted_residuals) *inserted_residuals = R;
+    return RC_OK;
+}
+
+// eds_wfl_insert_frame_residuals over the window's rows (the history's columns are tests/winflag_harness.py's): every point not hosted by
+// `frame` and without a residual towards it gets one at the end of its run, as eds_win_set_residuals leaves state IN and energy 0
+int wed_insert_frame_residuals(HostWin* h, HostWsv* s, int frame, int cap_residuals, int32_t* inserted) {
+    if (!h || frame < 0 || frame >= h->max_frames) return RC_INVALID;
+    const int n = h->n, m = h->m;
+    std::vector<int32_t> need((size_t)n + 1, 0), excl((size_t)n + 1), map_p((size_t)n + 1);
+    for (int p = 0; p < n; ++p) need[p] = edswfl::needs_residual(h->res_first.data(), h->res_target.data(), h->pts[p].host, p, frame);
+    const int K = edswed::scan_serial(need.data(), n, excl.data(), map_p.data());
+    const int m2 = m + K;
+    if (m2 > cap_residuals) return RC_STATE;
+    if (inserted) *inserted = K;
+    if (!K) return RC_OK;
+    std::vector<int32_t> map_r((size_t)m2, -1), res_point((size_t)m2), res_first((size_t)n + 1);
+    for (int r = 0; r < m; ++r) {
+        const int p = h->res_point[r], i = edswfl::moved_row(excl.data(), p, r);
+        map_r[i] = r; res_point[i] = p;
+    }
+    for (int q = 0; q <= n; ++q) res_first[q] = edswfl::moved_first(h->res_first.data(), excl.data(), q);
+    const bool with_state = rows_live(h, s);
+    {
+        Mover mv;
+        mv.add(h->res_target, 1, m2); mv.add(h->state, 1, m2); mv.add(h->new_state, 1, m2); mv.add(h->active, 1, m2);
+        mv.add(h->energy, 1, m2); mv.add(h->new_energy, 1, m2); mv.add(h->new_energy_wo, 1, m2); mv.add(h->ret, 1, m2);
+        mv.add(h->cp, 3, m2); mv.add(h->proj, 16, m2); mv.add(h->JpJdF, 8, m2);
+        if (with_state) { mv.add(s->lin, 1, m2); mv.add(s->rtz, 8, m2); mv.add(s->res_approx, 8, m2); }
+        mv.add(h->J, J_WORDS, m2, true); mv.add(h->efJ, J_WORDS, m2, true);
+        mv.run(map_r.data(), m2);
+    }
+    for (int p = 0; p < n; ++p) {
+        if (!need[p]) continue;
+        const int r = edswfl::new_row(h->res_first.data(), excl.data(), p);
+        res_point[r] = p; h->res_target[r] = frame; h->new_state[r] = ST_OUTLIER;
+    }
+    h->res_point.swap(res_point); h->res_first.swap(res_first);
+    h->m = m2;
+    return RC_OK;
+}
+
+// eds_wfl_flag_points' resetOOB: every residual of a point with mask[p] != 0 (the linearize, apply and fix that follow are the window's
+// and the solver's own functions over those points)
+int wed_reset_oob(HostWin* h, HostWsv* s, const int32_t* mask) {
+    if (!h || !s || (!mask && h->n)) return RC_INVALID;
+    if (!s->valid) return RC_STATE;
+    for (int r = 0; r < h->m; ++r)
+        if (mask[h->res_point[r]]) edswfl::reset_oob(r, h->state.data(), h->new_state.data(), h->energy.data(), h->new_energy.data(), s->lin.data());
+    return RC_OK;
+}
+
+// the maps of the last wed_insert_activated (n and m as it left them)
+int wed_last_insert_maps(int n, int m, int32_t* map_p, int32_t* map_r) {
+    if ((size_t)n != g_insert_map_p.size() || (size_t)m != g_insert_map_r.size()) return RC_STATE;
+    if (n) std::memcpy(map_p, g_insert_map_p.data(), (size_t)n * 4);
+    if (m) std::memcpy(map_r, g_insert_map_r.data(), (size_t)m * 4);
     return RC_OK;
 }
 
@@ -259,7 +322,7 @@ int wed_get(HostWin* h, HostWsv* s, const WedOut* o) {
     if (o->target && m) std::memcpy(o->target, h->res_target.data(), m * 4);
     if (o->res_first) std::memcpy(o->res_first, h->res_first.data(), (n + 1) * 4);
     if (o->idz && n) std::memcpy(o->idz, h->idz.data(), n * 4);
-    if (o->deltaF && n && s && s->valid) std::memcpy(o->deltaF, s->delta.data(), n * 4);
+    if (o->deltaF && n && rows_live(h, s) && s->delta.size() == n) std::memcpy(o->deltaF, s->delta.data(), n * 4);   // as on the device: the row outlives a frame's marginalisation
     if (o->backup && n) { if (s->have_backup) std::memcpy(o->backup, s->backup.data(), n * 4); else std::memset(o->backup, 0, n * 4); }
     for (size_t i = 0; i < n; ++i) {
         const Point& p = h->pts[i];

@@ -41,6 +41,9 @@ def load_harness():
         L.wed_marginalize_frame.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
         L.wed_set_state.argtypes = [vp, vp, C.c_int] + [vp] * 7
         L.wed_insert_activated.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 7 + [C.c_int, C.c_int, vp, vp]
+        L.wed_insert_frame_residuals.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+        L.wed_reset_oob.argtypes = [vp, vp, vp]
+        L.wed_last_insert_maps.argtypes = [C.c_int, C.c_int, vp, vp]
         L.wed_forget.argtypes = [vp]
         L.wed_counts.argtypes = [vp, vp, vp, vp]
         L.wed_edit_mirrors.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -95,6 +98,25 @@ class HostEdit:
         self.win.m += ir.value
         self.linearized = False
         return ip.value, ir.value
+
+    def last_insert_maps(self):
+        """where the last ``insert_activated`` put the rows: (new point row -> old row, or -2 - k for the k-th activated point; new
+        residual row -> old row, or -1 for a new residual)"""
+        map_p, map_r = np.zeros(self.win.n, np.int32), np.zeros(self.win.m, np.int32)
+        wsh._rc(self.L.wed_last_insert_maps(self.win.n, self.win.m, _vp(map_p), _vp(map_r)))
+        return map_p, map_r
+
+    def insert_frame_residuals(self, frame, max_residuals=1 << 24):
+        """the rows' half of ``WindowFlags.insert_frame_residuals`` (the history's is ``winflag_harness.insert_frame_residuals``)"""
+        inserted = C.c_int32()
+        wsh._rc(self.L.wed_insert_frame_residuals(self.win._h, self._s(), int(frame), int(max_residuals), C.cast(C.byref(inserted), C.c_void_p)))
+        self.win.m += inserted.value
+        return inserted.value
+
+    def reset_oob(self, mask):
+        """``resetOOB`` and isLinearized = 0 for every residual of the points with mask != 0: the first step of the re-linearization in
+        ``WindowFlags.flag_points``"""
+        wsh._rc(self.L.wed_reset_oob(self.win._h, self._s(), _vp(_i32(mask, self.win.n))))
 
     def remove_residuals(self, select=None):
         sel = None if select is None else _i32(select, self.win.m)
