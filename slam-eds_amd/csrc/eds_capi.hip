@@ -57,11 +57,11 @@ void fill_static(const eds_trk* h, int slot) {
 }
 
 void fill_pose(eds_trk* h, int slot, const double* p, const double* q, const double* v) {
-    if (h->gram_pending) { hipStreamSynchronize(h->st); h->gram_pending = false; }      // h_G as an earlier refresh left it
+    if (h->gram_pending) { hipStreamSynchronize(h->own.st); h->gram_pending = false; }      // h_G as an earlier refresh left it
     if (h->slots[slot].gram_host_stale) {           // set_idepth refreshed the Gram matrices in HBM only: fetch this slot's now
         const size_t off = (size_t)slot * EDS_MAX_BLOCKS * 36;
-        hipMemcpyAsync(h->h_G + off, h->dG + off, (size_t)EDS_MAX_BLOCKS * 36 * 8, hipMemcpyDeviceToHost, h->st);
-        hipStreamSynchronize(h->st);
+        hipMemcpyAsync(h->h_G + off, h->dG + off, (size_t)EDS_MAX_BLOCKS * 36 * 8, hipMemcpyDeviceToHost, h->own.st);
+        hipStreamSynchronize(h->own.st);
         h->slots[slot].gram_host_stale = false;
     }
     fill_static(h, slot);
@@ -71,7 +71,7 @@ void fill_pose(eds_trk* h, int slot, const double* p, const double* q, const dou
 
 int upload_pose(eds_trk* h, int first, int count) {
     EDS_HIP_TRY(hipMemcpyAsync(h->dpose + (size_t)first * EDS_POSE_STRIDE, h->h_pose + (size_t)first * EDS_POSE_STRIDE,
-                               sizeof(double) * EDS_POSE_STRIDE * count, hipMemcpyHostToDevice, h->st));
+                               sizeof(double) * EDS_POSE_STRIDE * count, hipMemcpyHostToDevice, h->own.st));
     return EDS_OK;
 }
 
@@ -101,9 +101,9 @@ int check_idle_slots(const eds_trk* h, int first, int count, int need) {
 int read_xy_planes(eds_trk* h, const double* plane, int first, int count, int stride, double* dst) {
     const size_t Np = (size_t)h->Np, n = (size_t)count * Np;
     std::vector<double> v(2 * n);
-    EDS_HIP_TRY(hipMemcpyAsync(v.data(), plane + Np * first, n * 8, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipMemcpyAsync(v.data() + n, plane + (size_t)h->B * Np + Np * first, n * 8, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(v.data(), plane + Np * first, n * 8, hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipMemcpyAsync(v.data() + n, plane + (size_t)h->B * Np + Np * first, n * 8, hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     for (int b = 0; b < count; ++b) {
         const double* x = v.data() + Np * b;
         double* d = dst + 2 * (size_t)b * stride;
@@ -114,19 +114,13 @@ int read_xy_planes(eds_trk* h, const double* plane, int first, int count, int st
 
 int workgroup_lds_limit(const eds_trk* h, size_t* bytes) {
     int v = 0;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->own.dev));
     *bytes = (size_t)v;
     return EDS_OK;
 }
 
 bool row_bins_fit(const eds_trk* h, size_t limit) { return 2 * ((size_t)h->H + 2) * 4 <= limit && h->W <= 65535 && h->H <= 65535; }
-
-bool device_alloc(std::initializer_list<DevAlloc> table) {
-    for (const DevAlloc& a : table)
-        if (hipMalloc(a.p, a.bytes) != hipSuccess) return false;
-    return true;
-}
 
 }  // namespace edscapi
 using namespace edscapi;
@@ -135,33 +129,12 @@ namespace {
 
 void free_all(eds_trk* h) {
     if (!h) return;
-    hipSetDevice(h->dev);
-    void* dptrs[] = {h->dkf, h->dpose, h->dG, h->dpart, h->dncstat,
-                     h->dmhat, h->dframe, h->dr, h->dJ, h->d_probe, h->d_bdev};
-    for (void* p : dptrs) if (p) hipFree(p);
-    eds_fused_free(&h->fused);
-    eds_strips_free(h);
-    eds_frame_free(&h->frame_build);
-    eds_points_free(&h->point_ops);
-    eds_depth_free(&h->depth);
-    eds_klt_free(&h->klt);
-    eds_epi_free(&h->epi);
-    eds_kfp_free(&h->kfp);
+    hipSetDevice(h->own.dev);
     edsmap_internal::release(h->map);
-    eds_kfs_free(&h->kfs);
-    eds_keyframe_free(&h->kf_build);
-    void* hptrs[] = {h->h_pose, h->h_part, h->h_G, h->h_f32, h->h_r, h->h_fstage, h->h_rmap, h->h_idp, h->h_fprog, h->h_bstage};
     for (hipEvent_t e : h->ev_bstage) hipEventDestroy(e);
-    for (void* p : hptrs) if (p) hipHostFree(p);
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->ev_stage) hipEventDestroy(h->ev_stage);
-    if (h->ev_idp) hipEventDestroy(h->ev_idp);
-    if (h->ev_up) hipEventDestroy(h->ev_up);
-    if (h->ev_dev_in) hipEventDestroy(h->ev_dev_in);
-    if (h->ev_dev_out) hipEventDestroy(h->ev_dev_out);
+    for (hipEvent_t e : {h->ev0, h->ev1, h->ev_stage, h->ev_idp, h->ev_up, h->ev_dev_in, h->ev_dev_out}) if (e) hipEventDestroy(e);
     if (h->st_up) hipStreamDestroy(h->st_up);
-    if (h->st) hipStreamDestroy(h->st);
+    h->own.close();
     delete h;
 }
 
@@ -174,7 +147,7 @@ int eds_internal_solve_host(eds_trk* h, int level, int first, int count) { retur
 int eds_stream_idle(eds_trk* h) {
     if (!h->stream_dirty) return EDS_OK;
     h->stream_dirty = false;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
@@ -232,7 +205,7 @@ int eds_trk_create(const eds_trk_cfg* cfg, int batch, int max_points_, int H, in
     eds_trk* h = new (std::nothrow) eds_trk();
     if (!h) return fail(EDS_ERR_INVALID, "out of memory");
     h->cfg = *cfg;
-    h->B = batch; h->Nmax = max_points_; h->H = H; h->W = W; h->dev = cfg->device;
+    h->B = batch; h->Nmax = max_points_; h->H = H; h->W = W;
     h->Hp = eds_frame_extent(H); h->Wp = eds_frame_extent(W);
     h->tiled = 1;
     if (const char* bad = eds_knobs_from_env(&h->knobs)) {      // the ONLY place the library reads tuning variables from the environment (eds_launch_rule.hpp)
@@ -252,79 +225,58 @@ int eds_trk_create(const eds_trk_cfg* cfg, int batch, int max_points_, int H, in
         std::memset(&s.info, 0, sizeof(s.info));
     }
     const size_t BN = (size_t)batch * h->Np;
-#define EDS_ALLOC(ptr, bytes)                                                                  \
-    do {                                                                                       \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                                    \
-        if (e_ != hipSuccess) { free_all(h); return fail(EDS_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e_)); } \
-    } while (0)
-#define EDS_HALLOC(ptr, bytes)                                                                 \
-    do {                                                                                       \
-        hipError_t e_ = hipHostMalloc((void**)&(ptr), (bytes), hipHostMallocDefault);          \
-        if (e_ != hipSuccess) { free_all(h); return fail(EDS_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e_)); } \
-    } while (0)
-    hipError_t e = hipSetDevice(h->dev);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev0);
+    if (int rc = h->own.open(cfg->device)) { delete h; return rc; }
+    hipError_t e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_idp, hipEventDisableTiming);
-    if (e != hipSuccess) { free_all(h); return fail(EDS_ERR_HIP, std::string("stream/event: ") + hipGetErrorString(e)); }
-    EDS_ALLOC(h->dkf, BN * 4 * EDS_KF_PLANES);
+    if (!h->own.st || e != hipSuccess) {
+        free_all(h);
+        return fail(EDS_ERR_HIP, std::string("stream/event: ") + (e != hipSuccess ? hipGetErrorString(e) : "the device refused a stream"));
+    }
+    h->h_f32_elems = std::max((size_t)h->Hp * h->Wp, (size_t)h->Np * 12);
+    if (!h->own.alloc({{(void**)&h->dkf, BN * 4 * EDS_KF_PLANES}, {(void**)&h->dmhat, BN * 4}, {(void**)&h->dr, BN * 4}, {(void**)&h->dJ, BN * 4 * 12},
+                       {(void**)&h->dframe, (size_t)batch * h->Hp * h->Wp * 4}, {(void**)&h->dpose, (size_t)batch * EDS_POSE_STRIDE * 8},
+                       {(void**)&h->dG, (size_t)batch * EDS_MAX_BLOCKS * 36 * 8}, {(void**)&h->dpart, (size_t)batch * h->max_seg * EDS_RED_K * 8},
+                       {(void**)&h->dncstat, (size_t)batch * EDS_MAX_BLOCKS * 8 * 8}})) {
+        free_all(h);
+        return fail(EDS_ERR_HIP, "hipMalloc: the device refused one of the tracker's buffers");
+    }
     h->dx = h->dkf + EDS_KF_X * BN; h->dy = h->dkf + EDS_KF_Y * BN; h->drho = h->dkf + EDS_KF_RHO * BN;
     h->dgx = h->dkf + EDS_KF_GX * BN; h->dgy = h->dkf + EDS_KF_GY * BN; h->dw = h->dkf + EDS_KF_W * BN;
     h->df0x = h->dkf + EDS_KF_F0X * BN; h->df0y = h->dkf + EDS_KF_F0Y * BN;
     h->dcell0 = reinterpret_cast<int*>(h->dkf + EDS_KF_CELL0 * BN);
-    EDS_ALLOC(h->dmhat, BN * 4); EDS_ALLOC(h->dr, BN * 4); EDS_ALLOC(h->dJ, BN * 4 * 12);
-    EDS_ALLOC(h->dframe, (size_t)batch * h->Hp * h->Wp * 4);
-    EDS_ALLOC(h->dpose, (size_t)batch * EDS_POSE_STRIDE * 8);
-    EDS_ALLOC(h->dG, (size_t)batch * EDS_MAX_BLOCKS * 36 * 8);
-    EDS_ALLOC(h->dpart, (size_t)batch * h->max_seg * EDS_RED_K * 8);
-    EDS_ALLOC(h->dncstat, (size_t)batch * EDS_MAX_BLOCKS * 8 * 8);
-    EDS_HALLOC(h->h_pose, (size_t)batch * EDS_POSE_STRIDE * 8);
-    EDS_HALLOC(h->h_part, (size_t)batch * h->max_seg * EDS_RED_K * 8);
-    EDS_HALLOC(h->h_G, (size_t)batch * EDS_MAX_BLOCKS * 36 * 8);
-    h->h_f32_elems = std::max((size_t)h->Hp * h->Wp, (size_t)h->Np * 12);
-    EDS_HALLOC(h->h_f32, h->h_f32_elems * 4);
-    EDS_HALLOC(h->h_r, BN * 4);
-    EDS_HALLOC(h->h_idp, (size_t)h->Np * 4);
-    if (hipHostGetDevicePointer((void**)&h->d_idp, h->h_idp, 0) != hipSuccess) { (void)hipGetLastError(); h->d_idp = nullptr; }
-    {   // mirror of the residual plane for the first few slots (eds_mirror_residuals)
-        const size_t nr = (size_t)std::min(batch, EDS_RHOST_SLOTS) * h->Np;
-        hipError_t e_ = hipHostMalloc((void**)&h->h_rmap, nr * 4, hipHostMallocMapped);
-        if (e_ == hipSuccess) e_ = hipHostGetDevicePointer((void**)&h->d_rmap, h->h_rmap, 0);
-        if (e_ != hipSuccess) { free_all(h); return fail(EDS_ERR_HIP, std::string("hipHostMalloc (residual mirror): ") + hipGetErrorString(e_)); }
-        std::memset(h->h_rmap, 0, nr * 4);
+    if (!h->own.alloc({pinned(h->h_pose, (size_t)batch * EDS_POSE_STRIDE * 8), pinned(h->h_part, (size_t)batch * h->max_seg * EDS_RED_K * 8),
+                       pinned(h->h_G, (size_t)batch * EDS_MAX_BLOCKS * 36 * 8), pinned(h->h_f32, h->h_f32_elems * 4), pinned(h->h_r, BN * 4),
+                       pinned(h->h_idp, (size_t)h->Np * 4)})) {
+        free_all(h);
+        return fail(EDS_ERR_HIP, "hipHostMalloc: the host refused one of the tracker's pinned buffers");
     }
-    {   // device-mapped: the tiling kernel reads the staging buffer in place
-        hipError_t e_ = hipHostMalloc((void**)&h->h_fstage, (size_t)H * W * 4, hipHostMallocMapped);
-        if (e_ == hipSuccess) e_ = hipHostGetDevicePointer((void**)&h->d_fstage, h->h_fstage, 0);
-        if (e_ != hipSuccess) { free_all(h); return fail(EDS_ERR_HIP, std::string("hipHostMalloc (frame staging): ") + hipGetErrorString(e_)); }
-    }
-    {   // progress / time-out words of the follower upload (eds_frame_store_follow); without them set_event_frame launches per band
-        hipError_t e_ = hipHostMalloc((void**)&h->h_fprog, 64, hipHostMallocMapped);
-        if (e_ == hipSuccess) e_ = hipHostGetDevicePointer((void**)&h->d_fprog, h->h_fprog, 0);
-        if (e_ != hipSuccess) { (void)hipGetLastError(); if (h->h_fprog) hipHostFree(h->h_fprog); h->h_fprog = nullptr; h->d_fprog = nullptr; }
-        else std::memset(h->h_fprog, 0, 64);
-    }
+    h->d_idp = h->own.device_view(h->h_idp);          // optional: without it the gram kernel reads the depths from HBM
+    // mirror of the residual plane for the first few slots (eds_mirror_residuals)
+    const size_t nr = (size_t)std::min(batch, EDS_RHOST_SLOTS) * h->Np;
+    if (!h->own.alloc_mapped(h->h_rmap, h->d_rmap, nr * 4)) { free_all(h); return fail(EDS_ERR_HIP, "hipHostMalloc (residual mirror) failed"); }
+    std::memset(h->h_rmap, 0, nr * 4);
+    // device-mapped: the tiling kernel reads the staging buffer in place
+    if (!h->own.alloc_mapped(h->h_fstage, h->d_fstage, (size_t)H * W * 4)) { free_all(h); return fail(EDS_ERR_HIP, "hipHostMalloc (frame staging) failed"); }
+    // progress / time-out words of the follower upload (eds_frame_store_follow); optional: without them set_event_frame launches per band
+    if (h->own.alloc_mapped(h->h_fprog, h->d_fprog, 64)) std::memset(h->h_fprog, 0, 64);
     std::memset(h->h_pose, 0, (size_t)batch * EDS_POSE_STRIDE * 8);
     std::memset(h->h_G, 0, (size_t)batch * EDS_MAX_BLOCKS * 36 * 8);
-    hipMemsetAsync(h->dcell0, 0, BN * 4, h->st);
+    hipMemsetAsync(h->dcell0, 0, BN * 4, h->own.st);
     float* f32s[] = {h->dx, h->dy, h->drho, h->dgx, h->dgy, h->dw, h->dmhat, h->dr, h->df0x, h->df0y};
-    for (float* p : f32s) hipMemsetAsync(p, 0, BN * 4, h->st);
-    hipMemsetAsync(h->dJ, 0, BN * 4 * 12, h->st);
-    hipMemsetAsync(h->dframe, 0, (size_t)batch * h->Hp * h->Wp * 4, h->st);
-    hipMemsetAsync(h->dpose, 0, (size_t)batch * EDS_POSE_STRIDE * 8, h->st);
-    hipMemsetAsync(h->dG, 0, (size_t)batch * EDS_MAX_BLOCKS * 36 * 8, h->st);
-    hipMemsetAsync(h->dpart, 0, (size_t)batch * h->max_seg * EDS_RED_K * 8, h->st);
-    hipMemsetAsync(h->dncstat, 0, (size_t)batch * EDS_MAX_BLOCKS * 8 * 8, h->st);
-    int rc = eds_fused_alloc(&h->fused, batch);
-    if (rc != 0) { free_all(h); return fail(EDS_ERR_HIP, "fused buffers: hipMalloc failed"); }
-    e = hipStreamSynchronize(h->st);
+    for (float* p : f32s) hipMemsetAsync(p, 0, BN * 4, h->own.st);
+    hipMemsetAsync(h->dJ, 0, BN * 4 * 12, h->own.st);
+    hipMemsetAsync(h->dframe, 0, (size_t)batch * h->Hp * h->Wp * 4, h->own.st);
+    hipMemsetAsync(h->dpose, 0, (size_t)batch * EDS_POSE_STRIDE * 8, h->own.st);
+    hipMemsetAsync(h->dG, 0, (size_t)batch * EDS_MAX_BLOCKS * 36 * 8, h->own.st);
+    hipMemsetAsync(h->dpart, 0, (size_t)batch * h->max_seg * EDS_RED_K * 8, h->own.st);
+    hipMemsetAsync(h->dncstat, 0, (size_t)batch * EDS_MAX_BLOCKS * 8 * 8, h->own.st);
+    if (eds_fused_alloc(h->own, &h->fused, batch) != 0) { free_all(h); return fail(EDS_ERR_HIP, "fused buffers: hipMalloc failed"); }
+    e = hipStreamSynchronize(h->own.st);
     if (e != hipSuccess) { free_all(h); return fail(EDS_ERR_HIP, std::string("init: ") + hipGetErrorString(e)); }
     *out = h;
     return EDS_OK;
-#undef EDS_ALLOC
-#undef EDS_HALLOC
 }
 
 void eds_trk_destroy(eds_trk* h) { free_all(h); }
@@ -340,10 +292,10 @@ int eds_trk_set_config(eds_trk* h, const eds_trk_cfg* cfg) {
             fill_static(h, s);
             int rc = upload_pose(h, s, 1);
             if (rc) return rc;
-            eds_launch_gram(h->arrays(), s, effective_blocks(h), h->st);
+            eds_launch_gram(h->arrays(), s, effective_blocks(h), h->own.st);
         }
-        EDS_HIP_TRY(hipMemcpyAsync(h->h_G, h->dG, (size_t)h->B * EDS_MAX_BLOCKS * 36 * 8, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(h->h_G, h->dG, (size_t)h->B * EDS_MAX_BLOCKS * 36 * 8, hipMemcpyDeviceToHost, h->own.st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     }
     return EDS_OK;
 }
@@ -436,23 +388,23 @@ static hipError_t wait_stream(eds_trk* h) {
             __builtin_ia32_pause();
         }
         h->stream_dirty = false;
-        return hipStreamSynchronize(h->st);
+        return hipStreamSynchronize(h->own.st);
     }
     h->stream_dirty = false;
     if (spin) {
         const auto t0 = std::chrono::steady_clock::now();
         for (;;) {
-            const hipError_t e = hipStreamQuery(h->st);
+            const hipError_t e = hipStreamQuery(h->own.st);
             if (e != hipErrorNotReady) return e;
             if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > EDS_SPIN_US) break;
         }
     }
-    return hipStreamSynchronize(h->st);
+    return hipStreamSynchronize(h->own.st);
 }
 
 int eds_trk_sync(eds_trk* h) {
     if (!h) return fail(EDS_ERR_INVALID, "null handle");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     EDS_HIP_TRY(wait_stream(h));
     if (h->h_fprog && (h->h_fprog[1] & 0x80000000u)) {      // a frame upload gave up waiting for the host: that slot's frame is incomplete
         h->h_fprog[1] = 0;
@@ -487,8 +439,8 @@ int eds_trk_get_trace(eds_trk* h, int slot, int max_iters, double* increments, d
 
 int eds_trk_timer_start(eds_trk* h) {
     if (!h) return fail(EDS_ERR_INVALID, "null handle");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipEventRecord(h->ev0, h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipEventRecord(h->ev0, h->own.st));
     return EDS_OK;
 }
 
@@ -497,13 +449,13 @@ int eds_trk_prepare_frames(eds_trk* h, int first, int count, int force, float* e
     if (rc) return rc;
     if (elapsed_ms) *elapsed_ms = 0.f;
     if (!h->tiled) return EDS_OK;      // (both samplers gather from the strips: the bilinear one reads the middle of the same patches)
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (force)
         for (int s = first; s < first + count; ++s) h->slots[h->slots[s].frame_slot >= 0 ? h->slots[s].frame_slot : s].strips_version = 0;
-    if (elapsed_ms) EDS_HIP_TRY(hipEventRecord(h->ev0, h->st));
+    if (elapsed_ms) EDS_HIP_TRY(hipEventRecord(h->ev0, h->own.st));
     if (!eds_strips_prepare(h, first, count)) return fail(EDS_ERR_HIP, "no memory for the strip copies of the frames");
     if (elapsed_ms) {
-        EDS_HIP_TRY(hipEventRecord(h->ev1, h->st));
+        EDS_HIP_TRY(hipEventRecord(h->ev1, h->own.st));
         EDS_HIP_TRY(hipEventSynchronize(h->ev1));
         EDS_HIP_TRY(hipEventElapsedTime(elapsed_ms, h->ev0, h->ev1));
     }
@@ -522,9 +474,10 @@ int eds_trk_set_knob(eds_trk* h, const char* name, const char* value) {
         // a new budget / phase count / policy: the copies are allocated again (with the new row phases) by the next solve that wants them
         h->strips_unavailable = false;
         if (h->dstrips && (std::strcmp(name, "EDS_STRIPS_PHASES") == 0 || std::strcmp(name, "EDS_STRIPS_BUDGET_PCT") == 0)) {
-            EDS_HIP_TRY(hipSetDevice(h->dev));
-            EDS_HIP_TRY(hipStreamSynchronize(h->st));
-            eds_strips_free(h);
+            EDS_HIP_TRY(hipSetDevice(h->own.dev));
+            EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
+            h->own.release(h->dstrips);
+            h->strips_bytes = 0;
             for (Slot& sl : h->slots) sl.strips_version = 0;
         }
     }
@@ -573,8 +526,8 @@ int eds_trk_last_launch(eds_trk* h, eds_trk_launch_info* out) {
 
 int eds_trk_timer_stop(eds_trk* h, float* elapsed_ms) {
     if (!h || !elapsed_ms) return fail(EDS_ERR_INVALID, "null argument");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    EDS_HIP_TRY(hipEventRecord(h->ev1, h->st));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    EDS_HIP_TRY(hipEventRecord(h->ev1, h->own.st));
     EDS_HIP_TRY(hipEventSynchronize(h->ev1));
     EDS_HIP_TRY(hipEventElapsedTime(elapsed_ms, h->ev0, h->ev1));
     return EDS_OK;
@@ -586,7 +539,7 @@ int eds_trk_update_points(eds_trk* h, int slot, int delete_out_points, double* c
     if (rc) return rc;
     Slot& s = h->slots[slot];
     if (!s.has_kf) return fail(EDS_ERR_STATE, "keyframe not set");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     int n = 0;
     if ((rc = eds_points_update(h, slot, delete_out_points != 0, coord_xy, tracks_xy, kept_index, &n, mean_sq_flow))) return rc;
     if (delete_out_points) s.epi_valid = false;     // the point set may have changed: the epiline's ef plane is stale
@@ -611,7 +564,7 @@ int eds_trk_update_points_batch(eds_trk* h, int first, int count, int delete_out
         maxN = std::max(maxN, h->slots[s].N);
     }
     if ((coord_xy || tracks_xy || kept_index) && stride < maxN) return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return update_points_range(h, first, count, delete_out_points, stride, coord_xy, tracks_xy, kept_index, n_kept, mean_sq_flow);
 }
 
@@ -635,7 +588,7 @@ int edscapi::update_points_range(eds_trk* h, int first, int count, int delete_ou
             else { s.has_kf = false; s.seeded = false; }
         }
     }
-    if (any) { EDS_HIP_TRY(hipStreamSynchronize(h->st)); h->gram_pending = false; }
+    if (any) { EDS_HIP_TRY(hipStreamSynchronize(h->own.st)); h->gram_pending = false; }
     return EDS_OK;
 }
 
@@ -659,7 +612,7 @@ int eds_trk_build_keyframe(eds_trk* h, int slot, int img_type, const void* img, 
     if (rc) return rc;
     if (!img || !sel) return fail(EDS_ERR_INVALID, "null image or selection parameters");
     if (n_depth < 0) return fail(EDS_ERR_INVALID, "negative depth-map size");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return eds_keyframe_build(h, slot, img_type, img, h->H, h->W, 1, sel, n_depth, depth_xy, depth_idp, fx, fy, cx, cy, n_points);
 }
 
@@ -670,14 +623,14 @@ int eds_trk_build_keyframe_image(eds_trk* h, int slot, int img_type, const void*
     if (rc) return rc;
     if (!img || !sel) return fail(EDS_ERR_INVALID, "null image or selection parameters");
     if (n_depth < 0) return fail(EDS_ERR_INVALID, "negative depth-map size");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return eds_keyframe_build(h, slot, img_type, img, img_H, img_W, channels, sel, n_depth, depth_xy, depth_idp, fx, fy, cx, cy, n_points);
 }
 
 int eds_trk_get_keyframe_points(eds_trk* h, int slot, double* coord_xy, double* norm_xy, double* grad_xy, double* idp, double* weights) {
     int rc = check_slot(h, slot);
     if (rc) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return eds_keyframe_get_points(h, slot, coord_xy, norm_xy, grad_xy, idp, weights);
 }
 

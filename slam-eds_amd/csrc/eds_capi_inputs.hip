@@ -116,7 +116,7 @@ static int upload_frame(eds_trk* h, int slot, const T* frame) {
         // complete) staging buffer with plain launches — a slot is never left holding a partial frame, has_frame stays truthful, and a
         // pyramid built on it (k_pyr_down) sees whole levels.
         if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_host).count() > 1.0) {
-            EDS_HIP_TRY(hipStreamSynchronize(h->st));
+            EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
             if (h->h_fprog[1] & 0x80000000u) {
                 h->h_fprog[1] = 0;
                 for (int k = 0; k < nbands; ++k) eds_frame_store_rowmajor(h, slot, h->d_fstage, rows_per * k, std::min(h->H, rows_per * (k + 1)));
@@ -130,7 +130,7 @@ static int upload_frame(eds_trk* h, int slot, const T* frame) {
         eds_frame_store_rowmajor(h, slot, h->d_fstage, rb, re);
     }
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipEventRecord(h->ev_stage, h->st));
+    EDS_HIP_TRY(hipEventRecord(h->ev_stage, h->own.st));
     h->stage_busy = true;
     h->slots[slot].has_frame = true;
     ++h->slots[slot].frame_version;             // its strip copy (eds_strips.hip) is out of date
@@ -156,21 +156,20 @@ static int upload_frames_batch(eds_trk* h, int first, int count, const T* const*
     const size_t fe = (size_t)h->H * h->W;
     const int S = std::min(count, 16);
     if (h->bstage_slots < S) {
-        if (h->h_bstage) { EDS_HIP_TRY(hipStreamSynchronize(h->st)); hipHostFree(h->h_bstage); h->h_bstage = nullptr; h->bstage_slots = 0; }
-        EDS_HIP_TRY(hipHostMalloc((void**)&h->h_bstage, (size_t)S * fe * sizeof(float), hipHostMallocMapped));
-        EDS_HIP_TRY(hipHostGetDevicePointer((void**)&h->d_bstage, h->h_bstage, 0));
-        h->bstage_slots = S;
+        if (h->h_bstage) EDS_HIP_TRY(hipStreamSynchronize(h->own.st));          // an earlier batch's store kernels may still read the ring
+        if (!h->own.regrow(h->bstage_slots, S, {mapped(h->h_bstage, h->d_bstage, (size_t)S * fe * sizeof(float))}))
+            return fail(EDS_ERR_HIP, "allocation of the batch upload's staging ring failed");
     }
     const bool dma = h->knobs.upload_dma != 0;
     const bool two_streams = !dma && h->knobs.upload_streams != 1 && count > 1;
     if (two_streams) {                  // the second stream starts behind everything the handle's stream holds so far ...
         if (!h->st_up) { EDS_HIP_TRY(hipStreamCreateWithFlags(&h->st_up, hipStreamNonBlocking)); EDS_HIP_TRY(hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming)); }
-        EDS_HIP_TRY(hipEventRecord(h->ev_up, h->st));
+        EDS_HIP_TRY(hipEventRecord(h->ev_up, h->own.st));
         EDS_HIP_TRY(hipStreamWaitEvent(h->st_up, h->ev_up, 0));
     }
-    if (dma && !h->d_bdev) EDS_HIP_TRY(hipMalloc((void**)&h->d_bdev, 2 * fe * sizeof(float)));
+    if (dma && !h->d_bdev && !h->own.alloc(h->d_bdev, 2 * fe * sizeof(float))) return fail(EDS_ERR_HIP, "allocation of the batch upload's scratch frames failed");
     while ((int)h->ev_bstage.size() < S) { hipEvent_t e; EDS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_bstage.push_back(e); }
-    if (h->bstage_busy) { EDS_HIP_TRY(hipStreamSynchronize(h->st)); h->bstage_busy = false; }      // an earlier batch's last reads of the ring
+    if (h->bstage_busy) { EDS_HIP_TRY(hipStreamSynchronize(h->own.st)); h->bstage_busy = false; }      // an earlier batch's last reads of the ring
     int nthr = h->knobs.upload_threads > 0 ? h->knobs.upload_threads : 4;      // measured (tools/bench_upload_batch.py): two threads already keep PCIe busy; more only contend
     nthr = std::max(1, std::min(nthr, std::min(count, (int)std::max(1u, std::thread::hardware_concurrency()))));
     std::atomic<int> next{0}, released{S};
@@ -206,12 +205,12 @@ static int upload_frames_batch(eds_trk* h, int first, int count, const T* const*
         }
         for (int spin = 0; !ready[i].load(std::memory_order_acquire); ++spin) if (spin > 256) std::this_thread::yield();
         if (dma) {          // copy engine: pinned staging slot -> row-major scratch in HBM, then the store kernel reads HBM
-            err = hipMemcpyAsync(h->d_bdev + (size_t)(i % 2) * fe, stage + (size_t)(i % S) * fe, fe * sizeof(float), hipMemcpyHostToDevice, h->st);
-            if (err == hipSuccess) err = hipEventRecord(h->ev_bstage[i % S], h->st);      // the staging slot is free once the copy is through
-            eds_frame_store_whole(h, first + i, h->d_bdev + (size_t)(i % 2) * fe, h->st);
+            err = hipMemcpyAsync(h->d_bdev + (size_t)(i % 2) * fe, stage + (size_t)(i % S) * fe, fe * sizeof(float), hipMemcpyHostToDevice, h->own.st);
+            if (err == hipSuccess) err = hipEventRecord(h->ev_bstage[i % S], h->own.st);      // the staging slot is free once the copy is through
+            eds_frame_store_whole(h, first + i, h->d_bdev + (size_t)(i % 2) * fe, h->own.st);
             if (err == hipSuccess) err = launch_error();                                  // the launch's own error, asked for BEFORE any event is polled
         } else {            // the store kernel reads the staging slot over PCIe; consecutive frames alternate between two streams, so that one
-            hipStream_t sx = two_streams && (i & 1) ? h->st_up : h->st;                  // kernel's tail overlaps the next one's ramp-up
+            hipStream_t sx = two_streams && (i & 1) ? h->st_up : h->own.st;                  // kernel's tail overlaps the next one's ramp-up
             eds_frame_store_whole(h, first + i, h->d_bstage + (size_t)(i % S) * fe, sx);
             err = launch_error();                   // the launch's own error: checked here, not behind the polls below (hipEventQuery's hipErrorNotReady
             if (err == hipSuccess) err = hipEventRecord(h->ev_bstage[i % S], sx);        // becomes the thread's last error on ROCm < 7: ADVICE r5)
@@ -226,12 +225,12 @@ static int upload_frames_batch(eds_trk* h, int first, int count, const T* const*
     for (auto& t : pool) t.join();
     if (two_streams && err == hipSuccess) {      // ... and the handle's stream goes on behind the second one's last kernel
         err = hipEventRecord(h->ev_up, h->st_up);
-        if (err == hipSuccess) err = hipStreamWaitEvent(h->st, h->ev_up, 0);
+        if (err == hipSuccess) err = hipStreamWaitEvent(h->own.st, h->ev_up, 0);
     }
     if (err != hipSuccess) {
         // Both streams are drained (kernels on st_up may still read the ring or write slots), and every slot whose store kernel was
         // launched may hold a partial frame: it no longer counts as holding one, and its strip copy is out of date.
-        hipStreamSynchronize(h->st);
+        hipStreamSynchronize(h->own.st);
         if (h->st_up) hipStreamSynchronize(h->st_up);
         (void)hipGetLastError();
         h->bstage_busy = false;
@@ -271,9 +270,9 @@ static int upload_points(eds_trk* h, int slot, int N, const double* norm_xy, con
     for (int k = 0; k < 8; ++k) {
         if ((k == 3 || k == 4) && !grad_xy) continue;
         if (k == 5 && !w) continue;
-        EDS_HIP_TRY(hipMemcpyAsync(dst[k] + off, f + (size_t)k * Np, (size_t)Np * 4, hipMemcpyHostToDevice, h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(dst[k] + off, f + (size_t)k * Np, (size_t)Np * 4, hipMemcpyHostToDevice, h->own.st));
     }
-    EDS_HIP_TRY(hipMemcpyAsync(h->dcell0 + off, cell, (size_t)Np * 4, hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->dcell0 + off, cell, (size_t)Np * 4, hipMemcpyHostToDevice, h->own.st));
     return EDS_OK;
 }
 
@@ -282,12 +281,12 @@ int refresh_gram(eds_trk* h, int slot, bool wait) {
     fill_static(h, slot);
     int rc = upload_pose(h, slot, 1);
     if (rc) return rc;
-    eds_launch_gram(h->arrays(), slot, effective_blocks(h), h->st);
+    eds_launch_gram(h->arrays(), slot, effective_blocks(h), h->own.st);
     EDS_HIP_TRY(hipGetLastError());
     const size_t off = (size_t)slot * EDS_MAX_BLOCKS * 36;
-    EDS_HIP_TRY(hipMemcpyAsync(h->h_G + off, h->dG + off, (size_t)EDS_MAX_BLOCKS * 36 * 8, hipMemcpyDeviceToHost, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->h_G + off, h->dG + off, (size_t)EDS_MAX_BLOCKS * 36 * 8, hipMemcpyDeviceToHost, h->own.st));
     h->slots[slot].gram_host_stale = false;
-    if (wait) { EDS_HIP_TRY(hipStreamSynchronize(h->st)); h->gram_pending = false; }
+    if (wait) { EDS_HIP_TRY(hipStreamSynchronize(h->own.st)); h->gram_pending = false; }
     else h->gram_pending = true;        // the device solvers read dG on the stream; host readers of h_G wait in fill_pose
     return EDS_OK;
 }
@@ -301,7 +300,7 @@ int eds_trk_set_keyframe(eds_trk* h, int slot, int N, const double* norm_xy, con
     if (rc) return rc;
     if (N < 1 || N > h->Nmax) return fail(EDS_ERR_INVALID, "N out of range for this handle");
     if (!norm_xy || !grad_xy || !idp || !w) return fail(EDS_ERR_INVALID, "null keyframe array");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     Slot& s = h->slots[slot];
     s.N = N; s.K[0] = fx; s.K[1] = fy; s.K[2] = cx; s.K[3] = cy;
     s.num_points = N;                   // KeyFrame::num_points of a keyframe that arrives with its points
@@ -327,7 +326,7 @@ int eds_trk_set_idepth_strided(eds_trk* h, int slot, int N, const double* idp, i
     Slot& s = h->slots[slot];
     if (!s.has_kf) return fail(EDS_ERR_STATE, "keyframe not set");
     if (N != s.N || !idp) return fail(EDS_ERR_INVALID, "idp size mismatch");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     // only the inverse-depth plane changes (the geometry uses rho' = idp + 1e-5, the model the raw idp)
     // (Tracker.cpp:167 re-reads the depths on every optimize: this is on the live path, so nothing here waits for the GPU)
     if (h->idp_busy) { EDS_HIP_TRY(hipEventSynchronize(h->ev_idp)); h->idp_busy = false; }
@@ -336,15 +335,15 @@ int eds_trk_set_idepth_strided(eds_trk* h, int slot, int N, const double* idp, i
         // ONE launch: the Gram kernel reads the new depths out of the mapped staging, stores them into the rho plane on its way and
         // leaves the Gram matrices in HBM, where the device solvers read them; the host copy is fetched only if a host-side solver or
         // eval asks for it (fill_pose).  (Round 2: copy + event + pose upload + launch + copy back = ~20 us of host time.)
-        eds_launch_gram(h->arrays(), slot, effective_blocks(h), h->st, h->d_idp);
+        eds_launch_gram(h->arrays(), slot, effective_blocks(h), h->own.st, h->d_idp);
         EDS_HIP_TRY(hipGetLastError());
-        EDS_HIP_TRY(hipEventRecord(h->ev_idp, h->st));
+        EDS_HIP_TRY(hipEventRecord(h->ev_idp, h->own.st));
         h->idp_busy = true;
         s.gram_host_stale = true;
         return EDS_OK;
     }
-    EDS_HIP_TRY(hipMemcpyAsync(h->drho + (size_t)slot * h->Np, h->h_idp, (size_t)h->Np * 4, hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipEventRecord(h->ev_idp, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->drho + (size_t)slot * h->Np, h->h_idp, (size_t)h->Np * 4, hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipEventRecord(h->ev_idp, h->own.st));
     h->idp_busy = true;
     return refresh_gram(h, slot, false);
 }
@@ -353,7 +352,7 @@ int eds_trk_set_event_frame(eds_trk* h, int slot, const double* frame) {
     int rc = check_slot(h, slot);
     if (rc) return rc;
     if (!frame) return fail(EDS_ERR_INVALID, "null frame");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return upload_frame(h, slot, frame);
 }
 
@@ -361,7 +360,7 @@ int eds_trk_set_event_frame_f32(eds_trk* h, int slot, const float* frame) {
     int rc = check_slot(h, slot);
     if (rc) return rc;
     if (!frame) return fail(EDS_ERR_INVALID, "null frame");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return upload_frame(h, slot, frame);
 }
 
@@ -369,7 +368,7 @@ int eds_trk_set_event_frames(eds_trk* h, int first, int count, const double* con
     if (!h || !frames) return fail(EDS_ERR_INVALID, "null argument");
     if (first < 0 || count < 1 || first + count > h->B) return fail(EDS_ERR_INVALID, "bad slot range");
     for (int i = 0; i < count; ++i) if (!frames[i]) return fail(EDS_ERR_INVALID, "null frame");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return upload_frames_batch(h, first, count, frames);
 }
 
@@ -377,14 +376,14 @@ int eds_trk_set_event_frames_f32(eds_trk* h, int first, int count, const float* 
     if (!h || !frames) return fail(EDS_ERR_INVALID, "null argument");
     if (first < 0 || count < 1 || first + count > h->B) return fail(EDS_ERR_INVALID, "bad slot range");
     for (int i = 0; i < count; ++i) if (!frames[i]) return fail(EDS_ERR_INVALID, "null frame");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return upload_frames_batch(h, first, count, frames);
 }
 
 int eds_trk_set_undistort_map(eds_trk* h, const float* mapx, const float* mapy) {
     if (!h) return fail(EDS_ERR_INVALID, "null handle");
     if ((mapx == nullptr) != (mapy == nullptr)) return fail(EDS_ERR_INVALID, "mapx and mapy must both be given or both be NULL");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return eds_frame_set_map(h, mapx, mapy, h->H, h->W);
 }
 
@@ -392,7 +391,7 @@ int eds_trk_set_undistort_map_sized(eds_trk* h, const float* mapx, const float* 
     if (!h) return fail(EDS_ERR_INVALID, "null handle");
     if ((mapx == nullptr) != (mapy == nullptr)) return fail(EDS_ERR_INVALID, "mapx and mapy must both be given or both be NULL");
     if (mapx && (sensor_H < 1 || sensor_W < 1)) return fail(EDS_ERR_INVALID, "bad sensor size");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return eds_frame_set_map(h, mapx, mapy, sensor_H, sensor_W);
 }
 
@@ -402,7 +401,7 @@ int eds_trk_build_event_frame(eds_trk* h, int slot, int n_events, const uint16_t
     if (rc) return rc;
     if (n_events < 0 || level < 0 || level > 16) return fail(EDS_ERR_INVALID, "bad event count or level");
     if (n_events > 0 && (!x || !y || !polarity)) return fail(EDS_ERR_INVALID, "null event array");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = unshare_frames(h, slot, 1))) return rc;
     return eds_frame_build_levels(h, slot, level, 1, n_events, x, y, polarity, h->H, h->W, blur_sigma, use_exp_weights, norm_out);
 }
@@ -416,7 +415,7 @@ int eds_trk_build_event_frames(eds_trk* h, int first_slot, int num_levels, int n
     if (n_events > 0 && (!x || !y || !polarity)) return fail(EDS_ERR_INVALID, "null event array");
     if (sensor_H <= 0 || sensor_W <= 0) { sensor_H = h->H; sensor_W = h->W; }
     if (sensor_H < 2 || sensor_W < 2) return fail(EDS_ERR_INVALID, "bad sensor size");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     { int rc_ = unshare_frames(h, first_slot, num_levels); if (rc_) return rc_; }
     return eds_frame_build_levels(h, first_slot, 0, num_levels, n_events, x, y, polarity, sensor_H, sensor_W, blur_sigma, use_exp_weights, norms);
 }
@@ -432,7 +431,7 @@ int eds_trk_build_event_frames_aos(eds_trk* h, int first_slot, int num_levels, i
         return fail(EDS_ERR_INVALID, "bad event layout (x, y: 2-byte aligned uint16 fields inside an even stride)");
     if (sensor_H <= 0 || sensor_W <= 0) { sensor_H = h->H; sensor_W = h->W; }
     if (sensor_H < 2 || sensor_W < 2) return fail(EDS_ERR_INVALID, "bad sensor size");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     { int rc_ = unshare_frames(h, first_slot, num_levels); if (rc_) return rc_; }
     const EdsEventAos aos = {events, stride, off_x, off_y, off_polarity};
     return eds_frame_build_levels(h, first_slot, 0, num_levels, n_events, nullptr, nullptr, nullptr, sensor_H, sensor_W, blur_sigma, use_exp_weights,
@@ -480,7 +479,7 @@ int eds_trk_build_event_frame_batch(eds_trk* h, int first_slot, int count, const
     if (!offsets || offsets[0] < 0) return fail(EDS_ERR_INVALID, "bad offsets");
     if (level < 0 || level > 16) return fail(EDS_ERR_INVALID, "bad level");
     if (offsets[count] > offsets[0] && (!x || !y || !polarity)) return fail(EDS_ERR_INVALID, "null event array");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     { int rc_ = unshare_frames(h, first_slot, count); if (rc_) return rc_; }
     return eds_frame_build_batch(h, first_slot, count, offsets, x, y, polarity, level, blur_sigma, use_exp_weights, norms);
 }
@@ -493,7 +492,7 @@ int eds_trk_share_event_frame(eds_trk* h, int slot, int src_slot) {
     const Slot& src = h->slots[src_slot];
     if (src.frame_slot >= 0 && src_slot != slot) return fail(EDS_ERR_INVALID, "the source slot itself shares another slot's frame");
     if (!src.has_frame && src_slot != slot) return fail(EDS_ERR_STATE, "the source slot has no event frame yet");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     s.frame_slot = src_slot == slot ? -1 : src_slot;
     if (src_slot != slot) s.has_frame = true;
     fill_static(h, slot);
@@ -504,9 +503,9 @@ int eds_trk_get_event_frame(eds_trk* h, int slot, double* frame) {
     int rc = check_slot(h, slot);
     if (rc) return rc;
     if (!frame) return fail(EDS_ERR_INVALID, "null output");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t n = (size_t)h->Hp * h->Wp;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));                    // set_event_frame does not wait for its own upload
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));                    // set_event_frame does not wait for its own upload
     const int fs = h->slots[slot].frame_slot >= 0 ? h->slots[slot].frame_slot : slot;      // a sharing slot: the frame it samples
     EDS_HIP_TRY(hipMemcpy(h->h_f32, h->dframe + (size_t)fs * n, n * 4, hipMemcpyDeviceToHost));
     for (int r = 0; r < h->H; ++r)

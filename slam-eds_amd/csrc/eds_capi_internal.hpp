@@ -37,7 +37,6 @@ int check_idle_slots(const eds_trk* h, int first, int count, int need);
 int read_xy_planes(eds_trk* h, const double* plane, int first, int count, int stride, double* dst);
 int workgroup_lds_limit(const eds_trk* h, size_t* bytes);     // selects the handle's device; the LDS one workgroup may ask for
 bool row_bins_fit(const eds_trk* h, size_t limit);            // k_klt_bin's two [H + 2] int arrays fit `limit`, H and W fit a key's 16 bits
-bool device_alloc(std::initializer_list<DevAlloc> table);     // hipMalloc of every entry in turn; false at the first that fails
 // eds_trk_update_points_batch after its argument checks; dev: see eds_points_update_batch
 int update_points_range(eds_trk* h, int first, int count, int delete_out_points, int stride, double* coord_xy, double* tracks_xy,
                         int32_t* kept_index, int* n_kept, double* mean_sq_flow, const EdsPointsDev* dev = nullptr);

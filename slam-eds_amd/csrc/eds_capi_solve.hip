@@ -51,22 +51,22 @@ int run_pass(eds_trk* h, int first, int count, int ncols, bool refresh_model, bo
     const int nchunk = (N + EDS_TPB - 1) / EDS_TPB;
     int rc = upload_pose(h, first, count);
     if (rc) return rc;
-    if (refresh_model && ncols == 6) eds_launch_model(A, first, count, nchunk, h->st);
-    eds_launch_resjac(A, h->cfg.sampling, ncols, first, count, nchunk, h->st);
-    if (ncols == 12 && h->cfg.nc) eds_launch_nc_normalise(A, first, count, effective_blocks(h), nchunk, h->st);
+    if (refresh_model && ncols == 6) eds_launch_model(A, first, count, nchunk, h->own.st);
+    eds_launch_resjac(A, h->cfg.sampling, ncols, first, count, nchunk, h->own.st);
+    if (ncols == 12 && h->cfg.nc) eds_launch_nc_normalise(A, first, count, effective_blocks(h), nchunk, h->own.st);
     if (with_reduction) {
         const int nb_red = (ncols == 12) ? effective_blocks(h) : 1;
         int cpb, nseg;
         reduce_geometry(N, nb_red, ncols, &cpb, &nseg, h->knobs.reduce_ppl);
         if (nseg > h->max_seg) return fail(EDS_ERR_INVALID, "reduction grid exceeds allocation");
-        eds_launch_reduce(A, ncols, first, count, nseg, nb_red, cpb, h->st, h->knobs.reduce_ppl);
+        eds_launch_reduce(A, ncols, first, count, nseg, nb_red, cpb, h->own.st, h->knobs.reduce_ppl);
         if (fetch)
             EDS_HIP_TRY(hipMemcpyAsync(h->h_part + (size_t)first * h->max_seg * EDS_RED_K,
                                        h->dpart + (size_t)first * h->max_seg * EDS_RED_K,
-                                       sizeof(double) * h->max_seg * EDS_RED_K * count, hipMemcpyDeviceToHost, h->st));
+                                       sizeof(double) * h->max_seg * EDS_RED_K * count, hipMemcpyDeviceToHost, h->own.st));
     }
     EDS_HIP_TRY(hipGetLastError());
-    if (fetch) EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (fetch) EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
@@ -117,8 +117,8 @@ void gather12(const eds_trk* h, int slot, int range_max_N, edss::Sums12* S) {
 
 int fetch_residuals(eds_trk* h, int first, int count) {
     EDS_HIP_TRY(hipMemcpyAsync(h->h_r + (size_t)first * h->Np, h->dr + (size_t)first * h->Np,
-                               sizeof(float) * h->Np * count, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+                               sizeof(float) * h->Np * count, hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     for (int s = first; s < first + count; ++s) {
         Slot& sl = h->slots[s];
         sl.residuals.resize(sl.N);
@@ -254,7 +254,7 @@ int materialise_residuals(eds_trk* h, int slot) {
         s.res_on_device = false; s.res_in_hostmap = false;
         return EDS_OK;
     }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     int rc = fetch_residuals(h, slot, 1);
     if (rc) return rc;
     s.res_on_device = false;
@@ -274,7 +274,7 @@ int eds_trk_eval(eds_trk* h, int slot, const double p[3], const double q[4], con
     if (!p || !q || !v) return fail(EDS_ERR_INVALID, "null state");
     Slot& s = h->slots[slot];
     if (!s.has_kf || !s.has_frame) return fail(EDS_ERR_STATE, "keyframe or event frame not set");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     fill_pose(h, slot, p, q, v);
     if ((rc = run_pass(h, slot, 1, ncols, true, true, true))) return rc;
     const int N = s.N;
@@ -321,7 +321,7 @@ static int solve_range(eds_trk* h, int level, int first, int count) {
     if (first < 0 || count < 1 || first + count > h->B) return fail(EDS_ERR_INVALID, "slot range out of bounds");
     if (h->cfg.nc && h->cfg.solver != EDS_SOLVER_REF12)
         return fail(EDS_ERR_INVALID, "the NC residual (cfg.nc) is defined for EDS_SOLVER_REF12 only");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (h->cfg.exec == EDS_EXEC_DEVICE) return eds_fused_solve(h, level, first, count);
     return solve_host(h, level, first, count);
 }
@@ -378,7 +378,7 @@ int eds_trk_loss_param(eds_trk* h, int slot, int method, double* tau) {
     // One slot: bring the residuals over (8 KB; the caller wants them for kf->residuals anyway, Tracker.cpp:223-230) and
     // select on the host — 40 us against 80 us for the LDS sort of a single alignment.  Batches use
     // eds_trk_loss_param_batch, which selects on the device (0.5 us per alignment).
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = materialise_residuals(h, slot))) return rc;
     if ((int)s.residuals.size() != s.N || s.N < 1) return fail(EDS_ERR_STATE, "no residuals stored");
     std::vector<double>& r = s.residuals;
@@ -486,7 +486,7 @@ int eds_trk_bench_eval(eds_trk* h, int first, int count, int ncols, int with_red
     if (first < 0 || count < 1 || first + count > h->B || reps < 1) return fail(EDS_ERR_INVALID, "bad range");
     if (ncols != 6 && ncols != 12) return fail(EDS_ERR_INVALID, "ncols must be 6 or 12");
     if (ncols == 6 && h->cfg.nc) return fail(EDS_ERR_INVALID, "the NC residual (cfg.nc) has 12-column rows only");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     for (int s = first; s < first + count; ++s) {
         const Slot& sl = h->slots[s];
         if (!sl.has_kf || !sl.has_frame) return fail(EDS_ERR_STATE, "keyframe or event frame not set");
@@ -494,19 +494,19 @@ int eds_trk_bench_eval(eds_trk* h, int first, int count, int ncols, int with_red
     }
     int rc = run_pass(h, first, count, ncols, true, with_reduction != 0, false);   // warm-up + model
     if (rc) return rc;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     const EdsArrays A = arrays_for_pass(h, first, count);
     const int N = max_points(h, first, count);
     const int nchunk = (N + EDS_TPB - 1) / EDS_TPB;
     const int nb_red = (ncols == 12) ? effective_blocks(h) : 1;
     int cpb, nseg;
     reduce_geometry(N, nb_red, ncols, &cpb, &nseg, h->knobs.reduce_ppl);
-    EDS_HIP_TRY(hipEventRecord(h->ev0, h->st));
+    EDS_HIP_TRY(hipEventRecord(h->ev0, h->own.st));
     for (int i = 0; i < reps; ++i) {
-        eds_launch_resjac(A, h->cfg.sampling, ncols, first, count, nchunk, h->st);
-        if (with_reduction) eds_launch_reduce(A, ncols, first, count, nseg, nb_red, cpb, h->st, h->knobs.reduce_ppl);
+        eds_launch_resjac(A, h->cfg.sampling, ncols, first, count, nchunk, h->own.st);
+        if (with_reduction) eds_launch_reduce(A, ncols, first, count, nseg, nb_red, cpb, h->own.st, h->knobs.reduce_ppl);
     }
-    EDS_HIP_TRY(hipEventRecord(h->ev1, h->st));
+    EDS_HIP_TRY(hipEventRecord(h->ev1, h->own.st));
     EDS_HIP_TRY(hipEventSynchronize(h->ev1));
     float ms = 0.f;
     EDS_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -529,10 +529,8 @@ __global__ __launch_bounds__(256) void eds_probe_kernel(const float4* __restrict
 
 static int probe_buffers(eds_trk* h, size_t bytes) {
     if (h->probe_bytes >= bytes) return EDS_OK;
-    if (h->d_probe) { hipFree(h->d_probe); h->d_probe = nullptr; h->probe_bytes = 0; }
-    EDS_HIP_TRY(hipMalloc(&h->d_probe, 2 * bytes + 256));
-    EDS_HIP_TRY(hipMemsetAsync(h->d_probe, 0, 2 * bytes + 256, h->st));
-    h->probe_bytes = bytes;
+    if (!h->own.regrow(h->probe_bytes, bytes, {{&h->d_probe, 2 * bytes + 256}})) return fail(EDS_ERR_HIP, "allocation of the probe buffers failed");
+    EDS_HIP_TRY(hipMemsetAsync(h->d_probe, 0, 2 * bytes + 256, h->own.st));
     return EDS_OK;
 }
 
@@ -540,7 +538,7 @@ int eds_trk_hbm_probe(eds_trk* h, size_t bytes, int reps, float* read_GBps, floa
     if (!h || !read_GBps || !copy_GBps) return fail(EDS_ERR_INVALID, "null argument");
     if (bytes < (1u << 20) || reps < 1) return fail(EDS_ERR_INVALID, "bad size");
     bytes &= ~(size_t)255;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     int rc = probe_buffers(h, bytes);
     if (rc) return rc;
     const float4* a = reinterpret_cast<const float4*>(h->d_probe);
@@ -548,10 +546,10 @@ int eds_trk_hbm_probe(eds_trk* h, size_t bytes, int reps, float* read_GBps, floa
     float* sink = reinterpret_cast<float*>(reinterpret_cast<char*>(h->d_probe) + 2 * bytes);
     const size_t n = bytes / 16;
     for (int mode = 0; mode < 2; ++mode) {
-        hipLaunchKernelGGL(eds_probe_kernel, dim3(8192), dim3(256), 0, h->st, a, b, sink, n, mode);      // warm-up
-        EDS_HIP_TRY(hipEventRecord(h->ev0, h->st));
-        for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(eds_probe_kernel, dim3(8192), dim3(256), 0, h->st, a, b, sink, n, mode);
-        EDS_HIP_TRY(hipEventRecord(h->ev1, h->st));
+        hipLaunchKernelGGL(eds_probe_kernel, dim3(8192), dim3(256), 0, h->own.st, a, b, sink, n, mode);      // warm-up
+        EDS_HIP_TRY(hipEventRecord(h->ev0, h->own.st));
+        for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(eds_probe_kernel, dim3(8192), dim3(256), 0, h->own.st, a, b, sink, n, mode);
+        EDS_HIP_TRY(hipEventRecord(h->ev1, h->own.st));
         EDS_HIP_TRY(hipEventSynchronize(h->ev1));
         float ms = 0.f;
         EDS_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -572,7 +570,7 @@ int eds_trk_bench_kernel_cold(eds_trk* h, int first, int count, int ncols, int w
     if (ncols != 6 && ncols != 12) return fail(EDS_ERR_INVALID, "ncols must be 6 or 12");
     if (which != 0 && which != 1) return fail(EDS_ERR_INVALID, "which: 0 residual/Jacobian, 1 reduction");
     if (ncols == 6 && h->cfg.nc) return fail(EDS_ERR_INVALID, "the NC residual (cfg.nc) has 12-column rows only");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     for (int s = first; s < first + count; ++s) {
         const Slot& sl = h->slots[s];
         if (!sl.has_kf || !sl.has_frame) return fail(EDS_ERR_STATE, "keyframe or event frame not set");
@@ -582,7 +580,7 @@ int eds_trk_bench_kernel_cold(eds_trk* h, int first, int count, int ncols, int w
     if (rc) return rc;
     const size_t evict_bytes = (size_t)1 << 30;
     if ((rc = probe_buffers(h, evict_bytes))) return rc;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     const EdsArrays A = arrays_for_pass(h, first, count);
     const int N = max_points(h, first, count);
     const int nchunk = (N + EDS_TPB - 1) / EDS_TPB;
@@ -596,11 +594,11 @@ int eds_trk_bench_kernel_cold(eds_trk* h, int first, int count, int ncols, int w
     for (int i = 0; i < reps; ++i) {
         // (a READ-only pass: lines a copy had written would sit in the Infinity Cache dirty, and their write-back — forced by the very
         // reads under test — would be billed to the kernel: 70 instead of 45 us for the reduction's 229 MB)
-        hipLaunchKernelGGL(eds_probe_kernel, dim3(8192), dim3(256), 0, h->st, a, b, sink, evict_bytes / 16, 0);
-        EDS_HIP_TRY(hipEventRecord(h->ev0, h->st));
-        if (which == 0) eds_launch_resjac(A, h->cfg.sampling, ncols, first, count, nchunk, h->st);
-        else eds_launch_reduce(A, ncols, first, count, nseg, nb_red, cpb, h->st, h->knobs.reduce_ppl);
-        EDS_HIP_TRY(hipEventRecord(h->ev1, h->st));
+        hipLaunchKernelGGL(eds_probe_kernel, dim3(8192), dim3(256), 0, h->own.st, a, b, sink, evict_bytes / 16, 0);
+        EDS_HIP_TRY(hipEventRecord(h->ev0, h->own.st));
+        if (which == 0) eds_launch_resjac(A, h->cfg.sampling, ncols, first, count, nchunk, h->own.st);
+        else eds_launch_reduce(A, ncols, first, count, nseg, nb_red, cpb, h->own.st, h->knobs.reduce_ppl);
+        EDS_HIP_TRY(hipEventRecord(h->ev1, h->own.st));
         EDS_HIP_TRY(hipEventSynchronize(h->ev1));
         float ms = 0.f;
         EDS_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -617,7 +615,7 @@ int eds_trk_loss_param_batch(eds_trk* h, int first, int count, int method, doubl
     if (!tau) return fail(EDS_ERR_INVALID, "null output");
     if (method == EDS_LP_CONSTANT) return EDS_OK;
     if (method != EDS_LP_MAD && method != EDS_LP_STD) return fail(EDS_ERR_INVALID, "unknown loss-param method");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     bool on_device = eds_points_supported(h, first, count);
     for (int s = first; s < first + count && on_device; ++s) on_device = h->slots[s].res_on_device;
     if (on_device) return eds_points_loss_param(h, first, count, method, tau);

@@ -259,23 +259,17 @@ int ensure(eds_trk* h) {
     EdsDepthBuffers& d = h->depth;
     if (d.seeds) return EDS_OK;
     const size_t B = (size_t)h->B, Np = (size_t)h->Np;
-    if (hipMalloc((void**)&d.seeds, 4 * B * Np * 8) != hipSuccess || hipMalloc((void**)&d.d_par, B * EDS_DP_STRIDE * 8) != hipSuccess ||
-        hipMalloc((void**)&d.d_sum, B * EDS_DEPTH_SUM * 4) != hipSuccess || hipMalloc((void**)&d.d_stats, B * 4 * 8) != hipSuccess ||
-        hipHostMalloc((void**)&d.h_par, B * EDS_DP_STRIDE * 8, 0) != hipSuccess || hipHostMalloc((void**)&d.h_sum, B * EDS_DEPTH_SUM * 4, 0) != hipSuccess ||
-        hipHostMalloc((void**)&d.h_stats, B * 4 * 8, 0) != hipSuccess) {
-        eds_depth_free(&d);
+    if (!h->own.alloc({{(void**)&d.seeds, 4 * B * Np * 8}, {(void**)&d.d_par, B * EDS_DP_STRIDE * 8}, {(void**)&d.d_sum, B * EDS_DEPTH_SUM * 4},
+                       {(void**)&d.d_stats, B * 4 * 8}, pinned(d.h_par, B * EDS_DP_STRIDE * 8), pinned(d.h_sum, B * EDS_DEPTH_SUM * 4),
+                       pinned(d.h_stats, B * 4 * 8)}))
         return fail(EDS_ERR_HIP, "allocation of the depth-filter buffers failed");
-    }
     return EDS_OK;
 }
 
 int ensure_input(eds_trk* h) {
     EdsDepthBuffers& d = h->depth;
     if (d.d_in) return EDS_OK;
-    if (hipMalloc((void**)&d.d_in, 4 * (size_t)h->B * h->Np * 8) != hipSuccess) {
-        d.d_in = nullptr;
-        return fail(EDS_ERR_HIP, "allocation of the depth-filter input buffer failed");
-    }
+    if (!h->own.alloc(d.d_in, 4 * (size_t)h->B * h->Np * 8)) return fail(EDS_ERR_HIP, "allocation of the depth-filter input buffer failed");
     return EDS_OK;
 }
 
@@ -285,10 +279,10 @@ int upload_rows(eds_trk* h, int first, int count, const double* src, int stride,
     const size_t Np = (size_t)h->Np, w = (size_t)width * 8;
     const size_t row = (size_t)std::min(stride, h->Np) * w;
     if (count > 1)
-        EDS_HIP_TRY(hipMemcpy2DAsync(dst, Np * w, src, (size_t)stride * w, row, (size_t)count - 1, hipMemcpyHostToDevice, h->st));
+        EDS_HIP_TRY(hipMemcpy2DAsync(dst, Np * w, src, (size_t)stride * w, row, (size_t)count - 1, hipMemcpyHostToDevice, h->own.st));
     const int nl = h->slots[first + count - 1].N;
     EDS_HIP_TRY(hipMemcpyAsync(dst + (size_t)(count - 1) * Np * width, src + (size_t)(count - 1) * stride * width, (size_t)nl * w,
-                               hipMemcpyHostToDevice, h->st));
+                               hipMemcpyHostToDevice, h->own.st));
     return EDS_OK;
 }
 
@@ -296,8 +290,8 @@ int upload_rows(eds_trk* h, int first, int count, const double* src, int stride,
 // for a host-side reader); the caller waits for the stream
 int finish_planes(eds_trk* h, int first, int count) {
     const int nb = effective_blocks(h);
-    if (count == 1) eds_launch_gram(h->arrays(), first, nb, h->st);
-    else eds_launch_gram_batch(h->arrays(), first, count, nb, h->st);
+    if (count == 1) eds_launch_gram(h->arrays(), first, nb, h->own.st);
+    else eds_launch_gram_batch(h->arrays(), first, count, nb, h->own.st);
     EDS_HIP_TRY(hipGetLastError());
     for (int s = first; s < first + count; ++s) h->slots[s].gram_host_stale = true;
     return EDS_OK;
@@ -305,35 +299,27 @@ int finish_planes(eds_trk* h, int first, int count) {
 
 int launch_init(eds_trk* h, int first, int count, int source, double mu0, double s20, double a0, double b0, const double* in) {
     const int nchunk = (h->Np + EDS_DEPTH_TPB - 1) / EDS_DEPTH_TPB;
-    hipLaunchKernelGGL(k_depth_init, dim3((unsigned)count * nchunk), dim3(EDS_DEPTH_TPB), 0, h->st, h->arrays(), h->depth.seeds, first, nchunk,
+    hipLaunchKernelGGL(k_depth_init, dim3((unsigned)count * nchunk), dim3(EDS_DEPTH_TPB), 0, h->own.st, h->arrays(), h->depth.seeds, first, nchunk,
                        source, mu0, s20, a0, b0, in);
     EDS_HIP_TRY(hipGetLastError());
     int rc = finish_planes(h, first, count);
     if (rc) return rc;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
 int read_plane(eds_trk* h, int slot, int c, double* dst) {
     EDS_HIP_TRY(hipMemcpyAsync(dst, h->depth.seeds + (size_t)c * h->B * h->Np + (size_t)slot * h->Np, (size_t)h->slots[slot].N * 8,
-                               hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+                               hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
 }  // namespace
 
-void eds_depth_free(EdsDepthBuffers* d) {
-    void* dp[] = {d->seeds, d->d_par, d->d_sum, d->d_stats, d->d_in};
-    for (void* p : dp) if (p) hipFree(p);
-    void* hp[] = {d->h_par, d->h_sum, d->h_stats};
-    for (void* p : hp) if (p) hipHostFree(p);
-    *d = EdsDepthBuffers();
-}
-
 void eds_depth_compact(eds_trk* h, int first, int count, const int* kept) {
     if (!h->depth.seeds) return;
-    hipLaunchKernelGGL(k_depth_compact, dim3(count), dim3(EDS_COMPACT_THREADS), 0, h->st, h->arrays(), h->depth.seeds, first, kept);
+    hipLaunchKernelGGL(k_depth_compact, dim3(count), dim3(EDS_COMPACT_THREADS), 0, h->own.st, h->arrays(), h->depth.seeds, first, kept);
 }
 
 extern "C" {
@@ -355,7 +341,7 @@ int eds_depth_init(eds_trk* h, int first, int count, const eds_depth_params* prm
         if (!idp) return fail(EDS_ERR_INVALID, "null inverse depths");
         if (stride < max_points(h, first, count)) return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
     }
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = ensure(h))) return rc;
     if (source == EDS_DEPTH_INIT_HOST && ((rc = ensure_input(h)) || (rc = upload_rows(h, first, count, idp, stride, 1, h->depth.d_in)))) return rc;
     const double mu_range = prm->max_depth - prm->min_depth;
@@ -391,7 +377,7 @@ int eds_depth_update_impl(eds_trk* h, int first, int count, int coords, const do
     if ((xy || kf_xy) && stride < max_points(h, first, count)) return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
     if (coords == EDS_DEPTH_DEVICE_TRACKS && !h->klt.tracks)
         return fail(EDS_ERR_STATE, "no device tracks: eds_klt_track_points has not run on this handle (include/eds_hip_klt.h)");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     EdsDepthBuffers& d = h->depth;
     const size_t half = 2 * (size_t)h->B * h->Np;
     if (xy || kf_xy) {
@@ -430,15 +416,15 @@ int eds_depth_update_impl(eds_trk* h, int first, int count, int coords, const do
         edsm::quat_to_RmI(s.q, P + EDS_DP_D);       // getCoord's pose (eds_points.hip)
         for (int r = 0; r < 3; ++r) P[EDS_DP_P + r] = s.p[r];
     }
-    EDS_HIP_TRY(hipMemcpyAsync(d.d_par, d.h_par, (size_t)count * EDS_DP_STRIDE * 8, hipMemcpyHostToDevice, h->st));
-    EDS_HIP_TRY(hipMemsetAsync(d.d_sum, 0, (size_t)count * EDS_DEPTH_SUM * 4, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(d.d_par, d.h_par, (size_t)count * EDS_DP_STRIDE * 8, hipMemcpyHostToDevice, h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(d.d_sum, 0, (size_t)count * EDS_DEPTH_SUM * 4, h->own.st));
     const int nchunk = (h->Np + EDS_DEPTH_TPB - 1) / EDS_DEPTH_TPB;
-    hipLaunchKernelGGL(k_depth_update, dim3((unsigned)count * nchunk), dim3(EDS_DEPTH_TPB), 0, h->st, h->arrays(), d.seeds, d.d_par, first, nchunk,
+    hipLaunchKernelGGL(k_depth_update, dim3((unsigned)count * nchunk), dim3(EDS_DEPTH_TPB), 0, h->own.st, h->arrays(), d.seeds, d.d_par, first, nchunk,
                        coords, dev_ef ? dev_ef : (xy ? d.d_in : nullptr), kf_xy ? d.d_in + half : nullptr, h->klt.tracks, d.d_sum);
     EDS_HIP_TRY(hipGetLastError());
     if ((rc = finish_planes(h, first, count))) return rc;
-    EDS_HIP_TRY(hipMemcpyAsync(d.h_sum, d.d_sum, (size_t)count * EDS_DEPTH_SUM * 4, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(d.h_sum, d.d_sum, (size_t)count * EDS_DEPTH_SUM * 4, hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     if (out) std::memcpy(out, d.h_sum, (size_t)count * sizeof(eds_depth_summary));
     return EDS_OK;
 }
@@ -449,7 +435,7 @@ int eds_depth_get(eds_trk* h, int slot, double* mu_s2_a_b, uint8_t* converged) {
     int rc = check_range(h, slot, 1);
     if (rc || (rc = check_idle_slots(h, slot, 1, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!mu_s2_a_b && !converged) return fail(EDS_ERR_INVALID, "null output");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const Slot& s = h->slots[slot];
     const size_t N = (size_t)s.N;
     std::vector<double> v(4 * N);
@@ -468,9 +454,9 @@ int eds_depth_set(eds_trk* h, int slot, const double* mu_s2_a_b) {
     int rc = check_range(h, slot, 1);
     if (rc || (rc = check_idle_slots(h, slot, 1, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!mu_s2_a_b) return fail(EDS_ERR_INVALID, "null seeds");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = ensure_input(h))) return rc;
-    EDS_HIP_TRY(hipMemcpyAsync(h->depth.d_in, mu_s2_a_b, (size_t)h->slots[slot].N * 32, hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->depth.d_in, mu_s2_a_b, (size_t)h->slots[slot].N * 32, hipMemcpyHostToDevice, h->own.st));
     return launch_init(h, slot, 1, EDS_DEPTH_INIT_SEEDS, 0.0, 0.0, 0.0, 0.0, h->depth.d_in);
 }
 
@@ -478,7 +464,7 @@ int eds_depth_get_idepth(eds_trk* h, int slot, double* mu) {
     int rc = check_range(h, slot, 1);
     if (rc || (rc = check_idle_slots(h, slot, 1, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!mu) return fail(EDS_ERR_INVALID, "null output");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return read_plane(h, slot, 0, mu);
 }
 
@@ -486,12 +472,12 @@ int eds_depth_stats(eds_trk* h, int first, int count, double* out4) {
     int rc = check_range(h, first, count);
     if (rc || (rc = check_idle_slots(h, first, count, EDS_NEED_KF | EDS_NEED_SEEDS))) return rc;
     if (!out4) return fail(EDS_ERR_INVALID, "null output");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     EdsDepthBuffers& d = h->depth;
-    hipLaunchKernelGGL(k_depth_stats, dim3(count), dim3(EDS_LP_THREADS), 0, h->st, h->arrays(), d.seeds, first, d.d_stats);
+    hipLaunchKernelGGL(k_depth_stats, dim3(count), dim3(EDS_LP_THREADS), 0, h->own.st, h->arrays(), d.seeds, first, d.d_stats);
     EDS_HIP_TRY(hipGetLastError());
-    EDS_HIP_TRY(hipMemcpyAsync(d.h_stats, d.d_stats, (size_t)count * 32, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(d.h_stats, d.d_stats, (size_t)count * 32, hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     std::memcpy(out4, d.h_stats, (size_t)count * 32);
     return EDS_OK;
 }

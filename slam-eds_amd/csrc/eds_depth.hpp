@@ -20,7 +20,6 @@ struct EdsDepthBuffers {
     double* d_in = nullptr;         // [2][B][Np][2] host inputs of an update (xy, kf_xy) or of init / set; allocated at first need
 };
 
-void eds_depth_free(EdsDepthBuffers* db);
 // getCoord's compaction of slots first .. first + count - 1 has just been launched with its kept indices in `kept` ([count][Np],
 // device view): gather the seeds of those slots the same way, on the same stream (eds_points.hip)
 void eds_depth_compact(eds_trk* h, int first, int count, const int* kept);

@@ -1,7 +1,8 @@
-// What the host code of the DSO-side handles shares (eds_imm, eds_ct, eds_win, eds_sel and the eds_act / eds_wsv / eds_wed states that hang
-// off them): one owner for a handle's device, stream and device memory, the check and upload of caller images, the read-back, and the
-// small argument checks.  Host code only; the one kernel pair the handles share, a level of makeImages, is eds_dso_image.hip's and is
-// queued through queue_level below.  Nothing here is part of the ABI.
+// What the host code of the handles shares (eds_trk and the Eds*Buffers structs that hang off it; eds_imm, eds_ct, eds_win, eds_sel, eds_ini,
+// eds_und and the eds_act / eds_wsv / eds_wed states beside them): one owner for a handle's device, stream, device memory and pinned host
+// memory, the check and upload of caller images, the read-back, and the small argument checks.  Host code only; the one kernel pair the
+// DSO-side handles share, a level of makeImages, is eds_dso_image.hip's and is queued through queue_level below.  Nothing here is part of
+// the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,18 +29,26 @@ int fail(int code, const std::string& msg);          // records the message for 
             return edscapi::fail(EDS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
     } while (0)
 
-struct DevAlloc { void** p; size_t bytes; };
+// One entry of an alloc() / regrow() table: hipMalloc when `host` is DEVICE; pinned host memory otherwise, and for MAPPED *view receives the
+// device's pointer to the same block.  pinned() and mapped() spell the latter two.
+struct DevAlloc {
+    enum Kind { DEVICE, PINNED, MAPPED };
+    void** p; size_t bytes; Kind host = DEVICE; void** view = nullptr;
+};
 
 #pragma GCC visibility push(hidden)                   // inline host code: none of it joins the library's exported symbols
 
-// The device, the stream and every hipMalloc of one handle.  It records pointer VALUES, not the addresses of the fields that hold them,
-// so fields may exchange their pointers (eds_winedit.hip) and close() still frees each buffer once.  Plain data: a handle holds one by
-// value and calls close() itself.
+template <class T> DevAlloc pinned(T*& p, size_t bytes) { return {(void**)&p, bytes, DevAlloc::PINNED, nullptr}; }
+template <class T, class U> DevAlloc mapped(T*& host, U*& dev, size_t bytes) { return {(void**)&host, bytes, DevAlloc::MAPPED, (void**)&dev}; }
+
+// The device, the stream and every hipMalloc and hipHostMalloc of one handle, in two lists.  It records pointer VALUES, not the addresses
+// of the fields that hold them, so fields may exchange their pointers (eds_winedit.hip) and close() still frees each buffer once.  Plain
+// data: a handle holds one by value and calls close() itself.
 struct DeviceOwner {
     int dev = 0;
     hipStream_t st = nullptr;
-    void** owned = nullptr;
-    size_t n_owned = 0, cap = 0;
+    struct List { void** v = nullptr; size_t n = 0, cap = 0; };
+    List owned, pins;                                 // device memory; pinned host memory
 
     // EDS_ERR_NO_DEVICE, EDS_ERR_INVALID for the ordinal, EDS_ERR_HIP when the device cannot be selected.  A refused stream is not an
     // error here: st stays NULL, every alloc() then returns false, and the creator reports "refused a stream or an allocation" once.
@@ -56,47 +65,90 @@ struct DeviceOwner {
         return EDS_OK;
     }
 
-    size_t live() const { return n_owned; }
+    size_t live() const { return owned.n; }
+    size_t live_pinned() const { return pins.n; }
 
+    // room for one more entry; false when the owner never opened or the host refuses
+    bool room(List& l) {
+        if (!st) return false;
+        if (l.n == l.cap) {
+            void** grown = static_cast<void**>(std::realloc(l.v, (l.cap + 32) * sizeof(void*)));
+            if (!grown) return false;
+            l.v = grown; l.cap += 32;
+        }
+        return true;
+    }
     // hipMalloc, recorded; false (p untouched, the runtime's error cleared) when the device or the owner refuses
     template <class T> bool alloc(T*& p, size_t bytes) {
-        if (!st) return false;
-        if (n_owned == cap) {
-            void** grown = static_cast<void**>(std::realloc(owned, (cap + 32) * sizeof(void*)));
-            if (!grown) return false;
-            owned = grown; cap += 32;
-        }
         void* q = nullptr;
+        if (!room(owned)) return false;
         if (hipMalloc(&q, bytes) != hipSuccess || !q) { (void)hipGetLastError(); return false; }
-        owned[n_owned++] = q;
+        owned.v[owned.n++] = q;
         p = static_cast<T*>(q);
+        return true;
+    }
+    // hipHostMalloc, recorded in the second list; refusal as above
+    template <class T> bool alloc_pinned(T*& host, size_t bytes, unsigned flags = hipHostMallocDefault) {
+        void* q = nullptr;
+        if (!room(pins)) return false;
+        if (hipHostMalloc(&q, bytes, flags) != hipSuccess || !q) { (void)hipGetLastError(); return false; }
+        pins.v[pins.n++] = q;
+        host = static_cast<T*>(q);
+        return true;
+    }
+    // the device's pointer to a pinned block, NULL (the runtime's error cleared) when it has none
+    template <class T> T* device_view(T* host) {
+        void* d = nullptr;
+        if (!host || hipHostGetDevicePointer(&d, host, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        return static_cast<T*>(d);
+    }
+    // pinned and device-mapped: the block and the device's pointer to it, or neither (the block freed again, both NULL, the error cleared)
+    template <class T, class U> bool alloc_mapped(T*& host, U*& dev_view, size_t bytes) {
+        void* q = nullptr;
+        host = nullptr; dev_view = nullptr;
+        if (!alloc_pinned(q, bytes, hipHostMallocMapped)) return false;
+        void* d = device_view(q);
+        if (!d) { release(q); return false; }
+        host = static_cast<T*>(q); dev_view = static_cast<U*>(d);
         return true;
     }
     // every entry in turn; at the first that fails the entries before it are freed again, every entry is NULL, and the answer is false
     bool alloc(std::initializer_list<DevAlloc> table) {
-        const size_t mark = n_owned;
+        const size_t mark = owned.n, pin_mark = pins.n;
         for (const DevAlloc& a : table)
-            if (!alloc(*a.p, a.bytes)) {
-                release_from(mark);
-                for (const DevAlloc& b : table) *b.p = nullptr;
+            if (!(a.host == DevAlloc::DEVICE ? alloc(*a.p, a.bytes) : a.host == DevAlloc::PINNED ? alloc_pinned(*a.p, a.bytes) : alloc_mapped(*a.p, *a.view, a.bytes))) {
+                release_from(mark, pin_mark);
+                for (const DevAlloc& b : table) { *b.p = nullptr; if (b.view) *b.view = nullptr; }
                 return false;
             }
         return true;
     }
+    // Grows what a capacity field counts: releases the table's buffers, then allocates them at the sizes the caller worked out for `want`.
+    // On refusal every entry is NULL and cap is 0, so the caller's next "cap >= need" test cannot believe in a buffer that is gone.
+    template <class Cap> bool regrow(Cap& cap, Cap want, std::initializer_list<DevAlloc> table) {
+        for (const DevAlloc& a : table) { release(*a.p); if (a.view) *a.view = nullptr; }
+        cap = alloc(table) ? want : Cap(0);
+        return cap != Cap(0);
+    }
 
-    // frees one recorded pointer; p is NULL afterwards (a pointer that was never recorded is only set to NULL)
+    // frees one recorded pointer of either list; p is NULL afterwards (a pointer that was never recorded is only set to NULL)
     template <class T> void release(T*& p) {
-        for (size_t i = 0; i < n_owned; ++i)
-            if (owned[i] == p) {
-                (void)hipFree(owned[i]);
-                std::memmove(owned + i, owned + i + 1, (--n_owned - i) * sizeof(void*));
-                break;
-            }
+        if (p && !drop(owned, p, false)) drop(pins, p, true);
         p = nullptr;
     }
-    // frees what was recorded since live() was `mark`: a state that did not come to life
-    void release_from(size_t mark) {
-        while (n_owned > mark) (void)hipFree(owned[--n_owned]);
+    bool drop(List& l, const void* p, bool host) {
+        for (size_t i = 0; i < l.n; ++i)
+            if (l.v[i] == p) {
+                (void)(host ? hipHostFree(l.v[i]) : hipFree(l.v[i]));
+                std::memmove(l.v + i, l.v + i + 1, (--l.n - i) * sizeof(void*));
+                return true;
+            }
+        return false;
+    }
+    // frees what was recorded since live() was `mark` (and live_pinned() `pin_mark`, when given): a state that did not come to life
+    void release_from(size_t mark, size_t pin_mark = SIZE_MAX) {
+        while (owned.n > mark) (void)hipFree(owned.v[--owned.n]);
+        while (pins.n > pin_mark) (void)hipHostFree(pins.v[--pins.n]);
     }
 
     // waits for the stream, frees everything recorded, destroys the stream.  Harmless on an owner that never opened, and twice.
@@ -104,11 +156,12 @@ struct DeviceOwner {
         if (st) {
             (void)hipSetDevice(dev);
             (void)hipStreamSynchronize(st);
-            release_from(0);
+            release_from(0, 0);
             (void)hipStreamDestroy(st);
         }
-        std::free(owned);
-        owned = nullptr; st = nullptr; n_owned = cap = 0;
+        std::free(owned.v); std::free(pins.v);
+        owned = pins = List();
+        st = nullptr;
     }
 };
 

@@ -339,30 +339,23 @@ __global__ __launch_bounds__(256) void k_epi_to_aos(EdsArrays A, int first, cons
 }
 
 template <typename T>
-int grow(T*& p, size_t& cap, size_t n) {
-    if (cap >= n) return EDS_OK;
-    if (p) hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc((void**)&p, n * sizeof(T)) != hipSuccess) { p = nullptr; return fail(EDS_ERR_HIP, "allocation of the epiline work buffers failed"); }
-    cap = n;
-    return EDS_OK;
+int grow(eds_trk* h, T*& p, size_t& cap, size_t n) {
+    if (cap >= n || h->own.regrow(cap, n, {{(void**)&p, n * sizeof(T)}})) return EDS_OK;
+    return fail(EDS_ERR_HIP, "allocation of the epiline work buffers failed");
 }
 
 int ensure(eds_trk* h) {
     EdsEpiBuffers& e = h->epi;
     if (e.ef) return EDS_OK;
     const size_t B = (size_t)h->B, Np = (size_t)h->Np, H = (size_t)h->H, W = (size_t)h->W;
-    if (!device_alloc({{(void**)&e.ef, 2 * B * Np * 8}, {(void**)&e.kpix, 2 * B * Np * 8}, {(void**)&e.mval, B * Np * 8},
+    if (!h->own.alloc({{(void**)&e.ef, 2 * B * Np * 8}, {(void**)&e.kpix, 2 * B * Np * 8}, {(void**)&e.mval, B * Np * 8},
                        {(void**)&e.keys_tmp, B * Np * 8}, {(void**)&e.keys, B * Np * 8}, {(void**)&e.row_start, B * (H + 2) * 4},
                        {(void**)&e.model, B * H * W * 8}, {(void**)&e.par, B * EDS_EPI_PAR * 8}, {(void**)&e.best, 2 * B * Np * 8},
                        {(void**)&e.ef_tmp, 2 * B * Np * 8}, {(void**)&e.loc, 4 * B * Np * 4}, {(void**)&e.score, 2 * B * Np * 8},
                        {(void**)&e.erase, B * Np}, {(void**)&e.coord, 2 * B * Np * 8}, {(void**)&e.kept, B * Np * 4},
-                       {(void**)&e.ef_aos, 2 * B * Np * 8}}) ||
-        hipHostMalloc((void**)&e.h_par, B * EDS_EPI_PAR * 8, hipHostMallocDefault) != hipSuccess) {
-        eds_epi_free(&e);
+                       {(void**)&e.ef_aos, 2 * B * Np * 8}, pinned(e.h_par, B * EDS_EPI_PAR * 8)}))
         return fail(EDS_ERR_HIP, "allocation of the epiline buffers failed");
-    }
-    EDS_HIP_TRY(hipMemsetAsync(e.ef, 0, 2 * B * Np * 8, h->st));
+    EDS_HIP_TRY(hipMemsetAsync(e.ef, 0, 2 * B * Np * 8, h->own.st));
     return EDS_OK;
 }
 
@@ -377,15 +370,15 @@ int build_model(eds_trk* h, int first, int count) {
         P[10] = sl.seeded ? 1.0 : 0.0;
     }
     EDS_HIP_TRY(hipMemcpyAsync(e.par + (size_t)first * EDS_EPI_PAR, e.h_par + (size_t)first * EDS_EPI_PAR, (size_t)count * EDS_EPI_PAR * 8,
-                               hipMemcpyHostToDevice, h->st));
-    hipLaunchKernelGGL(k_epi_values, dim3(count), dim3(EDS_EPI_VAL_THREADS), 0, h->st, h->arrays(), first, e.par, h->depth.seeds, e.kpix, e.mval);
+                               hipMemcpyHostToDevice, h->own.st));
+    hipLaunchKernelGGL(k_epi_values, dim3(count), dim3(EDS_EPI_VAL_THREADS), 0, h->own.st, h->arrays(), first, e.par, h->depth.seeds, e.kpix, e.mval);
     EDS_HIP_TRY(hipGetLastError());
     int rc = eds_klt_bin_launch(h, first, count, e.kpix, e.keys_tmp, e.keys, e.row_start, 1);
     if (rc) return rc;
     double k0, k1;
     gauss3_sigma_half(k0, k1);
     const int tiles = ((h->W + EDS_EPI_MODEL_TW - 1) / EDS_EPI_MODEL_TW) * ((h->H + EDS_EPI_MODEL_TH - 1) / EDS_EPI_MODEL_TH);
-    hipLaunchKernelGGL(k_epi_model, dim3(tiles, count), dim3(256), 0, h->st, h->arrays(), first, k0, k1, k0, e.kpix, e.mval, e.keys, e.row_start,
+    hipLaunchKernelGGL(k_epi_model, dim3(tiles, count), dim3(256), 0, h->own.st, h->arrays(), first, k0, k1, k0, e.kpix, e.mval, e.keys, e.row_start,
                        e.model);
     EDS_HIP_TRY(hipGetLastError());
     return EDS_OK;
@@ -415,52 +408,52 @@ int track(eds_trk* h, int first, int count, int r, int border, int bval, int era
     const int H = h->H, W = h->W, K = (2 * r + 1) * (2 * r + 1);
     const size_t Np = (size_t)h->Np, Hp2 = (size_t)H + 2 * r, Wp2 = (size_t)W + 2 * r;
     const int cap = std::min(count, EDS_EPI_CHUNK);
-    if ((rc = grow(e.pad, e.pad_cap, cap * Hp2 * Wp2)) || (rc = grow(e.rowsq, e.rowsq_cap, cap * Hp2 * W)) ||
-        (rc = grow(e.energy, e.energy_cap, (size_t)cap * H * W)) || (rc = grow(e.taps, e.taps_cap, cap * Np * K)) ||
-        (rc = grow(e.tmeta, e.tmeta_cap, cap * Np)))
+    if ((rc = grow(h, e.pad, e.pad_cap, cap * Hp2 * Wp2)) || (rc = grow(h, e.rowsq, e.rowsq_cap, cap * Hp2 * W)) ||
+        (rc = grow(h, e.energy, e.energy_cap, (size_t)cap * H * W)) || (rc = grow(h, e.taps, e.taps_cap, cap * Np * K)) ||
+        (rc = grow(h, e.tmeta, e.tmeta_cap, cap * Np)))
         return rc;
     const int maxN = max_points(h, first, count);
     // 1. the model images
     if ((rc = build_model(h, first, count))) return rc;
-    EDS_HIP_TRY(hipMemsetAsync(e.best + 2 * Np * first, 0xff, 2 * Np * count * 8, h->st));
+    EDS_HIP_TRY(hipMemsetAsync(e.best + 2 * Np * first, 0xff, 2 * Np * count * 8, h->own.st));
     // 2 .. 4, a chunk of alignments at a time
     const int ntiles = ((W + EDS_EPI_TW - 1) / EDS_EPI_TW) * ((H + EDS_EPI_TH - 1) / EDS_EPI_TH);
     const int ngroups = (maxN + EDS_EPI_GROUP - 1) / EDS_EPI_GROUP;
     for (int c0 = 0; c0 < count; c0 += cap) {
         const int cn = std::min(cap, count - c0), f = first + c0;
-        hipLaunchKernelGGL(k_epi_templates, dim3(maxN, cn), dim3(64), 0, h->st, h->arrays(), f, r, border, (double)bval, pitch, e.kpix, e.model,
+        hipLaunchKernelGGL(k_epi_templates, dim3(maxN, cn), dim3(64), 0, h->own.st, h->arrays(), f, r, border, (double)bval, pitch, e.kpix, e.model,
                            e.taps, e.tmeta);
-        hipLaunchKernelGGL(k_epi_pad, dim3((unsigned)((Hp2 * Wp2 + 255) / 256), cn), dim3(256), 0, h->st, h->arrays(), f, r, border, (float)bval,
+        hipLaunchKernelGGL(k_epi_pad, dim3((unsigned)((Hp2 * Wp2 + 255) / 256), cn), dim3(256), 0, h->own.st, h->arrays(), f, r, border, (float)bval,
                            e.pad);
-        hipLaunchKernelGGL(k_epi_rowsq, dim3((unsigned)((Hp2 * W + 255) / 256), cn), dim3(256), 0, h->st, H, W, r, e.pad, e.rowsq);
-        hipLaunchKernelGGL(k_epi_energy, dim3((unsigned)(((size_t)H * W + 255) / 256), cn), dim3(256), 0, h->st, H, W, r, e.rowsq, e.energy);
-        hipLaunchKernelGGL(k_epi_match, dim3(ntiles, ngroups, cn), dim3(256), match_lds, h->st, h->arrays(), f, r, pitch, e.pad, e.energy, e.taps,
+        hipLaunchKernelGGL(k_epi_rowsq, dim3((unsigned)((Hp2 * W + 255) / 256), cn), dim3(256), 0, h->own.st, H, W, r, e.pad, e.rowsq);
+        hipLaunchKernelGGL(k_epi_energy, dim3((unsigned)(((size_t)H * W + 255) / 256), cn), dim3(256), 0, h->own.st, H, W, r, e.rowsq, e.energy);
+        hipLaunchKernelGGL(k_epi_match, dim3(ntiles, ngroups, cn), dim3(256), match_lds, h->own.st, h->arrays(), f, r, pitch, e.pad, e.energy, e.taps,
                            e.tmeta, reinterpret_cast<unsigned long long*>(e.best));
         EDS_HIP_TRY(hipGetLastError());
     }
     const unsigned nchunk = (unsigned)((maxN + 255) / 256);
-    hipLaunchKernelGGL(k_epi_finish, dim3(nchunk, count), dim3(256), 0, h->st, h->arrays(), first,
+    hipLaunchKernelGGL(k_epi_finish, dim3(nchunk, count), dim3(256), 0, h->own.st, h->arrays(), first,
                        reinterpret_cast<const unsigned long long*>(e.best), e.loc, e.score, e.ef_tmp, e.erase);
     EDS_HIP_TRY(hipGetLastError());
     // the per-original-point outputs, before the compaction
     std::vector<int32_t> vloc;
     std::vector<double> vsc;
-    if (ssd_xy || ncc_xy) { vloc.resize(4 * Np * count); EDS_HIP_TRY(hipMemcpyAsync(vloc.data(), e.loc + 4 * Np * first, vloc.size() * 4, hipMemcpyDeviceToHost, h->st)); }
-    if (scores) { vsc.resize(2 * Np * count); EDS_HIP_TRY(hipMemcpyAsync(vsc.data(), e.score + 2 * Np * first, vsc.size() * 8, hipMemcpyDeviceToHost, h->st)); }
+    if (ssd_xy || ncc_xy) { vloc.resize(4 * Np * count); EDS_HIP_TRY(hipMemcpyAsync(vloc.data(), e.loc + 4 * Np * first, vloc.size() * 4, hipMemcpyDeviceToHost, h->own.st)); }
+    if (scores) { vsc.resize(2 * Np * count); EDS_HIP_TRY(hipMemcpyAsync(vsc.data(), e.score + 2 * Np * first, vsc.size() * 8, hipMemcpyDeviceToHost, h->own.st)); }
     std::vector<int> n0(count);
     for (int b = 0; b < count; ++b) n0[b] = h->slots[first + b].N;
     // 5. the cull: getCoord's compaction, erasing by flag
     if (erase) {
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
         const EdsPointsDev dev = {e.coord, e.kept, e.erase};
         if ((rc = update_points_range(h, first, count, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dev))) return rc;
     }
-    hipLaunchKernelGGL(k_epi_gather, dim3(nchunk, count), dim3(256), 0, h->st, h->arrays(), first, erase ? e.kept : nullptr, e.ef_tmp, e.ef);
+    hipLaunchKernelGGL(k_epi_gather, dim3(nchunk, count), dim3(256), 0, h->own.st, h->arrays(), first, erase ? e.kept : nullptr, e.ef_tmp, e.ef);
     EDS_HIP_TRY(hipGetLastError());
     std::vector<int32_t> vk;
-    if (kept_index && erase) { vk.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), e.kept + Np * first, Np * count * 4, hipMemcpyDeviceToHost, h->st)); }
+    if (kept_index && erase) { vk.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), e.kept + Np * first, Np * count * 4, hipMemcpyDeviceToHost, h->own.st)); }
     if (ef_xy && (rc = read_xy_planes(h, e.ef, first, count, stride, ef_xy))) return rc;
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     for (int b = 0; b < count; ++b) {
         Slot& sl = h->slots[first + b];
         sl.epi_valid = sl.has_kf && sl.N > 0;
@@ -479,14 +472,6 @@ int track(eds_trk* h, int first, int count, int r, int border, int bval, int era
 
 }  // namespace
 
-void eds_epi_free(EdsEpiBuffers* eb) {
-    void* dp[] = {eb->ef, eb->kpix, eb->mval, eb->keys_tmp, eb->keys, eb->row_start, eb->model, eb->par, eb->best, eb->ef_tmp, eb->loc,
-                  eb->score, eb->erase, eb->coord, eb->kept, eb->ef_aos, eb->pad, eb->rowsq, eb->energy, eb->taps, eb->tmeta};
-    for (void* p : dp) if (p) hipFree(p);
-    if (eb->h_par) hipHostFree(eb->h_par);
-    *eb = EdsEpiBuffers();
-}
-
 extern "C" {
 
 int eds_epi_abi_version(void) { return EDS_HIP_EPILINE_ABI_VERSION; }
@@ -502,7 +487,7 @@ int eds_epi_get(eds_trk* h, int slot, double* ef_xy) {
     if (!ef_xy) return fail(EDS_ERR_INVALID, "null output");
     if ((rc = check_idle_slots(h, slot, 1, EDS_NEED_KF))) return rc;
     if (!h->epi.ef || !h->slots[slot].epi_valid) return fail(EDS_ERR_STATE, "the slot's ef plane is not current: run eds_epi_track_points");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     return read_xy_planes(h, h->epi.ef, slot, 1, h->slots[slot].N, ef_xy);
 }
 
@@ -516,8 +501,8 @@ int eds_epi_get_model(eds_trk* h, int slot, double* model) {
     if (!row_bins_fit(h, max_lds)) return fail(EDS_ERR_NOT_USABLE, "the row bins of this frame size do not fit the workgroup's LDS");
     if ((rc = ensure(h)) || (rc = build_model(h, slot, 1))) return rc;
     const size_t n = (size_t)h->H * h->W;
-    EDS_HIP_TRY(hipMemcpyAsync(model, h->epi.model + n * slot, n * 8, hipMemcpyDeviceToHost, h->st));
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(model, h->epi.model + n * slot, n * 8, hipMemcpyDeviceToHost, h->own.st));
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     return EDS_OK;
 }
 
@@ -528,8 +513,8 @@ int eds_epi_depth_update(eds_trk* h, int first, int count, const double* T_kf_ef
     for (int s = first; s < first + count; ++s)
         if (!h->epi.ef || !h->slots[s].epi_valid || !h->slots[s].has_kf)
             return fail(EDS_ERR_STATE, "the slot's ef plane is not current: run eds_epi_track_points");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    hipLaunchKernelGGL(k_epi_to_aos, dim3((h->Np + 255) / 256, count), dim3(256), 0, h->st, h->arrays(), first, h->epi.ef, h->epi.ef_aos);
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    hipLaunchKernelGGL(k_epi_to_aos, dim3((h->Np + 255) / 256, count), dim3(256), 0, h->own.st, h->arrays(), first, h->epi.ef, h->epi.ef_aos);
     EDS_HIP_TRY(hipGetLastError());
     return eds_depth_update_impl(h, first, count, EDS_DEPTH_EF_COORD, nullptr, nullptr, 0, T_kf_ef, filter, out, h->epi.ef_aos);
 }

@@ -34,4 +34,3 @@ struct EdsEpiBuffers {
     float4* tmeta = nullptr; size_t tmeta_cap = 0;      // [chunk][Np] (tap count, S, sqrt S, -)
 };
 
-void eds_epi_free(EdsEpiBuffers* eb);

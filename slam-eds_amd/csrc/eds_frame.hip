@@ -318,7 +318,7 @@ __global__ void k_mirror_rows(const float* __restrict__ src, float* __restrict__
 bool eds_mirror_residuals(eds_trk* h, int first, int count) {
     if (!h->d_rmap || first + count > EDS_RHOST_SLOTS) return false;
     const int n = count * h->Np;                                  // Np is a multiple of 4 (EDS_POINT_ALIGN)
-    hipLaunchKernelGGL(k_mirror_rows, dim3((n / 4 + 255) / 256), dim3(256), 0, h->st, h->dr + (size_t)first * h->Np, h->d_rmap + (size_t)first * h->Np, n);
+    hipLaunchKernelGGL(k_mirror_rows, dim3((n / 4 + 255) / 256), dim3(256), 0, h->own.st, h->dr + (size_t)first * h->Np, h->d_rmap + (size_t)first * h->Np, n);
     return true;
 }
 
@@ -326,7 +326,7 @@ bool eds_mirror_residuals(eds_trk* h, int first, int count) {
 void eds_frame_store_rowmajor(eds_trk* h, int slot, const float* d_src, int row_b, int row_e) {
     const int lo = row_b <= 0 ? -EDS_FRAME_MARGIN : row_b, hi = row_e >= h->H ? h->Hp - EDS_FRAME_MARGIN : row_e;
     if (hi <= lo) return;
-    hipLaunchKernelGGL(k_store_rowmajor, dim3((h->Wp + 255) / 256, hi - lo), dim3(256), 0, h->st, d_src,
+    hipLaunchKernelGGL(k_store_rowmajor, dim3((h->Wp + 255) / 256, hi - lo), dim3(256), 0, h->own.st, d_src,
                        h->dframe + (size_t)slot * h->Hp * h->Wp, h->H, h->W, h->Hp, h->Wp, h->tiled, lo);
 }
 
@@ -358,36 +358,38 @@ void eds_frame_store_whole(eds_trk* h, int slot, const float* d_src, hipStream_t
 // One launch that follows the host through the staging buffer (k_store_follow); the caller publishes its progress in h->h_fprog[0].
 void eds_frame_store_follow(eds_trk* h, int slot, unsigned seq, int rows_per) {
     const int nbands = (h->H + rows_per - 1) / rows_per;
-    hipLaunchKernelGGL(k_store_follow, dim3(nbands * EDS_FOLLOW_PARTS), dim3(EDS_FOLLOW_THREADS), 0, h->st, h->d_fstage,
+    hipLaunchKernelGGL(k_store_follow, dim3(nbands * EDS_FOLLOW_PARTS), dim3(EDS_FOLLOW_THREADS), 0, h->own.st, h->d_fstage,
                        h->dframe + (size_t)slot * h->Hp * h->Wp, h->H, h->W, h->Hp, h->Wp, h->tiled, h->d_fprog, seq, rows_per, nbands);
 }
 
-void eds_frame_free(EdsFrameBuffers* fb) {
-    void* d[] = {fb->d_mapx, fb->d_mapy, fb->d_img, fb->d_tmp, fb->d_norm, fb->d_planes};
-    for (void* p : d) if (p) hipFree(p);
-    if (fb->h_events) hipHostFree(fb->h_events);       // d_ex, d_ey, d_pol are its device view
-    if (fb->h_norm_out) hipHostFree(fb->h_norm_out);
-    if (fb->h_aos) hipHostFree(fb->h_aos);
-    void* bd[] = {fb->b_img, fb->b_tmp, fb->b_planes, fb->b_norm};
-    for (void* q : bd) if (q) hipFree(q);
-    if (fb->h_bmeta) hipHostFree(fb->h_bmeta);
-    *fb = EdsFrameBuffers();
+// The mapped staging of SoA events [x | y | polarity], grown to hold n_events: k_vote reads it in place.
+static int ensure_events(eds_trk* h, long long n_events) {
+    EdsFrameBuffers& fb = h->frame_build;
+    if (n_events <= fb.cap_events) return EDS_OK;
+    const int want = (int)((n_events + n_events / 4 + 1024 + 7) & ~7ll);
+    uint8_t* dev = nullptr;
+    fb.d_ex = fb.d_ey = nullptr; fb.d_pol = nullptr;
+    if (!h->own.regrow(fb.cap_events, want, {edscapi::mapped(fb.h_events, dev, (size_t)want * 5)})) return eds_internal_fail(EDS_ERR_HIP, "hipHostMalloc (events)");
+    fb.d_ex = reinterpret_cast<uint16_t*>(dev);
+    fb.d_ey = fb.d_ex + fb.cap_events;
+    fb.d_pol = reinterpret_cast<uint8_t*>(fb.d_ey + fb.cap_events);
+    return EDS_OK;
 }
 
 int eds_frame_set_map(eds_trk* h, const float* mapx, const float* mapy, int mH, int mW) {
     EdsFrameBuffers& fb = h->frame_build;
     if (!mapx || !mapy) {               // identity LUT
-        if (fb.d_mapx) { hipFree(fb.d_mapx); hipFree(fb.d_mapy); fb.d_mapx = fb.d_mapy = nullptr; }
+        h->own.release(fb.d_mapx); h->own.release(fb.d_mapy);
         fb.map_H = fb.map_W = 0;
         return EDS_OK;
     }
     const size_t n = (size_t)mH * mW;
-    if (fb.d_mapx && (fb.map_H != mH || fb.map_W != mW)) { hipFree(fb.d_mapx); hipFree(fb.d_mapy); fb.d_mapx = fb.d_mapy = nullptr; }
-    if (!fb.d_mapx) {
-        if (hipMalloc((void**)&fb.d_mapx, n * 4) != hipSuccess || hipMalloc((void**)&fb.d_mapy, n * 4) != hipSuccess)
-            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc(undistortion map)");
+    if (!fb.d_mapx || fb.map_H != mH || fb.map_W != mW) {          // both planes or neither, and no size without them
+        h->own.release(fb.d_mapx); h->own.release(fb.d_mapy);
+        fb.map_H = fb.map_W = 0;
+        if (!h->own.alloc({{(void**)&fb.d_mapx, n * 4}, {(void**)&fb.d_mapy, n * 4}})) return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (undistortion map)");
+        fb.map_H = mH; fb.map_W = mW;
     }
-    fb.map_H = mH; fb.map_W = mW;
     if (hipMemcpy(fb.d_mapx, mapx, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(fb.d_mapy, mapy, n * 4, hipMemcpyHostToDevice) != hipSuccess)
         return eds_internal_fail(EDS_ERR_HIP, "hipMemcpy(undistortion map)");
@@ -404,53 +406,28 @@ int eds_frame_build_levels(eds_trk* h, int first_slot, int level0, int nlevels, 
     const size_t n = (size_t)H * W, ns = (size_t)sH * sW;
     if (fb.d_mapx && (fb.map_H != sH || fb.map_W != sW)) return eds_internal_fail(EDS_ERR_INVALID, "undistortion map and sensor size differ");
     if (fb.img_elems < std::max(n, ns)) {
-        if (fb.d_img) { hipFree(fb.d_img); hipFree(fb.d_tmp); fb.d_img = fb.d_tmp = nullptr; }
-        fb.img_elems = std::max(n, ns);
+        const size_t want = std::max(n, ns);
         fb.img_clean = false;
-        if (hipMalloc((void**)&fb.d_img, fb.img_elems * 8) != hipSuccess || hipMalloc((void**)&fb.d_tmp, fb.img_elems * 8) != hipSuccess)
-            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc(frame accumulation)");
+        if (!h->own.regrow(fb.img_elems, want, {{(void**)&fb.d_img, want * 8}, {(void**)&fb.d_tmp, want * 8}}))
+            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (frame accumulation)");
     }
     constexpr size_t NORM_SET = (size_t)EDS_MAX_LEVELS * EDS_SUMSQ_WAYS;
     if (!fb.d_norm) {
-        if (hipMalloc((void**)&fb.d_norm, 8 * 2 * NORM_SET) != hipSuccess || hipMemset(fb.d_norm, 0, 8 * 2 * NORM_SET) != hipSuccess ||
-            hipHostMalloc((void**)&fb.h_norm_out, 8 * EDS_MAX_LEVELS, hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&fb.d_norm_out, fb.h_norm_out, 0) != hipSuccess)
-            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc(norms)");
+        if (!h->own.alloc({{(void**)&fb.d_norm, 8 * 2 * NORM_SET}, edscapi::mapped(fb.h_norm_out, fb.d_norm_out, 8 * EDS_MAX_LEVELS)}))
+            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (norms)");
+        if (hipMemset(fb.d_norm, 0, 8 * 2 * NORM_SET) != hipSuccess) {
+            h->own.release(fb.d_norm); h->own.release(fb.h_norm_out); fb.d_norm_out = nullptr;
+            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (norms)");
+        }
     }
-    if (fb.plane_levels < nlevels) {
-        if (fb.d_planes) hipFree(fb.d_planes);
-        fb.d_planes = nullptr; fb.plane_levels = 0;
-        if (hipMalloc((void**)&fb.d_planes, n * 8 * nlevels) != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, "hipMalloc(level planes)");
-        fb.plane_levels = nlevels;
-    }
+    if (fb.plane_levels < nlevels && !h->own.regrow(fb.plane_levels, nlevels, {{(void**)&fb.d_planes, n * 8 * nlevels}}))
+        return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (level planes)");
     if (aos) {
-        const size_t bytes = (size_t)n_events * aos->stride;
-        if (bytes > fb.cap_aos) {
-            if (fb.h_aos) hipHostFree(fb.h_aos);
-            fb.h_aos = fb.d_aos = nullptr;
-            fb.cap_aos = bytes + bytes / 4 + 4096;
-            if (hipHostMalloc((void**)&fb.h_aos, fb.cap_aos, hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&fb.d_aos, fb.h_aos, 0) != hipSuccess) {
-                fb.cap_aos = 0;
-                return eds_internal_fail(EDS_ERR_HIP, "hipHostMalloc(events)");
-            }
-        }
-    } else
-    if (n_events > fb.cap_events) {
-        if (fb.h_events) hipHostFree(fb.h_events);
-        fb.d_ex = fb.d_ey = nullptr; fb.d_pol = nullptr; fb.h_events = nullptr;
-        fb.cap_events = (n_events + n_events / 4 + 1024 + 7) & ~7;
-        uint8_t* dev = nullptr;
-        if (hipHostMalloc((void**)&fb.h_events, (size_t)fb.cap_events * 5, hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&dev, fb.h_events, 0) != hipSuccess) {
-            fb.cap_events = 0;
-            return eds_internal_fail(EDS_ERR_HIP, "hipHostMalloc(events)");
-        }
-        fb.d_ex = reinterpret_cast<uint16_t*>(dev);
-        fb.d_ey = fb.d_ex + fb.cap_events;
-        fb.d_pol = reinterpret_cast<uint8_t*>(fb.d_ey + fb.cap_events);
-    }
-    hipStream_t st = h->st;
+        const size_t bytes = (size_t)n_events * aos->stride, want = bytes + bytes / 4 + 4096;
+        if (bytes > fb.cap_aos && !h->own.regrow(fb.cap_aos, want, {edscapi::mapped(fb.h_aos, fb.d_aos, want)}))
+            return eds_internal_fail(EDS_ERR_HIP, "hipHostMalloc (events)");
+    } else if (int rc = ensure_events(h, n_events)) return rc;
+    hipStream_t st = h->own.st;
     hipError_t e = hipSuccess;
     if (n_events > 0 && aos) {
         std::memcpy(fb.h_aos, aos->data, (size_t)n_events * aos->stride);     // as they are: k_vote_aos picks the fields
@@ -518,20 +495,14 @@ int eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offs
     const size_t n = (size_t)H * W;
     if (fb.d_mapx && (fb.map_H != H || fb.map_W != W)) return eds_internal_fail(EDS_ERR_INVALID, "undistortion map and frame size differ");
     const int C = std::min(count, EDS_FRAME_BATCH);
-    if (fb.batch_cap < C) {
-        void* d[] = {fb.b_img, fb.b_tmp, fb.b_planes, fb.b_norm};
-        for (void* q : d) if (q) hipFree(q);
-        fb.b_img = fb.b_tmp = fb.b_planes = fb.b_norm = nullptr; fb.batch_cap = 0;
-        if (hipMalloc((void**)&fb.b_img, C * n * 8) != hipSuccess || hipMalloc((void**)&fb.b_tmp, C * n * 8) != hipSuccess ||
-            hipMalloc((void**)&fb.b_planes, C * n * 8) != hipSuccess || hipMalloc((void**)&fb.b_norm, (size_t)C * EDS_SUMSQ_WAYS * 8) != hipSuccess)
-            return eds_internal_fail(EDS_ERR_HIP, "allocation of the batched event-frame buffers failed");
-        fb.batch_cap = C;
-    }
+    if (fb.batch_cap < C && !h->own.regrow(fb.batch_cap, C, {{(void**)&fb.b_img, C * n * 8}, {(void**)&fb.b_tmp, C * n * 8}, {(void**)&fb.b_planes, C * n * 8},
+                                                             {(void**)&fb.b_norm, (size_t)C * EDS_SUMSQ_WAYS * 8}}))
+        return eds_internal_fail(EDS_ERR_HIP, "allocation of the batched event-frame buffers failed");
     // A GROUP of chunks is queued without waiting in between: events of chunk k + 1 are copied into the pinned staging while the device
     // works on chunk k (every chunk has its own part of the staging, of the offsets and of the totals; the image buffers are reused
     // in stream order).  Groups are bounded by EDS_FRAME_GROUP_EVENTS so that the pinned staging stays small.
     constexpr long long EDS_FRAME_GROUP_EVENTS = 8ll << 20;
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     const dim3 b2(256);
     int g0 = 0;
     while (g0 < count) {
@@ -546,30 +517,16 @@ int eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offs
         }
         const int gn = g1 - g0;
         if (fb.meta_cap < gn) {
-            if (fb.h_bmeta) hipHostFree(fb.h_bmeta);
-            fb.h_bmeta = nullptr; fb.meta_cap = 0;
-            char* dmeta = nullptr;
             const int cap = std::max(gn, 64);
-            if (hipHostMalloc((void**)&fb.h_bmeta, (size_t)cap * 8 + (size_t)(cap + 1) * 4, hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&dmeta, fb.h_bmeta, 0) != hipSuccess)
+            if (!h->own.regrow(fb.meta_cap, cap, {edscapi::mapped(fb.h_bmeta, fb.d_bmeta, (size_t)cap * 8 + (size_t)(cap + 1) * 4)}))
                 return eds_internal_fail(EDS_ERR_HIP, "allocation of the batched event-frame buffers failed");
-            fb.d_bmeta = dmeta; fb.meta_cap = cap;
         }
         double* h_tot = reinterpret_cast<double*>(fb.h_bmeta);                       // [meta_cap] totals out
         int* h_off = reinterpret_cast<int*>(fb.h_bmeta + (size_t)fb.meta_cap * 8);     // [meta_cap + 1] event offsets relative to the group
         double* d_tot = reinterpret_cast<double*>(fb.d_bmeta);
         int* d_off = reinterpret_cast<int*>(fb.d_bmeta + (size_t)fb.meta_cap * 8);
-        if (!dev_events && gev > fb.cap_events) {           // the mapped staging of the single-slice builder, grown
-            if (fb.h_events) hipHostFree(fb.h_events);
-            fb.h_events = nullptr; fb.d_ex = fb.d_ey = nullptr; fb.d_pol = nullptr;
-            fb.cap_events = (int)((gev + gev / 4 + 1024 + 7) & ~7ll);
-            uint8_t* dev = nullptr;
-            if (hipHostMalloc((void**)&fb.h_events, (size_t)fb.cap_events * 5, hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer((void**)&dev, fb.h_events, 0) != hipSuccess) { fb.cap_events = 0; return eds_internal_fail(EDS_ERR_HIP, "hipHostMalloc(events)"); }
-            fb.d_ex = reinterpret_cast<uint16_t*>(dev);
-            fb.d_ey = fb.d_ex + fb.cap_events;
-            fb.d_pol = reinterpret_cast<uint8_t*>(fb.d_ey + fb.cap_events);
-        }
+        if (!dev_events)            // the mapped staging of the single-slice builder, grown
+            if (int rc = ensure_events(h, gev)) return rc;
         const int ge0 = offsets[g0];
         for (int b = 0; b <= gn; ++b) h_off[b] = offsets[g0 + b] - ge0;
         for (int b = 0; b < gn; ++b) if (h_off[b + 1] < h_off[b]) return eds_internal_fail(EDS_ERR_INVALID, "offsets must not decrease");

@@ -1139,24 +1139,19 @@ void eds_fused6_launch_bilinear(const EdsFused6Launch& L, int ppt, int team, int
 }
 #endif
 #ifndef EDS_FUSED_BILINEAR_TU
-int eds_fused_alloc(EdsFusedBuffers* fb, int B) {
+int eds_fused_alloc(edscapi::DeviceOwner& own, EdsFusedBuffers* fb, int B) {
+    using edscapi::mapped;
     fb->B = B;
     // start states and compact results live in pinned host memory that the kernels read / write directly (a solve moves ~100 bytes
-    // each way per alignment): no copy calls on the latency path of a single optimize — each HIP call costs 3-5 us of host time
-    if (hipMalloc(&fb->d_sv, sizeof(edss::Solver6) * (size_t)B) != hipSuccess) return -1;
-    if (hipHostMalloc((void**)&fb->h_in, sizeof(EdsFusedIn) * B, hipHostMallocMapped) != hipSuccess) return -1;
-    if (hipHostMalloc((void**)&fb->h_out, sizeof(EdsFusedOut) * B, hipHostMallocMapped) != hipSuccess) return -1;
-    if (hipHostMalloc((void**)&fb->h_out12, sizeof(EdsFused12Out) * B, hipHostMallocMapped) != hipSuccess) return -1;
-    if (hipHostGetDevicePointer((void**)&fb->d_in, fb->h_in, 0) != hipSuccess) return -1;
-    if (hipHostGetDevicePointer((void**)&fb->d_out, fb->h_out, 0) != hipSuccess) return -1;
-    if (hipHostGetDevicePointer((void**)&fb->d_out12, fb->h_out12, 0) != hipSuccess) return -1;
-    if (hipHostMalloc((void**)&fb->h_done, sizeof(unsigned) * EDS_DONE_WORDS * (size_t)B, hipHostMallocMapped) != hipSuccess) return -1;
-    if (hipHostGetDevicePointer((void**)&fb->d_done, fb->h_done, 0) != hipSuccess) return -1;
+    // each way per alignment): no copy calls on the latency path of a single optimize — each HIP call costs 3-5 us of host time.
+    // Team launches (eds_fused6_kernel TEAM > 1): granule mailboxes of EDS_TEAM_SLOTS alignments + the ticket counter.  All or nothing.
+    if (!own.alloc({{(void**)&fb->d_sv, sizeof(edss::Solver6) * (size_t)B}, mapped(fb->h_in, fb->d_in, sizeof(EdsFusedIn) * B),
+                    mapped(fb->h_out, fb->d_out, sizeof(EdsFusedOut) * B), mapped(fb->h_out12, fb->d_out12, sizeof(EdsFused12Out) * B),
+                    mapped(fb->h_done, fb->d_done, sizeof(unsigned) * EDS_DONE_WORDS * (size_t)B), {(void**)&fb->d_mail, EDS_TEAM_MAIL_BYTES},
+                    {(void**)&fb->d_ticket, sizeof(int)}}))
+        return -1;
     std::memset(fb->h_done, 0, sizeof(unsigned) * EDS_DONE_WORDS * (size_t)B);
-    // team launches (eds_fused6_kernel TEAM > 1): granule mailboxes of EDS_TEAM_SLOTS alignments + the ticket counter
-    if (hipMalloc((void**)&fb->d_mail, EDS_TEAM_MAIL_BYTES) != hipSuccess) return -1;
     if (hipMemset(fb->d_mail, 0, EDS_TEAM_MAIL_BYTES) != hipSuccess) return -1;
-    if (hipMalloc((void**)&fb->d_ticket, sizeof(int)) != hipSuccess) return -1;
     if (hipMemset(fb->d_ticket, 0, sizeof(int)) != hipSuccess) return -1;
     fb->ticket_base = 0;
     fb->epoch = 0;
@@ -1188,23 +1183,11 @@ void eds_team_timed_out(eds_trk* h) {
     fb.team_cooldown = fb.team_backoff = next;
     fb.team_clean = 0;
     // workgroups of the short launch may have taken tickets the host never accounted for (or the reverse): start over
-    hipMemsetAsync(fb.d_ticket, 0, sizeof(int), h->st);
+    hipMemsetAsync(fb.d_ticket, 0, sizeof(int), h->own.st);
     fb.ticket_base = 0;
 }
 void eds_team_clean(EdsFusedBuffers* fb) {
     if (fb->team_backoff > 0 && ++fb->team_clean >= EDS_TEAM_REARM_CLEAN) { fb->team_backoff = 0; fb->team_clean = 0; }
-}
-
-void eds_fused_free(EdsFusedBuffers* fb) {
-    if (fb->d_sv) hipFree(fb->d_sv);
-    if (fb->h_in) hipHostFree(fb->h_in);
-    if (fb->h_out) hipHostFree(fb->h_out);
-    if (fb->d_mail) hipFree(fb->d_mail);
-    if (fb->d_mail12) hipFree(fb->d_mail12);
-    if (fb->d_ticket) hipFree(fb->d_ticket);
-    if (fb->h_out12) hipHostFree(fb->h_out12);
-    if (fb->h_done) hipHostFree(fb->h_done);
-    *fb = EdsFusedBuffers();
 }
 
 int eds_fused_solve(eds_trk* h, int level, int first, int count) {
@@ -1248,7 +1231,7 @@ int eds_fused_solve(eds_trk* h, int level, int first, int count) {
     fb.pending_paused = pl.wants_team && !team_ok && !fb.pending_retry;
     eds_lm6_plan_team(kn, rin, team_ok ? 1 : 0, fb.team_cooldown > 0 ? 1 : 0, pl);
     fb.pending_ticks = count <= 64 && !(pl.team <= 1 && pl.stream);   // the latency regime: time stamps from inside the kernel instead of event packets
-    if (!fb.pending_ticks) hipEventRecord(h->ev0, h->st);             // (a conversion of frames to strips that this solve asks for is inside the measured span)
+    if (!fb.pending_ticks) hipEventRecord(h->ev0, h->own.st);             // (a conversion of frames to strips that this solve asks for is inside the measured span)
     const bool strips = pl.strips_eligible && eds_strips_for_solve(h, first, count);
     eds_lm6_plan_finish(kn, rin, strips ? 1 : 0, pl);
     A.strips = h->dstrips; A.strip_phases = h->strip_phases;
@@ -1276,7 +1259,7 @@ int eds_fused_solve(eds_trk* h, int level, int first, int count) {
         if (pl.bilinear_tu) {
             const EdsFused6Launch L{&A, fb.d_in, fb.d_out, fb.d_sv, f0, cnt, block, iters, damped, h->cfg.lambda0, tau, nb,
                                     K > 1 ? fb.d_mail : nullptr, K > 1 ? fb.d_ticket : nullptr, K > 1 ? ticket_base : 0u, K > 1 ? fb.epoch : 0u,
-                                    K > 1 ? drop : 0, h->st};
+                                    K > 1 ? drop : 0, h->own.st};
             eds_fused6_launch_bilinear(L, pl.P, K, groups);
             return;
         }
@@ -1285,14 +1268,14 @@ int eds_fused_solve(eds_trk* h, int level, int first, int count) {
         const unsigned tb = K > 1 ? ticket_base : 0u, ep = K > 1 ? fb.epoch : 0u;
 #define EDS_INST_LAUNCH_(S_, P_, T_, Q_, K_)                                                                                          \
         if (pl.S == S_ && pl.P == P_ && pl.T == T_ && pl.Q == Q_ && K == K_) {                                                       \
-            hipLaunchKernelGGL((eds_fused6_kernel<S_, P_, T_, Q_, K_>), dim3(wg), dim3(block), 0, h->st, A, fb.d_in, fb.d_out, svp, f0, \
+            hipLaunchKernelGGL((eds_fused6_kernel<S_, P_, T_, Q_, K_>), dim3(wg), dim3(block), 0, h->own.st, A, fb.d_in, fb.d_out, svp, f0, \
                                iters, damped, h->cfg.lambda0, tau, nb, mail, ticket, tb, ep);                                        \
             return;                                                                                                                   \
         }
         if (groups > 1) {
 #define EDS_INST_LAUNCH6_(S_, P_, T_, Q_, K_, G_)                                                                                      \
             if (pl.S == S_ && pl.P == P_ && pl.T == T_ && pl.Q == Q_ && K == K_ && groups == G_) {                                    \
-                hipLaunchKernelGGL((eds_fused6_kernel<S_, P_, T_, Q_, K_, G_>), dim3(wg), dim3(block), 0, h->st, A, fb.d_in, fb.d_out, svp, f0, \
+                hipLaunchKernelGGL((eds_fused6_kernel<S_, P_, T_, Q_, K_, G_>), dim3(wg), dim3(block), 0, h->own.st, A, fb.d_in, fb.d_out, svp, f0, \
                                    iters, damped, h->cfg.lambda0, tau, nb, mail, ticket, tb, ep);                                    \
                 return;                                                                                                               \
             }
@@ -1310,7 +1293,7 @@ int eds_fused_solve(eds_trk* h, int level, int first, int count) {
         for (int c0 = 0; c0 < count; c0 += per_launch) {
             const int f0 = first + c0, cnt = std::min(per_launch, count - c0);
             if (++fb.epoch >= (1u << 24)) {              // tags are (epoch << 8 | pass): start over with clean mailboxes
-                hipMemsetAsync(fb.d_mail, 0, EDS_TEAM_MAIL_BYTES, h->st);
+                hipMemsetAsync(fb.d_mail, 0, EDS_TEAM_MAIL_BYTES, h->own.st);
                 fb.epoch = 1;
             }
             const unsigned ticket_base = fb.ticket_base;
@@ -1321,12 +1304,12 @@ int eds_fused_solve(eds_trk* h, int level, int first, int count) {
     } else if (pl.kind == EDS_K6_STREAM) {
         std::snprintf(fb.last_kernel, sizeof(fb.last_kernel), "eds_stream6_kernel<%d, %d, %d>", pl.S, pl.T, pl.P);
         fb.last_workgroups = count; fb.last_team = 1; fb.last_layout = 1;
-        eds_stream6_launch(A, h->cfg.sampling, pl.wide ? 1 : 0, fb.d_in, fb.d_out, fb.d_sv, first, count, iters, damped, h->cfg.lambda0, tau, nb, h->st);
+        eds_stream6_launch(A, h->cfg.sampling, pl.wide ? 1 : 0, fb.d_in, fb.d_out, fb.d_sv, first, count, iters, damped, h->cfg.lambda0, tau, nb, h->own.st);
     } else {
         if (fb.pending_ticks) for (int s = first; s < first + count; ++s) fb.h_out[s].t_end = 0;      // (the completion word wait_stream polls)
         launch(first, count, 0u);
     }
-    if (!fb.pending_ticks) hipEventRecord(h->ev1, h->st);
+    if (!fb.pending_ticks) hipEventRecord(h->ev1, h->own.st);
     fb.pending_host_r = rmap_in_kernel ? true : eds_mirror_residuals(h, first, count);
     if (fb.pending_host_r && !rmap_in_kernel) fb.pending_vteam = 0;      // a mirror launch follows the solve: only the stream says when IT is through
     e = hipGetLastError();
@@ -1376,7 +1359,7 @@ int eds_fused_collect(eds_trk* h) {
             fb.pending_retry = true;
             int rc = eds_fused_solve(h, fb.pending_level, pf, pc);
             if (rc != EDS_OK) { fb.pending_retry = false; return rc; }
-            hipError_t e = hipStreamSynchronize(h->st);
+            hipError_t e = hipStreamSynchronize(h->own.st);
             if (e != hipSuccess) { fb.pending_retry = false; return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e)); }
             return eds_fused_collect(h);
         }

@@ -12,6 +12,7 @@
 #include <vector>
 
 struct eds_trk;
+namespace edscapi { struct DeviceOwner; }
 
 struct EdsFusedIn {            // start state of a slot
     double p[3], q[4], v[6], pad[3];
@@ -84,25 +85,23 @@ struct EdsFusedBuffers {
     double launch_wall_us = 0.0;
 };
 
-int  eds_fused_alloc(EdsFusedBuffers* fb, int B);
+int  eds_fused_alloc(edscapi::DeviceOwner& own, EdsFusedBuffers* fb, int B);      // all of its buffers or none
 // time-out policy (eds_fused.hip): may this solve form teams?  (counts the cool-down down); a team launch timed out / ended clean
 unsigned eds_next_done_tag(EdsFusedBuffers* fb);     // the completion-word tag of the next small launch (eds_fused.hip)
 bool eds_team_allowed(EdsFusedBuffers* fb);
 void eds_team_timed_out(eds_trk* h);
 void eds_team_clean(EdsFusedBuffers* fb);
-void eds_fused_free(EdsFusedBuffers* fb);
-int  eds_fused_solve(eds_trk* h, int level, int first, int count);   // asynchronous on h->st
+int  eds_fused_solve(eds_trk* h, int level, int first, int count);   // asynchronous on h->own.st
 int  eds_fused_collect(eds_trk* h);                                  // after the stream is idle
 int  eds_fused_fetch_trace(eds_trk* h, int slot);                    // D2H of one slot's trace
 struct eds_trk_launch_info;
 int  eds_fused_last_launch(eds_trk* h, eds_trk_launch_info* out);
 
 // eds_strips.hip: makes the strip copies of the frames the slots [first, first + count) sample current (allocates them at the first call;
-// one conversion launch per run of stale slots, on h->st).  false: no memory for them — the caller uses the tiles.
+// one conversion launch per run of stale slots, on h->own.st).  false: no memory for them — the caller uses the tiles.
 bool eds_strips_prepare(eds_trk* h, int first, int count);
 bool eds_strips_for_solve(eds_trk* h, int first, int count);      // the solve kernels' question: gather from strips this time? (converts what the policy says)
 bool eds_strips_current(const eds_trk* h, int first, int count);  // every sampled slot of the range has an up-to-date strip copy (nothing is converted)
-void eds_strips_free(eds_trk* h);
 
 bool eds_fused12_supported(const eds_trk* h, int first, int count);
 int  eds_fused12_solve(eds_trk* h, int level, int first, int count);
@@ -147,7 +146,6 @@ struct EdsFrameBuffers {
     unsigned calls = 0;
     bool img_clean = false;
 };
-void eds_frame_free(EdsFrameBuffers* fb);
 int  eds_frame_build_batch(eds_trk* h, int first_slot, int count, const int* offsets, const uint16_t* ex, const uint16_t* ey, const uint8_t* pol,
                            int level, double blur_sigma, int use_exp_weights, double* norms_out, bool dev_events = false);
 // few alignments per launch: one more (tiny) launch writes the kept residuals into pinned host memory as well, so that reading
@@ -176,7 +174,6 @@ struct EdsPointBuffers {
     int* d_kept = nullptr;
     double *h_tau = nullptr, *d_tau = nullptr;    // loss scales of a batch: mapped pinned memory, host / device view
 };
-void eds_points_free(EdsPointBuffers* pb);
 bool eds_points_supported(const eds_trk* h, int first, int count);
 int  eds_points_loss_param(eds_trk* h, int first, int count, int method, double* tau_out);
 int  eds_points_update(eds_trk* h, int slot, int delete_out, double* coord_xy, double* tracks_xy, int32_t* kept_index, int* n_kept,
@@ -199,7 +196,6 @@ struct EdsKeyframeBuffers {
     int cap_depth = 0, last_slot = -1, last_N = 0, last_candidates = 0;
     double K[4] = {0, 0, 0, 0};
 };
-void eds_keyframe_free(EdsKeyframeBuffers* kb);
 int  eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int img_H, int img_W, int channels, const eds_kf_select* sel, int n_depth,
                         const double* depth_xy, const double* depth_idp, double fx, double fy, double cx, double cy, int* n_points);
 int  eds_keyframe_get_points(eds_trk* h, int slot, double* coord_xy, double* norm_xy, double* grad_xy, double* idp, double* weights);

@@ -845,17 +845,16 @@ int eds_fused12_solve(eds_trk* h, int level, int first, int count) {
     fb.pending_paused = pl.wants_team && !team_ok;
     eds_ref12_plan_team(kn, rin, team_ok ? 1 : 0, fb.team_cooldown > 0 ? 1 : 0, pl);
     if (pl.team > 1 && !fb.d_mail12) {
-        if (hipMalloc((void**)&fb.d_mail12, EDS_TEAM12_MAIL_BYTES) != hipSuccess) {       // no mailboxes: one CU per alignment
-            (void)hipGetLastError();
+        if (!h->own.alloc(fb.d_mail12, EDS_TEAM12_MAIL_BYTES)) {       // no mailboxes: one CU per alignment
             EdsKnobs k1 = kn; k1.ref12_team = 1;
             eds_ref12_plan_team(k1, rin, 0, 1, pl);
-        } else hipMemsetAsync(fb.d_mail12, 0, EDS_TEAM12_MAIL_BYTES, h->st);
+        } else hipMemsetAsync(fb.d_mail12, 0, EDS_TEAM12_MAIL_BYTES, h->own.st);
     }
     const int team = pl.team;
     if (team > 1) {
         if (++fb.epoch >= (1u << 24)) {
-            hipMemsetAsync(fb.d_mail, 0, EDS_TEAM_MAIL_BYTES, h->st);
-            hipMemsetAsync(fb.d_mail12, 0, EDS_TEAM12_MAIL_BYTES, h->st);
+            hipMemsetAsync(fb.d_mail, 0, EDS_TEAM_MAIL_BYTES, h->own.st);
+            hipMemsetAsync(fb.d_mail12, 0, EDS_TEAM12_MAIL_BYTES, h->own.st);
             fb.epoch = 1;
         }
     }
@@ -866,7 +865,7 @@ int eds_fused12_solve(eds_trk* h, int level, int first, int count) {
     const bool rmap_in_kernel = (team > 1 || done_words) && h->d_rmap && first + count <= EDS_RHOST_SLOTS;       // (see eds_fused_solve)
     A.rmap = rmap_in_kernel ? h->d_rmap : nullptr;
     const unsigned ticket_base = fb.ticket_base;
-    if (!fb.pending_ticks) hipEventRecord(h->ev0, h->st);
+    if (!fb.pending_ticks) hipEventRecord(h->ev0, h->own.st);
     // the strip copies of the frames: asked for only where an instantiation reads them (teams of up to 4, both one-CU shapes)
     const bool strips = pl.strips_eligible && eds_strips_for_solve(h, first, count);
     eds_ref12_plan_finish(kn, rin, strips ? 1 : 0, pl);
@@ -890,7 +889,7 @@ int eds_fused12_solve(eds_trk* h, int level, int first, int count) {
 #define EDS_INST_LAUNCH12G_(S_, T_, C_, N_, K_, Q_, G_)                                                                               \
     if (!launched && groups == G_ && pl.S == S_ && pl.T == T_ && pl.CAP == C_ && (pl.NC != 0) == N_ && pl.K == K_ && pl.Q == Q_) {   \
         launched = true;                                                                                                              \
-        hipLaunchKernelGGL((eds_fused12_kernel<S_, T_, C_, N_, K_, Q_, G_>), dim3(count * K_ * G_ - drop), dim3(T_), 0, h->st, A, fb.d_in, \
+        hipLaunchKernelGGL((eds_fused12_kernel<S_, T_, C_, N_, K_, Q_, G_>), dim3(count * K_ * G_ - drop), dim3(T_), 0, h->own.st, A, fb.d_in, \
                            fb.d_out12, first, iters, h->cfg.loss_type, h->cfg.loss_param, h->cfg.function_tolerance, h->cfg.gradient_tolerance, \
                            h->cfg.parameter_tolerance, nb, fb.d_mail12, fb.d_ticket, ticket_base, fb.epoch);                         \
     }
@@ -899,13 +898,13 @@ int eds_fused12_solve(eds_trk* h, int level, int first, int count) {
 #define EDS_INST_LAUNCH12_(S_, T_, C_, N_, K_, Q_)                                                                                    \
     if (!launched && groups == 1 && pl.S == S_ && pl.T == T_ && pl.CAP == C_ && (pl.NC != 0) == N_ && pl.K == K_ && pl.Q == Q_) {    \
         launched = true;                                                                                                              \
-        hipLaunchKernelGGL((eds_fused12_kernel<S_, T_, C_, N_, K_, Q_>), dim3(count * K_ - ((K_) > 1 ? drop : 0)), dim3(T_), 0, h->st, A, fb.d_in, \
+        hipLaunchKernelGGL((eds_fused12_kernel<S_, T_, C_, N_, K_, Q_>), dim3(count * K_ - ((K_) > 1 ? drop : 0)), dim3(T_), 0, h->own.st, A, fb.d_in, \
                            fb.d_out12, first, iters, h->cfg.loss_type, h->cfg.loss_param, h->cfg.function_tolerance, h->cfg.gradient_tolerance, \
                            h->cfg.parameter_tolerance, nb, fb.d_mail12, fb.d_ticket, ticket_base, fb.epoch);                         \
     }
     EDS_FUSED12_INSTANCES(EDS_INST_LAUNCH12_)
 #undef EDS_INST_LAUNCH12_
-    if (!fb.pending_ticks) hipEventRecord(h->ev1, h->st);
+    if (!fb.pending_ticks) hipEventRecord(h->ev1, h->own.st);
     fb.pending_host_r = rmap_in_kernel ? true : eds_mirror_residuals(h, first, count);
     if (fb.pending_host_r && !rmap_in_kernel) fb.pending_vteam = 0;      // (a mirror launch follows: see eds_fused_solve)
     e = hipGetLastError();
@@ -930,7 +929,7 @@ int eds_fused12_collect(eds_trk* h) {
             fb.pending_retry = true;
             int rc = eds_fused12_solve(h, fb.pending_level, pf, pc);
             if (rc != EDS_OK) { fb.pending_retry = false; return rc; }
-            hipError_t e = hipStreamSynchronize(h->st);
+            hipError_t e = hipStreamSynchronize(h->own.st);
             if (e != hipSuccess) { fb.pending_retry = false; return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e)); }
             return eds_fused12_collect(h);
         }

@@ -6,6 +6,7 @@
 
 #include "../../include/eds_hip.h"
 #include "eds_depth.hpp"
+#include "eds_device_owner.hpp"
 #include "eds_epiline.hpp"
 #include "eds_klt.hpp"
 #include "eds_kfpoints.hpp"
@@ -56,9 +57,9 @@ struct eds_trk {
     EdsKnobs knobs;                     // tuning knobs (eds_launch_rule.hpp): the environment as it was at eds_trk_create, then eds_trk_set_knob
     bool strips_unavailable = false;    // the strip copies did not fit the memory budget: remembered, not retried on every solve
     size_t strips_bytes = 0;            // what they take (eds_trk_strips_bytes)
-    int B = 0, Nmax = 0, Np = 0, H = 0, W = 0, max_seg = 0, dev = 0;
+    edscapi::DeviceOwner own;           // the device, the stream and every device and pinned allocation below (eds_device_owner.hpp)
+    int B = 0, Nmax = 0, Np = 0, H = 0, W = 0, max_seg = 0;
     int Hp = 0, Wp = 0, tiled = 1;      // frame allocation (eds_device.hpp FrameView)
-    hipStream_t st = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // device
     double *dpose = nullptr, *dG = nullptr, *dpart = nullptr, *dncstat = nullptr;

@@ -208,18 +208,18 @@ int eds_dev_download(void* h_dst, const void* d_src, size_t bytes) {
 
 int eds_dev_wait_stream(eds_trk* h, void* producer_stream) {
     if (!h) return fail(EDS_ERR_INVALID, "null handle");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (!h->ev_dev_in) EDS_HIP_TRY(hipEventCreateWithFlags(&h->ev_dev_in, hipEventDisableTiming));
     EDS_HIP_TRY(hipEventRecord(h->ev_dev_in, static_cast<hipStream_t>(producer_stream)));
-    EDS_HIP_TRY(hipStreamWaitEvent(h->st, h->ev_dev_in, 0));
+    EDS_HIP_TRY(hipStreamWaitEvent(h->own.st, h->ev_dev_in, 0));
     return EDS_OK;
 }
 
 int eds_dev_signal_stream(eds_trk* h, void* consumer_stream) {
     if (!h) return fail(EDS_ERR_INVALID, "null handle");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (!h->ev_dev_out) EDS_HIP_TRY(hipEventCreateWithFlags(&h->ev_dev_out, hipEventDisableTiming));
-    EDS_HIP_TRY(hipEventRecord(h->ev_dev_out, h->st));
+    EDS_HIP_TRY(hipEventRecord(h->ev_dev_out, h->own.st));
     EDS_HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_dev_out, 0));
     return EDS_OK;
 }
@@ -235,16 +235,16 @@ int eds_dev_set_event_frames(eds_trk* h, int first, int count, int dtype, const 
         return fail(EDS_ERR_INVALID, "bad strides: row_stride >= W and frame_stride >= (H - 1) * row_stride + W, in elements (0 = dense)");
     const size_t esz = dtype == EDS_IMG_F32 ? 4 : 8;
     if (d_frames && (reinterpret_cast<uintptr_t>(d_frames) & (esz - 1))) return fail(EDS_ERR_INVALID, "d_frames is not aligned to its element size");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    if ((rc = check_named(h->dev, d_frames, (size_t)((count - 1) * frame_stride + (H - 1) * row_stride + W) * esz, "d_frames"))) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    if ((rc = check_named(h->own.dev, d_frames, (size_t)((count - 1) * frame_stride + (H - 1) * row_stride + W) * esz, "d_frames"))) return rc;
     if ((rc = unshare_frames(h, first, count))) return rc;
     const dim3 grid((h->Wp + SF_COLS - 1) / SF_COLS, h->Hp / 4, count);
     float* frames = h->dframe;
     if (dtype == EDS_IMG_F32)
-        hipLaunchKernelGGL(k_store_frames_dev<float>, grid, dim3(SF_T), 0, h->st, static_cast<const float*>(d_frames), (long long)frame_stride,
+        hipLaunchKernelGGL(k_store_frames_dev<float>, grid, dim3(SF_T), 0, h->own.st, static_cast<const float*>(d_frames), (long long)frame_stride,
                            (long long)row_stride, frames, first, h->H, h->W, h->Hp, h->Wp, h->tiled);
     else
-        hipLaunchKernelGGL(k_store_frames_dev<double>, grid, dim3(SF_T), 0, h->st, static_cast<const double*>(d_frames), (long long)frame_stride,
+        hipLaunchKernelGGL(k_store_frames_dev<double>, grid, dim3(SF_T), 0, h->own.st, static_cast<const double*>(d_frames), (long long)frame_stride,
                            (long long)row_stride, frames, first, h->H, h->W, h->Hp, h->Wp, h->tiled);
     const hipError_t e = hipGetLastError();
     // after a failed launch the slots no longer count as holding a frame (include/eds_hip_device.h), and their strip copies are stale
@@ -260,13 +260,13 @@ int eds_dev_build_event_frames(eds_trk* h, int first_slot, int count, const int*
     if (!offsets || offsets[0] < 0) return fail(EDS_ERR_INVALID, "bad offsets");
     for (int b = 0; b < count; ++b) if (offsets[b + 1] < offsets[b]) return fail(EDS_ERR_INVALID, "offsets must not decrease");
     if (level < 0 || level > 16) return fail(EDS_ERR_INVALID, "bad level");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t e0 = (size_t)offsets[0], ne = (size_t)offsets[count] - e0;
     if (ne > 0) {
         if (reinterpret_cast<uintptr_t>(d_x) & 1 || reinterpret_cast<uintptr_t>(d_y) & 1) return fail(EDS_ERR_INVALID, "d_x / d_y are not aligned to uint16");
-        if ((rc = check_named(h->dev, d_x ? d_x + e0 : nullptr, ne * 2, "d_x"))) return rc;
-        if ((rc = check_named(h->dev, d_y ? d_y + e0 : nullptr, ne * 2, "d_y"))) return rc;
-        if ((rc = check_named(h->dev, d_polarity ? d_polarity + e0 : nullptr, ne, "d_polarity"))) return rc;
+        if ((rc = check_named(h->own.dev, d_x ? d_x + e0 : nullptr, ne * 2, "d_x"))) return rc;
+        if ((rc = check_named(h->own.dev, d_y ? d_y + e0 : nullptr, ne * 2, "d_y"))) return rc;
+        if ((rc = check_named(h->own.dev, d_polarity ? d_polarity + e0 : nullptr, ne, "d_polarity"))) return rc;
     }
     if ((rc = unshare_frames(h, first_slot, count))) return rc;
     return eds_frame_build_batch(h, first_slot, count, offsets, d_x, d_y, d_polarity, level, blur_sigma, use_exp_weights, norms, true);
@@ -286,11 +286,11 @@ int eds_dev_set_keyframes(eds_trk* h, int first, int count, const int* N, const 
     for (int b = 0; b < count; ++b) extent = std::max<int64_t>(extent, b * stride + N[b]);
     const double* arrs[4] = {d_norm_xy, d_grad_xy, d_idp, d_w};
     for (const double* a : arrs) if (reinterpret_cast<uintptr_t>(a) & 7) return fail(EDS_ERR_INVALID, "a keyframe array is not aligned to a double");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    if ((rc = check_named(h->dev, d_norm_xy, (size_t)extent * 16, "d_norm_xy"))) return rc;
-    if ((rc = check_named(h->dev, d_grad_xy, (size_t)extent * 16, "d_grad_xy"))) return rc;
-    if ((rc = check_named(h->dev, d_idp, (size_t)extent * 8, "d_idp"))) return rc;
-    if ((rc = check_named(h->dev, d_w, (size_t)extent * 8, "d_w"))) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    if ((rc = check_named(h->own.dev, d_norm_xy, (size_t)extent * 16, "d_norm_xy"))) return rc;
+    if ((rc = check_named(h->own.dev, d_grad_xy, (size_t)extent * 16, "d_grad_xy"))) return rc;
+    if ((rc = check_named(h->own.dev, d_idp, (size_t)extent * 8, "d_idp"))) return rc;
+    if ((rc = check_named(h->own.dev, d_w, (size_t)extent * 8, "d_w"))) return rc;
     for (int b = 0; b < count; ++b) {                   // N and K reach the kernels through the slots' pose blocks
         Slot& s = h->slots[first + b];
         s.N = N[b];
@@ -302,11 +302,11 @@ int eds_dev_set_keyframes(eds_trk* h, int first, int count, const int* N, const 
     // longer count as holding a keyframe (include/eds_hip_device.h) — the same rule as a failed eds_trk_set_event_frames for has_frame
     hipError_t e = hipSuccess;
     if ((rc = upload_pose(h, first, count)) == EDS_OK) {
-        hipLaunchKernelGGL(k_ingest_points, dim3(h->Np / IP_T, count), dim3(IP_T), 0, h->st, h->arrays(), first, (long long)stride, (long long)extent,
+        hipLaunchKernelGGL(k_ingest_points, dim3(h->Np / IP_T, count), dim3(IP_T), 0, h->own.st, h->arrays(), first, (long long)stride, (long long)extent,
                            d_norm_xy, d_grad_xy, d_idp, d_w);
         e = hipGetLastError();
         if (e == hipSuccess) {
-            eds_launch_gram_batch(h->arrays(), first, count, effective_blocks(h), h->st);
+            eds_launch_gram_batch(h->arrays(), first, count, effective_blocks(h), h->own.st);
             e = hipGetLastError();
         }
         if (e != hipSuccess) rc = fail(EDS_ERR_HIP, hipGetErrorString(e));
@@ -340,13 +340,13 @@ int eds_dev_set_idepths(eds_trk* h, int first, int count, const double* d_idp, i
     if (stride < maxN || stride > (int64_t)1 << 40) return fail(EDS_ERR_INVALID, "stride must be at least the largest N of the range");
     for (int b = 0; b < count; ++b) extent = std::max<int64_t>(extent, (b * stride + h->slots[first + b].N - 1) * elem_stride + 1);
     if (reinterpret_cast<uintptr_t>(d_idp) & 7) return fail(EDS_ERR_INVALID, "d_idp is not aligned to a double");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    if ((rc = check_named(h->dev, d_idp, (size_t)extent * 8, "d_idp"))) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    if ((rc = check_named(h->own.dev, d_idp, (size_t)extent * 8, "d_idp"))) return rc;
     // (the pose blocks in HBM hold the slots' N already: eds_trk_set_idepth's one-launch path relies on the same)
-    hipLaunchKernelGGL(k_ingest_idepths, dim3(h->Np / IP_T, count), dim3(IP_T), 0, h->st, h->arrays(), first, (long long)stride, elem_stride, (long long)extent, d_idp);
+    hipLaunchKernelGGL(k_ingest_idepths, dim3(h->Np / IP_T, count), dim3(IP_T), 0, h->own.st, h->arrays(), first, (long long)stride, elem_stride, (long long)extent, d_idp);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
-        eds_launch_gram_batch(h->arrays(), first, count, effective_blocks(h), h->st);
+        eds_launch_gram_batch(h->arrays(), first, count, effective_blocks(h), h->own.st);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {              // rho planes and Gram matrices may disagree: the slots need their keyframe again

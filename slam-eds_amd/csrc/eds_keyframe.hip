@@ -26,29 +26,15 @@
 
 #include "eds_keyframe_kernels.hpp"
 
-void eds_keyframe_free(EdsKeyframeBuffers* kb) {
-    if (kb->d_src) hipFree(kb->d_src);
-    void* d[] = {kb->d_raw, kb->d_log, kb->d_gx, kb->d_gy, kb->d_mag, kb->d_partial, kb->d_cand, kb->d_cnt, kb->d_off,
-                 kb->d_coord, kb->d_grad, kb->d_idp, kb->d_w, kb->d_dxy, kb->d_didp, kb->d_summary};
-    for (void* p : d) if (p) hipFree(p);
-    *kb = EdsKeyframeBuffers();
-}
-
 static int ensure(eds_trk* h) {
     EdsKeyframeBuffers& kb = h->kf_build;
     if (kb.d_raw) return EDS_OK;
     const size_t n = (size_t)h->H * h->W;
-    hipError_t e = hipMalloc(&kb.d_raw, n * 8);
-    double** planes[] = {&kb.d_log, &kb.d_gx, &kb.d_gy, &kb.d_mag, &kb.d_idp, &kb.d_w};
-    for (double** p : planes) if (e == hipSuccess) e = hipMalloc((void**)p, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&kb.d_coord, n * 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&kb.d_grad, n * 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&kb.d_partial, 2 * 256 * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&kb.d_cand, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&kb.d_cnt, (n / 4 + 2) * 4);       // cells are at least 2 x 2
-    if (e == hipSuccess) e = hipMalloc((void**)&kb.d_off, (n / 4 + 2) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&kb.d_summary, 16);
-    if (e != hipSuccess) { eds_keyframe_free(&kb); return eds_internal_fail(EDS_ERR_HIP, "hipMalloc(keyframe set-up buffers)"); }
+    if (!h->own.alloc({{&kb.d_raw, n * 8}, {(void**)&kb.d_log, n * 8}, {(void**)&kb.d_gx, n * 8}, {(void**)&kb.d_gy, n * 8}, {(void**)&kb.d_mag, n * 8},
+                       {(void**)&kb.d_idp, n * 8}, {(void**)&kb.d_w, n * 8}, {(void**)&kb.d_coord, n * 16}, {(void**)&kb.d_grad, n * 16},
+                       {(void**)&kb.d_partial, 2 * 256 * 8}, {(void**)&kb.d_cand, n * 4}, {(void**)&kb.d_cnt, (n / 4 + 2) * 4},       // cells are at least 2 x 2
+                       {(void**)&kb.d_off, (n / 4 + 2) * 4}, {(void**)&kb.d_summary, 16}}))
+        return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (keyframe set-up buffers)");
     return EDS_OK;
 }
 
@@ -71,26 +57,19 @@ int eds_keyframe_build(eds_trk* h, int slot, int img_type, const void* img, int 
     EdsKeyframeBuffers& kb = h->kf_build;
     kb.last_slot = -1;
     if (n_depth > kb.cap_depth) {
-        if (kb.d_dxy) { hipFree(kb.d_dxy); hipFree(kb.d_didp); kb.d_dxy = kb.d_didp = nullptr; }
-        kb.cap_depth = n_depth + n_depth / 4 + 256;
-        if (hipMalloc((void**)&kb.d_dxy, (size_t)kb.cap_depth * 16) != hipSuccess || hipMalloc((void**)&kb.d_didp, (size_t)kb.cap_depth * 8) != hipSuccess) {
-            kb.cap_depth = 0;
-            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc(depth map)");
-        }
+        const int want = n_depth + n_depth / 4 + 256;
+        if (!h->own.regrow(kb.cap_depth, want, {{(void**)&kb.d_dxy, (size_t)want * 16}, {(void**)&kb.d_didp, (size_t)want * 8}}))
+            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (depth map)");
     }
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     const size_t px = img_type == 0 ? 1 : (img_type == 1 ? 4 : 8);
     hipError_t e = hipSuccess;
     if (!prepare) {
         e = hipMemcpyAsync(kb.d_raw, img, n * px, hipMemcpyHostToDevice, st);
     } else {                            // resize and / or grey conversion on the device (KeyFrame.cpp:352-362), into the usual buffer
         const size_t src_bytes = (size_t)img_H * img_W * channels * px;
-        if (src_bytes > kb.src_bytes) {
-            if (kb.d_src) hipFree(kb.d_src);
-            kb.d_src = nullptr; kb.src_bytes = 0;
-            if (hipMalloc(&kb.d_src, src_bytes) != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, "hipMalloc(source image)");
-            kb.src_bytes = src_bytes;
-        }
+        if (src_bytes > kb.src_bytes && !h->own.regrow(kb.src_bytes, src_bytes, {{&kb.d_src, src_bytes}}))
+            return eds_internal_fail(EDS_ERR_HIP, "hipMalloc (source image)");
         e = hipMemcpyAsync(kb.d_src, img, src_bytes, hipMemcpyHostToDevice, st);
         const dim3 g((W + KF_T - 1) / KF_T, H), b(KF_T);
         if (img_type == 0) hipLaunchKernelGGL(k_prepare<uint8_t>, g, b, 0, st, (const uint8_t*)kb.d_src, img_H, img_W, channels, (uint8_t*)kb.d_raw, H, W);
@@ -167,7 +146,7 @@ int eds_keyframe_get_points(eds_trk* h, int slot, double* coord_xy, double* norm
     EdsKeyframeBuffers& kb = h->kf_build;
     if (kb.last_slot != slot || kb.last_N < 1) return eds_internal_fail(EDS_ERR_STATE, "this slot is not the one eds_trk_build_keyframe filled last");
     const size_t N = (size_t)kb.last_N;
-    hipError_t e = hipStreamSynchronize(h->st);
+    hipError_t e = hipStreamSynchronize(h->own.st);
     if (e == hipSuccess && (coord_xy || norm_xy)) {
         double* dst = coord_xy ? coord_xy : norm_xy;
         e = hipMemcpy(dst, kb.d_coord, N * 16, hipMemcpyDeviceToHost);

@@ -160,29 +160,18 @@ int ensure_flags(eds_trk* h) {
     EdsKfpBuffers& k = h->kfp;
     if (k.erase) return EDS_OK;
     const size_t B = (size_t)h->B, Np = (size_t)h->Np;
-    if (!device_alloc({{(void**)&k.range, B * Np * 8}, {(void**)&k.erase, B * Np}, {(void**)&k.coord, 2 * B * Np * 8}, {(void**)&k.kept, B * Np * 4}})) {
-        void* dp[] = {k.range, k.erase, k.coord, k.kept};
-        for (void* p : dp) if (p) hipFree(p);
-        k.range = nullptr; k.erase = nullptr; k.coord = nullptr; k.kept = nullptr;
+    if (!h->own.alloc({{(void**)&k.range, B * Np * 8}, {(void**)&k.erase, B * Np}, {(void**)&k.coord, 2 * B * Np * 8}, {(void**)&k.kept, B * Np * 4}}))
         return fail(EDS_ERR_HIP, "allocation of the keyframe point buffers failed");
-    }
     return EDS_OK;
 }
 
 int ensure_project(eds_trk* h, int cap) {
     EdsKfpBuffers& k = h->kfp;
     if (k.h_block && k.cap >= cap) return EDS_OK;
-    if (k.h_block) { hipHostFree(k.h_block); k.h_block = nullptr; k.cap = 0; }
     const size_t Np = (size_t)h->Np;
     const size_t bytes = (size_t)cap * (EDS_KFP_PAR * 8 + 8 + Np * 16 + Np * 8 + Np * 4);      // par | n (padded to 8) | xy | idp | src
     char* dblock = nullptr;
-    if (hipHostMalloc((void**)&k.h_block, bytes, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&dblock, k.h_block, 0) != hipSuccess) {
-        if (k.h_block) hipHostFree(k.h_block);
-        k.h_block = nullptr;
-        return fail(EDS_ERR_HIP, "allocation of the projection buffers failed");
-    }
-    k.cap = cap;
+    if (!h->own.regrow(k.cap, cap, {mapped(k.h_block, dblock, bytes)})) return fail(EDS_ERR_HIP, "allocation of the projection buffers failed");
     auto carve = [&](char* base) {
         double* par = reinterpret_cast<double*>(base);
         double* xy = par + (size_t)EDS_KFP_PAR * cap;
@@ -207,13 +196,13 @@ int finish_erase(eds_trk* h, int first, int count, bool erase_now, int stride, i
     const size_t Np = (size_t)h->Np;
     int rc;
     if (erase_now) {
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
         const EdsPointsDev dev = {k.coord, k.kept, k.erase};
         if ((rc = update_points_range(h, first, count, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dev))) return rc;
     }
     std::vector<int32_t> vk;
-    if (kept_index && erase_now) { vk.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), k.kept + Np * first, Np * count * 4, hipMemcpyDeviceToHost, h->st)); }
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (kept_index && erase_now) { vk.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), k.kept + Np * first, Np * count * 4, hipMemcpyDeviceToHost, h->own.st)); }
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     for (int b = 0; b < count; ++b) {
         const int nk = h->slots[first + b].N;
         if (n_kept) n_kept[b] = nk;
@@ -230,13 +219,6 @@ int common_checks(eds_trk* h, int first, int count, bool needs_stride, int strid
 }
 
 }  // namespace
-
-void eds_kfp_free(EdsKfpBuffers* kb) {
-    void* dp[] = {kb->range, kb->erase, kb->coord, kb->kept};
-    for (void* p : dp) if (p) hipFree(p);
-    if (kb->h_block) hipHostFree(kb->h_block);
-    *kb = EdsKfpBuffers();
-}
 
 int eds_kfp_check_transforms(int count, const double* T7, const double* K_dst) {
     for (int b = 0; b < count; ++b) {
@@ -270,7 +252,7 @@ int eds_kfp_project_queue(eds_trk* h, int first, int cn, const double* T7, const
         for (int j = 0; j < 4; ++j) { P[12 + j] = sl.K[j]; P[16 + j] = K_dst ? K_dst[4 * (size_t)b + j] : sl.K[j]; }
         P[20] = dW; P[21] = dH; P[22] = sl.seeded ? 1.0 : 0.0; P[23] = 0.0;
     }
-    hipLaunchKernelGGL(k_kfp_project, dim3(cn), dim3(EDS_KFP_PROJ_THREADS), 0, h->st, h->arrays(), first, d_par, h->depth.seeds, d_n,
+    hipLaunchKernelGGL(k_kfp_project, dim3(cn), dim3(EDS_KFP_PROJ_THREADS), 0, h->own.st, h->arrays(), first, d_par, h->depth.seeds, d_n,
                        d_xy, d_idp, d_src);
     EDS_HIP_TRY(hipGetLastError());
     return EDS_OK;
@@ -293,18 +275,18 @@ int eds_kfp_refine_points(eds_trk* h, int first, int count, double event_diff, i
     if (erase != 0 && erase != 1) return fail(EDS_ERR_INVALID, "erase must be 0 or 1");
     if (!std::isfinite(event_diff)) return fail(EDS_ERR_INVALID, "event_diff is not finite");
     if ((rc = common_checks(h, first, count, range || kept_index, stride, EDS_NEED_KF | EDS_NEED_FRAME))) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = ensure_flags(h))) return rc;
     EdsKfpBuffers& k = h->kfp;
     const size_t Np = (size_t)h->Np;
     const int maxN = max_points(h, first, count);
-    hipLaunchKernelGGL(k_kfp_range, dim3((maxN + EDS_KFP_WAVES - 1) / EDS_KFP_WAVES, count), dim3(64 * EDS_KFP_WAVES), 0, h->st, h->arrays(), first, r,
+    hipLaunchKernelGGL(k_kfp_range, dim3((maxN + EDS_KFP_WAVES - 1) / EDS_KFP_WAVES, count), dim3(64 * EDS_KFP_WAVES), 0, h->own.st, h->arrays(), first, r,
                        border_type, (float)border_value, event_diff, k.range, k.erase);
     EDS_HIP_TRY(hipGetLastError());
     std::vector<double> vr;
     std::vector<int> n0(count);
     for (int b = 0; b < count; ++b) n0[b] = h->slots[first + b].N;
-    if (range) { vr.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vr.data(), k.range + Np * first, Np * count * 8, hipMemcpyDeviceToHost, h->st)); }
+    if (range) { vr.resize(Np * count); EDS_HIP_TRY(hipMemcpyAsync(vr.data(), k.range + Np * first, Np * count * 8, hipMemcpyDeviceToHost, h->own.st)); }
     if ((rc = finish_erase(h, first, count, erase != 0, stride, kept_index, n_kept))) return rc;
     for (int b = 0; b < count; ++b) {
         if (erase) h->slots[first + b].num_points = h->slots[first + b].N;        // KeyFrame.cpp:1056
@@ -318,9 +300,9 @@ int eds_kfp_clean_points(eds_trk* h, int first, int count, double w_norm_thr, in
     if (rc) return rc;
     if (!std::isfinite(w_norm_thr)) return fail(EDS_ERR_INVALID, "w_norm_thr is not finite");
     if ((rc = common_checks(h, first, count, kept_index != nullptr, stride, EDS_NEED_KF))) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = ensure_flags(h))) return rc;
-    hipLaunchKernelGGL(k_kfp_clean, dim3((max_points(h, first, count) + 255) / 256, count), dim3(256), 0, h->st, h->arrays(), first, w_norm_thr,
+    hipLaunchKernelGGL(k_kfp_clean, dim3((max_points(h, first, count) + 255) / 256, count), dim3(256), 0, h->own.st, h->arrays(), first, w_norm_thr,
                        h->kfp.erase);
     EDS_HIP_TRY(hipGetLastError());
     return finish_erase(h, first, count, true, stride, kept_index, n_kept);
@@ -331,13 +313,13 @@ int eds_kfp_erase_points(eds_trk* h, int first, int count, int stride, const uin
     if (rc) return rc;
     if (!erase) return fail(EDS_ERR_INVALID, "null erase flags");
     if ((rc = common_checks(h, first, count, true, stride, EDS_NEED_KF))) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = ensure_flags(h))) return rc;
     const size_t Np = (size_t)h->Np;
     std::vector<unsigned char> flags(Np * count, 0);
     for (int b = 0; b < count; ++b)
         for (int i = 0; i < h->slots[first + b].N; ++i) flags[Np * b + i] = erase[(size_t)b * stride + i] ? 1 : 0;
-    EDS_HIP_TRY(hipMemcpyAsync(h->kfp.erase + Np * first, flags.data(), flags.size(), hipMemcpyHostToDevice, h->st));
+    EDS_HIP_TRY(hipMemcpyAsync(h->kfp.erase + Np * first, flags.data(), flags.size(), hipMemcpyHostToDevice, h->own.st));
     return finish_erase(h, first, count, true, stride, kept_index, n_kept);       // (waits for the stream before `flags` goes)
 }
 
@@ -358,7 +340,7 @@ int eds_kfp_project_depth_map(eds_trk* h, int first, int count, const double* T7
     if (rc) return rc;
     if ((rc = eds_kfp_check_transforms(count, T7, K_dst))) return rc;
     if ((rc = common_checks(h, first, count, depth_xy || depth_idp || src_index, stride, EDS_NEED_KF))) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if ((rc = ensure_project(h, std::min(count, EDS_KFP_BATCH)))) return rc;
     EdsKfpBuffers& k = h->kfp;
     const size_t Np = (size_t)h->Np;
@@ -367,7 +349,7 @@ int eds_kfp_project_depth_map(eds_trk* h, int first, int count, const double* T7
         const int cn = std::min(k.cap, count - c0);
         if ((rc = eds_kfp_project_queue(h, first + c0, cn, T7 ? T7 + 7 * (size_t)c0 : nullptr, K_dst ? K_dst + 4 * (size_t)c0 : nullptr, dW, dH, k.h_par,
                                         k.d_par, k.d_n, k.d_xy, k.d_idp, k.d_src))) return rc;
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
         for (int b = 0; b < cn; ++b) {
             const int n = k.h_n[b];
             const size_t o = (size_t)(c0 + b) * stride;

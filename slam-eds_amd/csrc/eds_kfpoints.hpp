@@ -26,7 +26,6 @@ struct EdsKfpBuffers {
     int *h_src = nullptr, *d_src = nullptr;         // [cap][Np]
 };
 
-void eds_kfp_free(EdsKfpBuffers* kb);
 // eds_kfp_project_depth_map's checks of T7 (count x 7) and K_dst (count x 4), either may be NULL
 int eds_kfp_check_transforms(int count, const double* T7, const double* K_dst);
 // fills the projection blocks of slots first .. first + cn - 1 (h_par / d_par: the two views of mapped pinned memory, EDS_KFP_PAR doubles

@@ -31,21 +31,6 @@ namespace {
 
 constexpr int KFS_NB = 256;             // blocks of the min / max passes, as the single build
 
-void free_maps(EdsKfsBuffers& k) {
-    void* dp[] = {k.d_mxy, k.d_midp, k.d_txy, k.d_tidp, k.d_msrc, k.d_perm};
-    for (void* p : dp) if (p) hipFree(p);
-    k.d_mxy = k.d_midp = k.d_txy = k.d_tidp = nullptr; k.d_msrc = k.d_perm = nullptr;
-    k.map_stride = 0;
-}
-
-void free_images(EdsKfsBuffers& k) {
-    void* dp[] = {k.d_raw, k.d_log, k.d_gx, k.d_gy, k.d_mag, k.d_partial, k.d_cand, k.d_cnt, k.d_off, k.d_coord, k.d_grad, k.d_idp, k.d_w};
-    for (void* p : dp) if (p) hipFree(p);
-    k.d_raw = nullptr;
-    k.d_log = k.d_gx = k.d_gy = k.d_mag = k.d_partial = k.d_coord = k.d_grad = k.d_idp = k.d_w = nullptr;
-    k.d_cand = k.d_cnt = k.d_off = nullptr;
-}
-
 // the small per-chunk blocks, and the right of k_kd_build to its LDS
 int ensure_small(eds_trk* h) {
     EdsKfsBuffers& k = h->kfs;
@@ -56,11 +41,8 @@ int ensure_small(eds_trk* h) {
     if (k.h_block) return EDS_OK;
     const size_t C = EDS_KFS_CHUNK, bytes = C * (4 + 16 + 32 + EDS_KFP_PAR * 8) + 64;
     char* dblock = nullptr;
-    if (hipHostMalloc((void**)&k.h_block, bytes, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&dblock, k.h_block, 0) != hipSuccess ||
-        !device_alloc({{(void**)&k.d_mn, C * 4}, {(void**)&k.d_flag, C * 4}, {(void**)&k.d_summary, C * 16}, {(void**)&k.d_K, C * 32}})) {
-        eds_kfs_free(&k);
+    if (!h->own.alloc({mapped(k.h_block, dblock, bytes), {(void**)&k.d_mn, C * 4}, {(void**)&k.d_flag, C * 4}, {(void**)&k.d_summary, C * 16}, {(void**)&k.d_K, C * 32}}))
         return fail(EDS_ERR_HIP, "allocation of the keyframe switch's blocks failed");
-    }
     k.h_par = reinterpret_cast<double*>(k.h_block);                    // doubles first: every part stays aligned
     k.d_par = reinterpret_cast<double*>(dblock);
     k.h_K = k.h_par + C * EDS_KFP_PAR;
@@ -73,14 +55,10 @@ int ensure_maps(eds_trk* h, size_t stride) {
     EdsKfsBuffers& k = h->kfs;
     if (stride < 1) stride = 1;
     if (k.d_mxy && k.map_stride >= stride) return EDS_OK;
-    free_maps(k);
     const size_t n = stride * EDS_KFS_CHUNK;
-    if (!device_alloc({{(void**)&k.d_mxy, n * 16}, {(void**)&k.d_midp, n * 8}, {(void**)&k.d_txy, n * 16}, {(void**)&k.d_tidp, n * 8},
-                       {(void**)&k.d_msrc, n * 4}, {(void**)&k.d_perm, n * 4}})) {
-        free_maps(k);
+    if (!h->own.regrow(k.map_stride, stride, {{(void**)&k.d_mxy, n * 16}, {(void**)&k.d_midp, n * 8}, {(void**)&k.d_txy, n * 16}, {(void**)&k.d_tidp, n * 8},
+                                             {(void**)&k.d_msrc, n * 4}, {(void**)&k.d_perm, n * 4}}))
         return fail(EDS_ERR_HIP, "allocation of the keyframe switch's map buffers failed");
-    }
-    k.map_stride = stride;
     return EDS_OK;
 }
 
@@ -90,19 +68,14 @@ int ensure_images(eds_trk* h, bool outputs) {
     EdsKfsBuffers& k = h->kfs;
     const size_t C = EDS_KFS_CHUNK, n = (size_t)h->H * h->W * C, cs = cell_stride_of(h) * C;
     if (!k.d_raw) {
-        if (!device_alloc({{&k.d_raw, n * 8}, {(void**)&k.d_log, n * 8}, {(void**)&k.d_gx, n * 8}, {(void**)&k.d_gy, n * 8}, {(void**)&k.d_mag, n * 8},
+        if (!h->own.alloc({{&k.d_raw, n * 8}, {(void**)&k.d_log, n * 8}, {(void**)&k.d_gx, n * 8}, {(void**)&k.d_gy, n * 8}, {(void**)&k.d_mag, n * 8},
                            {(void**)&k.d_idp, n * 8}, {(void**)&k.d_w, n * 8}, {(void**)&k.d_coord, n * 16}, {(void**)&k.d_grad, n * 16},
-                           {(void**)&k.d_partial, C * 2 * KFS_NB * 8}, {(void**)&k.d_cand, n * 4}, {(void**)&k.d_cnt, cs * 4}, {(void**)&k.d_off, cs * 4}})) {
-            free_images(k);
+                           {(void**)&k.d_partial, C * 2 * KFS_NB * 8}, {(void**)&k.d_cand, n * 4}, {(void**)&k.d_cnt, cs * 4}, {(void**)&k.d_off, cs * 4}}))
             return fail(EDS_ERR_HIP, "allocation of the keyframe switch's image buffers failed");
-        }
     }
     if (outputs && !k.h_out) {
         k.out_n = std::min((size_t)h->Np, (size_t)h->H * h->W);
-        if (hipHostMalloc((void**)&k.h_out, C * 6 * k.out_n * 8, hipHostMallocDefault) != hipSuccess) {
-            k.h_out = nullptr;
-            return fail(EDS_ERR_HIP, "allocation of the keyframe switch's output staging failed");
-        }
+        if (!h->own.alloc_pinned(k.h_out, C * 6 * k.out_n * 8)) return fail(EDS_ERR_HIP, "allocation of the keyframe switch's output staging failed");
     }
     return EDS_OK;
 }
@@ -110,7 +83,7 @@ int ensure_images(eds_trk* h, bool outputs) {
 int launch_trees(eds_trk* h, int cn, const double* d_xy, const double* d_idp, size_t in_stride, int max_m, size_t out_stride, double* d_txy,
                  double* d_tidp) {
     EdsKfsBuffers& k = h->kfs;
-    return kd_build_launch(h->st, cn, d_xy, d_idp, in_stride, k.d_mn, max_m, out_stride, k.d_perm, d_txy, d_tidp, k.d_flag);
+    return kd_build_launch(h->own.st, cn, d_xy, d_idp, in_stride, k.d_mn, max_m, out_stride, k.d_perm, d_txy, d_tidp, k.d_flag);
 }
 
 struct Images {
@@ -164,13 +137,13 @@ int build_keyframes(eds_trk* h, int first, int count, int img_type, const Images
     }
     const bool vectors = out && (out->coord_xy || out->norm_xy || out->grad_xy || out->idp || out->weights);
     if (vectors && out->stride < h->Nmax) return fail(EDS_ERR_INVALID, "output stride smaller than the handle's max_points");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
-    if (!im.host && (rc = eds_dev_check_range(h->dev, im.dev, (size_t)((count - 1) * fs + (int64_t)(H - 1) * rs + W) * px))) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
+    if (!im.host && (rc = eds_dev_check_range(h->own.dev, im.dev, (size_t)((count - 1) * fs + (int64_t)(H - 1) * rs + W) * px))) return rc;
     if (source == EDS_KFS_DEPTH_DEVICE && max_n > 0) {
         if ((reinterpret_cast<uintptr_t>(depth->depth_xy) | reinterpret_cast<uintptr_t>(depth->depth_idp)) & 7)
             return fail(EDS_ERR_INVALID, "a depth-map array is not aligned to a double");
-        if ((rc = eds_dev_check_range(h->dev, depth->depth_xy, (size_t)extent * 16))) return rc;
-        if ((rc = eds_dev_check_range(h->dev, depth->depth_idp, (size_t)extent * 8))) return rc;
+        if ((rc = eds_dev_check_range(h->own.dev, depth->depth_xy, (size_t)extent * 16))) return rc;
+        if ((rc = eds_dev_check_range(h->own.dev, depth->depth_idp, (size_t)extent * 8))) return rc;
     }
     if ((rc = check_idle_slots(h, first, count, 0))) return rc;
     if (source == EDS_KFS_DEPTH_SLOTS && (rc = check_idle_slots(h, depth->src_first, count, EDS_NEED_KF))) return rc;
@@ -180,7 +153,7 @@ int build_keyframes(eds_trk* h, int first, int count, int img_type, const Images
     if ((rc = ensure_images(h, vectors))) return rc;
     EdsKfsBuffers& k = h->kfs;
     h->kf_build.last_slot = -1;               // eds_trk_get_keyframe_points speaks of the single build's last slot only
-    hipStream_t st = h->st;
+    hipStream_t st = h->own.st;
     const size_t cs = cell_stride_of(h);
     const int ncx = W / cell, ncy = H / cell, ncell = ncx * ncy, n2 = cell * cell;       // only whole cells (KeyFrame.cpp:752-754)
     const int k_per_cell = sel->method == EDS_KF_MAX ? (sel->num_points > 0 ? sel->num_points / ncell : 0) : 0;
@@ -330,16 +303,6 @@ int build_keyframes(eds_trk* h, int first, int count, int img_type, const Images
 
 }  // namespace
 
-void eds_kfs_free(EdsKfsBuffers* kb) {
-    free_maps(*kb);
-    free_images(*kb);
-    void* dp[] = {kb->d_mn, kb->d_flag, kb->d_summary, kb->d_K};
-    for (void* p : dp) if (p) hipFree(p);
-    if (kb->h_block) hipHostFree(kb->h_block);
-    if (kb->h_out) hipHostFree(kb->h_out);
-    *kb = EdsKfsBuffers();
-}
-
 extern "C" {
 
 int eds_kfs_abi_version(void) { return EDS_HIP_KFSWITCH_ABI_VERSION; }
@@ -357,9 +320,9 @@ int eds_kfs_build_tree(eds_trk* h, int count, const int* n, const double* d_dept
     if (stride < std::max<int64_t>(max_n, 1) || stride > (int64_t)1 << 40) return fail(EDS_ERR_INVALID, "stride must be at least the largest n");
     for (int b = 0; b < count; ++b) if (n[b] > 0) extent = std::max<int64_t>(extent, b * stride + n[b]);
     if (reinterpret_cast<uintptr_t>(d_depth_xy) & 7) return fail(EDS_ERR_INVALID, "d_depth_xy is not aligned to a double");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     int rc;
-    if (extent > 0 && (rc = eds_dev_check_range(h->dev, d_depth_xy, (size_t)extent * 16))) return rc;
+    if (extent > 0 && (rc = eds_dev_check_range(h->own.dev, d_depth_xy, (size_t)extent * 16))) return rc;
     if (h->fused.pending_count > 0) return fail(EDS_ERR_STATE, "a batch is in flight: call eds_trk_sync first");
     if (extent == 0) { if (on_host_out) std::memset(on_host_out, 0, count); return EDS_OK; }
     if ((rc = ensure_small(h))) return rc;
@@ -373,11 +336,11 @@ int eds_kfs_build_tree(eds_trk* h, int count, const int* n, const double* d_dept
         const int cn = std::min(EDS_KFS_CHUNK, count - c0);
         int max_m = 0;
         for (int b = 0; b < cn; ++b) { k.h_mn[b] = n[c0 + b]; max_m = std::max(max_m, n[c0 + b]); }
-        EDS_HIP_TRY(hipMemcpyAsync(k.d_mn, k.h_mn, (size_t)cn * 4, hipMemcpyHostToDevice, h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(k.d_mn, k.h_mn, (size_t)cn * 4, hipMemcpyHostToDevice, h->own.st));
         if ((rc = launch_trees(h, cn, d_depth_xy + 2 * (size_t)c0 * stride, nullptr, (size_t)stride, max_m, ps, nullptr, nullptr))) return rc;
-        EDS_HIP_TRY(hipMemcpyAsync(flags, k.d_flag, (size_t)cn * 4, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipMemcpyAsync(perm.data(), k.d_perm, (size_t)cn * ps * 4, hipMemcpyDeviceToHost, h->st));
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        EDS_HIP_TRY(hipMemcpyAsync(flags, k.d_flag, (size_t)cn * 4, hipMemcpyDeviceToHost, h->own.st));
+        EDS_HIP_TRY(hipMemcpyAsync(perm.data(), k.d_perm, (size_t)cn * ps * 4, hipMemcpyDeviceToHost, h->own.st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
         for (int b = 0; b < cn; ++b) {
             const int m = n[c0 + b];
             int32_t* dst = perm_out + (size_t)(c0 + b) * stride;

@@ -29,4 +29,3 @@ struct EdsKfsBuffers {
     size_t out_n = 0;
 };
 
-void eds_kfs_free(EdsKfsBuffers* kb);

@@ -239,15 +239,13 @@ int ensure(eds_trk* h) {
     EdsKltBuffers& k = h->klt;
     if (k.tracks) return EDS_OK;
     const size_t B = (size_t)h->B, Np = (size_t)h->Np, H = (size_t)h->H;
-    if (!device_alloc({{(void**)&k.tracks, 2 * B * Np * 8}, {(void**)&k.flow, 2 * B * Np * 8}, {(void**)&k.coord, 2 * B * Np * 8},
+    if (!h->own.alloc({{(void**)&k.tracks, 2 * B * Np * 8}, {(void**)&k.flow, 2 * B * Np * 8}, {(void**)&k.coord, 2 * B * Np * 8},
                        {(void**)&k.kept, B * Np * 4}, {(void**)&k.keys_tmp, B * Np * 8}, {(void**)&k.keys, B * Np * 8},
-                       {(void**)&k.row_start, B * (H + 2) * 4}})) {
-        eds_klt_free(&k);
+                       {(void**)&k.row_start, B * (H + 2) * 4}}))
         return fail(EDS_ERR_HIP, "allocation of the KLT buffers failed");
-    }
     // every KeyFrame::create zeroes flow (KeyFrame.cpp:447-448); tracks are zero until getCoord writes them
-    EDS_HIP_TRY(hipMemsetAsync(k.tracks, 0, 2 * B * Np * 8, h->st));
-    EDS_HIP_TRY(hipMemsetAsync(k.flow, 0, 2 * B * Np * 8, h->st));
+    EDS_HIP_TRY(hipMemsetAsync(k.tracks, 0, 2 * B * Np * 8, h->own.st));
+    EDS_HIP_TRY(hipMemsetAsync(k.flow, 0, 2 * B * Np * 8, h->own.st));
     return EDS_OK;
 }
 
@@ -282,17 +280,17 @@ int run(eds_trk* h, int first, int count, int r, int L, bool pyr, int stride, do
     if ((rc = update_points_range(h, first, count, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dev))) return rc;
     const int maxN = max_points(h, first, count);
     // 2. bins, 3. windows
-    hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), bin_lds, h->st, h->arrays(), first, kb.coord, kb.keys_tmp, kb.keys,
+    hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), bin_lds, h->own.st, h->arrays(), first, kb.coord, kb.keys_tmp, kb.keys,
                        kb.row_start, 0);
     EDS_HIP_TRY(hipGetLastError());
     double k0, k1;
     gauss3_sigma_half(k0, k1);
     if (maxN > 0) {
         if (pyr)
-            hipLaunchKernelGGL(k_klt_window<true>, dim3(maxN, count), dim3(64), win_lds, h->st, h->arrays(), first, r, L, k0, k1, k0, kb.coord,
+            hipLaunchKernelGGL(k_klt_window<true>, dim3(maxN, count), dim3(64), win_lds, h->own.st, h->arrays(), first, r, L, k0, k1, k0, kb.coord,
                                kb.keys, kb.row_start, kb.tracks, kb.flow);
         else
-            hipLaunchKernelGGL(k_klt_window<false>, dim3(maxN, count), dim3(64), win_lds, h->st, h->arrays(), first, r, L, k0, k1, k0, kb.coord,
+            hipLaunchKernelGGL(k_klt_window<false>, dim3(maxN, count), dim3(64), win_lds, h->own.st, h->arrays(), first, r, L, k0, k1, k0, kb.coord,
                                kb.keys, kb.row_start, kb.tracks, kb.flow);
         EDS_HIP_TRY(hipGetLastError());
     }
@@ -300,9 +298,9 @@ int run(eds_trk* h, int first, int count, int r, int L, bool pyr, int stride, do
     const size_t Np = (size_t)h->Np, n = (size_t)count * Np;
     std::vector<double> va;
     std::vector<int32_t> vk;
-    if (coord_xy) { va.resize(2 * n); EDS_HIP_TRY(hipMemcpyAsync(va.data(), kb.coord + 2 * Np * first, 2 * n * 8, hipMemcpyDeviceToHost, h->st)); }
-    if (kept_index) { vk.resize(n); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), kb.kept + Np * first, n * 4, hipMemcpyDeviceToHost, h->st)); }
-    EDS_HIP_TRY(hipStreamSynchronize(h->st));
+    if (coord_xy) { va.resize(2 * n); EDS_HIP_TRY(hipMemcpyAsync(va.data(), kb.coord + 2 * Np * first, 2 * n * 8, hipMemcpyDeviceToHost, h->own.st)); }
+    if (kept_index) { vk.resize(n); EDS_HIP_TRY(hipMemcpyAsync(vk.data(), kb.kept + Np * first, n * 4, hipMemcpyDeviceToHost, h->own.st)); }
+    EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
     for (int b = 0; b < count; ++b) {
         const int nk = h->slots[first + b].N;
         const size_t o = (size_t)b * stride;
@@ -317,14 +315,8 @@ int run(eds_trk* h, int first, int count, int r, int L, bool pyr, int stride, do
 
 }  // namespace
 
-void eds_klt_free(EdsKltBuffers* kb) {
-    void* dp[] = {kb->tracks, kb->flow, kb->coord, kb->kept, kb->keys_tmp, kb->keys, kb->row_start};
-    for (void* p : dp) if (p) hipFree(p);
-    *kb = EdsKltBuffers();
-}
-
 int eds_klt_bin_launch(eds_trk* h, int first, int count, const double* coord, uint64_t* keys_tmp, uint64_t* keys, int* row_start, int bias) {
-    hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), 2 * ((size_t)h->H + 2) * 4, h->st, h->arrays(), first, coord, keys_tmp,
+    hipLaunchKernelGGL(k_klt_bin, dim3(count), dim3(EDS_KLT_BIN_THREADS), 2 * ((size_t)h->H + 2) * 4, h->own.st, h->arrays(), first, coord, keys_tmp,
                        keys, row_start, bias);
     return hipGetLastError() == hipSuccess ? EDS_OK : fail(EDS_ERR_HIP, "launch of k_klt_bin failed");
 }
@@ -333,8 +325,8 @@ void eds_klt_reset_slot(eds_trk* h, int slot) {
     if (!h->klt.tracks) return;
     const size_t Np = (size_t)h->Np, plane = (size_t)h->B * Np, o = (size_t)slot * Np;
     for (double* p : {h->klt.tracks, h->klt.flow}) {
-        hipMemsetAsync(p + o, 0, Np * 8, h->st);
-        hipMemsetAsync(p + plane + o, 0, Np * 8, h->st);
+        hipMemsetAsync(p + o, 0, Np * 8, h->own.st);
+        hipMemsetAsync(p + plane + o, 0, Np * 8, h->own.st);
     }
 }
 
@@ -360,7 +352,7 @@ int eds_klt_get(eds_trk* h, int slot, double* tracks_xy, double* flow_xy) {
     if (!tracks_xy && !flow_xy) return fail(EDS_ERR_INVALID, "null output");
     if ((rc = check_idle_slots(h, slot, 1, EDS_NEED_KF))) return rc;
     if (!h->klt.tracks) return fail(EDS_ERR_STATE, "no device tracks: eds_klt_track_points has not run on this handle");
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const int N = h->slots[slot].N;
     if (tracks_xy && (rc = read_xy_planes(h, h->klt.tracks, slot, 1, N, tracks_xy))) return rc;
     if (flow_xy && (rc = read_xy_planes(h, h->klt.flow, slot, 1, N, flow_xy))) return rc;

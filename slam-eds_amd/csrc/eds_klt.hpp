@@ -26,7 +26,6 @@ struct EdsPointsDev {
     const unsigned char* erase = nullptr;
 };
 
-void eds_klt_free(EdsKltBuffers* kb);
 // a new keyframe: zero the slot's tracks and flow (KeyFrame::create, KeyFrame.cpp:447-448), on the handle's stream
 void eds_klt_reset_slot(eds_trk* h, int slot);
 // k_klt_bin for slots first .. first + count - 1 over the pixel coordinates `coord` ([B][Np][2], indexed by slot): keys and row starts

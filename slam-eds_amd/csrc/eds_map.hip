@@ -29,20 +29,16 @@
 using namespace edscapi;
 
 // the scratch of one handle: a pinned, device-mapped block (poses of the destinations, counts) and device memory for results that go to
-// host memory.  `own` NULL: an eds_trk, whose device memory is freed here.
+// host memory.  Both belong to the handle's owner.
 struct eds_map_state {
     char *h_pin = nullptr, *d_pin = nullptr;
     size_t pin_bytes = 0;
     char* stage = nullptr;
     size_t stage_bytes = 0;
-    bool stage_is_ours = false;
 };
 
 namespace edsmap_internal {
 void release(eds_map_state*& s) {
-    if (!s) return;
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
-    if (s->stage && s->stage_is_ours) (void)hipFree(s->stage);
     delete s;
     s = nullptr;
 }
@@ -231,35 +227,14 @@ __global__ __launch_bounds__(TB) void k_map_slot_cloud(EdsArrays A, SlotArgs a, 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-// the state with a pinned block of at least pin_bytes and, through `own` (NULL: plain hipMalloc), device scratch of at least stage_bytes
-int ensure_state(eds_map_state*& s, DeviceOwner* own, size_t pin_bytes, size_t stage_bytes) {
+// the state with a pinned block of at least pin_bytes and device scratch of at least stage_bytes, both the owner's
+int ensure_state(eds_map_state*& s, DeviceOwner& own, size_t pin_bytes, size_t stage_bytes) {
     if (!s) s = new eds_map_state;
-    if (pin_bytes > s->pin_bytes) {
-        if (s->h_pin) (void)hipHostFree(s->h_pin);
-        s->h_pin = s->d_pin = nullptr; s->pin_bytes = 0;
-        const size_t want = std::max<size_t>(pin_bytes, 4096);
-        if (hipHostMalloc((void**)&s->h_pin, want, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&s->d_pin, s->h_pin, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            if (s->h_pin) (void)hipHostFree(s->h_pin);
-            s->h_pin = s->d_pin = nullptr;
-            return fail(EDS_ERR_HIP, "eds_map: allocation of the pinned block failed");
-        }
-        s->pin_bytes = want;
-    }
-    if (stage_bytes > s->stage_bytes) {
-        if (own) own->release(s->stage);
-        else if (s->stage) { (void)hipFree(s->stage); s->stage = nullptr; }
-        s->stage_bytes = 0;
-        bool ok;
-        if (own) ok = own->alloc(s->stage, stage_bytes);
-        else {
-            ok = hipMalloc((void**)&s->stage, stage_bytes) == hipSuccess && s->stage;
-            if (!ok) { (void)hipGetLastError(); s->stage = nullptr; }
-            s->stage_is_ours = true;
-        }
-        if (!ok) return fail(EDS_ERR_HIP, "eds_map: allocation of the device scratch failed");
-        s->stage_bytes = stage_bytes;
-    }
+    const size_t want = std::max<size_t>(pin_bytes, 4096);
+    if (pin_bytes > s->pin_bytes && !own.regrow(s->pin_bytes, want, {mapped(s->h_pin, s->d_pin, want)}))
+        return fail(EDS_ERR_HIP, "eds_map: allocation of the pinned block failed");
+    if (stage_bytes > s->stage_bytes && !own.regrow(s->stage_bytes, stage_bytes, {{(void**)&s->stage, stage_bytes}}))
+        return fail(EDS_ERR_HIP, "eds_map: allocation of the device scratch failed");
     return EDS_OK;
 }
 
@@ -302,7 +277,7 @@ int eds_map_window_cloud(eds_win* h, int F, uint32_t frame_mask, const double* T
     if (total && on_device && (rc = eds_dev_check_range(h->own.dev, points, bytes))) return rc;
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
     if (total) {
-        if (!on_device && (rc = ensure_state(h->map, &h->own, 0, bytes))) return rc;
+        if (!on_device && (rc = ensure_state(h->map, h->own, 0, bytes))) return rc;
         WinArgs a;
         std::memset(&a, 0, sizeof(a));
         for (int f = 0, q = 0; f <= edsmap::MAX_FRAMES; ++f) {
@@ -346,7 +321,7 @@ int eds_map_window_depth_maps(eds_win* h, int F, uint32_t frame_mask, const doub
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t par_bytes = (size_t)count * 16 * sizeof(double), cells = (size_t)count * (size_t)nsel;
     const size_t o_idp = round16(cells * 16), o_src = o_idp + round16(cells * 8);
-    if ((rc = ensure_state(h->map, &h->own, par_bytes + (size_t)count * sizeof(int), on_device || !cells ? 0 : o_src + cells * 4))) return rc;
+    if ((rc = ensure_state(h->map, h->own, par_bytes + (size_t)count * sizeof(int), on_device || !cells ? 0 : o_src + cells * 4))) return rc;
     eds_map_state* s = h->map;
     double* h_par = reinterpret_cast<double*>(s->h_pin);
     int* h_n = reinterpret_cast<int*>(s->h_pin + par_bytes);
@@ -418,7 +393,7 @@ int eds_map_immature_cloud(eds_imm* h, int n_hosts, uint32_t host_mask, const do
     if (!most) { *n_out = 0; return EDS_OK; }
     EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t par_bytes = (size_t)n_hosts * 12 * sizeof(double), o_col = round16(room * 24), o_st = o_col + round16(room * 32);
-    if ((rc = ensure_state(h->map, &h->own, par_bytes + 2 * sizeof(int), on_device || !room ? 0 : o_st + round16(room)))) return rc;
+    if ((rc = ensure_state(h->map, h->own, par_bytes + 2 * sizeof(int), on_device || !room ? 0 : o_st + round16(room)))) return rc;
     eds_map_state* s = h->map;
     std::memcpy(s->h_pin, T_w_c, par_bytes);
     int* h_n = reinterpret_cast<int*>(s->h_pin + par_bytes);
@@ -482,10 +457,10 @@ int eds_map_slot_cloud(eds_trk* h, int first, int count, const double* T_w_kf, i
     if (stride < maxN || stride < 1) return fail(EDS_ERR_INVALID, "stride smaller than the largest point count");
     if ((rc = check_idle_slots(h, first, count, EDS_NEED_KF))) return rc;
     const size_t extent = ((size_t)(count - 1) * (size_t)stride + (size_t)h->slots[first + count - 1].N) * 24;
-    if (on_device && (rc = eds_dev_check_range(h->dev, points, extent))) return rc;
-    EDS_HIP_TRY(hipSetDevice(h->dev));
+    if (on_device && (rc = eds_dev_check_range(h->own.dev, points, extent))) return rc;
+    EDS_HIP_TRY(hipSetDevice(h->own.dev));
     const size_t Np = (size_t)h->Np;
-    if (!on_device && (rc = ensure_state(h->map, nullptr, 0, (size_t)SLOT_BATCH * Np * 24))) return rc;
+    if (!on_device && (rc = ensure_state(h->map, h->own, 0, (size_t)SLOT_BATCH * Np * 24))) return rc;
     std::vector<double> back;
     for (int c0 = 0; c0 < count; c0 += SLOT_BATCH) {
         const int cn = std::min(SLOT_BATCH, count - c0);
@@ -495,14 +470,14 @@ int eds_map_slot_cloud(eds_trk* h, int first, int count, const double* T_w_kf, i
         std::memcpy(a.T, T_w_kf + 12 * (size_t)c0, 12 * (size_t)cn * sizeof(double));
         double* dst = on_device ? points + (size_t)c0 * (size_t)stride * 3 : reinterpret_cast<double*>(h->map->stage);
         const long long st = on_device ? (long long)stride : (long long)Np;
-        hipLaunchKernelGGL(k_map_slot_cloud, dim3(blocks(max_points(h, first + c0, cn), TB), cn), dim3(TB), 0, h->st, h->arrays(), a, first + c0,
+        hipLaunchKernelGGL(k_map_slot_cloud, dim3(blocks(max_points(h, first + c0, cn), TB), cn), dim3(TB), 0, h->own.st, h->arrays(), a, first + c0,
                            h->depth.seeds, st, dst);
         EDS_HIP_TRY(hipGetLastError());
         if (!on_device) {
             back.resize((size_t)cn * Np * 3);
-            EDS_HIP_TRY(hipMemcpyAsync(back.data(), dst, back.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+            EDS_HIP_TRY(hipMemcpyAsync(back.data(), dst, back.size() * sizeof(double), hipMemcpyDeviceToHost, h->own.st));
         }
-        EDS_HIP_TRY(hipStreamSynchronize(h->st));
+        EDS_HIP_TRY(hipStreamSynchronize(h->own.st));
         for (int b = 0; !on_device && b < cn; ++b)
             std::memcpy(points + (size_t)(c0 + b) * (size_t)stride * 3, back.data() + (size_t)b * Np * 3, (size_t)h->slots[first + c0 + b].N * 24);
     }

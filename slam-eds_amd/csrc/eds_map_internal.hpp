@@ -5,7 +5,7 @@
 struct eds_map_state;
 
 namespace edsmap_internal {
-// frees the state's pinned block and deletes the struct (its device memory belongs to the handle's owner, or is freed here when the
-// handle has none); s is NULL afterwards.  Harmless on NULL.
+// deletes the struct (its pinned block and its device memory belong to the handle's owner, whose close() frees them); s is NULL
+// afterwards.  Harmless on NULL.
 void release(eds_map_state*& s);
 }  // namespace edsmap_internal

@@ -186,28 +186,16 @@ __global__ __launch_bounds__(EDS_PTS_THREADS) void k_update_points(EdsArrays A, 
 
 }  // namespace
 
-void eds_points_free(EdsPointBuffers* pbuf) {
-    if (pbuf->h_block) hipHostFree(pbuf->h_block);
-    if (pbuf->h_tau) hipHostFree(pbuf->h_tau);
-    *pbuf = EdsPointBuffers();
-}
-
 #define EDS_PTS_BATCH 64                // alignments per launch of the batched getCoord (4.7 MB of pinned outputs at 2 048 points)
 static int ensure(eds_trk* h, int cap = 1) {
     EdsPointBuffers& pb = h->point_ops;
     if (pb.h_block && pb.cap >= cap) return EDS_OK;
-    if (pb.h_block) { hipHostFree(pb.h_block); pb.h_block = nullptr; }
     const size_t Np = (size_t)h->Np;
     const size_t bytes = (size_t)cap * (16 + 128 + Np * 16 + Np * 16 + Np * 4);        // summary | pose | coord | track | kept, `cap` of each
     char* dblock = nullptr;
-    if (hipHostMalloc((void**)&pb.h_block, bytes, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&dblock, pb.h_block, 0) != hipSuccess ||
-        (!pb.h_tau && (hipHostMalloc((void**)&pb.h_tau, (size_t)h->B * 8, hipHostMallocMapped) != hipSuccess ||
-                       hipHostGetDevicePointer((void**)&pb.d_tau, pb.h_tau, 0) != hipSuccess))) {
-        eds_points_free(&pb);
+    if ((!pb.h_tau && !h->own.alloc_mapped(pb.h_tau, pb.d_tau, (size_t)h->B * 8)) ||
+        !h->own.regrow(pb.cap, cap, {edscapi::mapped(pb.h_block, dblock, bytes)}))
         return eds_internal_fail(EDS_ERR_HIP, "allocation of the point buffers failed");
-    }
-    pb.cap = cap;
     auto carve = [&](char* base) {
         double* sum = reinterpret_cast<double*>(base);
         double* pose = sum + 2 * (size_t)cap;
@@ -233,9 +221,9 @@ int eds_points_loss_param(eds_trk* h, int first, int count, int method, double* 
     int rc = ensure(h);
     if (rc) return rc;
     EdsPointBuffers& pb = h->point_ops;
-    hipLaunchKernelGGL(k_loss_param, dim3(count), dim3(EDS_LP_THREADS), 0, h->st, h->arrays(), first, method, pb.d_tau);
+    hipLaunchKernelGGL(k_loss_param, dim3(count), dim3(EDS_LP_THREADS), 0, h->own.st, h->arrays(), first, method, pb.d_tau);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->own.st);
     if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
     std::memcpy(tau_out, pb.h_tau, (size_t)count * 8);      // the kernel wrote the scales into mapped pinned memory: no copy call
     return EDS_OK;
@@ -268,12 +256,12 @@ int eds_points_update_batch(eds_trk* h, int first, int count, int delete_out, in
         // the KLT (dev) keeps coordinates and kept indices in HBM for its own kernels (eds_klt.hip)
         double* dcoord = dev ? dev->coord + 2 * Np * (size_t)(first + c0) : (coord_xy ? pb.d_coord : nullptr);
         int* dkept = dev ? dev->kept + Np * (size_t)(first + c0) : ((kept_index || seeded) ? pb.d_kept : nullptr);
-        hipLaunchKernelGGL(k_update_points, dim3(cn), dim3(EDS_PTS_THREADS), 0, h->st, h->arrays(), first + c0, ppt, delete_out, pb.d_pose,
+        hipLaunchKernelGGL(k_update_points, dim3(cn), dim3(EDS_PTS_THREADS), 0, h->own.st, h->arrays(), first + c0, ppt, delete_out, pb.d_pose,
                            dcoord, tracks_xy ? pb.d_track : nullptr, dkept, pb.d_summary, h->klt.tracks, h->klt.flow,
                            dev && dev->erase ? dev->erase + Np * (size_t)(first + c0) : nullptr);
         if (seeded) eds_depth_compact(h, first + c0, cn, dkept);
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(h->st);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->own.st);
         if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
         for (int b = 0; b < cn; ++b) {
             const int n = (int)pb.h_summary[2 * b];

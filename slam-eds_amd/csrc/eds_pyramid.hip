@@ -116,8 +116,8 @@ int eds_pyr_set_keyframe_slot(eds_pyr* p, int slot, int level, int N, const doub
 // builder — is on that stream too), one launch behind the other; the other levels' streams then wait for ONE event.  The host
 // waits for nothing: a level's solve is ordered behind its frame on the level's own stream.
 static int build_levels(eds_pyr* p, int first = 0, int count = 1) {
-    hipStream_t st0 = p->lv[0]->st;
-    hipError_t e = hipSetDevice(p->lv[0]->dev);
+    hipStream_t st0 = p->lv[0]->own.st;
+    hipError_t e = hipSetDevice(p->lv[0]->own.dev);
     if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
     for (int l = 1; l < p->levels; ++l) {
         eds_trk* s = p->lv[l - 1];
@@ -129,7 +129,7 @@ static int build_levels(eds_pyr* p, int first = 0, int count = 1) {
     e = hipGetLastError();
     if (e == hipSuccess && p->levels > 1) {
         e = hipEventRecord(p->ev_levels, st0);
-        for (int l = 1; l < p->levels && e == hipSuccess; ++l) e = hipStreamWaitEvent(p->lv[l]->st, p->ev_levels, 0);
+        for (int l = 1; l < p->levels && e == hipSuccess; ++l) e = hipStreamWaitEvent(p->lv[l]->own.st, p->ev_levels, 0);
     }
     if (e != hipSuccess) return eds_internal_fail(EDS_ERR_HIP, hipGetErrorString(e));
     for (int k = first; k < first + count; ++k) p->slot_has_frame[k] = 1;

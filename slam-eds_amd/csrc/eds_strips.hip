@@ -51,8 +51,7 @@ bool eds_strips_prepare(eds_trk* h, int first, int count) {
         phases = eds_strips_phases_for_budget(phases, (unsigned long long)h->B, two_copies, free_b, h->knobs.strips_budget_pct);
         for (; phases >= 1; phases >>= 1) {
             const size_t bytes = (size_t)h->B * phases * two_copies;
-            if (hipMalloc((void**)&h->dstrips, bytes) == hipSuccess) { h->strips_bytes = bytes; break; }
-            (void)hipGetLastError(); h->dstrips = nullptr;
+            if (h->own.alloc(h->dstrips, bytes)) { h->strips_bytes = bytes; break; }
         }
         if (!h->dstrips) { h->strips_unavailable = true; return false; }
         h->strip_phases = phases;
@@ -71,7 +70,7 @@ bool eds_strips_prepare(eds_trk* h, int first, int count) {
         if (!stale[s]) { ++s; continue; }
         int e = s;
         while (e < h->B && stale[e] && e - s < 65535) ++e;
-        hipLaunchKernelGGL(k_tiles_to_strips, dim3((pieces + 255) / 256, e - s), dim3(256), 0, h->st, h->dframe, h->dstrips, s, h->Hp, h->Wp, h->strip_phases);
+        hipLaunchKernelGGL(k_tiles_to_strips, dim3((pieces + 255) / 256, e - s), dim3(256), 0, h->own.st, h->dframe, h->dstrips, s, h->Hp, h->Wp, h->strip_phases);
         for (int k = s; k < e; ++k) {
             if (h->slots[k].frame_version == 0) h->slots[k].frame_version = 1;       // (frames written before versions were kept)
             h->slots[k].strips_version = h->slots[k].frame_version;
@@ -118,8 +117,3 @@ bool eds_strips_for_solve(eds_trk* h, int first, int count) {
     return eds_strips_prepare(h, first, count);
 }
 
-void eds_strips_free(eds_trk* h) {
-    if (h->dstrips) hipFree(h->dstrips);
-    h->dstrips = nullptr;
-    h->strips_bytes = 0;
-}

@@ -1,5 +1,5 @@
-"""slam-eds_amd/csrc/eds_device_owner.hpp, which owns the device memory, the uploads and the read-backs of eds_imm, eds_ct, eds_win and
-eds_sel and of the eds_act / eds_wsv / eds_wed states beside them.
+"""slam-eds_amd/csrc/eds_device_owner.hpp, which owns the device and pinned memory, the uploads and the read-backs of eds_imm, eds_ct,
+eds_win and eds_sel, of the eds_act / eds_wsv / eds_wed states beside them, and the memory of the tracker handle eds_trk.
 
 Without a device: the owner on its own (tests/cpp/device_owner_check.cpp under AddressSanitizer and UBSan, a stand-alone program), and
 the four creators, whose argument checks stay ahead of the device check.  On the device: the same program built plainly; one image
@@ -60,7 +60,9 @@ def test_creators_check_their_arguments_before_the_device(capi, kind):
 
 @pytest.mark.gpu
 def test_owner_walk_on_the_device(gpu, tmp_path):
-    """open, three buffers, release, a refused 2^60-byte request (alone and in a table), exchanged pointers, close twice, reopen"""
+    """open, three buffers, release, a refused 2^60-byte request (alone and in a table), exchanged pointers, a pinned block and a mapped
+    pair read through its device pointer, a buffer regrown 256 -> 4096 bytes, refused pinned requests that leave NULL pointers and a zero
+    capacity, close twice with both lists empty, reopen"""
     exe = _build(tmp_path / "device_owner_check")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "owner ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
